@@ -6,7 +6,18 @@ render kernel over every pixel of the workload's framebuffer.  Default workload
 at N = 1 = BASELINE.json configs[2], the configuration the metric is quoted on:
 3840x2160 over a 4096^2 heightmap, spherical hfov 180, step_dist 0.25 ("C3").
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--dump-outputs DIR] [--full]
+
+A plain run sets up, preconditions and warms up, times the K steps, writes the outputs if asked and prints
+the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload's counts.
+`--full` adds everything else described below: the timed frames checked against the instrumented kernel,
+`roofline`, the secondary blocks, the one-GPU legs of the N > 1 line and `cpu_baseline`.
+
+--dump-outputs DIR: what the last timed step rendered (rank 0's frame; the gathered frame in strips mode), as
+float32 in DIR/frame_sample.npy -- the RGBA8 values of a fixed, seeded sample of at most 2^21 pixels in
+raster order, (n, 4); every pixel where the frame has fewer -- and DIR/frame_row_sums.npy, float64 (rows, 4):
+each row's channel sums over the whole frame.  The inputs are synthetic and seeded: the same arguments give
+the same inputs on every run.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process is only a LAUNCHER: before anything
 touches the GPU (torch is not even imported) it starts `python -m torch.distributed.run --nnodes=1
@@ -16,7 +27,7 @@ directly (WORLD_SIZE set: what the driver does) the same file is a rank.  `--dry
 rendezvous, sharding and the gather on CPU (gloo, a pattern instead of the renderer): the CPU test of
 the launch path (tests/test_bench_launch.py); its line says "dry_launch": true and carries no value.
 `--share-gpu` is the rehearsal of the N > 1 line on a box with fewer GPUs than ranks: the ranks share the GPUs that are
-there, the collectives run over gloo on host copies, every block and pixel check of the line runs
+there, the collectives run over gloo on host copies, every block and pixel check of the line runs (with --full)
 ("share_gpu": true; the rates are no scaling figures).
 
 N = 1: `value` / `ms_per_step` = K frames of the workload's static pose launched BACK TO BACK ON ONE
@@ -24,7 +35,7 @@ N = 1: `value` / `ms_per_step` = K frames of the workload's static pose launched
        describes (`roofline.kernel_ms` = the same launches timed with HIP events on the launch stream).
        Before the warm-up the pose is rendered 12 times with a synchronisation in between so that the
        library's launch-order calibration has settled (`preconditioning`).
-       Secondary blocks in the same line (never `value`):
+       With --full, secondary blocks in the same line (never `value`):
          value_moving_camera  ray-steps/s of `fresh_camera`'s timed frames: every frame a camera the
                            library has never seen (host set-up inside the loop) -- what a moving
                            camera gets; the headline's static pose is the best case;
@@ -48,7 +59,7 @@ N > 1: one process per GPU over RCCL, maps replicated.  `value` = frames of BASE
        64-frame orbit ("C5"; `--workload` overrides), frame k on GPU k mod N, K frames per GPU on one
        stream each, no data-path collective, scaling "weak" (`per_rank_ms_per_step`: every rank's own time; `ms_per_step` is
        their maximum).  The same line carries `rccl_ranks`
-       (distinct (host, device, bus) triples seen by an all_gather), `one_gpu_same_leg` (rank 0 alone
+       (distinct (host, device, bus) triples seen by an all_gather) and, with --full, `one_gpu_same_leg` (rank 0 alone
        rendering K frames of the same orbit in the same run) with the speed-up and efficiency against
        it, `static_pose_replicas` (the N = 1 line's own step on every GPU: comparable with that line's
        `value`) and `c4_strips`: ONE 7680x4320 frame over the 8192^2 map (BASELINE configs[3]) in
@@ -65,7 +76,7 @@ production kernel proves most of those loads unnecessary and skips them, so the
 line also says `"equivalent_steps": true` and carries the height samples and
 pyramid look-ups the kernel really executes; `mrays_per_s` is the algorithm-neutral rate.
 
-roofline: the kernel is bound by VALU issue, not by HBM, so
+roofline (--full): the kernel is bound by VALU issue, not by HBM, so
 `bound` = "valu-issue": achieved = VALU pipe-busy SIMD-cycles per second (PMC counts
 from profiles/traffic.json priced with tools/valu_calib.hip's cycles per instruction
 class, over the kernel duration measured live with HIP events on the launch stream),
@@ -75,7 +86,7 @@ kernel sources it was collected on equals this tree's (else frac is null).
 BASELINE.md algorithmic-bytes figure (8 B per reference step) is kept under
 `algorithmic_equivalent` -- it exceeds the HBM peak because those loads are not
 executed, and is not a roofline fraction.
-cpu_baseline = the oracle (C port of the reference loop, OpenMP) timed on a bounded
+cpu_baseline (--full) = the oracle (C port of the reference loop, OpenMP) timed on a bounded
 row sample of the same frame on this host, median of 3 repetitions.
 """
 import argparse
@@ -120,6 +131,11 @@ def parse_args(argv=None):
                          "line runs; the rates say nothing about scaling (the line carries \"share_gpu\": true)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="CPU rehearsal of the launch path: gloo instead of RCCL, a pattern instead of the renderer, no GPU touched")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the timed frames checked against the instrumented kernel, roofline, "
+                         "secondary blocks, one-GPU legs of the N > 1 line, CPU baseline (--no-* flags trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step rendered (rank 0) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -295,6 +311,23 @@ def cpu_baseline(hmrm, wl, rgb, cmap, params, cam, target_s=15.0, reps=3):
             "sample": f"every {stride}th row of the {cam.width}x{cam.height} frame ({nrows} rows, "
                       f"{steps} ray-steps, {dt:.2f} s wall x {cores} threads, median of {reps}; "
                       f"gcc -O2 -fopenmp -ffp-contract=off)"}
+
+
+DUMP_PIXELS = 1 << 21  # 2^21 pixels x 4 channels x 4 B = 32 MiB, inside the 64 MB the dump may take
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: frame (rows, cols, 4) uint8 -> out_dir/frame_sample.npy (float32, a fixed seeded sample of pixels
+    in raster order) and out_dir/frame_row_sums.npy (float64, every row's channel sums over the whole frame)."""
+    import numpy as np
+    rows, cols, ch = frame.shape
+    px = frame.reshape(rows * cols, ch)
+    n = min(rows * cols, DUMP_PIXELS)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows * cols, size=n, replace=False)) if n < rows * cols else slice(None)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_sample.npy"), px[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_row_sums.npy"), frame.sum(axis=1, dtype=np.float64))
 
 
 def workload_text(wl):
@@ -479,11 +512,11 @@ def main(argv=None):
         """n_frames launches of one pose on `in_flight` streams (1 = back to back), timed by the contract's harness.
         Ranks with active=False take part in the barriers only.  -> (seconds (max over ranks), check callable: the
         frames just timed against the instrumented kernel's -- called after any HIP-event timing that should see the
-        GPU in the same state, the read-back idles it)."""
+        GPU in the same state, the read-back idles it; last-frame callable: the host copy of what the last step rendered)."""
         if not active:
-            return timed(lambda: None, n_frames), lambda: None
+            return timed(lambda: None, n_frames), lambda: None, lambda: None
         keep, lanes = make_lanes(in_flight, the_cam.width, the_cam.height)
-        nxt, _ = round_robin(lanes)
+        nxt, state = round_robin(lanes)
 
         def step():
             st_, o_ = nxt()
@@ -497,15 +530,19 @@ def main(argv=None):
                 if not np.array_equal(o_.cpu().numpy(), ref_frame):
                     raise SystemExit("bench.py: a timed static-pose leg produced a different frame than hmrm_render_stats")
             keep.clear()
-        return dt, check
+
+        def last_frame():
+            torch.cuda.synchronize()
+            return lanes[(state["n"] - 1) % len(lanes)][1].cpu().numpy()
+        return dt, check, last_frame
 
     def orbit_leg(the_wl, the_scene, n_frames, n_warm, in_flight, solo=False):
         """Frame k of the workload's 64-frame orbit on rank k mod world, n_frames timed per rank after n_warm untimed;
         cameras pre-rendered once (cached host set-up: this leg measures the GPU path).  solo: rank 0 alone renders
         frames 0, 1, 2, .. (the one-GPU reference of the same leg); the others only stand in the barriers.
-        -> (seconds, total steps, check callable)."""
+        -> (seconds, total steps, check callable, last-frame callable)."""
         if solo and rank != 0:
-            return timed(lambda: None, n_frames), total_over_ranks(0), lambda: None
+            return timed(lambda: None, n_frames), total_over_ranks(0), lambda: None, lambda: None
         mine = strips.orbit_frames_of_rank(0 if solo else rank, 1 if solo else world, n_warm + n_frames, ORBIT_FRAMES)
         cams = {k: the_wl.camera(k, ORBIT_FRAMES) for k in sorted(set(mine))}
         steps_of = {k: int(the_scene.render_stats(c)[1].steps) for k, c in cams.items()}  # untimed, instrumented
@@ -530,8 +567,12 @@ def main(argv=None):
             for (st_, o_), k in zip(lanes, last):
                 if k is not None and not np.array_equal(o_.cpu().numpy(), the_scene.render_stats(cams[k])[0]):
                     raise SystemExit(f"bench.py: rank {rank} rendered a different orbit frame {k} than hmrm_render_stats")
+
+        def last_frame():
+            torch.cuda.synchronize()
+            return lanes[(state["n"] - 1) % len(lanes)][1].cpu().numpy()
         del keep
-        return dt, total_over_ranks(sum(steps_of[k] for k in mine[n_warm:])), check
+        return dt, total_over_ranks(sum(steps_of[k] for k in mine[n_warm:])), check, last_frame
 
     def frame_over_ranks(plan, the_rank, render_rows_fn, dist_or_none, strip, block):
         """strips.render_frame_distributed; under --share-gpu the gather runs over gloo on host copies of the strips."""
@@ -688,8 +729,8 @@ def main(argv=None):
         precondition(the_scene, c)
         # (the shorter of two repetitions: these legs are a few milliseconds long, and a single host hiccup -- one was seen: 58 ms
         # inside a 3 ms leg -- would otherwise be the number)
-        dt, check = static_leg(the_scene, c, n_frames, n_warm, 1, fb)
-        dt_b, check_b = static_leg(the_scene, c, n_frames, n_warm, 1, fb)
+        dt, check, _ = static_leg(the_scene, c, n_frames, n_warm, 1, fb)
+        dt_b, check_b, _ = static_leg(the_scene, c, n_frames, n_warm, 1, fb)
         dt = min(dt, dt_b)
         kms = the_scene.bench_kernel_ms(c, min(50, max(10, n_frames)))  # (straight behind the timed launches: same clocks)
         check()
@@ -718,28 +759,19 @@ def main(argv=None):
     extra = {}
     in_flight = max(1, min(args.frames_in_flight, 4))
     if not multi:
-        elapsed, check_headline = static_leg(scene, cam, args.steps, args.warmup, in_flight, fb_ref)
+        elapsed, check_headline, last_frame = static_leg(scene, cam, args.steps, args.warmup, in_flight, fb_ref)
         total_steps_timed = frame_steps * args.steps
         rays_timed = frame_rays * args.steps
         scaling = "weak"
         parallelism = "1 GPU, launches back to back on one stream" if in_flight == 1 else \
                       f"1 GPU, {in_flight} frames in flight on {in_flight} HIP streams"
     elif args.mode == "frames":
-        elapsed, total_steps_timed, check_orbit = orbit_leg(wl, scene, args.steps, args.warmup, in_flight)
+        elapsed, total_steps_timed, check_headline, last_frame = orbit_leg(wl, scene, args.steps, args.warmup, in_flight)
         extra["per_rank_ms_per_step"] = [round(v * 1e3 / args.steps, 5) for v in job.last_rank_seconds]
-        check_orbit()
-        check_headline = lambda: None  # noqa: E731
         rays_timed = frame_rays * args.steps * world
         scaling = "weak"
         parallelism = (f"{ORBIT_FRAMES}-frame orbit, frame k on GPU k mod {world} ({args.steps} frames per GPU), "
                        f"no collective" + (f"; {in_flight} frames in flight per GPU" if in_flight > 1 else ""))
-        # the same leg on ONE GPU, same run: rank 0 renders frames 0 .. K-1 of the orbit alone
-        dt1, steps1, check1 = orbit_leg(wl, scene, args.steps, min(args.warmup, 8), in_flight, solo=True)
-        check1()
-        extra["one_gpu_same_leg"] = {"ms_per_step": dt1 * 1e3 / args.steps, "value": steps1 / dt1, "frames": args.steps,
-                                     "note": "rank 0 alone renders frames 0 .. K-1 of the same orbit while the other ranks wait"}
-        extra["speedup_vs_one_gpu"] = (total_steps_timed / elapsed) / (steps1 / dt1)
-        extra["efficiency_vs_one_gpu"] = extra["speedup_vs_one_gpu"] / world
     else:
         plan = strips.BandPlan(height=H, width=W, band_rows=BAND_ROWS, world=world)
         strip = torch.zeros((plan.strip_rows, W, 4), dtype=torch.uint8, device="cuda")
@@ -758,14 +790,31 @@ def main(argv=None):
         rays_timed = frame_rays * args.steps
         scaling = "strong"
         parallelism = f"cyclic {BAND_ROWS}-row bands over {world} GPUs + RCCL gather to rank 0"
-        if rank == 0 and not np.array_equal(result["frame"].cpu().numpy(), fb_ref):
-            raise SystemExit("bench.py: timed path produced a different frame than hmrm_render_stats")
-        check_headline = lambda: None  # noqa: E731
 
-    # dominant kernel: mean launch duration by HIP events on the launch stream (full frame, static pose, back to back)
-    kernel_ms = scene.bench_kernel_ms(cam, 50) if rank == 0 else None
-    # correctness of what was just timed, against the instrumented kernel (another instantiation, host read-back path)
-    check_headline()
+        def last_frame():
+            return result["frame"].cpu().numpy() if rank == 0 else None
+
+        def check_headline():
+            if rank == 0 and not np.array_equal(last_frame(), fb_ref):
+                raise SystemExit("bench.py: timed path produced a different frame than hmrm_render_stats")
+
+    kernel_ms = None
+    if args.full:
+        if multi and args.mode == "frames":
+            # the same leg on ONE GPU, same run: rank 0 renders frames 0 .. K-1 of the orbit alone
+            dt1, steps1, check1, _ = orbit_leg(wl, scene, args.steps, min(args.warmup, 8), in_flight, solo=True)
+            check1()
+            extra["one_gpu_same_leg"] = {"ms_per_step": dt1 * 1e3 / args.steps, "value": steps1 / dt1, "frames": args.steps,
+                                         "note": "rank 0 alone renders frames 0 .. K-1 of the same orbit while the other ranks wait"}
+            extra["speedup_vs_one_gpu"] = (total_steps_timed / elapsed) / (steps1 / dt1)
+            extra["efficiency_vs_one_gpu"] = extra["speedup_vs_one_gpu"] / world
+        # dominant kernel: mean launch duration by HIP events on the launch stream (full frame, static pose, back to back)
+        kernel_ms = scene.bench_kernel_ms(cam, 50) if rank == 0 else None
+        # correctness of what was just timed, against the instrumented kernel (another instantiation, host read-back path)
+        check_headline()
+    # (after kernel_ms: the read-back idles the GPU; nothing above renders into the timed leg's buffers)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_frame())
 
     secondary = {}
 
@@ -777,10 +826,10 @@ def main(argv=None):
         except Exception as e:  # noqa: BLE001  (SystemExit is not an Exception)
             secondary.setdefault("secondary_errors", {})[name] = f"{type(e).__name__}: {e}"
 
-    if not args.no_secondary and not multi:
+    if args.full and not args.no_secondary and not multi:
         # ---- three frames in flight (a throughput mode for sequences of independent frames, hmap.cpp:1131-1144)
         def blk_in_flight():
-            dt3, check3 = static_leg(scene, cam, args.steps, 50 + args.warmup, 3, fb_ref)
+            dt3, check3, _ = static_leg(scene, cam, args.steps, 50 + args.warmup, 3, fb_ref)
             check3()
             secondary["frames_in_flight"] = {"streams": 3, "ms_per_step": dt3 * 1e3 / args.steps,
                                              "value": frame_steps * args.steps / dt3,
@@ -939,16 +988,16 @@ def main(argv=None):
         if not args.no_c4 and wl.name == "C3":
             guarded("workloads.C4", blk_c4)
         torch.cuda.synchronize()
-    elif not args.no_secondary and multi and args.mode == "frames":
+    elif args.full and not args.no_secondary and multi and args.mode == "frames":
         # ---- the N = 1 line's own step on every GPU (C3's static pose, one stream): comparable with that line's `value`
         w3 = synth.WORKLOADS["C3"]
         if w3.map_size == wl.map_size and wl.content == "smooth":
             c3 = w3.camera()
             fb3, st3, _, _ = scene.render_stats(c3)
             precondition(scene, c3)
-            dt_all, check_all = static_leg(scene, c3, args.steps, args.warmup, 1, fb3)
+            dt_all, check_all, _ = static_leg(scene, c3, args.steps, args.warmup, 1, fb3)
             check_all()
-            dt_one, check_one = static_leg(scene, c3, args.steps, args.warmup, 1, fb3, active=rank == 0)
+            dt_one, check_one, _ = static_leg(scene, c3, args.steps, args.warmup, 1, fb3, active=rank == 0)
             check_one()
             secondary["static_pose_replicas"] = {
                 "workload": workload_text(w3), "frames_per_gpu": args.steps, "ms_per_step": dt_all * 1e3 / args.steps,
@@ -969,67 +1018,68 @@ def main(argv=None):
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
         value = total_steps_timed / elapsed
-        kernel_s = kernel_ms * 1e-3
-        pmc, prov = _pmc_from_profiles(wl.name, hmrm.kernel_src_sha())
-        traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
-        valu = (pmc or {}).get("valu") or {}
-        cnt = (pmc or {}).get("counters_per_frame") or {}
-        # VALU pipe-busy cycles per launch, three ways (tools/pmc_summary.py): `isa` = SQ_INSTS_VALU x the calibrated
-        # pipe cost of the march loop's own instruction mix (tools/isa_cost.py on the compiler's assembly,
-        # profiles/r02_valu_calibration.txt) -- the best estimate, and `frac`; `weighted` prices only the classes the
-        # counters separate and everything else as a 2.3-cycle instruction -- a lower bound; `upper` =
-        # SQ_ACTIVE_INST_VALU x 4, i.e. rocprofv3's derived metric VALUBusy, which charges every instruction 4 cycles.
-        busy_lower = valu.get("busy_cycles_weighted")
-        busy_upper = valu.get("busy_cycles_upper")
-        busy = valu.get("busy_cycles_isa") or busy_lower
-        peak = SIMDS * PEAK_CLOCK_GHZ  # G SIMD-cycles/s
-        achieved = busy / kernel_s / 1e9 if busy else None
-        frac = achieved / peak if achieved else None
-        if frac is not None and frac > 1.0:  # a fraction above 1 would mean the pricing is wrong: do not print it
-            prov["status"] += "; the priced VALU figure exceeded the peak and was dropped"
-            achieved = frac = None
-        roofline = {
-            "bound": "valu-issue", "achieved": achieved, "peak": peak, "unit": "G SIMD-cycles/s", "frac": frac,
-            "frac_basis": ("SQ_INSTS_VALU x %.2f cycles (the loop's instruction mix at calibrated pipe costs)"
-                           % valu["cycles_per_inst_isa"]) if valu.get("busy_cycles_isa") else
-                          ("counter-separable classes priced, the rest at 2.3 cycles (lower bound)" if busy_lower else None),
-            "frac_lower_bound": (busy_lower / kernel_s / 1e9 / peak) if busy_lower else None,
-            "frac_if_every_valu_held_the_pipe_4_cycles": (busy_upper / kernel_s / 1e9 / peak) if busy_upper else None,  # = VALUBusy
-            # the same fraction with numerator AND denominator from the profile round's box (rocprofv3's mean launch duration
-            # of that run): boxes of the pool differ by +-3 %, `frac` mixes this run's kernel_ms with that box's counters
-            "frac_on_the_profiled_box": (busy / ((pmc or {}).get("kernel_us_per_frame_rocprof") * 1e-6) / 1e9 / peak)
-                                        if busy and (pmc or {}).get("kernel_us_per_frame_rocprof") else None,
-            "traffic": traffic,
-            "hbm": {"achieved": (traffic / kernel_s / 1e9) if traffic else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": (traffic / kernel_s / 1e9 / HBM_PEAK_GBS) if traffic else None},
-            "lane_util": (pmc or {}).get("lane_util"),
-            # what the busy pipe is busy with (utilisation is not useful work): shares of the VALU wave-instructions
-            # by the classes the counters separate, and the fraction with idle lanes taken out
-            "valu_mix": ({k: (cnt.get(c, 0.0) / valu["insts"]) for k, c in (("fp64_add_mul_fma", None), ("int32", "SQ_INSTS_VALU_INT32"),
-                                                                               ("int64", "SQ_INSTS_VALU_INT64"), ("conversions", "SQ_INSTS_VALU_CVT"),
-                                                                               ("fp64_rcp_sqrt", "SQ_INSTS_VALU_TRANS_F64")) if c}
-                         | {"fp64_add_mul_fma": valu.get("f64_add_mul_fma", 0.0) / valu["insts"]}) if valu.get("insts") else None,
-            "frac_lane_weighted": (frac * pmc["lane_util"]) if (frac and (pmc or {}).get("lane_util")) else None,
-            "wave_time": (pmc or {}).get("wave_time"),
-            "kernel": "k_render_fast", "kernel_ms": kernel_ms,
-            "kernel_ray_steps_per_s": frame_steps / kernel_s,
-            "operating_point": "launches of the workload's static pose back to back on one stream (the same as `value` at N = 1)",
-            # BASELINE.md's nominal figure: bytes the REFERENCE's loop would move for this frame over the
-            # measured duration.  Not executed traffic (the loads are skipped), hence not a fraction of a peak.
-            # (The kernel that does execute them: `literal_kernel.roofline`.)
-            "algorithmic_equivalent": {"bytes_per_launch": algo_bytes, "gbs": algo_bytes / kernel_s / 1e9,
-                                       "times_hbm_peak": algo_bytes / kernel_s / 1e9 / HBM_PEAK_GBS},
-            "pmc": prov,
-        }
-        if pmc and pmc.get("in_flight"):
-            # VALU-busy over the overlapped window of three frames in flight (its own PMC pass, tools/profile_round.sh)
-            secondary.setdefault("frames_in_flight", {})["pmc"] = pmc["in_flight"]
-        for name, blk in (secondary.get("workloads") or {}).items():
-            p2, prov2 = _pmc_from_profiles(name, hmrm.kernel_src_sha())
-            if p2 and (p2.get("valu") or {}).get("busy_cycles_isa"):
-                blk["valu_frac"] = p2["valu"]["busy_cycles_isa"] / (blk["kernel_ms"] * 1e-3) / 1e9 / peak
-                blk["hbm_bytes_per_launch"] = p2.get("hbm_bytes_per_launch")
-                blk["pmc_source"] = prov2.get("source")
+        if args.full:
+            kernel_s = kernel_ms * 1e-3
+            pmc, prov = _pmc_from_profiles(wl.name, hmrm.kernel_src_sha())
+            traffic = pmc.get("hbm_bytes_per_launch") if pmc else None
+            valu = (pmc or {}).get("valu") or {}
+            cnt = (pmc or {}).get("counters_per_frame") or {}
+            # VALU pipe-busy cycles per launch, three ways (tools/pmc_summary.py): `isa` = SQ_INSTS_VALU x the calibrated
+            # pipe cost of the march loop's own instruction mix (tools/isa_cost.py on the compiler's assembly,
+            # profiles/r02_valu_calibration.txt) -- the best estimate, and `frac`; `weighted` prices only the classes the
+            # counters separate and everything else as a 2.3-cycle instruction -- a lower bound; `upper` =
+            # SQ_ACTIVE_INST_VALU x 4, i.e. rocprofv3's derived metric VALUBusy, which charges every instruction 4 cycles.
+            busy_lower = valu.get("busy_cycles_weighted")
+            busy_upper = valu.get("busy_cycles_upper")
+            busy = valu.get("busy_cycles_isa") or busy_lower
+            peak = SIMDS * PEAK_CLOCK_GHZ  # G SIMD-cycles/s
+            achieved = busy / kernel_s / 1e9 if busy else None
+            frac = achieved / peak if achieved else None
+            if frac is not None and frac > 1.0:  # a fraction above 1 would mean the pricing is wrong: do not print it
+                prov["status"] += "; the priced VALU figure exceeded the peak and was dropped"
+                achieved = frac = None
+            roofline = {
+                "bound": "valu-issue", "achieved": achieved, "peak": peak, "unit": "G SIMD-cycles/s", "frac": frac,
+                "frac_basis": ("SQ_INSTS_VALU x %.2f cycles (the loop's instruction mix at calibrated pipe costs)"
+                               % valu["cycles_per_inst_isa"]) if valu.get("busy_cycles_isa") else
+                              ("counter-separable classes priced, the rest at 2.3 cycles (lower bound)" if busy_lower else None),
+                "frac_lower_bound": (busy_lower / kernel_s / 1e9 / peak) if busy_lower else None,
+                "frac_if_every_valu_held_the_pipe_4_cycles": (busy_upper / kernel_s / 1e9 / peak) if busy_upper else None,  # = VALUBusy
+                # the same fraction with numerator AND denominator from the profile round's box (rocprofv3's mean launch duration
+                # of that run): boxes of the pool differ by +-3 %, `frac` mixes this run's kernel_ms with that box's counters
+                "frac_on_the_profiled_box": (busy / ((pmc or {}).get("kernel_us_per_frame_rocprof") * 1e-6) / 1e9 / peak)
+                                            if busy and (pmc or {}).get("kernel_us_per_frame_rocprof") else None,
+                "traffic": traffic,
+                "hbm": {"achieved": (traffic / kernel_s / 1e9) if traffic else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": (traffic / kernel_s / 1e9 / HBM_PEAK_GBS) if traffic else None},
+                "lane_util": (pmc or {}).get("lane_util"),
+                # what the busy pipe is busy with (utilisation is not useful work): shares of the VALU wave-instructions
+                # by the classes the counters separate, and the fraction with idle lanes taken out
+                "valu_mix": ({k: (cnt.get(c, 0.0) / valu["insts"]) for k, c in (("fp64_add_mul_fma", None), ("int32", "SQ_INSTS_VALU_INT32"),
+                                                                                   ("int64", "SQ_INSTS_VALU_INT64"), ("conversions", "SQ_INSTS_VALU_CVT"),
+                                                                                   ("fp64_rcp_sqrt", "SQ_INSTS_VALU_TRANS_F64")) if c}
+                             | {"fp64_add_mul_fma": valu.get("f64_add_mul_fma", 0.0) / valu["insts"]}) if valu.get("insts") else None,
+                "frac_lane_weighted": (frac * pmc["lane_util"]) if (frac and (pmc or {}).get("lane_util")) else None,
+                "wave_time": (pmc or {}).get("wave_time"),
+                "kernel": "k_render_fast", "kernel_ms": kernel_ms,
+                "kernel_ray_steps_per_s": frame_steps / kernel_s,
+                "operating_point": "launches of the workload's static pose back to back on one stream (the same as `value` at N = 1)",
+                # BASELINE.md's nominal figure: bytes the REFERENCE's loop would move for this frame over the
+                # measured duration.  Not executed traffic (the loads are skipped), hence not a fraction of a peak.
+                # (The kernel that does execute them: `literal_kernel.roofline`.)
+                "algorithmic_equivalent": {"bytes_per_launch": algo_bytes, "gbs": algo_bytes / kernel_s / 1e9,
+                                           "times_hbm_peak": algo_bytes / kernel_s / 1e9 / HBM_PEAK_GBS},
+                "pmc": prov,
+            }
+            if pmc and pmc.get("in_flight"):
+                # VALU-busy over the overlapped window of three frames in flight (its own PMC pass, tools/profile_round.sh)
+                secondary.setdefault("frames_in_flight", {})["pmc"] = pmc["in_flight"]
+            for name, blk in (secondary.get("workloads") or {}).items():
+                p2, prov2 = _pmc_from_profiles(name, hmrm.kernel_src_sha())
+                if p2 and (p2.get("valu") or {}).get("busy_cycles_isa"):
+                    blk["valu_frac"] = p2["valu"]["busy_cycles_isa"] / (blk["kernel_ms"] * 1e-3) / 1e9 / peak
+                    blk["hbm_bytes_per_launch"] = p2.get("hbm_bytes_per_launch")
+                    blk["pmc_source"] = prov2.get("source")
         line = {
             "metric": "ray-steps/s at 3840x2160, 4096^2 heightmap" if wl.map_size == 4096 else
                       f"ray-steps/s at {W}x{H}, {wl.map_size}^2 heightmap",
@@ -1046,8 +1096,9 @@ def main(argv=None):
                        "ray_steps_per_frame": frame_steps, "rays_per_frame": frame_rays,
                        "hits_per_frame": frame_hits, "parallelism": parallelism,
                        "maps_sha256": synth.maps_sha256(rgb, cmap)[:16]},
-            "roofline": roofline,
         }
+        if args.full:
+            line["roofline"] = roofline
         line.update(extra)
         if job.share_gpu:
             line["share_gpu"] = True  # (a rehearsal: ranks share GPUs, collectives over gloo on host copies; not a scaling figure)
@@ -1070,7 +1121,7 @@ def main(argv=None):
                 "worst_content": ({"what": "the headline camera over `" + worst[0] + "` (rough_terrain)", "kernel_ms": worst[1]["kernel_ms"],
                                    "kernel": worst[1]["kernel_chosen_by_probe"]} if worst else None),
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(hmrm, wl, rgb, cmap, params, cam, args.cpu_seconds)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())

@@ -3,7 +3,8 @@
 These rows ARE pinned against the reference: tests/golden/png_decode.npz and
 png_encode.json hold what the reference's own vendored stb (v2.27 / v1.16,
 built from /root/reference/vendor as oracle/_ref) produces, and where that
-build is present the comparison is also made live.
+build is present the comparison is also made live; where it is not, the "live"
+tests compare against what it returned for the same inputs (tests/stb_ref.py).
 """
 import hashlib
 import json
@@ -44,18 +45,17 @@ def test_decode_matches_reference_stb_golden(hmrm):
 
 
 def test_decode_matches_reference_stb_live(hmrm, stb_ref):
-    if stb_ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here); golden vectors cover it")
     import make_golden
     for name, blob in make_golden.png_fixture_files().items():
         for req in range(5):
-            exp, n = stb_ref.load(blob, req)
             if name == "p6_16" and req not in (0, 3):
+                # (refused here; stb's own result for these reads uninitialised memory and differs from run to run)
                 with pytest.raises(hmrm.HmrmError):
                     hmrm.image_load_memory(blob, req)
                 continue
+            exp, n = stb_ref.load(blob, req)
             arr, n2 = hmrm.image_load_memory(blob, req)
-            assert n2 == n and np.array_equal(arr, exp), (name, req)
+            assert n2 == n and stb_ref.same(arr, exp), (name, req)
 
 
 def test_jpeg_decode_matches_reference_stb_golden(hmrm):
@@ -74,8 +74,6 @@ def test_jpeg_decode_matches_reference_stb_golden(hmrm):
 
 
 def test_jpeg_decode_matches_reference_stb_live(hmrm, stb_ref):
-    if stb_ref is None:
-        pytest.skip("oracle/_ref not built; golden vectors cover it")
     pytest.importorskip("PIL")
     import make_golden
     files = make_golden.jpeg_fixture_files()
@@ -83,7 +81,7 @@ def test_jpeg_decode_matches_reference_stb_live(hmrm, stb_ref):
         for req in range(5):
             exp, n = stb_ref.load(blob, req)
             arr, n2 = hmrm.image_load_memory(blob, req)
-            assert n2 == n and np.array_equal(arr, exp), (name, req)
+            assert n2 == n and stb_ref.same(arr, exp), (name, req)
     # a truncated file is refused by both
     blob = files["rgb_420_q50"]
     assert stb_ref.load(blob[: len(blob) // 2], 3)[0] is None
@@ -94,8 +92,6 @@ def test_jpeg_decode_matches_reference_stb_live(hmrm, stb_ref):
 def test_jpeg_random_files_match_reference_stb_live(hmrm, stb_ref):
     """120 random JPEGs (sizes 1..80, all PIL subsamplings, baseline / progressive / optimised tables,
     grey / YCbCr / CMYK, restart intervals) against the reference's stb build, every req_comp."""
-    if stb_ref is None:
-        pytest.skip("oracle/_ref not built; golden vectors cover the fixed set")
     Image = pytest.importorskip("PIL.Image")
     import io
     rng = np.random.RandomState(4242)
@@ -126,7 +122,7 @@ def test_jpeg_random_files_match_reference_stb_live(hmrm, stb_ref):
             exp, n = stb_ref.load(blob, req)
             assert exp is not None, (trial, kw)
             arr, n2 = hmrm.image_load_memory(blob, req)
-            assert n2 == n and np.array_equal(arr, exp), (trial, mode, w, h, kw, req)
+            assert n2 == n and stb_ref.same(arr, exp), (trial, mode, w, h, kw, req)
             checked += 1
     assert checked == 600
 
@@ -144,7 +140,7 @@ def test_bmp_tga_decode_matches_reference_stb(hmrm, stb_ref):
             assert arr.shape == data[f"{name}/req{req}"].shape and np.array_equal(arr, data[f"{name}/req{req}"]), (name, req)
             if stb_ref is not None:
                 exp, n2 = stb_ref.load(blob, req)
-                assert n2 == n and np.array_equal(arr, exp), (name, req)
+                assert n2 == n and stb_ref.same(arr, exp), (name, req)
             checked += 1
     assert checked >= 110
     # refused like stb refuses them: RLE-compressed BMP, truncated header
@@ -181,7 +177,7 @@ def test_gif_psd_pic_hdr_decode_matches_reference_stb(hmrm, stb_ref):
             assert n == want_n and arr.shape == exp.shape and np.array_equal(arr, exp), (name, req)
             if stb_ref is not None:
                 live, n2 = stb_ref.load(blob, req)
-                assert n2 == n and np.array_equal(arr, live), (name, req)
+                assert n2 == n and stb_ref.same(arr, live), (name, req)
             checked += 1
     assert checked >= 250 and refused >= 5
     # files on which the reference's loader crashes or never returns: refused here, promptly
@@ -238,7 +234,7 @@ def test_hdr_dimensions_narrow_like_the_reference_loader(hmrm, stb_ref):
                 exp, _ = stb_ref.load(blob, req)
                 assert (exp is None) == (got is None), (h_txt, w_txt, req)
                 if exp is not None:
-                    assert np.array_equal(exp, got)
+                    assert stb_ref.same(got, exp)
 
 
 def test_decode_large_random_png_roundtrip(hmrm, stb_ref):
@@ -260,7 +256,7 @@ def test_decode_large_random_png_roundtrip(hmrm, stb_ref):
     assert np.array_equal(arr4[:, :, :3], img) and (arr4[:, :, 3] == 255).all()
     if stb_ref is not None:
         exp, _ = stb_ref.load(png, 4)
-        assert np.array_equal(arr4, exp)
+        assert stb_ref.same(arr4, exp)
 
 
 def test_decode_errors(hmrm, tmp_path):
@@ -293,8 +289,6 @@ def test_png_encode_matches_reference_stb_golden(hmrm):
 
 
 def test_png_encode_matches_reference_stb_live(hmrm, stb_ref):
-    if stb_ref is None:
-        pytest.skip("oracle/_ref not built; golden hashes cover it")
     rng = np.random.RandomState(3)
     for (h, w, c) in ((1, 1, 1), (2, 3, 3), (31, 17, 4), (64, 64, 4), (5, 300, 2), (200, 150, 3)):
         for kind in ("noise", "smooth", "flat"):

@@ -1242,7 +1242,7 @@ def test_bench_two_ranks_sharing_this_gpu(gpu):
     env2 = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "HMRM_FORCE_DIST")}
     env2["OMP_NUM_THREADS"] = "2"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--workload", "C2", "--steps", "6",
-                        "--warmup", "2", "--no-c4", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env2)
+                        "--warmup", "2", "--full", "--no-c4", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env2)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1254,7 +1254,7 @@ def test_bench_two_ranks_sharing_this_gpu(gpu):
     assert "C2" in line["config"]["workload"] and "frame k on GPU k mod 2" in line["config"]["parallelism"]
     # the strips mode: one frame in cyclic bands over the two ranks, gathered to rank 0 and checked there
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--workload", "C2", "--mode", "strips",
-                        "--steps", "4", "--warmup", "1", "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env2)
+                        "--steps", "4", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env2)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert line["scaling"] == "strong" and "cyclic 16-row bands over 2 GPUs" in line["config"]["parallelism"]
@@ -1272,7 +1272,7 @@ def test_strips_over_rccl_two_gpus(gpu):
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                             "--master-addr", "127.0.0.1", "--master-port", "29631", os.path.join(root, "bench.py"),
                             "--gpus", "2", "--steps", "4", "--warmup", "2", "--workload", "C2", "--mode", mode,
-                            "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=root)
+                            "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=root)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert line["n_gpus"] == 2 and line["value"] > 0

@@ -7,7 +7,7 @@ trap 'cp $P/_variants/libhmrm_A.so $P/libhmrm.so' EXIT
 for r in $(seq 1 ${2:-2}); do
   for v in ${1:-A K}; do
     cp $P/_variants/libhmrm_$v.so $P/libhmrm.so
-    timeout -k 5 40 python bench.py --no-secondary --no-cpu-baseline 2>/dev/null | python -c "
+    timeout -k 5 40 python bench.py --full --no-secondary --no-cpu-baseline 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('variant $v round $r: ms_per_step %.5f kernel_ms %.5f' % (d['ms_per_step'], d['roofline']['kernel_ms']))"

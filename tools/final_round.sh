@@ -8,4 +8,4 @@ echo "pytest -m gpu: $((t1 - t0)) s wall, exit status $rc" | tee "$out/gpu_suite
 tail -5 "$out/gpu_suite.txt"
 [ $rc -eq 0 ] || exit 1
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 && \
-python bench.py > "$out/bench.json" 2> "$out/bench.err"; echo "bench rc $?"; tail -c 600 "$out/bench.json"
+python bench.py --full > "$out/bench.json" 2> "$out/bench.err"; echo "bench rc $?"; tail -c 600 "$out/bench.json"

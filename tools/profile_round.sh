@@ -11,7 +11,7 @@ WL=${WL:-C3}
 out=gpurun_out/prof_$tag
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf "$out"; mkdir -p "$out"
-timeout -k 10 300 python bench.py --workload $WL > "$out/bench.log" 2>&1
+timeout -k 10 300 python bench.py --full --workload $WL > "$out/bench.log" 2>&1
 # (the headline loop only -- one stream, launches back to back: the trace then holds the durations of single launches,
 # which is what roofline.kernel_ms of the bench line is; the secondary blocks overlap launches or render other cameras)
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python bench.py --workload $WL --no-cpu-baseline --no-secondary > "$out/bench_under_rocprof.log" 2>&1
