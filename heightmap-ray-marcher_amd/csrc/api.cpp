@@ -337,6 +337,31 @@ int check_camera(const hmrm_camera *cam) {
 	return HMRM_OK;
 }
 
+// Antialiasing (hmrm_render_aa, HMRM_AA): factor n in {1, 2, 4, 8} -> *shift = log2 n and *super = the camera of the
+// n x n larger "super frame" the kernel marches (everything else unchanged), which must itself pass check_camera.  Needs
+// no scene and no device: the rejections are testable without a GPU.
+int check_antialias(const hmrm_camera *cam, int32_t factor, hmrm_camera *super, int *shift) {
+	const int sh = factor == 1 ? 0 : factor == 2 ? 1 : factor == 4 ? 2 : factor == 8 ? 3 : -1;
+	if (sh < 0) return fail(HMRM_E_ARG, "antialias factor must be 1, 2, 4 or 8 (got " + std::to_string(factor) + ")");
+	if ((int64_t)cam->width * cam->height * ((int64_t)1 << (2 * sh)) > ((int64_t)1 << 31) / 4)
+		return fail(HMRM_E_ARG, "antialias: the " + std::to_string(factor) + "x super frame has more than 2^29 samples (the reference "
+		                        "indexes the framebuffer with int)");
+	*super = *cam;
+	super->width = cam->width << sh;
+	super->height = cam->height << sh;
+	*shift = sh;
+	return HMRM_OK;
+}
+
+// The antialias factor of a ticketed call's flags (HMRM_AA), refusing bits the ABI does not define.
+int antialias_of_flags(uint32_t flags, int32_t *factor) {
+	if (flags & ~(HMRM_NO_PROBE | HMRM_AA_MASK))
+		return fail(HMRM_E_ARG, "flags: unknown bits (defined: HMRM_NO_PROBE and the antialias factor HMRM_AA(n))");
+	const int32_t n = (int32_t)((flags & HMRM_AA_MASK) >> 8);
+	*factor = n == 0 ? 1 : n;
+	return HMRM_OK;
+}
+
 int ensure_bilinear_pyramid(hmrm_scene *s);
 int ensure_records(hmrm_scene *s);
 
@@ -1031,39 +1056,46 @@ int hmrm_scene_read_heights(const hmrm_scene *cs, double *out) {
 	return HMRM_OK;
 }
 
+// aa_factor > 1 (hmrm_render_aa): the launch marches the super frame and writes the W x H box-filtered frame (no per-pixel
+// arrays then).
 static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes,
-                         hmrm_stats *stats, uint32_t *steps_pp, double *entry_d, bool want_stats) {
+                         hmrm_stats *stats, uint32_t *steps_pp, double *entry_d, bool want_stats, int32_t aa_factor = 1) {
 	int rc = check_camera(cam);
 	if (rc) return rc;
+	hmrm_camera super;
+	int aa_shift = 0;
+	if ((rc = check_antialias(cam, aa_factor, &super, &aa_shift))) return rc;
 	if (!s || !rgba) return fail(HMRM_E_ARG, "NULL argument");
 	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
 	if (stride_bytes < W * 4) return fail(HMRM_E_ARG, "stride_bytes < width*4");
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
 	if ((rc = ensure_frame(s, W * H))) return rc;
-	if (want_stats && (rc = ensure_stats(s, W * H))) return rc;
+	if (want_stats && aa_shift == 0 && (rc = ensure_stats(s, W * H))) return rc;
 	StreamCtx *c = nullptr;
 	if ((rc = ctx_for(s, s->stream, &c))) return rc;
 	hmrm::DevFrame f;
 	FrameSlot *slot = nullptr;
-	if ((rc = prepare_frame(s, c, cam, &f, &slot))) return rc;
-	hmrm::RowMap rows{0, cam->height, 0, 0, 1, {}, {}, nullptr};
+	if ((rc = prepare_frame(s, c, &super, &f, &slot))) return rc;
+	f.aa_shift = aa_shift;
+	hmrm::RowMap rows{0, super.height, 0, 0, 1, {}, {}, nullptr};
 	if (want_stats) {
 		HIP_TRY(hipMemsetAsync(c->d_counters, 0, 2 * sizeof(unsigned long long), s->stream));
 		HIP_TRY(hipMemsetAsync(c->d_counters + 4, 0, 4 * sizeof(unsigned long long), s->stream));
 	}
 	HIP_TRY(hipEventRecord(s->ev0, s->stream));
-	if ((rc = launch_frame(s, c, f, slot, rows, s->d_frame, (int64_t)W, want_stats ? s->d_steps : nullptr,
-	                       want_stats ? s->d_entry : nullptr, want_stats)))
+	const bool per_pixel = want_stats && aa_shift == 0; // (per-pixel arrays are of the plain frame only)
+	if ((rc = launch_frame(s, c, f, slot, rows, s->d_frame, (int64_t)W, per_pixel ? s->d_steps : nullptr,
+	                       per_pixel ? s->d_entry : nullptr, want_stats)))
 		return rc;
 	HIP_TRY(hipEventRecord(s->ev1, s->stream));
 	HIP_TRY(hipMemcpy2DAsync(rgba, stride_bytes, s->d_frame, W * 4, W * 4, H, hipMemcpyDeviceToHost,
 	                         s->stream));
 	unsigned long long counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	HIP_TRY(hipMemcpyAsync(counters, c->d_counters, sizeof counters, hipMemcpyDeviceToHost, s->stream));
-	if (want_stats && steps_pp)
+	if (per_pixel && steps_pp)
 		HIP_TRY(hipMemcpyAsync(steps_pp, s->d_steps, W * H * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-	if (want_stats && entry_d)
+	if (per_pixel && entry_d)
 		HIP_TRY(hipMemcpyAsync(entry_d, s->d_entry, W * H * sizeof(double), hipMemcpyDeviceToHost, s->stream));
 	HIP_TRY(hipStreamSynchronize(s->stream));
 	float ms = 0.f;
@@ -1072,7 +1104,7 @@ static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, s
 	const unsigned long long capped = counters[2] - c->capped_seen;
 	c->capped_seen = counters[2];
 	if (stats) {
-		stats->rays = (uint64_t)W * H;
+		stats->rays = (uint64_t)super.width * (uint64_t)super.height;
 		stats->steps = counters[0];
 		stats->hits = counters[1];
 		stats->capped = capped;
@@ -1110,6 +1142,12 @@ int hmrm_render_cycle(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *
 		memcpy(rgba + y * stride_bytes + x * 4, &full[p * 4], 4);
 	}
 	return rc;
+}
+
+int hmrm_render_aa(const hmrm_scene *scene, const hmrm_camera *cam, int32_t factor, uint8_t *rgba, size_t stride_bytes,
+                   hmrm_stats *stats) {
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, stats, nullptr, nullptr, stats != nullptr,
+	                     factor);
 }
 
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
@@ -1303,6 +1341,10 @@ int hmrm_render_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, uin
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	int rc = check_camera(cam);
 	if (rc) return rc;
+	int32_t aa_factor = 1;
+	hmrm_camera super;
+	int aa_shift = 0;
+	if ((rc = antialias_of_flags(flags, &aa_factor)) || (rc = check_antialias(cam, aa_factor, &super, &aa_shift))) return rc;
 	if (!s || !ticket) return fail(HMRM_E_ARG, "NULL argument");
 	*ticket = -1;
 	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
@@ -1348,8 +1390,9 @@ int hmrm_render_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, uin
 	if ((rc = next_lane(s, &c))) return rc;
 	hmrm::DevFrame f;
 	FrameSlot *slot = nullptr;
-	if ((rc = prepare_frame(s, c, cam, &f, &slot))) return rc;
-	hmrm::RowMap rows{0, cam->height, 0, 0, 1, {}, {}, nullptr};
+	if ((rc = prepare_frame(s, c, &super, &f, &slot))) return rc;
+	f.aa_shift = aa_shift;
+	hmrm::RowMap rows{0, super.height, 0, 0, 1, {}, {}, nullptr};
 	if ((rc = launch_frame(s, c, f, slot, rows, r->d_frame, (int64_t)W, nullptr, nullptr, false, (flags & HMRM_NO_PROBE) != 0))) return rc;
 	r->ctx = c;
 	HIP_TRY(hipEventRecord(r->kernel_done, c->stream));
@@ -1413,6 +1456,10 @@ int hmrm_render_device_begin_flags(const hmrm_scene *scene, const hmrm_camera *c
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	int rc = check_camera(cam);
 	if (rc) return rc;
+	int32_t aa_factor = 1;
+	hmrm_camera super;
+	int aa_shift = 0;
+	if ((rc = antialias_of_flags(flags, &aa_factor)) || (rc = check_antialias(cam, aa_factor, &super, &aa_shift))) return rc;
 	if (!s || !d_rgba || !ticket) return fail(HMRM_E_ARG, "NULL argument");
 	*ticket = -1;
 	if (stride_bytes < (size_t)cam->width * 4 || (stride_bytes & 3) || stride_bytes / 4 > 0x7fffffffu)
@@ -1444,8 +1491,9 @@ int hmrm_render_device_begin_flags(const hmrm_scene *scene, const hmrm_camera *c
 	if ((rc = next_lane(s, &c))) return rc;
 	hmrm::DevFrame f;
 	FrameSlot *slot = nullptr;
-	if ((rc = prepare_frame(s, c, cam, &f, &slot))) return rc;
-	hmrm::RowMap rows{0, cam->height, 0, 0, 1, {}, {}, nullptr};
+	if ((rc = prepare_frame(s, c, &super, &f, &slot))) return rc;
+	f.aa_shift = aa_shift;
+	hmrm::RowMap rows{0, super.height, 0, 0, 1, {}, {}, nullptr};
 	if ((rc = launch_frame(s, c, f, slot, rows, (uint32_t *)d_rgba, (int64_t)(stride_bytes / 4), nullptr, nullptr, false, (flags & HMRM_NO_PROBE) != 0))) return rc;
 	HIP_TRY(hipMemcpyAsync(t->h_capped, c->d_counters + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipEventRecord(t->done, c->stream));
@@ -1587,6 +1635,7 @@ const char *hmrm_config_colormap_path(const hmrm_config *c) { return c->cfg.colo
 const char *hmrm_config_output_path(const hmrm_config *c) { return c->cfg.output_path.c_str(); }
 int32_t hmrm_config_record_mode(const hmrm_config *c) { return c->cfg.record_mode; }
 int32_t hmrm_config_devices(const hmrm_config *c) { return c->cfg.devices; }
+int32_t hmrm_config_antialias(const hmrm_config *c) { return c->cfg.antialias; }
 
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *c, int32_t *w, int32_t *h) {
 	if (!c->cfg.have_heightmap) return nullptr;

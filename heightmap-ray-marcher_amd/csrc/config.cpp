@@ -12,7 +12,7 @@
 // keys at run time, :851-868, and only ever writes PNG):
 //   projection perspective|spherical|orthographic   (or 1|2|3)
 //   output <path>                                   (.png or .ppm)
-//   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32
+//   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8
 #include "config.hpp"
 
 #include <cmath>
@@ -181,6 +181,13 @@ void record_mode_key(Config &c, std::istream &in, const char *key, std::string *
 	c.log << key << " " << (c.record_mode == 1 ? "orbit" : "off") << "\n";
 }
 
+void antialias_key(Config &c, std::istream &in, const char *key, std::string *) { // n x n box-filtered samples per pixel
+	static const Word words[] = {{"1", 1}, {"2", 2}, {"4", 4}, {"8", 8}};
+	std::string seen;
+	if (!pick(in, words, &c.antialias, &seen)) c.warn << "WARNING: Unknown antialias: " << seen << "\n";
+	c.log << key << " " << c.antialias << "\n";
+}
+
 struct Row { const char *key; Handler apply; };
 const Row kGrammar[] = {
 	// the reference's 27 keys (main/hmap.cpp:314-488)
@@ -218,6 +225,7 @@ const Row kGrammar[] = {
 	{"heights", heights_type},
 	{"devices", device_count_key},
 	{"record", record_mode_key},
+	{"antialias", antialias_key},
 };
 
 } // namespace

@@ -38,6 +38,8 @@ struct Config {
 	int devices = 1;
 	// additive: `sampling nearest|bilinear` (nearest = the reference's truncating lookup), `heights f32` (= 2)
 	int sampling = 0;
+	// additive: `antialias n` -- hmrm_render_aa's factor (1 = off, 2, 4, 8)
+	int antialias = 1;
 
 	bool heightmap_dirty = false; // should_update_heightmap, sticky until taken
 	std::ostringstream log;       // what the reference prints to stdout

@@ -297,4 +297,37 @@ __device__ __forceinline__ void publish_counters(const StatsOut &st, unsigned lo
 	}
 }
 
+// Epilogue of the antialiased instantiations (hmrm_render_aa, hmrm.h HMRM_AA): the launch marches the super frame of
+// n x n samples per output pixel, n = 1 << shift <= 8, and each n x n block of samples -- always inside one wave's 8 x 8
+// pixels, lane = kWaveW * row + column, blocks aligned to n -- is box-filtered across the wave's lanes.  R | B << 16 and
+// G are summed in 16-bit fields (64 x 255 fits) by xor shuffles over the lane bits of x, then of y (the masks are
+// constants, the shift is uniform); the sums are rounded half up; the block's first lane writes the pixel to
+// out[(lrow >> shift) * stride + (px >> shift)].  Every lane of the wave calls this: a block is wholly live or wholly
+// dead (api.cpp makes the super frame's sides multiples of n), the shuffles of a dead block carry values nobody writes.
+__device__ __forceinline__ void store_box_filtered(uint32_t *__restrict__ out, int64_t out_stride_px, int shift, int lane,
+                                                   int px, int lrow, bool live, uint32_t rgba) {
+	static_assert(kWaveW == 8 && kWaveH == 8, "an n x n block (n <= 8) must lie inside one wave's pixels");
+	uint32_t rb = rgba & 0x00ff00ffu, g = (rgba >> 8) & 0xffu;
+#pragma unroll
+	for (int k = 0; k < 3; ++k) { // lane bits of x
+		if (shift > k) {
+			rb += (uint32_t)__shfl_xor((int)rb, 1 << k);
+			g += (uint32_t)__shfl_xor((int)g, 1 << k);
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 3; ++k) { // lane bits of y
+		if (shift > k) {
+			rb += (uint32_t)__shfl_xor((int)rb, kWaveW << k);
+			g += (uint32_t)__shfl_xor((int)g, kWaveW << k);
+		}
+	}
+	const int s2 = 2 * shift;
+	const uint32_t half = (1u << s2) >> 1;
+	const uint32_t r = ((rb & 0xffffu) + half) >> s2, b = ((rb >> 16) + half) >> s2, gg = (g + half) >> s2;
+	const int corner = ((1 << shift) - 1) * (kWaveW + 1); // lane bits that must be zero in a block's first lane
+	if (live && (lane & corner) == 0)
+		out[(uint64_t)(uint32_t)(lrow >> shift) * (uint64_t)out_stride_px + (uint32_t)(px >> shift)] = pack_rgba(r, gg, b);
+}
+
 } // namespace hmrm

@@ -65,7 +65,9 @@ struct DevFrame {
 	int32_t min_level;           // finest pyramid level worth an attempt (api.cpp, from min_window)
 	int32_t min_window;          // ... as a window size in cells (camera.cpp)
 	int32_t finest_pause;        // extra groups marched after a refused attempt at that level (camera.cpp)
-	int32_t pad4_;
+	int32_t aa_shift;            // antialiasing (hmrm_render_aa): log2 n of the n x n samples box-filtered into one output
+	                             // pixel, 0 = off.  Set per launch by api.cpp, not part of the cached record; the kernels read
+	                             // it only in their antialiased instantiations (device_common.hpp store_box_filtered).
 };
 
 // Window sizes S = 4 * 2^(kLevelStep*l) cells, placed every S/2 cells.  kLevelStep 1 (the build): S = 4, 8, 16, 32,

@@ -6,7 +6,8 @@
 // Instead of opening an SDL window (hmap.cpp:546-649, out of scope) it renders
 // ONE full frame (`cycle 1` semantics) on the GPU and saves it the way F12 does
 // (hmap.cpp:828-850 -> SavePNG :157-168): to the config's `output` path if
-// given (.ppm selects binary PPM), else screenshots/hmap_<epoch>.png.
+// given (.ppm selects binary PPM), else screenshots/hmap_<epoch>.png.  `antialias n` renders (and records)
+// n x n box-filtered samples per pixel (hmrm_render_aa).
 #include <sys/stat.h>
 
 #include <cmath>
@@ -59,6 +60,7 @@ int main(int argc, char *argv[]) {
 		std::cerr << "resolution must be positive and at most 2^29 pixels (the reference indexes the framebuffer with int)\n";
 		return 1;
 	}
+	const int32_t aa = hmrm_config_antialias(cfg);
 	hmrm_scene *scene = NULL;
 	if (hmrm_config_create_scene(cfg, &scene) != HMRM_OK) {
 		std::cerr << hmrm_last_error() << "\n";
@@ -97,8 +99,9 @@ int main(int argc, char *argv[]) {
 			if (rc == HMRM_OK) scenes.push_back(extra);
 		}
 		if (rc == HMRM_OK)
-			rc = hmrm_record_orbit_multi(scenes.data(), (int32_t)scenes.size(), &cam, cx, cy, radius, hang0,
-			                             hmrm_config_recording_frame_count(cfg), dir.c_str(), (long long)id, 0, 1);
+			rc = hmrm_record_orbit_flags(scenes.data(), (int32_t)scenes.size(), &cam, cx, cy, radius, hang0,
+			                             hmrm_config_recording_frame_count(cfg), dir.c_str(), (long long)id, 0, 1,
+			                             aa > 1 ? HMRM_AA(aa) : 0u);
 		if (rc != HMRM_OK) std::cerr << hmrm_last_error() << "\n";
 		for (size_t i = 1; i < scenes.size(); ++i) hmrm_scene_destroy(scenes[i]);
 		hmrm_scene_destroy(scene);
@@ -109,7 +112,9 @@ int main(int argc, char *argv[]) {
 	std::vector<uint8_t> framebuf((size_t)cam.width * cam.height * 4);
 	int visible_dev = 1;
 	const int want_dev = wanted_devices(cfg, &visible_dev);
-	if (want_dev > 1) {
+	if (want_dev > 1 && aa > 1)
+		std::cerr << "WARNING: antialias " << aa << " renders the single frame on one device (devices " << want_dev << " ignored)\n";
+	if (want_dev > 1 && aa == 1) {
 		// `devices n`: the frame's 16-row bands are dealt out over n GPUs (BASELINE config C4)
 		std::vector<hmrm_scene *> scenes(1, scene);
 		for (int d = 1; d < want_dev && rc == HMRM_OK; ++d) {
@@ -128,7 +133,7 @@ int main(int argc, char *argv[]) {
 		std::cout << "rendered " << (long long)cam.width * cam.height << " rays on " << want_dev << " devices\n";
 	} else {
 		hmrm_stats stats;
-		rc = hmrm_render_stats(scene, &cam, framebuf.data(), (size_t)cam.width * 4, &stats, NULL, NULL);
+		rc = hmrm_render_aa(scene, &cam, aa, framebuf.data(), (size_t)cam.width * 4, &stats);
 		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
 			std::cerr << hmrm_last_error() << "\n";
 			return 1;

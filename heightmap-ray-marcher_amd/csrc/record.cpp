@@ -54,9 +54,11 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices) {
 	return n_devices > 0 && frame >= 0 ? frame % n_devices : -1;
 }
 
-int hmrm_record_orbit_multi(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
+// `flags` go to every ticketed render (hmrm_render_begin_flags): HMRM_AA(n) records antialiased frames -- still W x H
+// in the ring and in the files.
+int hmrm_record_orbit_flags(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
                             double centre_y, double radius, double hang0, int32_t frames, const char *dir,
-                            long long id, int32_t encoder_threads, int32_t verbose) {
+                            long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags) {
 	if (!scenes || n_scenes <= 0 || !base || !dir || frames <= 0)
 		return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit: bad argument");
 	for (int i = 0; i < n_scenes; ++i)
@@ -174,7 +176,7 @@ int hmrm_record_orbit_multi(hmrm_scene *const *scenes, int32_t n_scenes, const h
 					hmrm_camera cam;
 					hmrm_orbit_camera(base, centre_x, centre_y, radius, hang0, next, frames, &cam);
 					int32_t ticket = -1;
-					const int rc = hmrm_render_begin(scenes[i], &cam, &ticket);
+					const int rc = hmrm_render_begin_flags(scenes[i], &cam, flags, &ticket);
 					if (rc != HMRM_OK) {
 						note_error(rc);
 						break;
@@ -216,12 +218,19 @@ int hmrm_record_orbit_multi(hmrm_scene *const *scenes, int32_t n_scenes, const h
 	return HMRM_OK;
 }
 
+int hmrm_record_orbit_multi(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
+                            double centre_y, double radius, double hang0, int32_t frames, const char *dir,
+                            long long id, int32_t encoder_threads, int32_t verbose) {
+	return hmrm_record_orbit_flags(scenes, n_scenes, base, centre_x, centre_y, radius, hang0, frames, dir, id, encoder_threads,
+	                               verbose, 0u);
+}
+
 int hmrm_record_orbit(const hmrm_scene *scene, const hmrm_camera *base, double centre_x, double centre_y,
                       double radius, double hang0, int32_t frames, const char *dir, long long id,
                       int32_t encoder_threads, int32_t verbose) {
 	hmrm_scene *one = const_cast<hmrm_scene *>(scene);
-	return hmrm_record_orbit_multi(&one, 1, base, centre_x, centre_y, radius, hang0, frames, dir, id, encoder_threads,
-	                               verbose);
+	return hmrm_record_orbit_flags(&one, 1, base, centre_x, centre_y, radius, hang0, frames, dir, id, encoder_threads,
+	                               verbose, 0u);
 }
 
 } // extern "C"

@@ -75,7 +75,8 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 	}
 }
 
-template <int PROJ, bool STATS>
+// AA: the antialiased epilogue (device_common.hpp store_box_filtered, f.aa_shift); the plain instantiations store per lane.
+template <int PROJ, bool STATS, bool AA>
 __global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, const RowMap rows,
                                                 const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap,
@@ -90,6 +91,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, cons
 
 	unsigned long long my_steps = 0;
 	uint32_t my_hit = 0, my_cap = 0;
+	uint32_t aa_rgba = 0; // (AA: this lane's sample, filtered by the whole wave below)
 
 	if (live) {
 		const DevRay ray = make_ray<PROJ>(f, px, py);
@@ -160,11 +162,13 @@ __global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, cons
 		} else {
 			my_hit = 1;
 		}
-		out[(int64_t)lrow * out_stride_px + px] = rgba;
+		if constexpr (AA) aa_rgba = rgba;
+		else out[(int64_t)lrow * out_stride_px + px] = rgba;
 		if (STATS && st.steps_per_pixel)
 			st.steps_per_pixel[(int64_t)py * f.screen_w + px] =
 			    my_steps > 0xffffffffull ? 0xffffffffu : (uint32_t)my_steps;
 	}
+	if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, (int)(threadIdx.x & 63), px, lrow, live, aa_rgba);
 
 	publish_counters<STATS>(st, my_steps, my_hit, my_cap);
 }
@@ -290,7 +294,7 @@ double max_key_to_double(unsigned long long key) {
 	return v;
 }
 
-template <bool STATS>
+template <bool STATS, bool AA>
 static hipError_t launch_render_t(const DevFrame &f, const RowMap &rows, const double *d_thr,
                                   const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
                                   StatsOut st, hipStream_t stream) {
@@ -300,15 +304,15 @@ static hipError_t launch_render_t(const DevFrame &f, const RowMap &rows, const d
 	const dim3 grid((unsigned)tiles_x, (unsigned)(tiles_y < 32768 ? tiles_y : 32768), (unsigned)((tiles_y + 32767) / 32768)), block(kBlockThreads);
 	switch (f.projection) {
 	case 1:
-		hipLaunchKernelGGL((k_render<1, STATS>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
+		hipLaunchKernelGGL((k_render<1, STATS, AA>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
 		                   out_stride_px, tiles_y, st);
 		break;
 	case 2:
-		hipLaunchKernelGGL((k_render<2, STATS>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
+		hipLaunchKernelGGL((k_render<2, STATS, AA>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
 		                   out_stride_px, tiles_y, st);
 		break;
 	default:
-		hipLaunchKernelGGL((k_render<3, STATS>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
+		hipLaunchKernelGGL((k_render<3, STATS, AA>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
 		                   out_stride_px, tiles_y, st);
 		break;
 	}
@@ -320,8 +324,11 @@ hipError_t launch_render(const DevFrame &f, const RowMap &rows, const double *d_
                          unsigned long long *d_counters, uint32_t *d_steps, double *d_entry,
                          bool stats, hipStream_t stream) {
 	StatsOut st{d_counters, d_steps, d_entry};
-	return stats ? launch_render_t<true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream)
-	             : launch_render_t<false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream);
+	if (f.aa_shift)
+		return stats ? launch_render_t<true, true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream)
+		             : launch_render_t<false, true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream);
+	return stats ? launch_render_t<true, false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream)
+	             : launch_render_t<false, false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream);
 }
 
 } // namespace hmrm

@@ -32,6 +32,12 @@ hipError_t launch_render_fast(const DevFrame &f, const RowMap &rows, const doubl
                               const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
                               unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
                               FastKernel kernel, const WindowRecord *d_records, hipStream_t stream);
+// The same launch with the antialiased epilogue (f.aa_shift != 0; render_fast_aa.hip, a translation unit of its own so
+// that the two halves of the kernel's instantiations compile in parallel).  launch_render_fast hands such frames to it.
+hipError_t launch_render_fast_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
+                                 const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
+                                 unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
+                                 FastKernel kernel, const WindowRecord *d_records, hipStream_t stream);
 // The record table of the thr table: rec_row(map_w) x ceil(map_h / 4) WindowRecords.
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream);
 // thr32[i] = (float)thr[i], round to nearest (the "float heights" mode).

@@ -176,7 +176,8 @@ __device__ TimelineRec *g_timeline = nullptr;
 // (-1: the grid row does not exist).  k_render_fast calls it with the tile = blockIdx (one tile per workgroup); round 4's
 // persistent-tile experiment (resident waves pulling tiles from queue heads) called it in a loop and was 1.4-1.9 x slower:
 // profiles/r04_experiments.txt section 1, code at commit 80527e9.
-template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP>
+// AA: the antialiased epilogue (device_common.hpp store_box_filtered; instantiated in render_fast_aa.hip only).
+template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
@@ -192,6 +193,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	diag.start();
 	unsigned long long my_steps = 0;
 	uint32_t my_hit = 0, my_cap = 0;
+	uint32_t aa_rgba = 0; // (AA: this lane's sample, filtered by the whole wave below)
 
 	if (pid.live) {
 		const DevRay ray = make_ray<PROJ>(f, pid.px, pid.py);
@@ -654,16 +656,18 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		if (real_hit) my_hit = 1;
 		else rgba = shade_miss(f, ray.dz);
 		// (row and pitch are below 2^31, api.cpp: one 32 x 32 -> 64-bit multiply-add)
-		out[(uint64_t)(uint32_t)pid.lrow * (uint32_t)out_stride_px + (uint32_t)pid.px] = rgba;
+		if constexpr (AA) aa_rgba = rgba;
+		else out[(uint64_t)(uint32_t)pid.lrow * (uint32_t)out_stride_px + (uint32_t)pid.px] = rgba;
 		if (STATS && st.steps_per_pixel)
 			st.steps_per_pixel[(int64_t)pid.py * f.screen_w + pid.px] = diag.pixel_value(f, my_steps);
 	}
+	if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, lane, pid.px, pid.lrow, pid.live, aa_rgba);
 	publish_counters<STATS>(st, my_steps, my_hit, my_cap);
 	diag.publish(st, f);
 	return pid.tile_y;
 }
 
-template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP>
+template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA>
 __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR void k_render_fast(const DevFrame f, const RowMap rows,
                                                      const double *__restrict__ thr,
                                                      const uint32_t *__restrict__ cmap,
@@ -675,7 +679,7 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
 	// calibration launches only (RowMap::measure): when did this wave start
 	unsigned long long wave_t0 = 0;
 	if (!STATS && rows.measure) wave_t0 = __builtin_amdgcn_s_memrealtime();
-	const int tile_y = render_wave_tile<PROJ, STATS, GWM, LEAP, SAMP>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
+	const int tile_y = render_wave_tile<PROJ, STATS, GWM, LEAP, SAMP, AA>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
 	                                                                  blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
 	                                                                  (int)(threadIdx.x & 63));
 	if (!STATS && rows.measure && tile_y >= 0 && (threadIdx.x & 63) == 0) {
@@ -696,6 +700,9 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
 #endif
 }
 
+// render_fast_aa.hip compiles this file again for the antialiased instantiations of the march kernel only: the
+// pyramid, record and calibration kernels and the public launchers below live in this translation unit alone.
+#ifndef HMRM_RENDER_FAST_AA
 // ---------------------------------------------------------------- pyramid ----
 __host__ __device__ __forceinline__ float round_up_to_float(double v) {
 	float r = (float)v;
@@ -869,58 +876,61 @@ hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, Windo
 	return hipGetLastError();
 }
 
+#endif // HMRM_RENDER_FAST_AA
+
 // ---------------------------------------------------------------- launch ----
-template <int PROJ, bool STATS, int GWM, int LEAP>
+template <int PROJ, bool STATS, int GWM, int LEAP, bool AA>
 static void launch_one(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
                        uint32_t *d_out, int64_t out_stride_px, StatsOut st, dim3 grid, int tiles_y,
                        hipStream_t stream) {
 	if constexpr (LEAP == kRecords) { // (nearest sampling only: launch_render_fast has checked)
-		hipLaunchKernelGGL((k_render_fast<PROJ, STATS, GWM, LEAP, 0>), grid, dim3(kBlockThreads), 0, stream, f, rows,
+		hipLaunchKernelGGL((k_render_fast<PROJ, STATS, GWM, LEAP, 0, AA>), grid, dim3(kBlockThreads), 0, stream, f, rows,
 		                   d_thr, d_cmap, d_out, out_stride_px, tiles_y, st);
 	} else {
 		if (f.sampling == 1)
-			hipLaunchKernelGGL((k_render_fast<PROJ, STATS, GWM, LEAP, 1>), grid, dim3(kBlockThreads), 0, stream, f, rows,
+			hipLaunchKernelGGL((k_render_fast<PROJ, STATS, GWM, LEAP, 1, AA>), grid, dim3(kBlockThreads), 0, stream, f, rows,
 			                   d_thr, d_cmap, d_out, out_stride_px, tiles_y, st);
 		else if (f.sampling == 2) // (d_thr is the float table here, see launch_render_fast)
-			hipLaunchKernelGGL((k_render_fast<PROJ, STATS, GWM, LEAP, 2>), grid, dim3(kBlockThreads), 0, stream, f, rows,
+			hipLaunchKernelGGL((k_render_fast<PROJ, STATS, GWM, LEAP, 2, AA>), grid, dim3(kBlockThreads), 0, stream, f, rows,
 			                   d_thr, d_cmap, d_out, out_stride_px, tiles_y, st);
 		else
-			hipLaunchKernelGGL((k_render_fast<PROJ, STATS, GWM, LEAP, 0>), grid, dim3(kBlockThreads), 0, stream, f, rows,
+			hipLaunchKernelGGL((k_render_fast<PROJ, STATS, GWM, LEAP, 0, AA>), grid, dim3(kBlockThreads), 0, stream, f, rows,
 			                   d_thr, d_cmap, d_out, out_stride_px, tiles_y, st);
 	}
 }
 
-template <int PROJ, bool STATS, int GWM>
+template <int PROJ, bool STATS, int GWM, bool AA>
 static void launch_leap(FastKernel kernel, const DevFrame &f, const RowMap &rows, const double *d_thr,
                         const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, StatsOut st, dim3 grid,
                         int tiles_y, hipStream_t stream) {
-	if (kernel == kLeaps) launch_one<PROJ, STATS, GWM, kLeaps>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
-	else if (kernel == kRecords) launch_one<PROJ, STATS, GWM, kRecords>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
-	else launch_one<PROJ, STATS, GWM, kPlainGroups>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
+	if (kernel == kLeaps) launch_one<PROJ, STATS, GWM, kLeaps, AA>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
+	else if (kernel == kRecords) launch_one<PROJ, STATS, GWM, kRecords, AA>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
+	else launch_one<PROJ, STATS, GWM, kPlainGroups, AA>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
 }
 
-template <int PROJ, bool STATS>
+template <int PROJ, bool STATS, bool AA>
 static void launch_gwm(FastKernel leap, const DevFrame &f, const RowMap &rows, const double *d_thr,
                        const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, StatsOut st, dim3 grid,
                        int tiles_y, hipStream_t stream) {
 	switch (f.grid_mode) {
-	case 0: launch_leap<PROJ, STATS, 0>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
-	case 1: launch_leap<PROJ, STATS, 1>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
-	default: launch_leap<PROJ, STATS, 2>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
+	case 0: launch_leap<PROJ, STATS, 0, AA>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
+	case 1: launch_leap<PROJ, STATS, 1, AA>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
+	default: launch_leap<PROJ, STATS, 2, AA>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
 	}
 }
 
-template <bool STATS>
+template <bool STATS, bool AA>
 static void launch_proj(FastKernel leap, const DevFrame &f, const RowMap &rows, const double *d_thr,
                         const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, StatsOut st, dim3 grid,
                         int tiles_y, hipStream_t stream) {
 	switch (f.projection) {
-	case 1: launch_gwm<1, STATS>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
-	case 2: launch_gwm<2, STATS>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
-	default: launch_gwm<3, STATS>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
+	case 1: launch_gwm<1, STATS, AA>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
+	case 2: launch_gwm<2, STATS, AA>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
+	default: launch_gwm<3, STATS, AA>(leap, f, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream); break;
 	}
 }
 
+#ifndef HMRM_RENDER_FAST_AA
 // Calibration records (RowMap::measure): kMeasureStride words per tile row, see k_render_fast's last lines.
 __global__ __launch_bounds__(256) void k_measure_init(unsigned long long *rec, int n_words) {
 	const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -958,7 +968,10 @@ hipError_t launch_thr_to_float(const double *d_thr, float *d_thr32, int64_t n, h
 	return hipGetLastError();
 }
 
-hipError_t launch_render_fast(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
+#endif // HMRM_RENDER_FAST_AA
+
+template <bool AA>
+static hipError_t launch_fast(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
                               const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
                               unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
                               FastKernel kernel, const WindowRecord *d_records, hipStream_t stream) {
@@ -1016,14 +1029,35 @@ hipError_t launch_render_fast(const DevFrame &f, const RowMap &rows, const doubl
 		}
 	}
 #endif
-	if (stats) launch_proj<true>(kernel, fr, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
-	else launch_proj<false>(kernel, fr, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
+	if (stats) launch_proj<true, AA>(kernel, fr, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
+	else launch_proj<false, AA>(kernel, fr, rows, d_thr, d_cmap, d_out, out_stride_px, st, grid, tiles_y, stream);
 	return hipGetLastError();
+}
+
+#ifndef HMRM_RENDER_FAST_AA
+hipError_t launch_render_fast(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
+                              const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
+                              unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
+                              FastKernel kernel, const WindowRecord *d_records, hipStream_t stream) {
+	if (f.aa_shift)
+		return launch_render_fast_aa(f, rows, d_thr_f64, d_thr32, d_cmap, d_out, out_stride_px, d_counters, d_steps, d_entry,
+		                             stats, kernel, d_records, stream);
+	return launch_fast<false>(f, rows, d_thr_f64, d_thr32, d_cmap, d_out, out_stride_px, d_counters, d_steps, d_entry, stats,
+	                          kernel, d_records, stream);
 }
 
 void render_tile_shape(int *tile_w, int *tile_h) {
 	*tile_w = kTileW;
 	*tile_h = kTileH;
 }
+#else
+hipError_t launch_render_fast_aa(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
+                                 const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
+                                 unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
+                                 FastKernel kernel, const WindowRecord *d_records, hipStream_t stream) {
+	return launch_fast<true>(f, rows, d_thr_f64, d_thr32, d_cmap, d_out, out_stride_px, d_counters, d_steps, d_entry, stats,
+	                         kernel, d_records, stream);
+}
+#endif
 
 } // namespace hmrm

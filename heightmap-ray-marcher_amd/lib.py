@@ -23,6 +23,12 @@ _PROJ_NAMES = {"perspective": 1, "spherical": 2, "orthographic": 3}
 
 
 NO_PROBE = 1  # HMRM_NO_PROBE (hmrm.h)
+AA_FACTORS = (1, 2, 4, 8)  # hmrm_render_aa's factors
+
+
+def aa_flags(n: int) -> int:
+    """HMRM_AA(n) (hmrm.h): the antialias factor field of the ticketed calls' flags (0 and 1 mean off)."""
+    return (int(n) & 15) << 8
 
 
 class HmrmError(RuntimeError):
@@ -115,6 +121,7 @@ def _load():
         "hmrm_debug_mip_layout": (C.c_int, [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "hmrm_band_local_rows": (i32, [i32, i32, i32, i32]),
         "hmrm_render_stats": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t, C.POINTER(Stats), vp, vp]),
+        "hmrm_render_aa": (C.c_int, [vp, C.POINTER(Camera), i32, vp, C.c_size_t, C.POINTER(Stats)]),
         "hmrm_debug_ray": (C.c_int, [vp, C.POINTER(Camera), i32, i32, dp, dp, dp]),
         "hmrm_debug_frame": (C.c_int, [C.POINTER(Camera), C.POINTER(SceneParams), i32, i32, vp, vp]),
         "hmrm_debug_plan_order": (C.c_int, [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), vp]),
@@ -127,8 +134,11 @@ def _load():
                                         C.c_char_p, C.c_longlong, i32, i32]),
         "hmrm_config_record_mode": (i32, [vp]),
         "hmrm_config_devices": (i32, [vp]),
+        "hmrm_config_antialias": (i32, [vp]),
         "hmrm_record_orbit_multi": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32]),
+        "hmrm_record_orbit_flags": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
+                                              C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32, C.c_uint32]),
         "hmrm_orbit_frame_owner": (i32, [i32, i32]),
         "hmrm_render_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(i32)]),
         "hmrm_render_begin_flags": (C.c_int, [vp, C.POINTER(Camera), C.c_uint32, C.POINTER(i32)]),
@@ -293,6 +303,16 @@ class Scene:
                allow=(HMRM_E_NOTERM,) if allow_capped else ())
         return fb, st, steps, entry
 
+    def render_aa(self, cam: Camera, factor: int, stats=False, allow_capped=False):
+        """The antialiased frame (hmrm_render_aa): the frame of factor x the resolution, box-filtered over factor x factor
+        blocks -> HxWx4 uint8, or (frame, Stats counted over the samples) with stats=True (the instrumented kernel)."""
+        self._sync_env()
+        fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
+        st = Stats() if stats else None
+        _check(lib.hmrm_render_aa(self._h, C.byref(cam), int(factor), _ptr(fb), cam.width * 4, C.byref(st) if stats else None),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return (fb, st) if stats else fb
+
     def render_rows_device(self, cam: Camera, d_ptr: int, stride_bytes: int, row_begin=0, row_end=0,
                            band_rows=0, band_index=0, band_count=1, stream: int = 0):
         self._sync_env()
@@ -300,11 +320,12 @@ class Scene:
                                            row_begin, row_end, band_rows, band_index, band_count,
                                            C.c_void_p(stream)))
 
-    def render_begin(self, cam: Camera, no_probe: bool = False) -> int:
-        """Enqueue a frame (kernel + copy into a pinned frame of the scene's ring) -> ticket.  no_probe = HMRM_NO_PROBE."""
+    def render_begin(self, cam: Camera, no_probe: bool = False, aa: int = 1) -> int:
+        """Enqueue a frame (kernel + copy into a pinned frame of the scene's ring) -> ticket.  no_probe = HMRM_NO_PROBE;
+        aa = antialias factor (HMRM_AA, the frame stays cam.width x cam.height)."""
         self._sync_env()
         t = C.c_int32()
-        _check(lib.hmrm_render_begin_flags(self._h, C.byref(cam), NO_PROBE if no_probe else 0, C.byref(t)))
+        _check(lib.hmrm_render_begin_flags(self._h, C.byref(cam), (NO_PROBE if no_probe else 0) | aa_flags(aa), C.byref(t)))
         return int(t.value)
 
     def render_wait(self, ticket: int, shape, allow_capped=False, copy=True) -> np.ndarray:
@@ -322,11 +343,13 @@ class Scene:
     def render_release(self, ticket: int):
         lib.hmrm_render_release(self._h, ticket)
 
-    def render_device_begin(self, cam: Camera, d_ptr: int, stride_bytes: int, no_probe: bool = False) -> int:
-        """Launch a frame into device memory on the next of the scene's launch streams -> ticket.  no_probe = HMRM_NO_PROBE."""
+    def render_device_begin(self, cam: Camera, d_ptr: int, stride_bytes: int, no_probe: bool = False, aa: int = 1) -> int:
+        """Launch a frame into device memory on the next of the scene's launch streams -> ticket.  no_probe = HMRM_NO_PROBE;
+        aa = antialias factor (HMRM_AA)."""
         self._sync_env()
         t = C.c_int32()
-        _check(lib.hmrm_render_device_begin_flags(self._h, C.byref(cam), C.c_void_p(d_ptr), stride_bytes, NO_PROBE if no_probe else 0, C.byref(t)))
+        _check(lib.hmrm_render_device_begin_flags(self._h, C.byref(cam), C.c_void_p(d_ptr), stride_bytes,
+                                                  (NO_PROBE if no_probe else 0) | aa_flags(aa), C.byref(t)))
         return int(t.value)
 
     def render_device_wait(self, ticket: int, allow_capped=False):
@@ -444,19 +467,29 @@ def orbit_camera(base: Camera, centre_x: float, centre_y: float, radius: float, 
 
 
 def record_orbit(scene: "Scene", base: Camera, centre_x, centre_y, radius, hang0, frames, directory, rec_id,
-                 encoder_threads=0, verbose=False):
-    _check(lib.hmrm_record_orbit(scene._h, C.byref(base), centre_x, centre_y, radius, hang0, frames,
-                                 os.fsencode(directory), rec_id, encoder_threads, int(verbose)),
-           allow=(HMRM_E_NOTERM,))
+                 encoder_threads=0, verbose=False, aa=1):
+    """aa: antialias factor of every frame (HMRM_AA through hmrm_record_orbit_flags)."""
+    if aa == 1:
+        _check(lib.hmrm_record_orbit(scene._h, C.byref(base), centre_x, centre_y, radius, hang0, frames,
+                                     os.fsencode(directory), rec_id, encoder_threads, int(verbose)),
+               allow=(HMRM_E_NOTERM,))
+    else:
+        record_orbit_multi([scene], base, centre_x, centre_y, radius, hang0, frames, directory, rec_id,
+                           encoder_threads, verbose, aa=aa)
 
 
 def record_orbit_multi(scenes, base: Camera, centre_x, centre_y, radius, hang0, frames, directory, rec_id,
-                       encoder_threads=0, verbose=False):
-    """The sweep sharded over several scenes (one per GPU): frame k on scenes[k mod len(scenes)]."""
+                       encoder_threads=0, verbose=False, aa=1):
+    """The sweep sharded over several scenes (one per GPU): frame k on scenes[k mod len(scenes)].  aa: antialias factor."""
     arr = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
-    _check(lib.hmrm_record_orbit_multi(arr, len(scenes), C.byref(base), centre_x, centre_y, radius, hang0, frames,
-                                       os.fsencode(directory), rec_id, encoder_threads, int(verbose)),
-           allow=(HMRM_E_NOTERM,))
+    if aa == 1:
+        _check(lib.hmrm_record_orbit_multi(arr, len(scenes), C.byref(base), centre_x, centre_y, radius, hang0, frames,
+                                           os.fsencode(directory), rec_id, encoder_threads, int(verbose)),
+               allow=(HMRM_E_NOTERM,))
+    else:
+        _check(lib.hmrm_record_orbit_flags(arr, len(scenes), C.byref(base), centre_x, centre_y, radius, hang0, frames,
+                                           os.fsencode(directory), rec_id, encoder_threads, int(verbose), aa_flags(aa)),
+               allow=(HMRM_E_NOTERM,))
 
 
 def render_multi(scenes, cam: Camera, allow_capped=False) -> np.ndarray:
@@ -540,6 +573,10 @@ class Config:
     @property
     def devices(self) -> int:
         return lib.hmrm_config_devices(self._h)
+
+    def antialias(self) -> int:
+        """Additive `antialias n`: hmrm_render_aa's factor (1 = off)."""
+        return int(lib.hmrm_config_antialias(self._h))
 
     @property
     def output_path(self) -> str:

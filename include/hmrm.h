@@ -173,6 +173,11 @@ int  hmrm_render_begin(const hmrm_scene *scene, const hmrm_camera *cam, int32_t 
  * its content: a 3-6 ms hiccup on a 4K frame) -- for a caller that counts on every frame's latency.  The probe
  * then waits for a frame without the flag (or the calibration of a repeated camera). */
 #define HMRM_NO_PROBE 1u
+/* HMRM_AA(n): the frame antialiased with factor n (hmrm_render_aa below), in bits 8..11 of the flags; HMRM_AA(0) and
+ * HMRM_AA(1) mean off.  Tickets with different factors may be in flight on one scene at once.  A flags word with a factor
+ * outside {0, 1, 2, 4, 8}, a super frame over the limit or any bit other than these is refused with HMRM_E_ARG. */
+#define HMRM_AA(n) (((uint32_t)(n) & 15u) << 8)
+#define HMRM_AA_MASK HMRM_AA(15)
 int  hmrm_render_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket);
 int  hmrm_render_wait(const hmrm_scene *scene, int32_t ticket, const uint8_t **rgba, size_t *stride_bytes);
 void hmrm_render_release(const hmrm_scene *scene, int32_t ticket);
@@ -226,6 +231,19 @@ int32_t hmrm_band_local_rows(int32_t height, int32_t band_rows, int32_t band_ind
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam,
                       uint8_t *rgba, size_t stride_bytes,
                       hmrm_stats *stats, uint32_t *steps_per_pixel, double *entry_d);
+
+/* Antialiased frame (build-side quality mode, not in the reference): the width x height frame is the frame the reference
+ * would render at (n*width) x (n*height) -- same camera and scene, exactly the rays GetRay(x/(n*width-1), y/(n*height-1))
+ * of that "super frame" -- box-filtered over n x n blocks: for c in R, G, B, out[y][x].c = (S + n*n/2) >> (2*log2 n),
+ * S = the integer sum of channel c over the samples (n*x+i, n*y+j), 0 <= i, j < n (rounds half up); out.A = 255.
+ * factor n is 1, 2, 4 or 8; n = 1 is hmrm_render byte for byte.  The super frame must itself be a frame the reference can
+ * index (at most 2^29 pixels; 3840 x 2160 at n = 8 fits).  Every sampling mode and projection works, with the scene's own
+ * kernel choice.  The samples are marched and reduced inside the kernel: no buffer of n*n*width*height pixels exists.
+ * stats (may be NULL: the production kernel; else the instrumented one) count samples: rays = n*n*width*height, steps /
+ * hits / capped summed over the samples; HMRM_E_NOTERM when any sample hits the step cap.  A bad factor or an oversized
+ * super frame is refused with HMRM_E_ARG before the scene is looked at. */
+int hmrm_render_aa(const hmrm_scene *scene, const hmrm_camera *cam, int32_t factor, uint8_t *rgba, size_t stride_bytes,
+                   hmrm_stats *stats);
 
 /* Device-side ImagePlane::GetRay (ImagePlane.hpp:10) and distance()
  * (AABB.hpp:12) for one pixel -- per-ray parity hooks. */
@@ -346,6 +364,11 @@ int hmrm_record_orbit(const hmrm_scene *scene, const hmrm_camera *base, double c
 int hmrm_record_orbit_multi(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base,
                             double centre_x, double centre_y, double radius, double hang0, int32_t frames,
                             const char *dir, long long id, int32_t encoder_threads, int32_t verbose);
+/* hmrm_record_orbit_multi with per-frame flags for its ticketed renders (hmrm_render_begin_flags: HMRM_AA(n) records an
+ * antialiased sweep, HMRM_NO_PROBE).  flags = 0 writes the files of hmrm_record_orbit_multi, which calls it so. */
+int hmrm_record_orbit_flags(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base,
+                            double centre_x, double centre_y, double radius, double hang0, int32_t frames,
+                            const char *dir, long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags);
 int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
 
 /* ------------------------------------------------------------------- config */
@@ -354,7 +377,8 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * every option to `echo_fd`-style sinks: echo text is appended to an internal
  * log retrievable with hmrm_config_log().  Additive keys (not in the reference,
  * named by north_star): `projection perspective|spherical|orthographic|1|2|3`,
- * `output <path.png|.ppm>`, `record orbit|off`, `devices n`, `sampling nearest|bilinear`, `heights f64|f32`.  Unknown key -> "WARNING: Unknown identifier: k". */
+ * `output <path.png|.ppm>`, `record orbit|off`, `devices n`, `sampling nearest|bilinear`, `heights f64|f32`,
+ * `antialias 1|2|4|8` (hmrm_render_aa's factor; another value warns "WARNING: Unknown antialias: v" and keeps the old one).  Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
 /* Consume a whole stream; loads heightmap/colormap images when those keys
@@ -372,6 +396,7 @@ const char  *hmrm_config_colormap_path(const hmrm_config *cfg);
 const char  *hmrm_config_output_path(const hmrm_config *cfg);
 int32_t      hmrm_config_record_mode(const hmrm_config *cfg);   /* additive `record orbit|off`: 1|0 */
 int32_t      hmrm_config_devices(const hmrm_config *cfg);       /* additive `devices n`: GPUs for recording, 0 = all */
+int32_t      hmrm_config_antialias(const hmrm_config *cfg);     /* additive `antialias n`: 1 (default, off), 2, 4 or 8 */
 /* Loaded maps (owned by cfg): RGB8 / RGBA8; NULL until the key was consumed. */
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *cfg, int32_t *w, int32_t *h);
 const uint8_t *hmrm_config_color_rgba(const hmrm_config *cfg, int32_t *w, int32_t *h);
