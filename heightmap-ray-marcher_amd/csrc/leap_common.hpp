@@ -112,13 +112,18 @@ __device__ __forceinline__ void axis_refresh(Axis &a, double p, double s) {
 	const uint32_t hp = hi32(p), hp1 = hi32(p1), hp2 = hi32(p2);
 	const uint32_t e = (hp >> 20) & 0x7ffu;
 	const double d = p1 - p;                  // exact: multiples of u, |d| < 2^53 u
-	const int ok = (int)((((hp ^ hp1) | (hp ^ hp2)) >> 20) == 0u) & (int)(e - 128u <= 1772u) & (int)((p2 - p1) == d);
+	// (the high-word differences are pinned to 32-bit registers: left alone, the compiler folds "high word >> 20 == 0"
+	// and "sign of the high word" into 64-bit xors and compares of the whole doubles -- twice the instructions)
+	uint32_t moved = (hp ^ hp1) | (hp ^ hp2), dsign = hi32(d) ^ hp;
+	asm("" : "+v"(moved), "+v"(dsign));
+	const int ok = (int)(moved < (1u << 20)) & (int)(e - 128u <= 1772u) & (int)((p2 - p1) == d);
 	a.key = ok ? (hp >> 20) : 0xffffffffu;
 	a.delta = d;
 	// |p| grows (d has p's sign): the limit is 2^(E+1), else 2^E; either way with p's sign.
 	// One integer add on the high word (E <= 1900, no overflow into the sign).
-	const uint32_t away = (((hi32(d) ^ hp) >> 31) ^ 1u) << 20;
-	const double lim = f64_from_hi((hp & 0xfff00000u) + away);
+	uint32_t lim_hi = (hp & 0xfff00000u) + ((~dsign >> 31) << 20); // (+ 2^20 when d has p's sign)
+	asm("" : "+v"(lim_hi));
+	const double lim = f64_from_hi(lim_hi);
 	const bool still = d == 0.0;              // the coordinate never moves (s == 0 or absorbed): unlimited room
 	a.lim = still ? p + 1.0 : lim;
 	a.rdel = still ? 0x1p40 : __builtin_amdgcn_rcp(d);

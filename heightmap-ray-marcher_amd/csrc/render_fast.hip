@@ -379,7 +379,9 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							}
 							room_z = sz < 0.0 ? (m - z) * az.rdel : 0x1p40;
 							z_bound = room_z < room;
-							room = __builtin_fmin(room, room_z);
+							// (a select on the compare just made: the same value as fmin for the lanes that use it -- neither
+							// is NaN there (z >= m, finite non-zero reciprocals) -- without fmin's canonicalising v_max)
+							room = STATS ? __builtin_fmin(room, room_z) : (z_bound ? room_z : room);
 							// (the saturating cast takes care of huge and negative estimates; the step budget caps the
 							// integer: a jump never takes more steps than the cap has left)
 							n = min(cvt_i32_sat(room * 0.998), budget) - 1;
@@ -580,19 +582,22 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					// in order: the first position that leaves the grid (:1006) or hits (:1016) ends the ray
 					int first = U, hit_j = 0;
 					unsigned hit_cell = 0u;
-					bool hit = false;
+					bool hit = false, stop = false;
 #pragma unroll
 					for (int j = U - 1; j >= 0; --j) { // (selects, last write = earliest position)
 						const bool h = inb[j] && Z[j] < T[j];
 						const bool s = !inb[j] || h;
-						first = s ? j : first;
+						if (STATS) first = s ? j : first;
+						stop = stop | s; // (lane masks: no VGPR select)
 						hit = s ? h : hit;
 						hit_cell = s ? cell[j] : hit_cell;
 						hit_j = s ? j : hit_j;
 					}
-					const int taken = first + (hit ? 1 : 0); // loads the reference executed in this group
-					budget -= taken;
-					done = first < U;
+					// loads the reference executed in this group: U unless the ray ends in it.  Only the instrumented kernel
+					// reads the budget of a ray that has ended (its step count), so only it counts the exact share of the
+					// last group; the others need the budget of rays that go on, and first + hit = U for those.
+					budget -= STATS ? first + (hit ? 1 : 0) : U;
+					done = stop;
 					if (hit) {
 						if constexpr (BILINEAR) {
 							// (the weights are rebuilt for the one position that hit: cheaper than keeping
