@@ -160,7 +160,11 @@ int hmrm_render_multi(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_ca
 /* The same frame without blocking: hmrm_render_begin enqueues the kernel and the device-to-host
  * copy into a pinned frame owned by the scene and returns a ticket; hmrm_render_wait blocks until
  * that frame is in host memory and lends it out (*rgba, valid until hmrm_render_release; returns
- * HMRM_E_NOTERM like hmrm_render, the frame is still valid then).  Copies run on their own
+ * HMRM_E_NOTERM like hmrm_render, the frame is still valid then).  Rays stopped by the step cap are counted per launch
+ * stream, not per ticket: they are reported -- once, with their number -- by a wait (hmrm_render_wait or
+ * hmrm_render_device_wait) on a ticket of that launch stream: at the latest by the wait for the frame's own ticket; a
+ * ticket of the same stream that is waited for earlier may have seen them already and reports them instead (the k-th
+ * ticket of a scene, host and device tickets counted together, uses stream k mod 3).  Copies run on their own
  * stream, so with two or more frames in flight kernel k+1 overlaps the PCIe transfer of frame k
  * (replaces the per-frame blit SDL_UpdateTexture, hmap.cpp:1082).  Up to 64 frames in flight per
  * scene; the ring grows on demand and is freed with the scene.

@@ -198,3 +198,158 @@ def test_cli_antialias_key(gpu, oracle, tmp_path):
     assert "antialias 2\n" in r.stdout
     assert f"rendered {4 * cam.width * cam.height} rays, {total} ray-steps" in r.stdout
     assert open(outp, "rb").read() == gpu.png_encode(want)
+
+
+def _orbit(gpu, cam, k):
+    c = gpu.Camera.from_buffer_copy(cam)
+    c.hang += 1e-3 * (k + 1)
+    return c
+
+
+@pytest.mark.parametrize("kind,proj", [("needles", 2), ("smooth", 1)])
+def test_calibration_and_both_probes_under_antialiasing(gpu, oracle, kind, proj, capfd):
+    """An antialiased frame shares the cache record, the launch-order calibration and the kernel probes with the plain frame of
+    its super camera (api.cpp check_antialias -> prepare_frame) but runs another kernel instantiation into a W x H buffer.  A
+    camera whose 4x super frame has 15 tile rows: rendered 16 times (first launch, measured trials of either kernel, settled
+    launches), then 14 cameras that never repeat through device tickets (the sixth unprobed frame is launched twice), each
+    interleaved with the plain frame of the super camera itself; on a map where the groups may win and on a smooth one; with
+    the probe on and off (HMRM_TRY_GROUP=0) and under an explicit pieced order.  Every frame is the oracle's, box-filtered
+    where antialiased; the library's own report (HMRM_ORDER_VERBOSE) shows that the calibration settled and the shadow probe
+    ran on these records."""
+    torch = pytest.importorskip("torch")
+    n = 4
+    rgb, cmap = gpu.synth.content_maps(256, kind)
+    params = gpu.SceneParams.make(0.0, 40.0, grid_width=1.0)
+    heights = oracle.update_heightmap(rgb, params)
+    cam = gpu.Camera.make(width=80, height=60, projection=proj, hfov=gpu.degrees_to_rads(150 if proj == 2 else 90), hang=gpu.degrees_to_rads(-45),
+                          vang=gpu.degrees_to_rads(118), pos=(-40.0, 40.0, 90.0), step_dist=0.5, bg=(3, 4, 5))
+    assert (cam.height * n + 15) // 16 >= 12
+
+    def both(c):
+        ofb, _, capped, *_ = oracle.render(oracle.make_cfg(super_camera(gpu, c, n), params, 256, 256), heights, cmap)
+        assert capped == 0
+        return box_filter(ofb, n), ofb
+    want, want_super = both(cam)
+    for try_group in (None, "0"):
+        capfd.readouterr()
+        with env(HMRM_ORDER_VERBOSE=1, **({} if try_group is None else {"HMRM_TRY_GROUP": try_group})):
+            scene = gpu.Scene(rgb, cmap, params)
+            for k in range(16):
+                assert np.array_equal(scene.render_aa(cam, n), want), (kind, try_group, k)
+                if k % 3 == 1:
+                    assert np.array_equal(scene.render(super_camera(gpu, cam, n)), want_super), (kind, try_group, k)
+            choice = scene.kernel_choice()
+            assert choice in (0, 1, 3) and (try_group is None or choice == 0) and (kind != "smooth" or choice == 0)
+            scene.update(params)  # (the verdict is forgotten: the moving cameras below are probed by themselves)
+            buf = torch.zeros((cam.height, cam.width, 4), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            for k in range(14):
+                c = _orbit(gpu, cam, k)
+                w, ws = both(c)
+                t = scene.render_device_begin(c, buf.data_ptr(), cam.width * 4, aa=n)
+                scene.render_device_wait(t)
+                assert np.array_equal(buf.cpu().numpy(), w), (kind, try_group, k)
+                if k % 4 == 2:
+                    assert np.array_equal(scene.render(super_camera(gpu, c, n)), ws), (kind, try_group, k)
+            assert scene.kernel_choice() in (0, 1, 3)
+            with env(HMRM_TILE_SEGMENTS="9:5,2:3"):
+                assert np.array_equal(scene.render_aa(cam, n), want), (kind, try_group, "pieces")
+            scene.close()
+        err = capfd.readouterr().err
+        assert err.count("hmrm order: settled") >= 1, err
+        assert (err.count("hmrm probe:") >= 1) == (try_group is None), err
+
+
+def test_capped_sample_in_a_doubled_antialiased_frame_is_counted_once(gpu, oracle, capfd):
+    """HMRM_STEP_CAP=60 over needles, antialiased cameras that never repeat: the scene's sixth full frame is launched twice
+    (shadow probe) and still reports each capped sample once -- the count of the instrumented launch and the oracle's.  Every
+    one of the nine frames has capped samples, the doubled one among them, and the library's own report (HMRM_ORDER_VERBOSE)
+    shows that the probe did run on these antialiased frames."""
+    n = 4
+    rgb, cmap = gpu.synth.content_maps(256, "needles")
+    params = gpu.SceneParams.make(0.0, 40.0, grid_width=1.0)
+    heights = oracle.update_heightmap(rgb, params)
+    cam = gpu.Camera.make(width=80, height=60, projection=2, hfov=gpu.degrees_to_rads(150), hang=gpu.degrees_to_rads(-45),
+                          vang=gpu.degrees_to_rads(118), pos=(-40.0, 40.0, 90.0), step_dist=0.5, bg=(3, 4, 5))
+    capfd.readouterr()
+    with env(HMRM_STEP_CAP=60, HMRM_ORDER_VERBOSE=1):
+        scene = gpu.Scene(rgb, cmap, params)
+        for k in range(9):
+            c = _orbit(gpu, cam, k)
+            ofb, total, capped, *_ = oracle.render(oracle.make_cfg(super_camera(gpu, c, n), params, 256, 256, step_cap=60), heights, cmap)
+            fb, st = scene.render_aa(c, n, stats=True, allow_capped=True)
+            assert np.array_equal(fb, box_filter(ofb, n)) and (st.capped, st.steps) == (capped, total), k
+            try:
+                scene.render_aa(c, n)
+                got = 0
+            except gpu.HmrmError as e:
+                assert e.code == gpu.HMRM_E_NOTERM
+                got = int(e.message.split()[0])
+            assert got == capped > 0, (k, got, capped)   # (the cap does stop samples of every frame, whichever is doubled)
+        scene.close()
+    assert capfd.readouterr().err.count("hmrm probe:") == 1
+
+
+@pytest.mark.parametrize("kind", ["white", "needles"])
+def test_hostile_content_full_size_factor_four(gpu, kind):
+    """The 1920x1080 frames of test_hostile_content_full_frames_match_oracle (test_parity_gpu.py checks them against the
+    oracle) as the super frames of 480x270 at n = 4, under all four HMRM_KERNEL values.  The reference here is the plain
+    kernel's frame, box-filtered in numpy -- not the oracle."""
+    wl = gpu.synth.content_workload("C2", kind)
+    rgb, cmap = wl.maps()
+    scene = gpu.Scene(rgb, cmap, wl.scene_params())
+    big = wl.camera()
+    assert (big.width, big.height) == (1920, 1080)
+    cam = gpu.Camera.from_buffer_copy(big)
+    cam.width, cam.height = 480, 270
+    want = box_filter(scene.render(big), 4)
+    for variant in ("leap", "group", "simple", "rec"):
+        with env(HMRM_KERNEL=variant):
+            assert np.array_equal(scene.render_aa(cam, 4), want), (kind, variant)
+            fb, st = scene.render_aa(cam, 4, stats=True)
+            assert np.array_equal(fb, want) and st.rays == 1920 * 1080, (kind, variant)
+    scene.close()
+
+
+def test_headline_frame_factor_eight(gpu):
+    """C3's 3840x2160 headline frame as the super frame of 480x270 at n = 8, against the plain kernel's frame box-filtered in
+    numpy (that frame against the oracle: test_baseline_config_full_size_subsampled_and_properties) -- not the oracle."""
+    wl = gpu.synth.WORKLOADS["C3"]
+    rgb, cmap = gpu.synth.synth_maps(wl.map_size)
+    scene = gpu.Scene(rgb, cmap, wl.scene_params())
+    big = wl.camera()
+    assert (big.width, big.height) == (3840, 2160)
+    cam = gpu.Camera.from_buffer_copy(big)
+    cam.width, cam.height = 480, 270
+    want = box_filter(scene.render(big), 8)
+    assert np.array_equal(scene.render_aa(cam, 8), want)
+    fb, st = scene.render_aa(cam, 8, stats=True)
+    assert np.array_equal(fb, want) and st.rays == 3840 * 2160
+    scene.close()
+
+
+def test_strides_wider_than_the_row(gpu, oracle):
+    """hmrm_render_aa into host memory and antialiased device tickets into device memory whose stride exceeds 4 W: the frame
+    is the oracle's, every byte of padding keeps what it held."""
+    import ctypes
+    torch = pytest.importorskip("torch")
+    _, rgb, cmap, params, cam = scenes.build_case(CASES["sph_outside_pow2"])
+    scene = gpu.Scene(rgb, cmap, params)
+    heights = oracle.update_heightmap(rgb, params)
+    W, H = cam.width, cam.height
+    for n, pad in ((1, 4), (2, 4), (4, 52), (8, 1024)):
+        want, *_ = _expected(gpu, oracle, heights, cmap, params, cam, n)
+        stride = W * 4 + pad
+        host = np.full((H, stride), 0x5A, dtype=np.uint8)
+        rc = gpu.lib.lib.hmrm_render_aa(scene._h, ctypes.byref(cam), n, host.ctypes.data_as(ctypes.c_void_p), stride, None)
+        assert rc == gpu.HMRM_OK, gpu.last_error()
+        assert np.array_equal(host[:, :W * 4].reshape(H, W, 4), want) and (host[:, W * 4:] == 0x5A).all(), (n, pad)
+        dev = torch.full((H, stride), 0x5A, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        t = scene.render_device_begin(cam, dev.data_ptr(), stride, aa=n)
+        scene.render_device_wait(t)
+        got = dev.cpu().numpy()
+        assert np.array_equal(got[:, :W * 4].reshape(H, W, 4), want) and (got[:, W * 4:] == 0x5A).all(), (n, pad)
+    with pytest.raises(gpu.HmrmError):   # (a device stride must be a multiple of 4)
+        scene.render_device_begin(cam, dev.data_ptr(), W * 4 + 2, aa=2)
+    scene.close()
