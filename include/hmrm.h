@@ -65,7 +65,13 @@ enum {
  * `sampling nearest|bilinear`.  HMRM_NEAREST_F32 (north_star: "float heights") keeps the reference's
  * loop and fp64 positions but compares against (float)(heightmap_buf[i] + min_height): a 4-byte
  * threshold table; a ray's hit step can move where z is within half a float ulp of the threshold
- * (tests bound it); additive config key `heights f64|f32`. */
+ * (tests bound it); additive config key `heights f64|f32`.  Bit-exactness (each mode against its
+ * definition) is tested for worlds whose lengths -- grid_width, heights, camera position, step_dist,
+ * ortho_width -- lie between 2^-900 and 2^900 times a unit-scale scene's (spherical and orthographic;
+ * perspective 2^-900 .. 2^24, whose image plane cam_pos + look degenerates beyond, and one all-NaN frame at
+ * 2^60), decimal scales 1e-12 .. 1e12 in every projection and a camera up to 1e10 away (perspective 1e8)
+ * included (tests/world_scale.py); beyond, where an intermediate of the reference's loop is subnormal or
+ * overflows, nothing is tested. */
 enum {
 	HMRM_NEAREST     = 0,
 	HMRM_BILINEAR    = 1,
