@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -224,6 +225,10 @@ struct hmrm_scene {
 	uint32_t *d_steps = nullptr;
 	double *d_entry = nullptr;
 	size_t stats_px = 0;
+	// staging of hmrm_trace_rays / hmrm_pick (host rays in, host records out): grown on demand, freed with the scene
+	hmrm::BatchRay *d_rays = nullptr;
+	hmrm::BatchHit *d_hits = nullptr;
+	size_t batch_cap = 0;
 	// launch state per stream; `mu` guards the list and the slot choice (launches themselves are
 	// asynchronous), so that threads driving different streams of one scene do not collide
 	std::mutex mu;
@@ -259,6 +264,12 @@ struct hmrm_scene {
 	std::vector<SettledOrder> settled;
 };
 
+static_assert(sizeof(hmrm_ray) == sizeof(hmrm::BatchRay) && sizeof(hmrm_ray_hit) == sizeof(hmrm::BatchHit) &&
+                  offsetof(hmrm_ray_hit, entry_d) == offsetof(hmrm::BatchHit, entry_d) &&
+                  offsetof(hmrm_ray_hit, steps) == offsetof(hmrm::BatchHit, steps) &&
+                  offsetof(hmrm_ray_hit, rgba) == offsetof(hmrm::BatchHit, rgba) &&
+                  offsetof(hmrm_ray_hit, status) == offsetof(hmrm::BatchHit, status) && sizeof(hmrm_trace_params) == 16,
+              "the kernels' mirrors of hmrm_ray / hmrm_ray_hit (frame.hpp)");
 // cached records and settled launch orders are looked up with memcmp on these two: no padding bytes allowed
 static_assert(sizeof(hmrm_camera) == 3 * sizeof(int32_t) + 4 + 8 * sizeof(double), "hmrm_camera has padding");
 static_assert(sizeof(hmrm_scene_params) == 6 * sizeof(double), "hmrm_scene_params has padding");
@@ -866,6 +877,101 @@ int run_update_heights(hmrm_scene *s) {
 	return HMRM_OK;
 }
 
+// ---- ray batches (hmrm_trace_rays, hmrm_trace_rays_device, hmrm_pick) ----
+constexpr int64_t kMaxBatch = (int64_t)1 << 29;
+int noterm(unsigned long long capped);
+
+// Needs no scene and no device: the refusals are testable without a GPU.
+int check_trace(const hmrm_trace_params *p, const void *rays, int64_t n, const void *hits) {
+	if (n < 0) return fail(HMRM_E_ARG, "trace: n must not be negative (got " + std::to_string(n) + ")");
+	if (n > kMaxBatch) return fail(HMRM_E_ARG, "trace: at most 2^29 rays per batch (got " + std::to_string(n) + ")");
+	if (n > 0 && (!p || !rays || !hits)) return fail(HMRM_E_ARG, "trace: NULL params, rays or hits");
+	if (p && p->sampling > HMRM_NEAREST_F32)
+		return fail(HMRM_E_ARG, "trace: sampling must be 0 (nearest), 1 (bilinear) or 2 (nearest, float heights)");
+	return HMRM_OK;
+}
+
+int ensure_batch(hmrm_scene *s, size_t n) {
+	if (n <= s->batch_cap) return HMRM_OK;
+	if (s->d_rays) (void)hipFree(s->d_rays);
+	if (s->d_hits) (void)hipFree(s->d_hits);
+	s->d_rays = nullptr;
+	s->d_hits = nullptr;
+	s->batch_cap = 0;
+	HIP_TRY(hipMalloc((void **)&s->d_rays, n * sizeof(hmrm::BatchRay)));
+	HIP_TRY(hipMalloc((void **)&s->d_hits, n * sizeof(hmrm::BatchHit)));
+	s->batch_cap = n;
+	return HMRM_OK;
+}
+
+// One batch on the context's stream.  The DevFrame has no camera: a zeroed record plus the scene's box, grid and pyramid,
+// laid out as a frame kBatchW pixels wide (frame.hpp RayBatch).  A batch is not a frame: it takes no cached record, is
+// never measured, never probes and does not count towards the scene's probe; it only READS the scene's kernel choice
+// (HMRM_KERNEL or the probe's verdict), and waits -- in stream order -- for a measured launch in flight like any launch.
+// The leap policy's hints come from a camera's step length in cells for frames (camera.cpp); a batch's directions have
+// any length, so it gets the fine-step defaults: windows from 4 cells on, no pause (HMRM_MIN_LEVEL / HMRM_FINEST_PAUSE apply).
+int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg[3], int sampling, const hmrm::BatchRay *d_rays,
+                 int64_t n, hmrm::BatchHit *d_hits) {
+	const bool huge_side = s->map_w >= (1 << 24) || s->map_h >= (1 << 24);
+	if (huge_side && sampling != 0) return fail(HMRM_E_ARG, "maps with a side of 2^24 cells or more support nearest sampling only");
+	if (sampling == HMRM_BILINEAR) {
+		const int rc_b = ensure_bilinear_pyramid(s);
+		if (rc_b) return rc_b;
+	}
+	hmrm::DevFrame f = hmrm::DevFrame();
+	hmrm::fill_scene_fields(s->map_w, s->map_h, s->params.min_height, s->params.max_height, s->params.grid_width, step_dist, &f);
+	f.screen_w = hmrm::kBatchW;
+	f.screen_h = (int32_t)((n + hmrm::kBatchW - 1) / hmrm::kBatchW);
+	f.projection = 4;
+	f.bg[0] = bg[0];
+	f.bg[1] = bg[1];
+	f.bg[2] = bg[2];
+	f.bg[3] = 255;
+	f.sampling = sampling;
+	f.thr_max = sampling == HMRM_BILINEAR ? s->thr_max_bil : s->thr_max;
+	f.mipbuf = s->d_mipbuf;
+	f.mipbuf_bil = s->d_mipbuf_bil;
+	f.mip_row = s->mip_row;
+	f.mip_plane_shift = s->mip_plane_shift;
+	f.step_cap = s->knobs.step_cap;
+	f.min_window = 4;
+	f.min_level = s->knobs.min_level >= 0 ? s->knobs.min_level : 0;
+	f.finest_pause = s->knobs.finest_pause >= 0 ? s->knobs.finest_pause : 0;
+	const hmrm::RayBatch batch{d_rays, d_hits, n};
+	int rc = wait_for_measure_fence(s, c);
+	if (rc) return rc;
+	if ((s->knobs.kernel == 2 || huge_side) && sampling == 0) { // (the literal loop only knows the reference's sampling)
+		HIP_TRY(hmrm::launch_trace_rays_literal(f, s->d_thr, s->d_cmap, batch, c->d_counters, c->stream));
+	} else {
+		const bool use_other = s->knobs.kernel == 0 && s->knobs.try_group && s->choice.use_group; // (the verdict, never a probe)
+		const hmrm::FastKernel k = (hmrm::FastKernel)hmrm::pick_fast_kernel(s->knobs.kernel, use_other, sampling == 0 && s->d_records, s->choice);
+		if (k == hmrm::kRecords && (rc = ensure_records(s))) return rc;
+		HIP_TRY(hmrm::launch_trace_rays(f, s->d_thr, s->d_thr32, s->d_cmap, batch, c->d_counters, k, s->d_records, c->stream));
+	}
+	return note_launch(s, c);
+}
+
+// The host-memory half of hmrm_trace_rays / hmrm_pick: the records of the scene's staging buffer and the stream's capped-ray
+// count come back, the stream is drained.  (s->mu held.)
+int finish_batch(hmrm_scene *s, StreamCtx *c, hmrm_ray_hit *hits, int64_t n, hmrm_stats *stats) {
+	HIP_TRY(hipMemcpyAsync(hits, s->d_hits, (size_t)n * sizeof(hmrm_ray_hit), hipMemcpyDeviceToHost, s->stream));
+	unsigned long long capped_now = 0;
+	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	const unsigned long long capped = capped_now - c->capped_seen;
+	c->capped_seen = capped_now;
+	if (stats) {
+		*stats = hmrm_stats{};
+		stats->rays = (uint64_t)n;
+		for (int64_t i = 0; i < n; ++i) {
+			stats->steps += hits[i].steps;
+			stats->hits += hits[i].status == HMRM_RAY_HIT ? 1u : 0u;
+		}
+		stats->capped = capped;
+	}
+	return capped ? noterm(capped) : HMRM_OK;
+}
+
 // Rays of this context that reached the step cap since the host last asked (the stream must be idle).
 int take_capped(StreamCtx *c, unsigned long long *out) {
 	unsigned long long now = 0;
@@ -1005,6 +1111,8 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	if (s->measure_fence) (void)hipEventDestroy(s->measure_fence);
 	if (s->d_steps) (void)hipFree(s->d_steps);
 	if (s->d_entry) (void)hipFree(s->d_entry);
+	if (s->d_rays) (void)hipFree(s->d_rays);
+	if (s->d_hits) (void)hipFree(s->d_hits);
 	if (s->ev0) (void)hipEventDestroy(s->ev0);
 	if (s->ev1) (void)hipEventDestroy(s->ev1);
 	if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -1728,6 +1836,86 @@ int hmrm_write_ppm(const char *path, int32_t w, int32_t h, int32_t comp, const u
 	if (!hmrm::write_file(path, pnm.data(), pnm.size()))
 		return fail(HMRM_E_IO, std::string("Failed to write image to ") + path);
 	return HMRM_OK;
+}
+
+int hmrm_trace_rays(const hmrm_scene *scene, const hmrm_trace_params *p, const hmrm_ray *rays, int64_t n, hmrm_ray_hit *hits,
+                    hmrm_stats *stats) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	int rc = check_trace(p, rays, n, hits);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	if (n == 0) {
+		if (stats) *stats = hmrm_stats{};
+		return HMRM_OK;
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	if ((rc = ensure_batch(s, (size_t)n))) return rc;
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, s->stream, &c))) return rc;
+	HIP_TRY(hipMemcpyAsync(s->d_rays, rays, (size_t)n * sizeof(hmrm_ray), hipMemcpyHostToDevice, s->stream));
+	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
+	if ((rc = launch_batch(s, c, p->step_dist, bg, p->sampling, s->d_rays, n, s->d_hits))) return rc;
+	return finish_batch(s, c, hits, n, stats);
+}
+
+int hmrm_trace_rays_device(const hmrm_scene *scene, const hmrm_trace_params *p, const void *d_rays, int64_t n, void *d_hits,
+                           void *hip_stream) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	int rc = check_trace(p, d_rays, n, d_hits);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	if (n == 0) return HMRM_OK;
+	if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 7u) return fail(HMRM_E_ARG, "trace: d_rays and d_hits must be 8-byte aligned");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
+	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
+	return launch_batch(s, c, p->step_dist, bg, p->sampling, static_cast<const hmrm::BatchRay *>(d_rays), n,
+	                    static_cast<hmrm::BatchHit *>(d_hits));
+}
+
+// Picking: GetRay of one pixel on the device (k_probe, as hmrm_debug_ray) and that ray traced as a batch of one.  Like a
+// batch it takes no cached per-frame record: the camera's record is built here and dropped, and a spherical camera's tables
+// go to the scene's scratch behind the probe's seven doubles.
+int hmrm_pick(const hmrm_scene *scene, const hmrm_camera *cam, int32_t px, int32_t py, hmrm_ray_hit *hit) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	int rc = check_camera(cam);
+	if (rc) return rc;
+	if (!s || !hit) return fail(HMRM_E_ARG, "NULL argument");
+	if (px < 0 || py < 0 || px >= cam->width || py >= cam->height) return fail(HMRM_E_ARG, "pixel out of range");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+	const bool spherical = cam->projection == HMRM_SPHERICAL;
+	if ((rc = ensure_stats(s, 8 + (spherical ? 2 * W + 2 * H : 0)))) return rc;
+	if ((rc = ensure_batch(s, 1))) return rc;
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, s->stream, &c))) return rc;
+	hmrm::HostCamera hc;
+	to_host_camera(cam, &hc);
+	std::vector<double> tables(spherical ? 2 * W + 2 * H : 0);
+	double *t = tables.data();
+	hmrm::DevFrame f;
+	hmrm::build_frame(hc, s->map_w, s->map_h, s->params.min_height, s->params.max_height, s->params.grid_width, &f,
+	                  spherical ? t : nullptr, spherical ? t + W : nullptr, spherical ? t + 2 * W : nullptr,
+	                  spherical ? t + 2 * W + H : nullptr);
+	if (spherical) {
+		double *d_t = s->d_entry + 8;
+		// (pageable source: the copy is staged before the call returns)
+		HIP_TRY(hipMemcpyAsync(d_t, t, tables.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+		f.col_cos_ha = d_t;
+		f.col_sin_ha = d_t + W;
+		f.row_sin_va = d_t + 2 * W;
+		f.row_cos_va = d_t + 2 * W + H;
+	}
+	// the probe's first six doubles -- pos, dir -- are an hmrm_ray
+	HIP_TRY(hmrm::launch_probe(f, px, py, s->d_entry, s->stream));
+	const uint8_t bg[3] = {cam->bg_r, cam->bg_g, cam->bg_b};
+	if ((rc = launch_batch(s, c, cam->step_dist, bg, cam->sampling, reinterpret_cast<const hmrm::BatchRay *>(s->d_entry), 1, s->d_hits)))
+		return rc;
+	return finish_batch(s, c, hit, 1, nullptr);
 }
 
 // Device-side GetRay + distance() for one pixel (test hook).

@@ -77,6 +77,34 @@ void fill_row_tables(const HostCamera &cam, int32_t begin, int32_t end, double *
 	}
 }
 
+// What a launch needs of the scene and the march, camera or not (a ray batch has none: api.cpp): the map's size, the box
+// corners, the nudge, the step and the helpers derived from grid_width.
+void fill_scene_fields(int32_t map_w, int32_t map_h, double min_height, double max_height, double grid_width,
+                       double step_dist, DevFrame *f) {
+	f->map_w = map_w;
+	f->map_h = map_h;
+
+	// hmap.cpp:968-974
+	f->c0[0] = 0.0;
+	f->c0[1] = 0.0;
+	f->c0[2] = min_height;
+	f->c1[0] = f->c0[0] + map_w * grid_width;
+	f->c1[1] = f->c0[1] - map_h * grid_width;
+	f->c1[2] = max_height;
+
+	f->grid_width = grid_width;
+	f->nudge = grid_width * 0.01; // hmap.cpp:998
+	f->step_dist = step_dist;
+
+	// x / 2^k == x * 2^-k bit for bit (both are the correctly rounded value of the
+	// same real number) as long as 2^-k is representable: normal power of two.
+	int e = 0;
+	const double m = std::frexp(grid_width, &e);
+	f->grid_pow2 = (std::isfinite(grid_width) && m == 0.5 && e > -1000 && e < 1000) ? 1 : 0;
+	f->inv_grid_width = 1.0 / grid_width;
+	f->grid_mode = grid_width == 1.0 ? 0 : (f->grid_pow2 ? 1 : 2);
+}
+
 void build_frame(const HostCamera &cam, int32_t map_w, int32_t map_h, double min_height,
                  double max_height, double grid_width, DevFrame *f, double *col_cos_ha,
                  double *col_sin_ha, double *row_sin_va, double *row_cos_va) {
@@ -84,8 +112,6 @@ void build_frame(const HostCamera &cam, int32_t map_w, int32_t map_h, double min
 	f->screen_w = cam.width;
 	f->screen_h = cam.height;
 	f->projection = cam.projection;
-	f->map_w = map_w;
-	f->map_h = map_h;
 	f->bg[0] = cam.bg_r;
 	f->bg[1] = cam.bg_g;
 	f->bg[2] = cam.bg_b;
@@ -134,13 +160,7 @@ void build_frame(const HostCamera &cam, int32_t map_w, int32_t map_h, double min
 		store(f->plane_down, (cam.height * ow) * (-u));
 	}
 
-	// hmap.cpp:968-974
-	f->c0[0] = 0.0;
-	f->c0[1] = 0.0;
-	f->c0[2] = min_height;
-	f->c1[0] = f->c0[0] + map_w * grid_width;
-	f->c1[1] = f->c0[1] - map_h * grid_width;
-	f->c1[2] = max_height;
+	fill_scene_fields(map_w, map_h, min_height, max_height, grid_width, cam.step_dist, f);
 
 	for (int i = 0; i < 3; ++i) {
 		auto high = [](double v) {
@@ -153,18 +173,6 @@ void build_frame(const HostCamera &cam, int32_t map_w, int32_t map_h, double min
 		f->box_side_known[i] = (moderate && ((h0 ^ h1) >> 31) == 0u) ? 1 : 0;
 		f->box_side[i] = f->box_side_known[i] ? h0 : 0u;
 	}
-
-	f->grid_width = grid_width;
-	f->nudge = grid_width * 0.01; // hmap.cpp:998
-	f->step_dist = cam.step_dist;
-
-	// x / 2^k == x * 2^-k bit for bit (both are the correctly rounded value of the
-	// same real number) as long as 2^-k is representable: normal power of two.
-	int e = 0;
-	const double m = std::frexp(grid_width, &e);
-	f->grid_pow2 = (std::isfinite(grid_width) && m == 0.5 && e > -1000 && e < 1000) ? 1 : 0;
-	f->inv_grid_width = 1.0 / grid_width;
-	f->grid_mode = grid_width == 1.0 ? 0 : (f->grid_pow2 ? 1 : 2);
 
 	// Scheduling hints only (never change a pixel).  The finest pyramid level has 4-cell windows
 	// placed every 2 cells, i.e. 2..4 cells of room; with steps longer than about a third of a

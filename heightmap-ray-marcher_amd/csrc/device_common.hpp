@@ -55,6 +55,32 @@ __device__ __forceinline__ DevRay make_ray(const DevFrame &f, int px, int py) {
 	return r;
 }
 
+// Ray batches (hmrm_trace_rays; PROJ == 4 in the kernels, frame.hpp RayBatch): ray `index` of the batch, the caller's, used
+// as given -- the reference's loop takes any Ray {pos, dir} (hmap.cpp:989-1038) and never normalises.
+__device__ __forceinline__ DevRay batch_ray(const RayBatch &b, int64_t index) {
+	const BatchRay *__restrict__ in = b.rays + index;
+	DevRay r;
+	r.px = in->pos[0]; r.py = in->pos[1]; r.pz = in->pos[2];
+	r.dx = in->dir[0]; r.dy = in->dir[1]; r.dz = in->dir[2];
+	return r;
+}
+// The record of a batch ray (hmrm.h hmrm_ray_hit): `hit` with the position and the cell at which hmap.cpp:1016 fired,
+// `capped` for a ray stopped by the step cap (`rgba` is the miss shade then, like a miss).
+__device__ __forceinline__ void store_batch_hit(const RayBatch &b, int64_t index, bool hit, bool capped, double x, double y,
+                                                double z, int cell_x, int cell_y, double d, uint32_t steps, uint32_t rgba) {
+	BatchHit *__restrict__ out = b.hits + index;
+	out->point[0] = hit ? x : 0.0;
+	out->point[1] = hit ? y : 0.0;
+	out->point[2] = hit ? z : 0.0;
+	out->entry_d = d;
+	out->steps = steps;
+	out->cell_x = hit ? cell_x : -1;
+	out->cell_y = hit ? cell_y : -1;
+	__builtin_memcpy(out->rgba, &rgba, 4);
+	out->status = hit ? 1u : (capped ? 2u : 0u);
+	out->reserved = 0u;
+}
+
 // AABB.cpp:49-77, axis order x,y,z, same comparisons (NaN => every test false).
 __device__ __forceinline__ double slab_distance(const DevRay &r, const DevFrame &f) {
 	const double inf = __builtin_huge_val();
@@ -157,7 +183,7 @@ __device__ __forceinline__ bool slab_points_away(const DevRay &r, const DevFrame
 	const double ro[3] = {r.px, r.py, r.pz};
 	const double rd[3] = {r.dx, r.dy, r.dz};
 	bool away = false;
-	if (PROJ != 3) {
+	if (PROJ == 1 || PROJ == 2) { // (orthographic frames and ray batches, PROJ 4: an origin per ray, the tests below)
 #pragma unroll
 		for (int i = 0; i < 3; ++i) {
 			if (!f.box_side_known[i]) continue; // (uniform)
@@ -235,6 +261,7 @@ constexpr int kWaveW = HMRM_WAVE_W, kWaveH = 64 / HMRM_WAVE_W;
 constexpr int kWavesX = HMRM_WAVES_X, kWavesY = HMRM_WAVES_Y;          // waves per workgroup
 constexpr int kBlockThreads = 64 * kWavesX * kWavesY;
 constexpr int kTileW = kWavesX * kWaveW, kTileH = kWavesY * kWaveH;
+static_assert(kBatchW == kWaveW, "a wave's 64 lanes hold 64 consecutive rays of a batch (frame.hpp RayBatch)");
 struct PixelId {
 	int px, py, lrow;
 	int tile_y; // tile row of the launch this workgroup renders (wave-uniform)

@@ -149,6 +149,35 @@ struct RowMap {
 constexpr int kMeasureStride = 33;
 constexpr int kOrderSegs = 4;
 
+// The struct is the first kernel argument of every render kernel; what reads past its old end costs every wave a
+// scalar-cache line at start-up (see box_side above).  A field that is needed goes into a slot that is free.
+static_assert(sizeof(DevFrame) == 352,"DevFrame must not grow");
+
+// ---- ray batches (hmrm_trace_rays, hmrm.h): caller-supplied rays through the same march, PROJ == 4 in the kernels ----
+// Mirrors of hmrm_ray / hmrm_ray_hit (api.cpp asserts the sizes agree), and what a launch is handed beside the
+// DevFrame -- extra arguments of the batch kernels' own __global__ entry points (render_rays.hip, render.hip), so
+// that neither DevFrame nor the frame kernels' argument lists change.  The DevFrame of a batch has no camera:
+// projection = 4, the plane fields zero, and the batch laid out as a "frame" kWaveW (8) pixels wide and
+// ceil(n / 8) rows tall -- ray 8 * py + px belongs to pixel (px, py), so a wave's 64 lanes hold 64 consecutive rays
+// and their 48-byte loads / 56-byte stores cover contiguous memory.
+struct BatchRay { double pos[3], dir[3]; };
+struct BatchHit {
+	double point[3];
+	double entry_d;
+	uint32_t steps;
+	int32_t cell_x, cell_y;
+	uint8_t rgba[4];
+	uint32_t status;    // 0 miss, 1 hit, 2 stopped by the step cap (HMRM_RAY_*)
+	uint32_t reserved;
+};
+static_assert(sizeof(BatchRay) == 48 && sizeof(BatchHit) == 56, "hmrm_ray / hmrm_ray_hit");
+struct RayBatch {
+	const BatchRay *rays;
+	BatchHit *hits;
+	int64_t n;
+};
+constexpr int kBatchW = 8; // (= device_common.hpp kWaveW, asserted there)
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.
@@ -163,6 +192,11 @@ void build_frame(const HostCamera &cam, int32_t map_w, int32_t map_h,
                  DevFrame *out,
                  double *col_cos_ha, double *col_sin_ha,   // width entries each (spherical) or null
                  double *row_sin_va, double *row_cos_va);  // height entries each (spherical) or null
+
+// The part of build_frame that needs no camera (camera.cpp): map size, box corners (hmap.cpp:968-974), nudge (:998),
+// step_dist (:68) and the grid_width helpers.  A ray batch's DevFrame is a zeroed one plus these (api.cpp).
+void fill_scene_fields(int32_t map_w, int32_t map_h, double min_height, double max_height, double grid_width,
+                       double step_dist, DevFrame *out);
 
 // The separable halves of Spherical::GetRay (src/Spherical.cpp:18-25), entries [begin, end): cos / sin of ha per
 // column (depend on hang, hfov, width), sin / cos of va per row (depend on vang, hfov, width, height).

@@ -75,17 +75,22 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 	}
 }
 
+// The literal loop for the pixel (or, PROJ 4, the batch ray: hmrm_trace_rays, frame.hpp RayBatch) of one lane.
 // AA: the antialiased epilogue (device_common.hpp store_box_filtered, f.aa_shift); the plain instantiations store per lane.
+// PROJ 4: the lane's ray comes from `batch` and its hmrm_ray_hit record goes there; `out` is not used.
 template <int PROJ, bool STATS, bool AA>
-__global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, const RowMap rows,
-                                                const double *__restrict__ thr,
-                                                const uint32_t *__restrict__ cmap,
-                                                uint32_t *__restrict__ out, int64_t out_stride_px,
-                                                int tiles_y, StatsOut st) {
-	// one small pixel tile per wave (device_common.hpp): neighbouring rays walk neighbouring
-	// ground tracks, so a wave's height loads share cache lines and its lanes leave the loop
-	// at similar times.
-	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+__device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId pid, const double *__restrict__ thr,
+                                                    const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
+                                                    int64_t out_stride_px, const StatsOut &st, const RayBatch &batch) {
+	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
+	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
+	// (what a batch adds is written as `if constexpr (RAYS)` statements beside the frame kernels' own, which stay as they
+	// were: they must keep compiling to the same instructions)
+	int64_t ray_index = 0;
+	if constexpr (RAYS) {
+		ray_index = (int64_t)pid.py * kBatchW + pid.px;
+		pid.live = pid.live && ray_index < batch.n;
+	}
 	const int px = pid.px, py = pid.py, lrow = pid.lrow;
 	const bool live = pid.live;
 
@@ -94,12 +99,15 @@ __global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, cons
 	uint32_t aa_rgba = 0; // (AA: this lane's sample, filtered by the whole wave below)
 
 	if (live) {
-		const DevRay ray = make_ray<PROJ>(f, px, py);
+		DevRay ray = make_ray<PROJ>(f, px, py);
+		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
 		const double d = slab_distance(ray, f);
 		if (STATS && st.entry_d) st.entry_d[(int64_t)py * f.screen_w + px] = d;
 
 		uint32_t rgba = 0;
 		bool real_hit = false;
+		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired, and in which cell)
+		int hgx = -1, hgy = -1;
 
 		// intersection(): AABB.cpp:33-44
 		if (!(d == __builtin_huge_val()) && !(d < 0.0)) {
@@ -135,11 +143,12 @@ __global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, cons
 				const int gridx = (int)qx, gridy = (int)qy;
 				const int64_t cell = (int64_t)gridy * f.map_w + gridx;
 				const double t = thr[cell]; // hmap.cpp:1013-1014 (+ c0.z folded in)
-				if (STATS) my_steps += 1;
+				if (COUNT) my_steps += 1;
 				if (z < t) { // hmap.cpp:1016
 					const uint32_t c = cmap[cell];
 					rgba = ((c >> 24) == 0) ? pack_rgba(f.bg[0], f.bg[1], f.bg[2]) : (c | 0xff000000u);
 					real_hit = true;
+					if constexpr (RAYS) { hx = x; hy = y; hz = z; hgx = gridx; hgy = gridy; }
 					break;
 				}
 				x = x + sx;
@@ -162,7 +171,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, cons
 		} else {
 			my_hit = 1;
 		}
-		if constexpr (AA) aa_rgba = rgba;
+		if constexpr (RAYS) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, d, (uint32_t)my_steps, rgba);
+		else if constexpr (AA) aa_rgba = rgba;
 		else out[(int64_t)lrow * out_stride_px + px] = rgba;
 		if (STATS && st.steps_per_pixel)
 			st.steps_per_pixel[(int64_t)py * f.screen_w + px] =
@@ -171,6 +181,29 @@ __global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, cons
 	if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, (int)(threadIdx.x & 63), px, lrow, live, aa_rgba);
 
 	publish_counters<STATS>(st, my_steps, my_hit, my_cap);
+}
+
+template <int PROJ, bool STATS, bool AA>
+__global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, const RowMap rows,
+                                                const double *__restrict__ thr,
+                                                const uint32_t *__restrict__ cmap,
+                                                uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                int tiles_y, StatsOut st) {
+	// one small pixel tile per wave (device_common.hpp): neighbouring rays walk neighbouring
+	// ground tracks, so a wave's height loads share cache lines and its lanes leave the loop
+	// at similar times.
+	render_lane_literal<PROJ, STATS, AA>(f, pixel_of_lane(f, rows, tiles_y), thr, cmap, out, out_stride_px, st, RayBatch{});
+}
+
+// The literal loop over a ray batch (HMRM_KERNEL=simple): the batch as a frame kBatchW pixels wide (frame.hpp RayBatch), one
+// workgroup per 128 consecutive rays, grid rows beyond 32768 in blockIdx.z.
+__global__ __launch_bounds__(kBlockThreads) void k_trace_rays_literal(const DevFrame f, const double *__restrict__ thr,
+                                                                      const uint32_t *__restrict__ cmap, const RayBatch batch,
+                                                                      int tiles_y, StatsOut st) {
+	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, 0, blockIdx.z * 32768u + blockIdx.x, (int)(threadIdx.x >> 6),
+	                                       (int)(threadIdx.x & 63));
+	render_lane_literal<4, false, false>(f, pid, thr, cmap, nullptr, 0, st, batch);
 }
 
 // Per-ray parity hook: GetRay + distance() of one pixel -> out[0..2] pos, [3..5] dir, [6] d.
@@ -316,6 +349,17 @@ static hipError_t launch_render_t(const DevFrame &f, const RowMap &rows, const d
 		                   out_stride_px, tiles_y, st);
 		break;
 	}
+	return hipGetLastError();
+}
+
+hipError_t launch_trace_rays_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
+                                     unsigned long long *d_counters, hipStream_t stream) {
+	if (batch.n <= 0) return hipSuccess;
+	if (batch.n > ((int64_t)1 << 29) || f.screen_w != kBatchW || (int64_t)f.screen_h * kBatchW < batch.n) return hipErrorInvalidValue;
+	const int tiles_y = (f.screen_h + kTileH - 1) / kTileH;
+	const dim3 grid((unsigned)(tiles_y < 32768 ? tiles_y : 32768), 1u, (unsigned)((tiles_y + 32767) / 32768));
+	hipLaunchKernelGGL(k_trace_rays_literal, grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_cmap, batch, tiles_y,
+	                   StatsOut{d_counters, nullptr, nullptr});
 	return hipGetLastError();
 }
 

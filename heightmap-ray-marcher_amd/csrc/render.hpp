@@ -38,6 +38,15 @@ hipError_t launch_render_fast_aa(const DevFrame &f, const RowMap &rows, const do
                                  const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
                                  unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
                                  FastKernel kernel, const WindowRecord *d_records, hipStream_t stream);
+// Ray batches (hmrm_trace_rays; render_rays.hip): batch.n caller-supplied rays through the same march, one hmrm_ray_hit
+// record per ray.  `f` is a DevFrame without a camera -- projection 4, kBatchW pixels wide, at least ceil(n / kBatchW) rows
+// (frame.hpp RayBatch); the row map is the identity.  d_counters[2] counts the rays stopped by the step cap, nothing else
+// is counted.  launch_trace_rays_literal (render.hip): the literal loop, nearest sampling only.
+hipError_t launch_trace_rays(const DevFrame &f, const double *d_thr, const float *d_thr32, const uint32_t *d_cmap,
+                             const RayBatch &batch, unsigned long long *d_counters, FastKernel kernel,
+                             const WindowRecord *d_records, hipStream_t stream);
+hipError_t launch_trace_rays_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
+                                     unsigned long long *d_counters, hipStream_t stream);
 // The record table of the thr table: rec_row(map_w) x ceil(map_h / 4) WindowRecords.
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream);
 // thr32[i] = (float)thr[i], round to nearest (the "float heights" mode).

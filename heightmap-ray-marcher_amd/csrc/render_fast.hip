@@ -44,6 +44,9 @@
 #include <cstdio>
 #include <cstdlib>
 #endif
+#if defined(HMRM_RENDER_FAST_AA) || defined(HMRM_RENDER_RAYS)
+#define HMRM_MARCH_ONLY 1 // (this translation unit instantiates the march kernel for its own purpose, see the end of k_render_fast)
+#endif
 #include "device_common.hpp"
 #include "leap_common.hpp"
 #include "leap_diag.hpp"
@@ -177,18 +180,31 @@ __device__ TimelineRec *g_timeline = nullptr;
 // persistent-tile experiment (resident waves pulling tiles from queue heads) called it in a loop and was 1.4-1.9 x slower:
 // profiles/r04_experiments.txt section 1, code at commit 80527e9.
 // AA: the antialiased epilogue (device_common.hpp store_box_filtered; instantiated in render_fast_aa.hip only).
+// PROJ 4 (instantiated in render_rays.hip only): a batch of caller-supplied rays (hmrm_trace_rays; frame.hpp RayBatch) -- the
+// lane's ray is loaded from `batch`, not made from a camera, and instead of a pixel the lane writes its hmrm_ray_hit record,
+// which wants distance()'s value for misses too and the ray's exact step count: the two things the instrumented
+// instantiation computes (COUNT below), without its diagnostics or its wave-wide counters.  `out` is not used then.
 template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
-                                                int wave, int lane) {
+                                                int wave, int lane, const RayBatch &batch) {
 	constexpr bool BILINEAR = SAMP == 1, F32 = SAMP == 2;
+	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
+	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	constexpr bool REC = LEAP == 2;                     // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
 	constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
 	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
 	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
 	const float *__restrict__ mip = BILINEAR ? f.mipbuf_bil : f.mipbuf; // the pyramid this sampling mode leaps on
-	const PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, lane);
+	PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, lane);
+	// (what a batch adds is written as `if constexpr (RAYS)` statements beside the frame kernels' own, which stay as they
+	// were: they must keep compiling to the same instructions)
+	int64_t ray_index = 0;
+	if constexpr (RAYS) {
+		ray_index = (int64_t)pid.py * kBatchW + pid.px;
+		pid.live = pid.live && ray_index < batch.n;
+	}
 	LoopDiag<STATS> diag; // (empty unless STATS: leap_diag.hpp)
 	diag.start();
 	unsigned long long my_steps = 0;
@@ -196,20 +212,23 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	uint32_t aa_rgba = 0; // (AA: this lane's sample, filtered by the whole wave below)
 
 	if (pid.live) {
-		const DevRay ray = make_ray<PROJ>(f, pid.px, pid.py);
+		DevRay ray = make_ray<PROJ>(f, pid.px, pid.py);
+		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
 		// most rays of a frame never touch the box: prove the miss cheaply where possible (the instrumented
 		// variant reports d, so it takes no shortcut for misses); most of the others get their entry distance
 		// from one division instead of six (slab_classify: the instrumented variant uses that path too, so the
 		// parity tests compare its d with the oracle's bit for bit)
 		double d = __builtin_huge_val();
-		if (STATS || !slab_points_away<PROJ>(ray, f)) {
-			const int verdict = slab_classify(ray, f, !STATS, &d);
+		if (COUNT || !slab_points_away<PROJ>(ray, f)) {
+			const int verdict = slab_classify(ray, f, !COUNT, &d);
 			if (verdict == 0) d = slab_distance(ray, f);
 		}
 		if (STATS && st.entry_d) st.entry_d[(int64_t)pid.py * f.screen_w + pid.px] = d;
 
 		uint32_t rgba = 0;
 		bool real_hit = false;
+		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired, and in which cell)
+		unsigned hcell = 0u;
 
 		if (!(d == __builtin_huge_val()) && !(d < 0.0)) { // intersection(), AABB.cpp:33-44
 			double x = ray.px + d * ray.dx;
@@ -587,16 +606,16 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					for (int j = U - 1; j >= 0; --j) { // (selects, last write = earliest position)
 						const bool h = inb[j] && Z[j] < T[j];
 						const bool s = !inb[j] || h;
-						if (STATS) first = s ? j : first;
+						if (COUNT) first = s ? j : first;
 						stop = stop | s; // (lane masks: no VGPR select)
 						hit = s ? h : hit;
 						hit_cell = s ? cell[j] : hit_cell;
 						hit_j = s ? j : hit_j;
 					}
 					// loads the reference executed in this group: U unless the ray ends in it.  Only the instrumented kernel
-					// reads the budget of a ray that has ended (its step count), so only it counts the exact share of the
-					// last group; the others need the budget of rays that go on, and first + hit = U for those.
-					budget -= STATS ? first + (hit ? 1 : 0) : U;
+					// and the ray batches read the budget of a ray that has ended (its step count), so only they count the exact
+					// share of the last group; the others need the budget of rays that go on, and first + hit = U for those.
+					budget -= COUNT ? first + (hit ? 1 : 0) : U;
 					done = stop;
 					if (hit) {
 						if constexpr (BILINEAR) {
@@ -613,6 +632,16 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							rgba = shade_hit(f, cmap[hit_cell]);
 						}
 						real_hit = true;
+						if constexpr (RAYS) {
+							hx = X[0]; hy = Y[0]; hz = Z[0];
+#pragma unroll
+							for (int j = 1; j < U; ++j) {
+								hx = hit_j == j ? X[j] : hx;
+								hy = hit_j == j ? Y[j] : hy;
+								hz = hit_j == j ? Z[j] : hz;
+							}
+							hcell = hit_cell;
+						}
 					}
 				} else {
 					// (almost never) close to the step cap: the literal loop, one position at a time, cap
@@ -638,6 +667,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 						if (zs < t) { // hmap.cpp:1016
 							rgba = BILINEAR ? shade_hit_bilinear(f, cmap, c, b) : shade_hit(f, cmap[c]);
 							real_hit = true;
+							if constexpr (RAYS) { hx = xs; hy = ys; hz = zs; hcell = (unsigned)c; }
 							done = true;
 							break;
 						}
@@ -655,13 +685,17 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					az.left -= U;
 				}
 			}
-			if (STATS) my_steps = (unsigned long long)(unsigned)(budget0 - budget);
+			if (COUNT) my_steps = (unsigned long long)(unsigned)(budget0 - budget);
 		}
 
 		if (real_hit) my_hit = 1;
 		else rgba = shade_miss(f, ray.dz);
 		// (row and pitch are below 2^31, api.cpp: one 32 x 32 -> 64-bit multiply-add)
-		if constexpr (AA) aa_rgba = rgba;
+		if constexpr (RAYS) {
+			const unsigned cy = hcell / (unsigned)f.map_w; // (gridx, gridy of hmap.cpp:1001-1004 from gridx + gridy * W)
+			store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy, d,
+			                (uint32_t)my_steps, rgba);
+		} else if constexpr (AA) aa_rgba = rgba;
 		else out[(uint64_t)(uint32_t)pid.lrow * (uint32_t)out_stride_px + (uint32_t)pid.px] = rgba;
 		if (STATS && st.steps_per_pixel)
 			st.steps_per_pixel[(int64_t)pid.py * f.screen_w + pid.px] = diag.pixel_value(f, my_steps);
@@ -686,7 +720,7 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
 	if (!STATS && rows.measure) wave_t0 = __builtin_amdgcn_s_memrealtime();
 	const int tile_y = render_wave_tile<PROJ, STATS, GWM, LEAP, SAMP, AA>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
 	                                                                  blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	                                                                  (int)(threadIdx.x & 63));
+	                                                                  (int)(threadIdx.x & 63), RayBatch{});
 	if (!STATS && rows.measure && tile_y >= 0 && (threadIdx.x & 63) == 0) {
 		// record of a tile row: [0] start of its first workgroup (rows are handed out left to right), [1 + k] longest
 		// wave among the tile columns = k mod 32 (32 addresses per row: the atomics of a row's 2 x 480 waves spread out)
@@ -705,9 +739,10 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
 #endif
 }
 
-// render_fast_aa.hip compiles this file again for the antialiased instantiations of the march kernel only: the
-// pyramid, record and calibration kernels and the public launchers below live in this translation unit alone.
-#ifndef HMRM_RENDER_FAST_AA
+// render_fast_aa.hip compiles this file again for the antialiased instantiations of the march kernel only, and
+// render_rays.hip for the ray batches' (HMRM_MARCH_ONLY): the pyramid, record and calibration kernels and the public
+// launchers below live in this translation unit alone.
+#ifndef HMRM_MARCH_ONLY
 // ---------------------------------------------------------------- pyramid ----
 __host__ __device__ __forceinline__ float round_up_to_float(double v) {
 	float r = (float)v;
@@ -881,7 +916,7 @@ hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, Windo
 	return hipGetLastError();
 }
 
-#endif // HMRM_RENDER_FAST_AA
+#endif // HMRM_MARCH_ONLY
 
 // ---------------------------------------------------------------- launch ----
 template <int PROJ, bool STATS, int GWM, int LEAP, bool AA>
@@ -935,7 +970,7 @@ static void launch_proj(FastKernel leap, const DevFrame &f, const RowMap &rows, 
 	}
 }
 
-#ifndef HMRM_RENDER_FAST_AA
+#ifndef HMRM_MARCH_ONLY
 // Calibration records (RowMap::measure): kMeasureStride words per tile row, see k_render_fast's last lines.
 __global__ __launch_bounds__(256) void k_measure_init(unsigned long long *rec, int n_words) {
 	const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -973,7 +1008,7 @@ hipError_t launch_thr_to_float(const double *d_thr, float *d_thr32, int64_t n, h
 	return hipGetLastError();
 }
 
-#endif // HMRM_RENDER_FAST_AA
+#endif // HMRM_MARCH_ONLY
 
 template <bool AA>
 static hipError_t launch_fast(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
@@ -1039,7 +1074,7 @@ static hipError_t launch_fast(const DevFrame &f, const RowMap &rows, const doubl
 	return hipGetLastError();
 }
 
-#ifndef HMRM_RENDER_FAST_AA
+#ifndef HMRM_MARCH_ONLY
 hipError_t launch_render_fast(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
                               const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
                               unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
@@ -1055,7 +1090,7 @@ void render_tile_shape(int *tile_w, int *tile_h) {
 	*tile_w = kTileW;
 	*tile_h = kTileH;
 }
-#else
+#elif defined(HMRM_RENDER_FAST_AA)
 hipError_t launch_render_fast_aa(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
                                  const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
                                  unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,

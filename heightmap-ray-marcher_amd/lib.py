@@ -77,6 +77,51 @@ class Stats(C.Structure):
                 ("leaped_steps", C.c_uint64)]
 
 
+RAY_MISS, RAY_HIT, RAY_CAPPED = 0, 1, 2  # hmrm_ray_hit.status (HMRM_RAY_*)
+MAX_RAYS = 1 << 29  # rays per batch
+
+
+class Ray(C.Structure):
+    """hmrm_ray -- the reference's Ray {pos, dir}; dir is used as given, not normalised."""
+    _fields_ = [("pos", C.c_double * 3), ("dir", C.c_double * 3)]
+
+
+class RayHit(C.Structure):
+    """hmrm_ray_hit -- one record per traced ray (hmrm.h)."""
+    _fields_ = [("point", C.c_double * 3), ("entry_d", C.c_double), ("steps", C.c_uint32),
+                ("cell_x", C.c_int32), ("cell_y", C.c_int32), ("rgba", C.c_uint8 * 4),
+                ("status", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TraceParams(C.Structure):
+    """hmrm_trace_params"""
+    _fields_ = [("step_dist", C.c_double), ("bg_r", C.c_uint8), ("bg_g", C.c_uint8), ("bg_b", C.c_uint8),
+                ("sampling", C.c_uint8)]
+
+    @classmethod
+    def make(cls, step_dist, bg=(0, 0, 0), sampling=NEAREST):
+        return cls(float(step_dist), int(bg[0]) & 255, int(bg[1]) & 255, int(bg[2]) & 255, int(sampling))
+
+
+# the same layouts as numpy structured dtypes (arrays of rays in, arrays of records out)
+RAY_DTYPE = np.dtype([("pos", np.float64, 3), ("dir", np.float64, 3)])
+RAY_HIT_DTYPE = np.dtype([("point", np.float64, 3), ("entry_d", np.float64), ("steps", np.uint32),
+                          ("cell_x", np.int32), ("cell_y", np.int32), ("rgba", np.uint8, 4),
+                          ("status", np.uint32), ("reserved", np.uint32)])
+assert RAY_DTYPE.itemsize == C.sizeof(Ray) == 48 and RAY_HIT_DTYPE.itemsize == C.sizeof(RayHit) == 56
+
+
+def as_rays(rays) -> np.ndarray:
+    """An (n, 6) float64 array (pos, dir per row) or a RAY_DTYPE array -> contiguous RAY_DTYPE array of n rays."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError("rays must be an (n, 6) float64 array (pos, dir) or an array of RAY_DTYPE")
+    return a.view(RAY_DTYPE).reshape(-1)
+
+
 def degrees_to_rads(deg: float) -> float:
     """DegreesToRads, main/hmap.cpp:131-133 (same two operations, same order)."""
     return (float(deg) / 180.0) * float(np.pi)
@@ -122,6 +167,9 @@ def _load():
         "hmrm_band_local_rows": (i32, [i32, i32, i32, i32]),
         "hmrm_render_stats": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t, C.POINTER(Stats), vp, vp]),
         "hmrm_render_aa": (C.c_int, [vp, C.POINTER(Camera), i32, vp, C.c_size_t, C.POINTER(Stats)]),
+        "hmrm_trace_rays": (C.c_int, [vp, C.POINTER(TraceParams), vp, C.c_int64, vp, C.POINTER(Stats)]),
+        "hmrm_trace_rays_device": (C.c_int, [vp, C.POINTER(TraceParams), vp, C.c_int64, vp, vp]),
+        "hmrm_pick": (C.c_int, [vp, C.POINTER(Camera), i32, i32, C.POINTER(RayHit)]),
         "hmrm_debug_ray": (C.c_int, [vp, C.POINTER(Camera), i32, i32, dp, dp, dp]),
         "hmrm_debug_frame": (C.c_int, [C.POINTER(Camera), C.POINTER(SceneParams), i32, i32, vp, vp]),
         "hmrm_debug_plan_order": (C.c_int, [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), vp]),
@@ -184,7 +232,7 @@ lib, EXPORTED_SYMBOLS = _load()
 
 # Device + launch sources: a PMC summary (profiles/traffic.json) is only valid for the kernel it was
 # collected on, so it carries this hash and bench.py refuses one that does not match the tree.
-KERNEL_SOURCES = ("render_fast.hip", "leap_common.hpp", "leap_diag.hpp", "render.hip", "device_common.hpp", "frame.hpp",
+KERNEL_SOURCES = ("render_fast.hip", "render_rays.hip", "leap_common.hpp", "leap_diag.hpp", "render.hip", "device_common.hpp", "frame.hpp",
                   "render.hpp", "api.cpp", "launch_order.cpp", "launch_order.hpp", "camera.cpp", "Makefile")
 
 
@@ -362,6 +410,36 @@ class Scene:
         _check(lib.hmrm_scene_take_capped(self._h, C.c_void_p(stream), C.byref(n)),
                allow=(HMRM_E_NOTERM,) if allow_capped else ())
         return int(n.value)
+
+    def trace_rays(self, rays, step_dist, bg=(0, 0, 0), sampling=NEAREST, stats=False, allow_capped=False):
+        """Trace a batch of rays (hmrm_trace_rays): `rays` is an (n, 6) float64 array (pos, dir per row) or a RAY_DTYPE
+        array -> RAY_HIT_DTYPE array of n records, or (records, Stats) with stats=True.  A ray stopped by the step cap
+        raises HMRM_E_NOTERM unless allow_capped (its record has status RAY_CAPPED)."""
+        self._sync_env()
+        r = as_rays(rays)
+        hits = np.zeros(r.shape[0], dtype=RAY_HIT_DTYPE)
+        p = TraceParams.make(step_dist, bg, sampling)
+        st = Stats() if stats else None
+        _check(lib.hmrm_trace_rays(self._h, C.byref(p), _ptr(r), r.shape[0], _ptr(hits), C.byref(st) if stats else None),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return (hits, st) if stats else hits
+
+    def trace_rays_device(self, d_rays_ptr: int, n: int, d_hits_ptr: int, step_dist, bg=(0, 0, 0), sampling=NEAREST,
+                          stream: int = 0):
+        """hmrm_trace_rays_device: n rays (48 bytes each) and n records (56 bytes each) in device memory, enqueued on
+        `stream` without a host sync; take_capped(stream) reports rays stopped by the step cap."""
+        self._sync_env()
+        p = TraceParams.make(step_dist, bg, sampling)
+        _check(lib.hmrm_trace_rays_device(self._h, C.byref(p), C.c_void_p(d_rays_ptr), int(n), C.c_void_p(d_hits_ptr),
+                                          C.c_void_p(stream)))
+
+    def pick(self, cam: Camera, px: int, py: int, allow_capped=False) -> np.ndarray:
+        """hmrm_pick: the record (RAY_HIT_DTYPE scalar) of the ray of pixel (px, py) of `cam`."""
+        self._sync_env()
+        hit = np.zeros(1, dtype=RAY_HIT_DTYPE)
+        _check(lib.hmrm_pick(self._h, C.byref(cam), int(px), int(py), hit.ctypes.data_as(C.POINTER(RayHit))),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return hit[0]
 
     def debug_ray(self, cam: Camera, px: int, py: int):
         pos, dirv, d = (C.c_double * 3)(), (C.c_double * 3)(), C.c_double()

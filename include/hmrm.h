@@ -255,6 +255,59 @@ int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam,
 int hmrm_render_aa(const hmrm_scene *scene, const hmrm_camera *cam, int32_t factor, uint8_t *rgba, size_t stride_bytes,
                    hmrm_stats *stats);
 
+/* ------------------------------------------------------------- ray queries */
+/* The march without a camera (build-side addition; the reference has no such entry, but its loop never looks at the
+ * camera either: hmap.cpp:989-1057 takes a Ray {pos, dir} and the scene).  A ray is the reference's `Ray`: `dir` is used as
+ * given and NOT normalised (the loop does not need unit length; the perspective plane normalises before the loop,
+ * Perspective.cpp:27); zero, infinite and NaN components behave as the reference's arithmetic does on them -- (int)NaN
+ * fails the range test of hmap.cpp:1006, so such a ray misses -- and no input faults the kernel.
+ * Each ray runs exactly the body of hmap.cpp:989-1057: intersection() (AABB.cpp:33-44) sees a miss for d == inf or d < 0, so
+ * a ray whose origin lies inside the box misses, as in the reference; the entry point is nudged by grid_width * 0.01 * dir
+ * (:998); then step_dist * dir is added step by step (:1037) until a cell's height is above the ray (:1016) or the ray
+ * leaves the grid (:1006).  There is no segment limit (the reference's loop has none): compare `steps`. */
+typedef struct hmrm_ray { double pos[3]; double dir[3]; } hmrm_ray;          /* 48 bytes */
+
+enum { HMRM_RAY_MISS = 0, HMRM_RAY_HIT = 1, HMRM_RAY_CAPPED = 2 };
+
+typedef struct hmrm_ray_hit {                                                /* 56 bytes */
+	double   point[3];   /* HIT: int_point when hmap.cpp:1016 fires, the reference's bits; else 0,0,0 */
+	double   entry_d;    /* distance(ray, c0, c1), AABB.cpp:49-77, bit for bit (inf, negative and NaN included) */
+	uint32_t steps;      /* height loads the reference loop executes for this ray (hmap.cpp:1013), the hitting one included;
+	                      * CAPPED: the step cap */
+	int32_t  cell_x, cell_y; /* HIT: gridx, gridy of hmap.cpp:1001-1004; else -1, -1 */
+	uint8_t  rgba[4];    /* the pixel the reference would write for this ray (hit colour :1018-1031, alpha-0 rule :1020, sky
+	                      * and background :1041-1057; CAPPED: as a miss); A = 255 */
+	uint32_t status;     /* HMRM_RAY_*; CAPPED: stopped by the step cap (HMRM_STEP_CAP), the reference would not return */
+	uint32_t reserved;   /* written as 0 */
+} hmrm_ray_hit;
+
+typedef struct hmrm_trace_params {
+	double  step_dist;   /* hmap.cpp:68, in units of |dir| */
+	uint8_t bg_r, bg_g, bg_b;
+	uint8_t sampling;    /* HMRM_NEAREST | HMRM_BILINEAR | HMRM_NEAREST_F32 */
+} hmrm_trace_params;
+
+/* Traces rays[0 .. n) (host memory) and writes hits[0 .. n) (host memory).  Synchronous, on the scene's own stream: one such
+ * call at a time per scene, like hmrm_render.  Returns HMRM_E_NOTERM when any ray was stopped by the step cap; all n records
+ * are valid then.  stats (may be NULL) receives rays = n and steps / hits / capped summed over the batch; the traversal
+ * diagnostics are 0.  n == 0 returns HMRM_OK and launches nothing.  A NULL p, rays or hits with n > 0, n < 0, n > 2^29 or a
+ * sampling outside the enum is refused with HMRM_E_ARG before the scene is looked at.
+ * A batch is not a frame: it never triggers or counts towards the launch-order calibration, the scene's kernel probe or the
+ * cache of per-frame records, and leaves hmrm_debug_kernel_choice and every later frame as they would have been.  It does run
+ * the scene's current kernel (the probe's verdict or HMRM_KERNEL; the window records apply to HMRM_NEAREST, the other
+ * sampling modes keep the production kernel, as frames do); every kernel writes the same records. */
+int hmrm_trace_rays(const hmrm_scene *scene, const hmrm_trace_params *p, const hmrm_ray *rays, int64_t n,
+                    hmrm_ray_hit *hits, hmrm_stats *stats /* may be NULL */);
+/* The same for rays and records in DEVICE memory (n * 48 and n * 56 bytes, 8-byte aligned), enqueued on `hip_stream` (a
+ * hipStream_t, NULL = default stream) without a host sync, under the contract of hmrm_render_rows_device: rays stopped by
+ * the step cap are reported by hmrm_scene_take_capped for that stream. */
+int hmrm_trace_rays_device(const hmrm_scene *scene, const hmrm_trace_params *p, const void *d_rays, int64_t n,
+                           void *d_hits, void *hip_stream);
+/* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
+ * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
+ * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
+int hmrm_pick(const hmrm_scene *scene, const hmrm_camera *cam, int32_t px, int32_t py, hmrm_ray_hit *hit);
+
 /* Device-side ImagePlane::GetRay (ImagePlane.hpp:10) and distance()
  * (AABB.hpp:12) for one pixel -- per-ray parity hooks. */
 int hmrm_debug_ray(const hmrm_scene *scene, const hmrm_camera *cam,
