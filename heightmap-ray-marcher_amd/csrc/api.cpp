@@ -229,6 +229,8 @@ struct hmrm_scene {
 	hmrm::BatchRay *d_rays = nullptr;
 	hmrm::BatchHit *d_hits = nullptr;
 	size_t batch_cap = 0;
+	uint32_t *d_limits = nullptr; // ... and of hmrm_trace_segments' per-ray limits
+	size_t limits_cap = 0;
 	// launch state per stream; `mu` guards the list and the slot choice (launches themselves are
 	// asynchronous), so that threads driving different streams of one scene do not collide
 	std::mutex mu;
@@ -268,7 +270,9 @@ static_assert(sizeof(hmrm_ray) == sizeof(hmrm::BatchRay) && sizeof(hmrm_ray_hit)
                   offsetof(hmrm_ray_hit, entry_d) == offsetof(hmrm::BatchHit, entry_d) &&
                   offsetof(hmrm_ray_hit, steps) == offsetof(hmrm::BatchHit, steps) &&
                   offsetof(hmrm_ray_hit, rgba) == offsetof(hmrm::BatchHit, rgba) &&
-                  offsetof(hmrm_ray_hit, status) == offsetof(hmrm::BatchHit, status) && sizeof(hmrm_trace_params) == 16,
+                  offsetof(hmrm_ray_hit, status) == offsetof(hmrm::BatchHit, status) && sizeof(hmrm_trace_params) == 16 &&
+                  sizeof(hmrm_segment_params) == 24 && offsetof(hmrm_segment_params, flags) == 12 &&
+                  offsetof(hmrm_segment_params, max_steps) == 16 && offsetof(hmrm_segment_params, reserved) == 20,
               "the kernels' mirrors of hmrm_ray / hmrm_ray_hit (frame.hpp)");
 // cached records and settled launch orders are looked up with memcmp on these two: no padding bytes allowed
 static_assert(sizeof(hmrm_camera) == 3 * sizeof(int32_t) + 4 + 8 * sizeof(double), "hmrm_camera has padding");
@@ -634,12 +638,17 @@ int launch_shadow_probe(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, co
 // The render kernel itself: the literal loop (HMRM_KERNEL=simple, or a map with a side of 2^24 cells or more -- the production
 // kernel indexes cells and windows with 24-bit multiplies, leap_common.hpp index_2d), else the production kernel or the other one (the plain groups,
 // with leaps over window records where the frame's sampling allows them).
+// `interior` (hmrm_render_interior): the same choice among the kernels built with the interior rule (render_interior.hip).
 int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hmrm::RowMap &rows_in_order, uint32_t *d_out,
-                  int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool use_group) {
+                  int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool use_group, bool interior = false) {
 	const bool huge_side = s->map_w >= (1 << 24) || s->map_h >= (1 << 24);
 	if (huge_side && f.sampling != 0)
 		return fail(HMRM_E_ARG, "maps with a side of 2^24 cells or more support nearest sampling only");
 	if ((s->knobs.kernel == 2 || huge_side) && f.sampling == 0) { // (the literal loop only knows the reference's sampling)
+		if (interior) {
+			HIP_TRY(hmrm::launch_render_interior_literal(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters, c->stream));
+			return HMRM_OK;
+		}
 		HIP_TRY(hmrm::launch_render(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters, d_steps,
 		                            d_entry, stats, c->stream));
 	} else {
@@ -648,6 +657,11 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		if (k == hmrm::kRecords) {
 			const int rc_r = ensure_records(s);
 			if (rc_r) return rc_r;
+		}
+		if (interior) {
+			HIP_TRY(hmrm::launch_render_interior(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px, c->d_counters, k,
+			                                     s->d_records, c->stream));
+			return HMRM_OK;
 		}
 		HIP_TRY(hmrm::launch_render_fast(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px,
 		                                 c->d_counters, d_steps, d_entry, stats, k, s->d_records, c->stream));
@@ -667,7 +681,8 @@ int note_launch(hmrm_scene *s, StreamCtx *c) {
 // The kernel launch -- bracketed, when it is a measured one, by the set-up of the records in front of it and their read-back,
 // the record's event and the scene's fence behind it.
 int launch_maybe_measured(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot *slot, hmrm::RowMap &rows_in_order, int tiles_y,
-                          bool measure_now, uint32_t *d_out, int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool use_group) {
+                          bool measure_now, uint32_t *d_out, int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool use_group,
+                          bool interior = false) {
 	if (measure_now) {
 		const int rc_m = ensure_meas(c);
 		if (rc_m) return rc_m;
@@ -675,7 +690,7 @@ int launch_maybe_measured(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, 
 		rows_in_order.measure = c->d_meas;
 		HIP_TRY(hmrm::launch_measure_init(rows_in_order.measure, tiles_y, c->stream));
 	}
-	const int rc_k = launch_kernel(s, c, f, rows_in_order, d_out, out_stride_px, d_steps, d_entry, stats, use_group);
+	const int rc_k = launch_kernel(s, c, f, rows_in_order, d_out, out_stride_px, d_steps, d_entry, stats, use_group, interior);
 	if (rc_k || !measure_now) return rc_k;
 	const size_t idx = (size_t)(slot - c->slots);
 	HIP_TRY(hmrm::launch_measure_readback(rows_in_order.measure, c->h_meas_dev + idx * 2 * kMaxMeasRows, tiles_y, c->stream));
@@ -689,17 +704,22 @@ int launch_maybe_measured(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, 
 // groups + exact leaps), "group" (speculative groups only), "simple" (the literal
 // one-step-at-a-time loop, kept for A/B runs and as an in-library cross-check).  All produce
 // identical pixels and counts.  `no_probe`: the caller cannot have this frame launched twice (HMRM_NO_PROBE).
+// `interior` (hmrm_render_interior; 0: not such a frame): launched the way an instrumented frame is -- plain rotation order,
+// never measured, never a probe, not counted towards the probe -- with the scene's current kernel (HMRM_KERNEL or the probe's
+// verdict, read only); 2: by the kernels built with the interior rule, 1: by the ordinary ones (the host saw that no ray of the
+// frame starts inside the box).
 int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot *slot, const hmrm::RowMap &rows,
-                 uint32_t *d_out, int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool no_probe = false) {
+                 uint32_t *d_out, int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool no_probe = false,
+                 int interior = 0) {
 	hmrm::RowMap rows_in_order = rows;
 	int tile_w = 1, tile_h = 1;
 	hmrm::render_tile_shape(&tile_w, &tile_h);
 	const int tiles_y = (rows.local_rows + tile_h - 1) / tile_h;
 	const bool pieces = s->knobs.seg_n > 0 && rows.band_rows == 0 && rows.row_begin == 0; // (HMRM_TILE_SEGMENTS: an explicit order)
 	const int rot = hmrm::choose_tile_rot(s->knobs.tile_order, slot->row_cost, rows, tile_h);
-	const bool may_probe = !stats && s->knobs.kernel == 0 && s->knobs.try_group;
+	const bool may_probe = !stats && !interior && s->knobs.kernel == 0 && s->knobs.try_group;
 	// calibration (launch_order.hpp): full frames of the fast kernels only
-	const bool eligible = !pieces && !stats && s->knobs.tile_order && s->knobs.order_mode == 2 && s->knobs.kernel != 2 &&
+	const bool eligible = !pieces && !stats && !interior && s->knobs.tile_order && s->knobs.order_mode == 2 && s->knobs.kernel != 2 &&
 	                      rows.band_rows == 0 && rows.row_begin == 0 && rows.local_rows == f.screen_h && tiles_y >= 12 &&
 	                      tiles_y <= kMaxMeasRows && s->map_w < (1 << 24) && s->map_h < (1 << 24);
 	int rc = wait_for_measure_fence(s, c);
@@ -711,6 +731,7 @@ int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot
 		for (int k = 0; k < 3; ++k) { order.b[k] = s->knobs.seg_b[k]; order.c[k] = s->knobs.seg_c[k]; }
 	}
 	bool use_group = may_probe && s->choice.use_group; // strips, bands, small frames: the scene's verdict
+	if (interior) use_group = s->knobs.kernel == 0 && s->knobs.try_group && s->choice.use_group; // (the verdict, never a probe)
 	bool measure_now = false;
 	if (eligible) {
 		poll_measured(s, c, slot, tiles_y, rot);
@@ -730,7 +751,7 @@ int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot
 	hmrm::set_tile_order(&rows_in_order, tiles_y, rot, order.n, order.b, order.c);
 	// (a measured launch that cannot be issued or reported must not stay "in flight" in the record: nothing would ever
 	// report it, and the record's next reuse would wait for an event that was never recorded)
-	if ((rc = launch_maybe_measured(s, c, f, slot, rows_in_order, tiles_y, measure_now, d_out, out_stride_px, d_steps, d_entry, stats, use_group))) {
+	if ((rc = launch_maybe_measured(s, c, f, slot, rows_in_order, tiles_y, measure_now, d_out, out_stride_px, d_steps, d_entry, stats, use_group, interior == 2))) {
 		if (measure_now) slot->cal.drop_in_flight();
 		return rc;
 	}
@@ -891,6 +912,26 @@ int check_trace(const hmrm_trace_params *p, const void *rays, int64_t n, const v
 	return HMRM_OK;
 }
 
+// hmrm_trace_segments' refusals: check_trace's, then the flags and the reserved word.
+int check_segments(const hmrm_segment_params *p, const void *rays, int64_t n, const void *hits, hmrm_trace_params *plain) {
+	if (p) *plain = hmrm_trace_params{p->step_dist, p->bg_r, p->bg_g, p->bg_b, p->sampling};
+	const int rc = check_trace(p ? plain : nullptr, rays, n, hits);
+	if (rc) return rc;
+	if (p && (p->flags & ~(uint32_t)HMRM_TRACE_INTERIOR)) return fail(HMRM_E_ARG, "trace: unknown flag bits (defined: HMRM_TRACE_INTERIOR)");
+	if (p && p->reserved != 0u) return fail(HMRM_E_ARG, "trace: hmrm_segment_params.reserved must be 0");
+	return HMRM_OK;
+}
+
+int ensure_limits(hmrm_scene *s, size_t n) {
+	if (n <= s->limits_cap) return HMRM_OK;
+	if (s->d_limits) (void)hipFree(s->d_limits);
+	s->d_limits = nullptr;
+	s->limits_cap = 0;
+	HIP_TRY(hipMalloc((void **)&s->d_limits, n * sizeof(uint32_t)));
+	s->limits_cap = n;
+	return HMRM_OK;
+}
+
 int ensure_batch(hmrm_scene *s, size_t n) {
 	if (n <= s->batch_cap) return HMRM_OK;
 	if (s->d_rays) (void)hipFree(s->d_rays);
@@ -910,8 +951,9 @@ int ensure_batch(hmrm_scene *s, size_t n) {
 // (HMRM_KERNEL or the probe's verdict), and waits -- in stream order -- for a measured launch in flight like any launch.
 // The leap policy's hints come from a camera's step length in cells for frames (camera.cpp); a batch's directions have
 // any length, so it gets the fine-step defaults: windows from 4 cells on, no pause (HMRM_MIN_LEVEL / HMRM_FINEST_PAUSE apply).
+// `seg` (hmrm_trace_segments; null: hmrm_trace_rays): the segment rules, run by the segment kernels (render_segments.hip).
 int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg[3], int sampling, const hmrm::BatchRay *d_rays,
-                 int64_t n, hmrm::BatchHit *d_hits) {
+                 int64_t n, hmrm::BatchHit *d_hits, const hmrm::SegRules *seg = nullptr) {
 	const bool huge_side = s->map_w >= (1 << 24) || s->map_h >= (1 << 24);
 	if (huge_side && sampling != 0) return fail(HMRM_E_ARG, "maps with a side of 2^24 cells or more support nearest sampling only");
 	if (sampling == HMRM_BILINEAR) {
@@ -941,12 +983,14 @@ int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg
 	int rc = wait_for_measure_fence(s, c);
 	if (rc) return rc;
 	if ((s->knobs.kernel == 2 || huge_side) && sampling == 0) { // (the literal loop only knows the reference's sampling)
-		HIP_TRY(hmrm::launch_trace_rays_literal(f, s->d_thr, s->d_cmap, batch, c->d_counters, c->stream));
+		if (seg) HIP_TRY(hmrm::launch_trace_segments_literal(f, s->d_thr, s->d_cmap, batch, *seg, c->d_counters, c->stream));
+		else HIP_TRY(hmrm::launch_trace_rays_literal(f, s->d_thr, s->d_cmap, batch, c->d_counters, c->stream));
 	} else {
 		const bool use_other = s->knobs.kernel == 0 && s->knobs.try_group && s->choice.use_group; // (the verdict, never a probe)
 		const hmrm::FastKernel k = (hmrm::FastKernel)hmrm::pick_fast_kernel(s->knobs.kernel, use_other, sampling == 0 && s->d_records, s->choice);
 		if (k == hmrm::kRecords && (rc = ensure_records(s))) return rc;
-		HIP_TRY(hmrm::launch_trace_rays(f, s->d_thr, s->d_thr32, s->d_cmap, batch, c->d_counters, k, s->d_records, c->stream));
+		if (seg) HIP_TRY(hmrm::launch_trace_segments(f, s->d_thr, s->d_thr32, s->d_cmap, batch, *seg, c->d_counters, k, s->d_records, c->stream));
+		else HIP_TRY(hmrm::launch_trace_rays(f, s->d_thr, s->d_thr32, s->d_cmap, batch, c->d_counters, k, s->d_records, c->stream));
 	}
 	return note_launch(s, c);
 }
@@ -1113,6 +1157,7 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	if (s->d_entry) (void)hipFree(s->d_entry);
 	if (s->d_rays) (void)hipFree(s->d_rays);
 	if (s->d_hits) (void)hipFree(s->d_hits);
+	if (s->d_limits) (void)hipFree(s->d_limits);
 	if (s->ev0) (void)hipEventDestroy(s->ev0);
 	if (s->ev1) (void)hipEventDestroy(s->ev1);
 	if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -1167,7 +1212,8 @@ int hmrm_scene_read_heights(const hmrm_scene *cs, double *out) {
 // aa_factor > 1 (hmrm_render_aa): the launch marches the super frame and writes the W x H box-filtered frame (no per-pixel
 // arrays then).
 static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes,
-                         hmrm_stats *stats, uint32_t *steps_pp, double *entry_d, bool want_stats, int32_t aa_factor = 1) {
+                         hmrm_stats *stats, uint32_t *steps_pp, double *entry_d, bool want_stats, int32_t aa_factor = 1,
+                         bool interior = false) {
 	int rc = check_camera(cam);
 	if (rc) return rc;
 	hmrm_camera super;
@@ -1187,6 +1233,15 @@ static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, s
 	if ((rc = prepare_frame(s, c, &super, &f, &slot))) return rc;
 	f.aa_shift = aa_shift;
 	hmrm::RowMap rows{0, super.height, 0, 0, 1, {}, {}, nullptr};
+	// hmrm_render_interior: perspective and spherical rays all start at the camera, so the rule is decided once per frame --
+	// a camera that is not strictly inside the box gets the ordinary kernel, hmrm_render's frame; orthographic origins differ
+	// per pixel, the kernel tests each
+	int interior_mode = 0;
+	if (interior) {
+		const double *o = f.cam;
+		const bool cam_inside = f.c0[0] < o[0] && o[0] < f.c1[0] && f.c1[1] < o[1] && o[1] < f.c0[1] && f.c0[2] < o[2] && o[2] < f.c1[2];
+		interior_mode = (cam->projection == HMRM_ORTHOGRAPHIC || cam_inside) ? 2 : 1;
+	}
 	if (want_stats) {
 		HIP_TRY(hipMemsetAsync(c->d_counters, 0, 2 * sizeof(unsigned long long), s->stream));
 		HIP_TRY(hipMemsetAsync(c->d_counters + 4, 0, 4 * sizeof(unsigned long long), s->stream));
@@ -1194,7 +1249,7 @@ static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, s
 	HIP_TRY(hipEventRecord(s->ev0, s->stream));
 	const bool per_pixel = want_stats && aa_shift == 0; // (per-pixel arrays are of the plain frame only)
 	if ((rc = launch_frame(s, c, f, slot, rows, s->d_frame, (int64_t)W, per_pixel ? s->d_steps : nullptr,
-	                       per_pixel ? s->d_entry : nullptr, want_stats)))
+	                       per_pixel ? s->d_entry : nullptr, want_stats, false, interior_mode)))
 		return rc;
 	HIP_TRY(hipEventRecord(s->ev1, s->stream));
 	HIP_TRY(hipMemcpy2DAsync(rgba, stride_bytes, s->d_frame, W * 4, W * 4, H, hipMemcpyDeviceToHost,
@@ -1256,6 +1311,10 @@ int hmrm_render_aa(const hmrm_scene *scene, const hmrm_camera *cam, int32_t fact
                    hmrm_stats *stats) {
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, stats, nullptr, nullptr, stats != nullptr,
 	                     factor);
+}
+
+int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes) {
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, nullptr, nullptr, nullptr, false, 1, true);
 }
 
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
@@ -1744,6 +1803,7 @@ const char *hmrm_config_output_path(const hmrm_config *c) { return c->cfg.output
 int32_t hmrm_config_record_mode(const hmrm_config *c) { return c->cfg.record_mode; }
 int32_t hmrm_config_devices(const hmrm_config *c) { return c->cfg.devices; }
 int32_t hmrm_config_antialias(const hmrm_config *c) { return c->cfg.antialias; }
+int32_t hmrm_config_interior(const hmrm_config *c) { return c->cfg.interior; }
 
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *c, int32_t *w, int32_t *h) {
 	if (!c->cfg.have_heightmap) return nullptr;
@@ -1874,6 +1934,51 @@ int hmrm_trace_rays_device(const hmrm_scene *scene, const hmrm_trace_params *p, 
 	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
 	return launch_batch(s, c, p->step_dist, bg, p->sampling, static_cast<const hmrm::BatchRay *>(d_rays), n,
 	                    static_cast<hmrm::BatchHit *>(d_hits));
+}
+
+int hmrm_trace_segments(const hmrm_scene *scene, const hmrm_segment_params *p, const hmrm_ray *rays, const uint32_t *max_steps,
+                        int64_t n, hmrm_ray_hit *hits, hmrm_stats *stats) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	hmrm_trace_params plain{};
+	int rc = check_segments(p, rays, n, hits, &plain);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	if (n == 0) {
+		if (stats) *stats = hmrm_stats{};
+		return HMRM_OK;
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	if ((rc = ensure_batch(s, (size_t)n))) return rc;
+	if (max_steps && (rc = ensure_limits(s, (size_t)n))) return rc;
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, s->stream, &c))) return rc;
+	HIP_TRY(hipMemcpyAsync(s->d_rays, rays, (size_t)n * sizeof(hmrm_ray), hipMemcpyHostToDevice, s->stream));
+	if (max_steps) HIP_TRY(hipMemcpyAsync(s->d_limits, max_steps, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
+	const hmrm::SegRules seg{max_steps ? s->d_limits : nullptr, p->max_steps, p->flags & HMRM_TRACE_INTERIOR};
+	if ((rc = launch_batch(s, c, p->step_dist, bg, p->sampling, s->d_rays, n, s->d_hits, &seg))) return rc;
+	return finish_batch(s, c, hits, n, stats);
+}
+
+int hmrm_trace_segments_device(const hmrm_scene *scene, const hmrm_segment_params *p, const void *d_rays, const void *d_max_steps,
+                               int64_t n, void *d_hits, void *hip_stream) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	hmrm_trace_params plain{};
+	int rc = check_segments(p, d_rays, n, d_hits, &plain);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	if (n == 0) return HMRM_OK;
+	if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 7u) return fail(HMRM_E_ARG, "trace: d_rays and d_hits must be 8-byte aligned");
+	if ((uintptr_t)d_max_steps & 3u) return fail(HMRM_E_ARG, "trace: d_max_steps must be 4-byte aligned");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
+	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
+	const hmrm::SegRules seg{static_cast<const uint32_t *>(d_max_steps), p->max_steps, p->flags & HMRM_TRACE_INTERIOR};
+	return launch_batch(s, c, p->step_dist, bg, p->sampling, static_cast<const hmrm::BatchRay *>(d_rays), n,
+	                    static_cast<hmrm::BatchHit *>(d_hits), &seg);
 }
 
 // Picking: GetRay of one pixel on the device (k_probe, as hmrm_debug_ray) and that ray traced as a batch of one.  Like a

@@ -12,7 +12,7 @@
 // keys at run time, :851-868, and only ever writes PNG):
 //   projection perspective|spherical|orthographic   (or 1|2|3)
 //   output <path>                                   (.png or .ppm)
-//   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8
+//   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8, interior on|off
 #include "config.hpp"
 
 #include <cmath>
@@ -188,6 +188,13 @@ void antialias_key(Config &c, std::istream &in, const char *key, std::string *) 
 	c.log << key << " " << c.antialias << "\n";
 }
 
+void interior_key(Config &c, std::istream &in, const char *key, std::string *) { // a camera inside the box sees the terrain (hmrm_render_interior)
+	static const Word words[] = {{"on", 1}, {"1", 1}, {"off", 0}, {"0", 0}};
+	std::string seen;
+	if (!pick(in, words, &c.interior, &seen)) c.warn << "WARNING: Unknown interior: " << seen << "\n";
+	c.log << key << " " << (c.interior ? "on" : "off") << "\n";
+}
+
 struct Row { const char *key; Handler apply; };
 const Row kGrammar[] = {
 	// the reference's 27 keys (main/hmap.cpp:314-488)
@@ -226,6 +233,7 @@ const Row kGrammar[] = {
 	{"devices", device_count_key},
 	{"record", record_mode_key},
 	{"antialias", antialias_key},
+	{"interior", interior_key},
 };
 
 } // namespace

@@ -40,6 +40,8 @@ struct Config {
 	int sampling = 0;
 	// additive: `antialias n` -- hmrm_render_aa's factor (1 = off, 2, 4, 8)
 	int antialias = 1;
+	// additive: `interior on|off|1|0` -- the CLI's single frame under the interior rule (hmrm_render_interior)
+	int interior = 0;
 
 	bool heightmap_dirty = false; // should_update_heightmap, sticky until taken
 	std::ostringstream log;       // what the reference prints to stdout

@@ -67,7 +67,8 @@ __device__ __forceinline__ DevRay batch_ray(const RayBatch &b, int64_t index) {
 // The record of a batch ray (hmrm.h hmrm_ray_hit): `hit` with the position and the cell at which hmap.cpp:1016 fired,
 // `capped` for a ray stopped by the step cap (`rgba` is the miss shade then, like a miss).
 __device__ __forceinline__ void store_batch_hit(const RayBatch &b, int64_t index, bool hit, bool capped, double x, double y,
-                                                double z, int cell_x, int cell_y, double d, uint32_t steps, uint32_t rgba) {
+                                                double z, int cell_x, int cell_y, double d, uint32_t steps, uint32_t rgba,
+                                                bool ended = false) { // (ended: HMRM_RAY_END, segment batches only)
 	BatchHit *__restrict__ out = b.hits + index;
 	out->point[0] = hit ? x : 0.0;
 	out->point[1] = hit ? y : 0.0;
@@ -77,8 +78,31 @@ __device__ __forceinline__ void store_batch_hit(const RayBatch &b, int64_t index
 	out->cell_x = hit ? cell_x : -1;
 	out->cell_y = hit ? cell_y : -1;
 	__builtin_memcpy(out->rgba, &rgba, 4);
-	out->status = hit ? 1u : (capped ? 2u : 0u);
+	out->status = hit ? 1u : (capped ? 2u : (ended ? 3u : 0u));
 	out->reserved = 0u;
+}
+
+// The segment rules (frame.hpp SegRules; hmrm_trace_segments, hmrm_render_interior).  Strictly inside the box: all six
+// comparisons true, NaN fails them; an origin exactly on a face is not inside.  (c1.y = -map_h * gw is the LOW end of y.)
+__device__ __forceinline__ bool origin_strictly_inside(const DevRay &r, const DevFrame &f) {
+	return f.c0[0] < r.px && r.px < f.c1[0] && f.c1[1] < r.py && r.py < f.c0[1] && f.c0[2] < r.pz && r.pz < f.c1[2];
+}
+// What a lane keeps for the rules (SEG in the kernels); empty in every other instantiation, which stay as they were.
+template <bool SEG> struct SegState {};
+template <> struct SegState<true> {
+	double d_record = 0.0; // distance()'s own value, for the record
+	int budget = 0;        // min(step cap, the ray's own limit)
+	bool ends = false;     // running out of it is the ray's own end (HMRM_RAY_END), not the step cap
+	bool ended = false;
+};
+// A ray's step budget under the rules: min(step cap, L), L = the smaller of the non-zero values among the batch's limit and
+// the ray's own (0 = none).  *ends: running out of it is the ray's own end (L != 0 && L < step cap), not the step cap.
+__device__ __forceinline__ int segment_budget(const SegRules &seg, int64_t index, int64_t step_cap, bool *ends) {
+	const uint32_t own = seg.max_steps ? seg.max_steps[index] : 0u;
+	const uint32_t l = seg.limit == 0u ? own : (own == 0u ? seg.limit : (own < seg.limit ? own : seg.limit));
+	const int cap = step_cap > 0x7fffffff ? 0x7fffffff : (int)step_cap;
+	*ends = l != 0u && (int64_t)l < (int64_t)cap;
+	return *ends ? (int)l : cap;
 }
 
 // AABB.cpp:49-77, axis order x,y,z, same comparisons (NaN => every test false).

@@ -178,6 +178,18 @@ struct RayBatch {
 };
 constexpr int kBatchW = 8; // (= device_common.hpp kWaveW, asserted there)
 
+// ---- segment rules (hmrm_trace_segments, hmrm_render_interior; SEG in the kernels) ----
+// interior: a ray whose origin lies strictly inside the box (c0.x < x < c1.x, c1.y < y < c0.y, c0.z < z < c1.z; NaN fails)
+// runs the body of hmap.cpp:989-1057 as if distance() had returned +0.0 -- the reference makes it a miss (AABB.cpp:37-39).
+// limit / max_steps[i]: the ray ends after L height loads (hmap.cpp:1013) when the L-th did not hit, L = the smaller of the
+// non-zero values of the two (0 = none); inside the grid then: HMRM_RAY_END, unless L >= the step cap (CAPPED as before).
+// An extra argument of the segment kernels' own __global__ entry points, like RayBatch: nothing existing changes.
+struct SegRules {
+	const uint32_t *max_steps; // per ray (batches), device memory, may be null
+	uint32_t limit;            // for every ray
+	uint32_t interior;         // != 0: the interior rule is on
+};
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

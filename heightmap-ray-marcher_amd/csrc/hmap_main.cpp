@@ -7,7 +7,9 @@
 // ONE full frame (`cycle 1` semantics) on the GPU and saves it the way F12 does
 // (hmap.cpp:828-850 -> SavePNG :157-168): to the config's `output` path if
 // given (.ppm selects binary PPM), else screenshots/hmap_<epoch>.png.  `antialias n` renders (and records)
-// n x n box-filtered samples per pixel (hmrm_render_aa).
+// n x n box-filtered samples per pixel (hmrm_render_aa).  `interior on` renders the single frame under the interior rule
+// (hmrm_render_interior: a camera inside the box sees the terrain); it is ignored, with a warning, together with
+// `antialias` > 1, `devices` > 1 or `record orbit`.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -61,6 +63,7 @@ int main(int argc, char *argv[]) {
 		return 1;
 	}
 	const int32_t aa = hmrm_config_antialias(cfg);
+	const bool interior = hmrm_config_interior(cfg) != 0;
 	hmrm_scene *scene = NULL;
 	if (hmrm_config_create_scene(cfg, &scene) != HMRM_OK) {
 		std::cerr << hmrm_last_error() << "\n";
@@ -68,6 +71,7 @@ int main(int argc, char *argv[]) {
 	}
 
 	if (hmrm_config_record_mode(cfg) == 1) {
+		if (interior) std::cerr << "WARNING: interior is ignored with record orbit\n";
 		// `record orbit`: recording_frame_count frames on a circle around the map centre through
 		// the configured camera position, always looking at the centre;
 		// files screenshots/hmap_<epoch>_<n>.png as hmap.cpp:1131-1144.
@@ -114,7 +118,18 @@ int main(int argc, char *argv[]) {
 	const int want_dev = wanted_devices(cfg, &visible_dev);
 	if (want_dev > 1 && aa > 1)
 		std::cerr << "WARNING: antialias " << aa << " renders the single frame on one device (devices " << want_dev << " ignored)\n";
-	if (want_dev > 1 && aa == 1) {
+	if (interior && (want_dev > 1 || aa > 1))
+		std::cerr << "WARNING: interior is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
+	if (interior && want_dev <= 1 && aa == 1) {
+		rc = hmrm_render_interior(scene, &cam, framebuf.data(), (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height << " rays under the interior rule in " << hmrm_last_kernel_ms()
+		          << " ms (kernel)\n";
+	} else if (want_dev > 1 && aa == 1) {
 		// `devices n`: the frame's 16-row bands are dealt out over n GPUs (BASELINE config C4)
 		std::vector<hmrm_scene *> scenes(1, scene);
 		for (int d = 1; d < want_dev && rc == HMRM_OK; ++d) {

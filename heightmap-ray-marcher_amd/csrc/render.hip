@@ -78,12 +78,15 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 // The literal loop for the pixel (or, PROJ 4, the batch ray: hmrm_trace_rays, frame.hpp RayBatch) of one lane.
 // AA: the antialiased epilogue (device_common.hpp store_box_filtered, f.aa_shift); the plain instantiations store per lane.
 // PROJ 4: the lane's ray comes from `batch` and its hmrm_ray_hit record goes there; `out` is not used.
-template <int PROJ, bool STATS, bool AA>
+// SEG: the segment rules (frame.hpp SegRules; hmrm_trace_segments, hmrm_render_interior), as in render_fast.hip.
+template <int PROJ, bool STATS, bool AA, bool SEG = false>
 __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId pid, const double *__restrict__ thr,
                                                     const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
-                                                    int64_t out_stride_px, const StatsOut &st, const RayBatch &batch) {
+                                                    int64_t out_stride_px, const StatsOut &st, const RayBatch &batch,
+                                                    const SegRules &seg = SegRules{}) {
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
+	static_assert(!SEG || (!AA && !STATS), "segment rules: production kernels only");
 	// (what a batch adds is written as `if constexpr (RAYS)` statements beside the frame kernels' own, which stay as they
 	// were: they must keep compiling to the same instructions)
 	int64_t ray_index = 0;
@@ -101,8 +104,15 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 	if (live) {
 		DevRay ray = make_ray<PROJ>(f, px, py);
 		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
-		const double d = slab_distance(ray, f);
-		if (STATS && st.entry_d) st.entry_d[(int64_t)py * f.screen_w + px] = d;
+		const double d_box = slab_distance(ray, f);
+		if (STATS && st.entry_d) st.entry_d[(int64_t)py * f.screen_w + px] = d_box;
+		double d = d_box;
+		SegState<SEG> sg; // (empty unless SEG: device_common.hpp)
+		if constexpr (SEG) {
+			sg.d_record = d_box; // (a record keeps distance()'s own value, not the d that was used)
+			if (seg.interior != 0u && origin_strictly_inside(ray, f)) d = 0.0; // as if distance() had returned +0.0
+			sg.budget = segment_budget(seg, RAYS ? ray_index : 0, f.step_cap, &sg.ends);
+		}
 
 		uint32_t rgba = 0;
 		bool real_hit = false;
@@ -126,6 +136,7 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 			const double c0x = f.c0[0], c0y = f.c0[1];
 			const bool pow2 = f.grid_pow2 != 0;
 			int64_t budget = f.step_cap;
+			if constexpr (SEG) budget = sg.budget; // (min(step cap, the ray's own limit))
 
 			for (;;) {
 				// hmap.cpp:1001-1004
@@ -171,7 +182,12 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 		} else {
 			my_hit = 1;
 		}
-		if constexpr (RAYS) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, d, (uint32_t)my_steps, rgba);
+		if constexpr (SEG) { // an END ray is not a capped one: not counted, never HMRM_E_NOTERM
+			sg.ended = my_cap != 0u && sg.ends;
+			my_cap = sg.ended ? 0u : my_cap;
+		}
+		if constexpr (RAYS && SEG) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
+		else if constexpr (RAYS) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, d_box, (uint32_t)my_steps, rgba);
 		else if constexpr (AA) aa_rgba = rgba;
 		else out[(int64_t)lrow * out_stride_px + px] = rgba;
 		if (STATS && st.steps_per_pixel)
@@ -204,6 +220,24 @@ __global__ __launch_bounds__(kBlockThreads) void k_trace_rays_literal(const DevF
 	const PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, 0, blockIdx.z * 32768u + blockIdx.x, (int)(threadIdx.x >> 6),
 	                                       (int)(threadIdx.x & 63));
 	render_lane_literal<4, false, false>(f, pid, thr, cmap, nullptr, 0, st, batch);
+}
+
+// The same two under the segment rules (hmrm_render_interior, hmrm_trace_segments with HMRM_KERNEL=simple).
+template <int PROJ>
+__global__ __launch_bounds__(kBlockThreads) void k_render_interior_literal(const DevFrame f, const RowMap rows,
+                                                                           const double *__restrict__ thr,
+                                                                           const uint32_t *__restrict__ cmap,
+                                                                           uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                           int tiles_y, StatsOut st, const SegRules seg) {
+	render_lane_literal<PROJ, false, false, true>(f, pixel_of_lane(f, rows, tiles_y), thr, cmap, out, out_stride_px, st, RayBatch{}, seg);
+}
+__global__ __launch_bounds__(kBlockThreads) void k_trace_segments_literal(const DevFrame f, const double *__restrict__ thr,
+                                                                          const uint32_t *__restrict__ cmap, const RayBatch batch,
+                                                                          const SegRules seg, int tiles_y, StatsOut st) {
+	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, 0, blockIdx.z * 32768u + blockIdx.x, (int)(threadIdx.x >> 6),
+	                                       (int)(threadIdx.x & 63));
+	render_lane_literal<4, false, false, true>(f, pid, thr, cmap, nullptr, 0, st, batch, seg);
 }
 
 // Per-ray parity hook: GetRay + distance() of one pixel -> out[0..2] pos, [3..5] dir, [6] d.
@@ -360,6 +394,34 @@ hipError_t launch_trace_rays_literal(const DevFrame &f, const double *d_thr, con
 	const dim3 grid((unsigned)(tiles_y < 32768 ? tiles_y : 32768), 1u, (unsigned)((tiles_y + 32767) / 32768));
 	hipLaunchKernelGGL(k_trace_rays_literal, grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_cmap, batch, tiles_y,
 	                   StatsOut{d_counters, nullptr, nullptr});
+	return hipGetLastError();
+}
+
+hipError_t launch_trace_segments_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
+                                         const SegRules &seg, unsigned long long *d_counters, hipStream_t stream) {
+	if (batch.n <= 0) return hipSuccess;
+	if (batch.n > ((int64_t)1 << 29) || f.screen_w != kBatchW || (int64_t)f.screen_h * kBatchW < batch.n) return hipErrorInvalidValue;
+	const int tiles_y = (f.screen_h + kTileH - 1) / kTileH;
+	const dim3 grid((unsigned)(tiles_y < 32768 ? tiles_y : 32768), 1u, (unsigned)((tiles_y + 32767) / 32768));
+	hipLaunchKernelGGL(k_trace_segments_literal, grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_cmap, batch, seg, tiles_y,
+	                   StatsOut{d_counters, nullptr, nullptr});
+	return hipGetLastError();
+}
+
+hipError_t launch_render_interior_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                          uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                          hipStream_t stream) {
+	const int tiles_x = (f.screen_w + kTileW - 1) / kTileW;
+	const int tiles_y = (rows.local_rows + kTileH - 1) / kTileH;
+	if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
+	const dim3 grid((unsigned)tiles_x, (unsigned)(tiles_y < 32768 ? tiles_y : 32768), (unsigned)((tiles_y + 32767) / 32768)), block(kBlockThreads);
+	const StatsOut st{d_counters, nullptr, nullptr};
+	const SegRules seg{nullptr, 0u, 1u};
+	switch (f.projection) {
+	case 1: hipLaunchKernelGGL(k_render_interior_literal<1>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
+	case 2: hipLaunchKernelGGL(k_render_interior_literal<2>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
+	default: hipLaunchKernelGGL(k_render_interior_literal<3>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
+	}
 	return hipGetLastError();
 }
 

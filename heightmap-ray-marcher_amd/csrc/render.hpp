@@ -47,6 +47,22 @@ hipError_t launch_trace_rays(const DevFrame &f, const double *d_thr, const float
                              const WindowRecord *d_records, hipStream_t stream);
 hipError_t launch_trace_rays_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
                                      unsigned long long *d_counters, hipStream_t stream);
+// The same two under the segment rules (frame.hpp SegRules; hmrm_trace_segments -- render_segments.hip, kernels of its own --
+// and the literal loop in render.hip).  Records: status 3 (HMRM_RAY_END) for a ray ended by its own limit inside the grid;
+// d_counters[2] counts CAPPED rays only.
+hipError_t launch_trace_segments(const DevFrame &f, const double *d_thr, const float *d_thr32, const uint32_t *d_cmap,
+                                 const RayBatch &batch, const SegRules &seg, unsigned long long *d_counters, FastKernel kernel,
+                                 const WindowRecord *d_records, hipStream_t stream);
+hipError_t launch_trace_segments_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
+                                         const SegRules &seg, unsigned long long *d_counters, hipStream_t stream);
+// Frames under the interior rule (hmrm_render_interior; render_interior.hip: the production kernels' instantiations with the
+// rule, a translation unit of its own, and the literal loop in render.hip).  Not instrumented, not antialiased, never measured.
+hipError_t launch_render_interior(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
+                                  const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                  FastKernel kernel, const WindowRecord *d_records, hipStream_t stream);
+hipError_t launch_render_interior_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                          uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                          hipStream_t stream);
 // The record table of the thr table: rec_row(map_w) x ceil(map_h / 4) WindowRecords.
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream);
 // thr32[i] = (float)thr[i], round to nearest (the "float heights" mode).

@@ -44,7 +44,7 @@
 #include <cstdio>
 #include <cstdlib>
 #endif
-#if defined(HMRM_RENDER_FAST_AA) || defined(HMRM_RENDER_RAYS)
+#if defined(HMRM_RENDER_FAST_AA) || defined(HMRM_RENDER_RAYS) || defined(HMRM_RENDER_SEGMENTS) || defined(HMRM_RENDER_INTERIOR)
 #define HMRM_MARCH_ONLY 1 // (this translation unit instantiates the march kernel for its own purpose, see the end of k_render_fast)
 #endif
 #include "device_common.hpp"
@@ -184,14 +184,19 @@ __device__ TimelineRec *g_timeline = nullptr;
 // lane's ray is loaded from `batch`, not made from a camera, and instead of a pixel the lane writes its hmrm_ray_hit record,
 // which wants distance()'s value for misses too and the ray's exact step count: the two things the instrumented
 // instantiation computes (COUNT below), without its diagnostics or its wave-wide counters.  `out` is not used then.
-template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA>
+// SEG (instantiated in render_segments.hip and render_interior.hip only; hmrm_trace_segments, hmrm_render_interior): the two
+// segment rules of frame.hpp SegRules -- a ray whose origin is strictly inside the box enters it at d = +0.0 instead of
+// missing, and a ray ends after its own number of height loads (HMRM_RAY_END) -- written like PROJ == 4, as `if constexpr`
+// statements beside the others' own.  The loop needs nothing new: it is position based and each lane has its budget.
+template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
-                                                int wave, int lane, const RayBatch &batch) {
+                                                int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{}) {
 	constexpr bool BILINEAR = SAMP == 1, F32 = SAMP == 2;
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
+	static_assert(!SEG || (!AA && !STATS), "segment rules: production kernels only");
 	constexpr bool REC = LEAP == 2;                     // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
 	constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
 	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
@@ -224,6 +229,12 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			if (verdict == 0) d = slab_distance(ray, f);
 		}
 		if (STATS && st.entry_d) st.entry_d[(int64_t)pid.py * f.screen_w + pid.px] = d;
+		SegState<SEG> sg; // (empty unless SEG: device_common.hpp)
+		if constexpr (SEG) {
+			sg.d_record = d; // (a record keeps distance()'s own value, not the d that was used)
+			if (seg.interior != 0u && origin_strictly_inside(ray, f)) d = 0.0; // as if distance() had returned +0.0
+			sg.budget = segment_budget(seg, RAYS ? ray_index : 0, f.step_cap, &sg.ends);
+		}
 
 		uint32_t rgba = 0;
 		bool real_hit = false;
@@ -243,6 +254,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			const unsigned wlim = (unsigned)f.map_w, hlim = (unsigned)f.map_h;
 			const int budget0 = f.step_cap > 0x7fffffff ? 0x7fffffff : (int)f.step_cap;
 			int budget = budget0; // every step taken or leaped comes off it: steps so far = budget0 - budget
+			if constexpr (SEG) budget = sg.budget; // (min(step cap, the ray's own limit): steps so far = sg.budget - budget)
 			// (int)NaN is INT_MIN on the reference's CPU: the first range test fails, the ray misses
 			const bool entry_nan = x != x || y != y;
 
@@ -686,13 +698,22 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				}
 			}
 			if (COUNT) my_steps = (unsigned long long)(unsigned)(budget0 - budget);
+			if constexpr (SEG && COUNT) my_steps = (unsigned long long)(unsigned)(sg.budget - budget);
 		}
 
 		if (real_hit) my_hit = 1;
 		else rgba = shade_miss(f, ray.dz);
+		if constexpr (SEG) { // an END ray is not a capped one: not counted, never HMRM_E_NOTERM
+			sg.ended = my_cap != 0u && sg.ends;
+			my_cap = sg.ended ? 0u : my_cap;
+		}
 		// (row and pitch are below 2^31, api.cpp: one 32 x 32 -> 64-bit multiply-add)
 		if constexpr (RAYS) {
 			const unsigned cy = hcell / (unsigned)f.map_w; // (gridx, gridy of hmap.cpp:1001-1004 from gridx + gridy * W)
+			if constexpr (SEG) {
+				store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy,
+				                sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
+			} else
 			store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy, d,
 			                (uint32_t)my_steps, rgba);
 		} else if constexpr (AA) aa_rgba = rgba;

@@ -78,6 +78,8 @@ class Stats(C.Structure):
 
 
 RAY_MISS, RAY_HIT, RAY_CAPPED = 0, 1, 2  # hmrm_ray_hit.status (HMRM_RAY_*)
+RAY_END = 3  # ... of hmrm_trace_segments: ended by the ray's own step limit, inside the grid
+TRACE_INTERIOR = 1  # hmrm_segment_params.flags (HMRM_TRACE_INTERIOR)
 MAX_RAYS = 1 << 29  # rays per batch
 
 
@@ -101,6 +103,17 @@ class TraceParams(C.Structure):
     @classmethod
     def make(cls, step_dist, bg=(0, 0, 0), sampling=NEAREST):
         return cls(float(step_dist), int(bg[0]) & 255, int(bg[1]) & 255, int(bg[2]) & 255, int(sampling))
+
+
+class SegmentParams(C.Structure):
+    """hmrm_segment_params (24 bytes)"""
+    _fields_ = [("step_dist", C.c_double), ("bg_r", C.c_uint8), ("bg_g", C.c_uint8), ("bg_b", C.c_uint8),
+                ("sampling", C.c_uint8), ("flags", C.c_uint32), ("max_steps", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def make(cls, step_dist, bg=(0, 0, 0), sampling=NEAREST, interior=False, max_steps=0):
+        return cls(float(step_dist), int(bg[0]) & 255, int(bg[1]) & 255, int(bg[2]) & 255, int(sampling),
+                   TRACE_INTERIOR if interior else 0, int(max_steps), 0)
 
 
 # the same layouts as numpy structured dtypes (arrays of rays in, arrays of records out)
@@ -169,6 +182,9 @@ def _load():
         "hmrm_render_aa": (C.c_int, [vp, C.POINTER(Camera), i32, vp, C.c_size_t, C.POINTER(Stats)]),
         "hmrm_trace_rays": (C.c_int, [vp, C.POINTER(TraceParams), vp, C.c_int64, vp, C.POINTER(Stats)]),
         "hmrm_trace_rays_device": (C.c_int, [vp, C.POINTER(TraceParams), vp, C.c_int64, vp, vp]),
+        "hmrm_trace_segments": (C.c_int, [vp, C.POINTER(SegmentParams), vp, vp, C.c_int64, vp, C.POINTER(Stats)]),
+        "hmrm_trace_segments_device": (C.c_int, [vp, C.POINTER(SegmentParams), vp, vp, C.c_int64, vp, vp]),
+        "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
         "hmrm_pick": (C.c_int, [vp, C.POINTER(Camera), i32, i32, C.POINTER(RayHit)]),
         "hmrm_debug_ray": (C.c_int, [vp, C.POINTER(Camera), i32, i32, dp, dp, dp]),
         "hmrm_debug_frame": (C.c_int, [C.POINTER(Camera), C.POINTER(SceneParams), i32, i32, vp, vp]),
@@ -183,6 +199,7 @@ def _load():
         "hmrm_config_record_mode": (i32, [vp]),
         "hmrm_config_devices": (i32, [vp]),
         "hmrm_config_antialias": (i32, [vp]),
+        "hmrm_config_interior": (i32, [vp]),
         "hmrm_record_orbit_multi": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32]),
         "hmrm_record_orbit_flags": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
@@ -334,6 +351,16 @@ class Scene:
         _check(lib.hmrm_render(self._h, C.byref(cam), _ptr(fb), cam.width * 4))
         return fb
 
+    def render_interior(self, cam: Camera, allow_capped=False) -> np.ndarray:
+        """One full frame under the interior rule (hmrm_render_interior): a camera strictly inside the box sees the terrain
+        around it instead of sky -> HxWx4 uint8.  An interior ray that never leaves the grid (straight up) reaches the step
+        cap: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
+        _check(lib.hmrm_render_interior(self._h, C.byref(cam), _ptr(fb), cam.width * 4),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
     def render_cycle(self, cam: Camera, framebuf: np.ndarray, cycle: int, cycle_period: int):
         """Progressive refresh (hmap.cpp:976-983): rewrites pixels p = cycle (mod cycle_period) in place."""
         assert framebuf.dtype == np.uint8 and framebuf.shape == (cam.height, cam.width, 4) and framebuf.flags.c_contiguous
@@ -432,6 +459,37 @@ class Scene:
         p = TraceParams.make(step_dist, bg, sampling)
         _check(lib.hmrm_trace_rays_device(self._h, C.byref(p), C.c_void_p(d_rays_ptr), int(n), C.c_void_p(d_hits_ptr),
                                           C.c_void_p(stream)))
+
+    def trace_segments(self, rays, step_dist, bg=(0, 0, 0), sampling=NEAREST, interior=False, max_steps=0,
+                       per_ray_max_steps=None, stats=False, allow_capped=False):
+        """trace_rays under the two segment rules (hmrm_trace_segments): interior = rays that start strictly inside the box
+        enter it at d = +0.0 instead of missing; max_steps / per_ray_max_steps (n uint32, 0 = none) = a ray ends after the
+        smaller non-zero one of the two height loads (status RAY_END when still inside the grid).  RAY_END rays are not
+        capped rays: only RAY_CAPPED ones raise HMRM_E_NOTERM (unless allow_capped)."""
+        self._sync_env()
+        r = as_rays(rays)
+        hits = np.zeros(r.shape[0], dtype=RAY_HIT_DTYPE)
+        lim = None
+        if per_ray_max_steps is not None:
+            lim = np.ascontiguousarray(per_ray_max_steps, dtype=np.uint32).reshape(-1)
+            if lim.shape[0] != r.shape[0]:
+                raise ValueError("per_ray_max_steps must hold one limit per ray")
+        p = SegmentParams.make(step_dist, bg, sampling, interior, max_steps)
+        st = Stats() if stats else None
+        _check(lib.hmrm_trace_segments(self._h, C.byref(p), _ptr(r), _ptr(lim) if lim is not None else None, r.shape[0],
+                                       _ptr(hits), C.byref(st) if stats else None),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return (hits, st) if stats else hits
+
+    def trace_segments_device(self, d_rays_ptr: int, n: int, d_hits_ptr: int, step_dist, bg=(0, 0, 0), sampling=NEAREST,
+                              interior=False, max_steps=0, d_max_steps_ptr: int = 0, stream: int = 0):
+        """hmrm_trace_segments_device: as trace_rays_device, with the rules; d_max_steps_ptr (n uint32 in device memory)
+        may be 0."""
+        self._sync_env()
+        p = SegmentParams.make(step_dist, bg, sampling, interior, max_steps)
+        _check(lib.hmrm_trace_segments_device(self._h, C.byref(p), C.c_void_p(d_rays_ptr),
+                                              C.c_void_p(d_max_steps_ptr) if d_max_steps_ptr else None, int(n),
+                                              C.c_void_p(d_hits_ptr), C.c_void_p(stream)))
 
     def pick(self, cam: Camera, px: int, py: int, allow_capped=False) -> np.ndarray:
         """hmrm_pick: the record (RAY_HIT_DTYPE scalar) of the ray of pixel (px, py) of `cam`."""
@@ -655,6 +713,10 @@ class Config:
     def antialias(self) -> int:
         """Additive `antialias n`: hmrm_render_aa's factor (1 = off)."""
         return int(lib.hmrm_config_antialias(self._h))
+
+    def interior(self) -> bool:
+        """Additive `interior on|off`: the CLI renders its single frame with hmrm_render_interior."""
+        return bool(lib.hmrm_config_interior(self._h))
 
     @property
     def output_path(self) -> str:

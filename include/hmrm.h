@@ -262,9 +262,9 @@ int hmrm_render_aa(const hmrm_scene *scene, const hmrm_camera *cam, int32_t fact
  * Perspective.cpp:27); zero, infinite and NaN components behave as the reference's arithmetic does on them -- (int)NaN
  * fails the range test of hmap.cpp:1006, so such a ray misses -- and no input faults the kernel.
  * Each ray runs exactly the body of hmap.cpp:989-1057: intersection() (AABB.cpp:33-44) sees a miss for d == inf or d < 0, so
- * a ray whose origin lies inside the box misses, as in the reference; the entry point is nudged by grid_width * 0.01 * dir
+ * a ray whose origin lies inside the box misses, as in the reference (hmrm_trace_segments below lifts that); the entry point is nudged by grid_width * 0.01 * dir
  * (:998); then step_dist * dir is added step by step (:1037) until a cell's height is above the ray (:1016) or the ray
- * leaves the grid (:1006).  There is no segment limit (the reference's loop has none): compare `steps`. */
+ * leaves the grid (:1006).  There is no segment limit here (the reference's loop has none): hmrm_trace_segments has one. */
 typedef struct hmrm_ray { double pos[3]; double dir[3]; } hmrm_ray;          /* 48 bytes */
 
 enum { HMRM_RAY_MISS = 0, HMRM_RAY_HIT = 1, HMRM_RAY_CAPPED = 2 };
@@ -303,6 +303,52 @@ int hmrm_trace_rays(const hmrm_scene *scene, const hmrm_trace_params *p, const h
  * the step cap are reported by hmrm_scene_take_capped for that stream. */
 int hmrm_trace_rays_device(const hmrm_scene *scene, const hmrm_trace_params *p, const void *d_rays, int64_t n,
                            void *d_hits, void *hip_stream);
+/* ------------------------------------------------ segments and interior origins */
+/* Two rules the reference does not have (build-side additions), both exact and both off unless asked for.
+ * Box: c0 = (0, 0, min_height), c1 = (map_w * grid_width, -map_h * grid_width, max_height) (hmap.cpp:968-974).
+ * INTERIOR RULE (HMRM_TRACE_INTERIOR; hmrm_render_interior): a ray is interior when its origin lies strictly inside the box --
+ * c0.x < pos.x < c1.x, c1.y < pos.y < c0.y, c0.z < pos.z < c1.z, all six true; NaN fails them.  The reference turns such a ray
+ * into a miss (AABB.cpp:37-39: distance() is negative, -inf or NaN there).  Under the rule it runs the body of
+ * hmap.cpp:989-1057 as if distance() had returned +0.0: int_point = pos + 0.0 * dir, then the nudge (:998), then the loop,
+ * unchanged; non-finite dir components go through that arithmetic as written.  Every other ray -- origins exactly on a face
+ * included -- is untouched.  In a record entry_d stays distance()'s own value bit for bit, not the d that was used.
+ * STEP LIMIT: a ray has an effective limit L (0 = none) and ends after L height loads (hmap.cpp:1013) when the L-th did not
+ * hit.  Order within a trip as for the step cap: the range test (:1006), then the budget, then the load -- a ray that leaves
+ * the grid after exactly L loads is a MISS; one still inside it gets HMRM_RAY_END with steps = L, the miss shade, point 0 and
+ * cell -1.  The budget is min(HMRM_STEP_CAP, L); running out of it is END when L != 0 && L < step cap, else CAPPED as before.
+ * END rays are not capped rays: they never cause HMRM_E_NOTERM and never show up in hmrm_scene_take_capped.  The limit is
+ * in loads, which is exact; with dir = (B - A) / N, step_dist = 1 and L = N a ray is the segment from A to B. */
+#define HMRM_TRACE_INTERIOR 1u
+enum { HMRM_RAY_END = 3 };   /* hmrm_ray_hit.status of hmrm_trace_segments: ended by the ray's own step limit, inside the grid */
+typedef struct hmrm_segment_params {      /* 24 bytes */
+	double  step_dist;   /* as hmrm_trace_params */
+	uint8_t bg_r, bg_g, bg_b;
+	uint8_t sampling;
+	uint32_t flags;      /* HMRM_TRACE_INTERIOR; any other bit: HMRM_E_ARG */
+	uint32_t max_steps;  /* limit for every ray, 0 = none */
+	uint32_t reserved;   /* must be 0 */
+} hmrm_segment_params;
+/* hmrm_trace_rays under the two rules.  max_steps (n entries, may be NULL; 0 = none) holds per-ray limits: ray i's L is the
+ * smaller of the non-zero values among p->max_steps and max_steps[i].  With flags = 0, p->max_steps = 0 and max_steps NULL
+ * the records are hmrm_trace_rays', byte for byte.  Contracts are those of hmrm_trace_rays / _device: refusals (a flag bit
+ * that is not defined, reserved != 0, a bad sampling, NULL p / rays / hits with n > 0, n < 0, n > 2^29) come before the scene
+ * is looked at; a batch is not a frame (no calibration, no probe, the camera cache untouched); stats->capped counts CAPPED
+ * rays only, and only they make the call return HMRM_E_NOTERM. */
+int hmrm_trace_segments(const hmrm_scene *scene, const hmrm_segment_params *p, const hmrm_ray *rays,
+                        const uint32_t *max_steps /* per ray, may be NULL */, int64_t n, hmrm_ray_hit *hits,
+                        hmrm_stats *stats /* may be NULL */);
+/* ... for rays, limits (n * 4 bytes, 4-byte aligned, may be NULL) and records in DEVICE memory, as hmrm_trace_rays_device. */
+int hmrm_trace_segments_device(const hmrm_scene *scene, const hmrm_segment_params *p, const void *d_rays,
+                               const void *d_max_steps /* may be NULL */, int64_t n, void *d_hits, void *hip_stream);
+/* hmrm_render under the interior rule: a camera below max_height -- a walker, a low fly-through -- sees the terrain around it
+ * instead of sky.  Synchronous, on the scene's stream, all three projections and sampling modes, with the scene's current
+ * kernel (HMRM_KERNEL or the probe's verdict).  Launched the way an instrumented frame is: never measured, never the scene's
+ * probe, not counted towards it.  A perspective or spherical camera that is not strictly inside the box gives hmrm_render's
+ * frame byte for byte (the ordinary kernel runs); orthographic origins are tested per pixel.  HMRM_E_NOTERM as hmrm_render:
+ * an interior ray with dir.x = dir.y = 0 that never hits (straight up) never leaves the grid and runs to the step cap.
+ * Not antialiased, no tickets, strips or recording: trace a batch for those. */
+int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -441,7 +487,9 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * log retrievable with hmrm_config_log().  Additive keys (not in the reference,
  * named by north_star): `projection perspective|spherical|orthographic|1|2|3`,
  * `output <path.png|.ppm>`, `record orbit|off`, `devices n`, `sampling nearest|bilinear`, `heights f64|f32`,
- * `antialias 1|2|4|8` (hmrm_render_aa's factor; another value warns "WARNING: Unknown antialias: v" and keeps the old one).  Unknown key -> "WARNING: Unknown identifier: k". */
+ * `antialias 1|2|4|8` (hmrm_render_aa's factor; another value warns "WARNING: Unknown antialias: v" and keeps the old one),
+ * `interior on|off|1|0` (default off; the CLI renders its single frame with hmrm_render_interior; another value warns
+ * "WARNING: Unknown interior: v" and keeps the old one).  Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
 /* Consume a whole stream; loads heightmap/colormap images when those keys
@@ -460,6 +508,7 @@ const char  *hmrm_config_output_path(const hmrm_config *cfg);
 int32_t      hmrm_config_record_mode(const hmrm_config *cfg);   /* additive `record orbit|off`: 1|0 */
 int32_t      hmrm_config_devices(const hmrm_config *cfg);       /* additive `devices n`: GPUs for recording, 0 = all */
 int32_t      hmrm_config_antialias(const hmrm_config *cfg);     /* additive `antialias n`: 1 (default, off), 2, 4 or 8 */
+int32_t      hmrm_config_interior(const hmrm_config *cfg);      /* additive `interior on|off`: 1|0 */
 /* Loaded maps (owned by cfg): RGB8 / RGBA8; NULL until the key was consumed. */
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *cfg, int32_t *w, int32_t *h);
 const uint8_t *hmrm_config_color_rgba(const hmrm_config *cfg, int32_t *w, int32_t *h);
