@@ -275,6 +275,7 @@ static_assert(sizeof(hmrm_ray) == sizeof(hmrm::BatchRay) && sizeof(hmrm_ray_hit)
                   offsetof(hmrm_segment_params, max_steps) == 16 && offsetof(hmrm_segment_params, reserved) == 20,
               "the kernels' mirrors of hmrm_ray / hmrm_ray_hit (frame.hpp)");
 // cached records and settled launch orders are looked up with memcmp on these two: no padding bytes allowed
+static_assert(sizeof(hmrm_sun) == 48, "hmrm_sun has padding");
 static_assert(sizeof(hmrm_camera) == 3 * sizeof(int32_t) + 4 + 8 * sizeof(double), "hmrm_camera has padding");
 static_assert(sizeof(hmrm_scene_params) == 6 * sizeof(double), "hmrm_scene_params has padding");
 
@@ -639,12 +640,23 @@ int launch_shadow_probe(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, co
 // kernel indexes cells and windows with 24-bit multiplies, leap_common.hpp index_2d), else the production kernel or the other one (the plain groups,
 // with leaps over window records where the frame's sampling allows them).
 // `interior` (hmrm_render_interior): the same choice among the kernels built with the interior rule (render_interior.hip).
+// `lit` (hmrm_render_lit): ... among the kernels that march the shadow rays too (render_lit.hip).
+struct LitFrame {
+	hmrm::SunRules sun;
+	bool primary_interior; // HMRM_TRACE_INTERIOR: the primary rays under the interior rule too
+};
 int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hmrm::RowMap &rows_in_order, uint32_t *d_out,
-                  int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool use_group, bool interior = false) {
+                  int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool use_group, bool interior = false,
+                  const LitFrame *lit = nullptr) {
 	const bool huge_side = s->map_w >= (1 << 24) || s->map_h >= (1 << 24);
 	if (huge_side && f.sampling != 0)
 		return fail(HMRM_E_ARG, "maps with a side of 2^24 cells or more support nearest sampling only");
 	if ((s->knobs.kernel == 2 || huge_side) && f.sampling == 0) { // (the literal loop only knows the reference's sampling)
+		if (lit) {
+			HIP_TRY(hmrm::launch_render_lit_literal(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters, lit->sun,
+			                                        lit->primary_interior, c->stream));
+			return HMRM_OK;
+		}
 		if (interior) {
 			HIP_TRY(hmrm::launch_render_interior_literal(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters, c->stream));
 			return HMRM_OK;
@@ -657,6 +669,11 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		if (k == hmrm::kRecords) {
 			const int rc_r = ensure_records(s);
 			if (rc_r) return rc_r;
+		}
+		if (lit) {
+			HIP_TRY(hmrm::launch_render_lit(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px, c->d_counters, k,
+			                                s->d_records, lit->sun, lit->primary_interior, c->stream));
+			return HMRM_OK;
 		}
 		if (interior) {
 			HIP_TRY(hmrm::launch_render_interior(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px, c->d_counters, k,
@@ -682,7 +699,7 @@ int note_launch(hmrm_scene *s, StreamCtx *c) {
 // the record's event and the scene's fence behind it.
 int launch_maybe_measured(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot *slot, hmrm::RowMap &rows_in_order, int tiles_y,
                           bool measure_now, uint32_t *d_out, int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool use_group,
-                          bool interior = false) {
+                          bool interior = false, const LitFrame *lit = nullptr) {
 	if (measure_now) {
 		const int rc_m = ensure_meas(c);
 		if (rc_m) return rc_m;
@@ -690,7 +707,7 @@ int launch_maybe_measured(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, 
 		rows_in_order.measure = c->d_meas;
 		HIP_TRY(hmrm::launch_measure_init(rows_in_order.measure, tiles_y, c->stream));
 	}
-	const int rc_k = launch_kernel(s, c, f, rows_in_order, d_out, out_stride_px, d_steps, d_entry, stats, use_group, interior);
+	const int rc_k = launch_kernel(s, c, f, rows_in_order, d_out, out_stride_px, d_steps, d_entry, stats, use_group, interior, lit);
 	if (rc_k || !measure_now) return rc_k;
 	const size_t idx = (size_t)(slot - c->slots);
 	HIP_TRY(hmrm::launch_measure_readback(rows_in_order.measure, c->h_meas_dev + idx * 2 * kMaxMeasRows, tiles_y, c->stream));
@@ -707,19 +724,19 @@ int launch_maybe_measured(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, 
 // `interior` (hmrm_render_interior; 0: not such a frame): launched the way an instrumented frame is -- plain rotation order,
 // never measured, never a probe, not counted towards the probe -- with the scene's current kernel (HMRM_KERNEL or the probe's
 // verdict, read only); 2: by the kernels built with the interior rule, 1: by the ordinary ones (the host saw that no ray of the
-// frame starts inside the box).
+// frame starts inside the box).  `lit` (hmrm_render_lit): launched the same way, by the kernels of render_lit.hip.
 int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot *slot, const hmrm::RowMap &rows,
                  uint32_t *d_out, int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool no_probe = false,
-                 int interior = 0) {
+                 int interior = 0, const LitFrame *lit = nullptr) {
 	hmrm::RowMap rows_in_order = rows;
 	int tile_w = 1, tile_h = 1;
 	hmrm::render_tile_shape(&tile_w, &tile_h);
 	const int tiles_y = (rows.local_rows + tile_h - 1) / tile_h;
 	const bool pieces = s->knobs.seg_n > 0 && rows.band_rows == 0 && rows.row_begin == 0; // (HMRM_TILE_SEGMENTS: an explicit order)
 	const int rot = hmrm::choose_tile_rot(s->knobs.tile_order, slot->row_cost, rows, tile_h);
-	const bool may_probe = !stats && !interior && s->knobs.kernel == 0 && s->knobs.try_group;
+	const bool may_probe = !stats && !interior && !lit && s->knobs.kernel == 0 && s->knobs.try_group;
 	// calibration (launch_order.hpp): full frames of the fast kernels only
-	const bool eligible = !pieces && !stats && !interior && s->knobs.tile_order && s->knobs.order_mode == 2 && s->knobs.kernel != 2 &&
+	const bool eligible = !pieces && !stats && !interior && !lit && s->knobs.tile_order && s->knobs.order_mode == 2 && s->knobs.kernel != 2 &&
 	                      rows.band_rows == 0 && rows.row_begin == 0 && rows.local_rows == f.screen_h && tiles_y >= 12 &&
 	                      tiles_y <= kMaxMeasRows && s->map_w < (1 << 24) && s->map_h < (1 << 24);
 	int rc = wait_for_measure_fence(s, c);
@@ -731,7 +748,7 @@ int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot
 		for (int k = 0; k < 3; ++k) { order.b[k] = s->knobs.seg_b[k]; order.c[k] = s->knobs.seg_c[k]; }
 	}
 	bool use_group = may_probe && s->choice.use_group; // strips, bands, small frames: the scene's verdict
-	if (interior) use_group = s->knobs.kernel == 0 && s->knobs.try_group && s->choice.use_group; // (the verdict, never a probe)
+	if (interior || lit) use_group = s->knobs.kernel == 0 && s->knobs.try_group && s->choice.use_group; // (the verdict, never a probe)
 	bool measure_now = false;
 	if (eligible) {
 		poll_measured(s, c, slot, tiles_y, rot);
@@ -751,7 +768,7 @@ int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot
 	hmrm::set_tile_order(&rows_in_order, tiles_y, rot, order.n, order.b, order.c);
 	// (a measured launch that cannot be issued or reported must not stay "in flight" in the record: nothing would ever
 	// report it, and the record's next reuse would wait for an event that was never recorded)
-	if ((rc = launch_maybe_measured(s, c, f, slot, rows_in_order, tiles_y, measure_now, d_out, out_stride_px, d_steps, d_entry, stats, use_group, interior == 2))) {
+	if ((rc = launch_maybe_measured(s, c, f, slot, rows_in_order, tiles_y, measure_now, d_out, out_stride_px, d_steps, d_entry, stats, use_group, interior == 2, lit))) {
 		if (measure_now) slot->cal.drop_in_flight();
 		return rc;
 	}
@@ -1213,7 +1230,7 @@ int hmrm_scene_read_heights(const hmrm_scene *cs, double *out) {
 // arrays then).
 static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes,
                          hmrm_stats *stats, uint32_t *steps_pp, double *entry_d, bool want_stats, int32_t aa_factor = 1,
-                         bool interior = false) {
+                         bool interior = false, const LitFrame *lit = nullptr) {
 	int rc = check_camera(cam);
 	if (rc) return rc;
 	hmrm_camera super;
@@ -1249,7 +1266,7 @@ static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, s
 	HIP_TRY(hipEventRecord(s->ev0, s->stream));
 	const bool per_pixel = want_stats && aa_shift == 0; // (per-pixel arrays are of the plain frame only)
 	if ((rc = launch_frame(s, c, f, slot, rows, s->d_frame, (int64_t)W, per_pixel ? s->d_steps : nullptr,
-	                       per_pixel ? s->d_entry : nullptr, want_stats, false, interior_mode)))
+	                       per_pixel ? s->d_entry : nullptr, want_stats, false, interior_mode, lit)))
 		return rc;
 	HIP_TRY(hipEventRecord(s->ev1, s->stream));
 	HIP_TRY(hipMemcpy2DAsync(rgba, stride_bytes, s->d_frame, W * 4, W * 4, H, hipMemcpyDeviceToHost,
@@ -1315,6 +1332,18 @@ int hmrm_render_aa(const hmrm_scene *scene, const hmrm_camera *cam, int32_t fact
 
 int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes) {
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, nullptr, nullptr, nullptr, false, 1, true);
+}
+
+// Sun shadows: hmrm_render's frame (hmrm_render_interior's with HMRM_TRACE_INTERIOR), the hit pixels' shadow rays marched
+// by the same launch.  The sun is checked before anything else is looked at.
+int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint8_t *rgba, size_t stride_bytes) {
+	if (!sun) return fail(HMRM_E_ARG, "NULL sun");
+	if (sun->flags & ~HMRM_TRACE_INTERIOR) return fail(HMRM_E_ARG, "hmrm_sun.flags: undefined bit");
+	for (uint8_t r : sun->reserved)
+		if (r) return fail(HMRM_E_ARG, "hmrm_sun.reserved must be 0");
+	const LitFrame lit{hmrm::SunRules{{sun->dir[0], sun->dir[1], sun->dir[2]}, sun->step_dist, sun->max_steps, sun->ambient},
+	                   (sun->flags & HMRM_TRACE_INTERIOR) != 0u};
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, nullptr, nullptr, nullptr, false, 1, false, &lit);
 }
 
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
@@ -1804,6 +1833,16 @@ int32_t hmrm_config_record_mode(const hmrm_config *c) { return c->cfg.record_mod
 int32_t hmrm_config_devices(const hmrm_config *c) { return c->cfg.devices; }
 int32_t hmrm_config_antialias(const hmrm_config *c) { return c->cfg.antialias; }
 int32_t hmrm_config_interior(const hmrm_config *c) { return c->cfg.interior; }
+int32_t hmrm_config_shadows(const hmrm_config *c) { return c->cfg.shadows; }
+void hmrm_config_get_sun(const hmrm_config *c, hmrm_sun *out) {
+	const hmrm::Config &g = c->cfg;
+	memset(out, 0, sizeof *out);
+	for (int k = 0; k < 3; ++k) out->dir[k] = g.sun_dir[k];
+	out->step_dist = g.have_shadow_step_dist ? g.shadow_step_dist : g.step_dist;
+	out->max_steps = (uint32_t)g.shadow_max_steps;
+	out->flags = g.interior ? HMRM_TRACE_INTERIOR : 0u;
+	out->ambient = (uint8_t)g.shadow_ambient;
+}
 
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *c, int32_t *w, int32_t *h) {
 	if (!c->cfg.have_heightmap) return nullptr;

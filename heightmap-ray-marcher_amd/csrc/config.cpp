@@ -12,7 +12,8 @@
 // keys at run time, :851-868, and only ever writes PNG):
 //   projection perspective|spherical|orthographic   (or 1|2|3)
 //   output <path>                                   (.png or .ppm)
-//   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8, interior on|off
+//   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8, interior on|off,
+//   shadows on|off, sun_dir x y z, shadow_ambient n, shadow_step_dist v, shadow_max_steps n
 #include "config.hpp"
 
 #include <cmath>
@@ -195,6 +196,41 @@ void interior_key(Config &c, std::istream &in, const char *key, std::string *) {
 	c.log << key << " " << (c.interior ? "on" : "off") << "\n";
 }
 
+// sun shadows of the single frame (hmrm_render_lit)
+void shadows_key(Config &c, std::istream &in, const char *key, std::string *) {
+	static const Word words[] = {{"on", 1}, {"1", 1}, {"off", 0}, {"0", 0}};
+	std::string seen;
+	if (!pick(in, words, &c.shadows, &seen)) c.warn << "WARNING: Unknown shadows: " << seen << "\n";
+	c.log << key << " " << (c.shadows ? "on" : "off") << "\n";
+}
+
+void sun_dir_key(Config &c, std::istream &in, const char *key, std::string *) { // towards the sun, used as given
+	in >> c.sun_dir[0] >> c.sun_dir[1] >> c.sun_dir[2];
+	c.log << key << " " << c.sun_dir[0] << " " << c.sun_dir[1] << " " << c.sun_dir[2] << "\n";
+}
+
+void shadow_ambient_key(Config &c, std::istream &in, const char *key, std::string *) { // what a shadowed pixel keeps, of 255
+	long long v = -1;
+	in >> v;
+	if (!in || v < 0 || v > 255) c.warn << "WARNING: shadow_ambient must be 0..255\n";
+	else c.shadow_ambient = (int)v;
+	c.log << key << " " << c.shadow_ambient << "\n";
+}
+
+void shadow_step_dist_key(Config &c, std::istream &in, const char *key, std::string *) {
+	in >> c.shadow_step_dist;
+	c.have_shadow_step_dist = true;
+	c.log << key << " " << c.shadow_step_dist << "\n";
+}
+
+void shadow_max_steps_key(Config &c, std::istream &in, const char *key, std::string *) { // 0 = no limit
+	long long v = -1;
+	in >> v;
+	if (!in || v < 0 || v > 0xffffffffll) c.warn << "WARNING: shadow_max_steps must be 0..4294967295\n";
+	else c.shadow_max_steps = v;
+	c.log << key << " " << c.shadow_max_steps << "\n";
+}
+
 struct Row { const char *key; Handler apply; };
 const Row kGrammar[] = {
 	// the reference's 27 keys (main/hmap.cpp:314-488)
@@ -234,6 +270,11 @@ const Row kGrammar[] = {
 	{"record", record_mode_key},
 	{"antialias", antialias_key},
 	{"interior", interior_key},
+	{"shadows", shadows_key},
+	{"sun_dir", sun_dir_key},
+	{"shadow_ambient", shadow_ambient_key},
+	{"shadow_step_dist", shadow_step_dist_key},
+	{"shadow_max_steps", shadow_max_steps_key},
 };
 
 } // namespace

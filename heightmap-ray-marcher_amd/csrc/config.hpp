@@ -42,6 +42,14 @@ struct Config {
 	int antialias = 1;
 	// additive: `interior on|off|1|0` -- the CLI's single frame under the interior rule (hmrm_render_interior)
 	int interior = 0;
+	// additive: sun shadows of the CLI's single frame (hmrm_render_lit): `shadows on|off|1|0`, `sun_dir x y z` (towards the sun,
+	// used as given), `shadow_ambient 0..255`, `shadow_step_dist v` (absent: the camera's step_dist), `shadow_max_steps n`
+	int shadows = 0;
+	double sun_dir[3] = {0.5, 0.5, 0.70710678118654757};
+	int shadow_ambient = 128;
+	double shadow_step_dist = 0.0;
+	bool have_shadow_step_dist = false;
+	long long shadow_max_steps = 0;
 
 	bool heightmap_dirty = false; // should_update_heightmap, sticky until taken
 	std::ostringstream log;       // what the reference prints to stdout

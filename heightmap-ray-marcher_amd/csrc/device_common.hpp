@@ -105,6 +105,25 @@ __device__ __forceinline__ int segment_budget(const SegRules &seg, int64_t index
 	return *ends ? (int)l : cap;
 }
 
+// Sun shadows (frame.hpp SunRules; hmrm_render_lit, LIT in the kernels): what a lane keeps between its primary ray and its
+// shadow ray; empty in every other instantiation, as SegState is.
+template <bool LIT> struct LitState {};
+template <> struct LitState<true> {
+	int phase = 0;             // 0: the primary rays, 1: the shadow rays of the lanes that hit (the same for a whole wave)
+	bool primary_hit = false;  // hmap.cpp:1016 fired for the primary ray
+	uint32_t rgba = 0;         // ... and this is its pixel
+	double hx = 0.0, hy = 0.0; // where it fired (int_point's x and y) ...
+	double t = 0.0;            // ... and the threshold z was compared with there (set once the march loop has ended)
+	double dz = 0.0;           // the primary ray's dir.z (the miss shade wants it after the shadow march)
+};
+// R, G and B of a shadowed pixel: (c * ambient + 127) / 255 in integers; A stays 255.  ambient = 255 gives c back.
+__device__ __forceinline__ uint32_t shade_shadowed(uint32_t rgba, uint32_t ambient) {
+	const uint32_t r = ((rgba & 255u) * ambient + 127u) / 255u;
+	const uint32_t g = (((rgba >> 8) & 255u) * ambient + 127u) / 255u;
+	const uint32_t b = (((rgba >> 16) & 255u) * ambient + 127u) / 255u;
+	return r | (g << 8) | (b << 16) | (rgba & 0xff000000u);
+}
+
 // AABB.cpp:49-77, axis order x,y,z, same comparisons (NaN => every test false).
 __device__ __forceinline__ double slab_distance(const DevRay &r, const DevFrame &f) {
 	const double inf = __builtin_huge_val();
@@ -125,6 +144,19 @@ __device__ __forceinline__ double slab_distance(const DevRay &r, const DevFrame 
 		if (dim_hi < hi) hi = dim_hi;
 	}
 	return (lo > hi) ? inf : lo;
+}
+// The shadow ray of a lane whose primary ray hit: from the surface above the hit point towards the sun ...
+__device__ __forceinline__ DevRay shadow_ray(const LitState<true> &lt, const SunRules &sun) {
+	DevRay r;
+	r.px = lt.hx; r.py = lt.hy; r.pz = lt.t;
+	r.dx = sun.dir[0]; r.dy = sun.dir[1]; r.dz = sun.dir[2];
+	return r;
+}
+// ... and the d it enters the loop with: +0.0 when its origin is strictly inside the box (the interior rule, always on for
+// shadow rays), else distance()'s own value -- an origin on or above max_height, t >= c1.z, is not inside and goes through
+// distance() as written.
+__device__ __forceinline__ double shadow_entry(const DevRay &r, const DevFrame &f) {
+	return origin_strictly_inside(r, f) ? 0.0 : slab_distance(r, f);
 }
 
 // Relative error of the hardware reciprocal.  MEASURED on gfx950 (tools/rcp_accuracy.py over 1.6e11 inputs: the

@@ -190,6 +190,18 @@ struct SegRules {
 	uint32_t interior;         // != 0: the interior rule is on
 };
 
+// ---- sun shadows (hmrm_render_lit; LIT in the kernels) ----
+// Every pixel whose primary ray HIT casts a shadow ray from (P.x, P.y, t) -- P the hit point, t the threshold the hitting load
+// compared z with -- along `dir` (as given, not normalised): a segment ray under the interior rule with step_dist and the limit
+// max_steps (0 = none).  A pixel whose shadow ray hits keeps (c * ambient + 127) / 255 of its R, G and B.  The primary rays'
+// own rules travel in a SegRules beside it.  An extra argument of the lit kernels' own __global__ entry points, like SegRules.
+struct SunRules {
+	double dir[3];
+	double step_dist;
+	uint32_t max_steps;
+	uint32_t ambient; // 0..255
+};
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

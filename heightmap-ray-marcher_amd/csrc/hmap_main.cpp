@@ -9,7 +9,8 @@
 // given (.ppm selects binary PPM), else screenshots/hmap_<epoch>.png.  `antialias n` renders (and records)
 // n x n box-filtered samples per pixel (hmrm_render_aa).  `interior on` renders the single frame under the interior rule
 // (hmrm_render_interior: a camera inside the box sees the terrain); it is ignored, with a warning, together with
-// `antialias` > 1, `devices` > 1 or `record orbit`.
+// `antialias` > 1, `devices` > 1 or `record orbit`.  `shadows on` renders the single frame with sun shadows (hmrm_render_lit;
+// under the interior rule too when `interior on`), and is ignored, with a warning, in the same three cases.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -64,6 +65,7 @@ int main(int argc, char *argv[]) {
 	}
 	const int32_t aa = hmrm_config_antialias(cfg);
 	const bool interior = hmrm_config_interior(cfg) != 0;
+	const bool shadows = hmrm_config_shadows(cfg) != 0;
 	hmrm_scene *scene = NULL;
 	if (hmrm_config_create_scene(cfg, &scene) != HMRM_OK) {
 		std::cerr << hmrm_last_error() << "\n";
@@ -72,6 +74,7 @@ int main(int argc, char *argv[]) {
 
 	if (hmrm_config_record_mode(cfg) == 1) {
 		if (interior) std::cerr << "WARNING: interior is ignored with record orbit\n";
+		if (shadows) std::cerr << "WARNING: shadows is ignored with record orbit\n";
 		// `record orbit`: recording_frame_count frames on a circle around the map centre through
 		// the configured camera position, always looking at the centre;
 		// files screenshots/hmap_<epoch>_<n>.png as hmap.cpp:1131-1144.
@@ -120,7 +123,20 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: antialias " << aa << " renders the single frame on one device (devices " << want_dev << " ignored)\n";
 	if (interior && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: interior is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (interior && want_dev <= 1 && aa == 1) {
+	if (shadows && (want_dev > 1 || aa > 1))
+		std::cerr << "WARNING: shadows is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
+	if (shadows && want_dev <= 1 && aa == 1) {
+		hmrm_sun sun;
+		hmrm_config_get_sun(cfg, &sun);
+		rc = hmrm_render_lit(scene, &cam, &sun, framebuf.data(), (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height << " rays with sun shadows" << (interior ? " under the interior rule" : "")
+		          << " in " << hmrm_last_kernel_ms() << " ms (kernel)\n";
+	} else if (interior && want_dev <= 1 && aa == 1) {
 		rc = hmrm_render_interior(scene, &cam, framebuf.data(), (size_t)cam.width * 4);
 		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
 			std::cerr << hmrm_last_error() << "\n";

@@ -79,12 +79,18 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 // AA: the antialiased epilogue (device_common.hpp store_box_filtered, f.aa_shift); the plain instantiations store per lane.
 // PROJ 4: the lane's ray comes from `batch` and its hmrm_ray_hit record goes there; `out` is not used.
 // SEG: the segment rules (frame.hpp SegRules; hmrm_trace_segments, hmrm_render_interior), as in render_fast.hip.
-template <int PROJ, bool STATS, bool AA, bool SEG = false>
+// LIT (hmrm_render_lit; frame.hpp SunRules; implies SEG): one of the two passes of a lit pixel, which hand each other `lit` in
+// registers and write no pixel themselves.  1: the primary ray -- its pixel, whether it hit, and where and under which
+// threshold, go to *lit.  2: the shadow ray of a lane whose primary ray hit, made from *lit and `sun` with the sun's step
+// (`seg` holds the sun's limit and the interior rule); a hit darkens lit->rgba.  The other lanes sit that pass out.
+template <int PROJ, bool STATS, bool AA, bool SEG = false, int LIT = 0>
 __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId pid, const double *__restrict__ thr,
                                                     const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                     int64_t out_stride_px, const StatsOut &st, const RayBatch &batch,
-                                                    const SegRules &seg = SegRules{}) {
+                                                    const SegRules &seg = SegRules{}, const SunRules &sun = SunRules{},
+                                                    LitState<true> *lit = nullptr) {
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
+	static_assert(LIT == 0 || (SEG && !RAYS), "sun shadows: frames, under the segment rules");
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || (!AA && !STATS), "segment rules: production kernels only");
 	// (what a batch adds is written as `if constexpr (RAYS)` statements beside the frame kernels' own, which stay as they
@@ -94,6 +100,7 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 		ray_index = (int64_t)pid.py * kBatchW + pid.px;
 		pid.live = pid.live && ray_index < batch.n;
 	}
+	if constexpr (LIT == 2) pid.live = pid.live && lit->primary_hit;
 	const int px = pid.px, py = pid.py, lrow = pid.lrow;
 	const bool live = pid.live;
 
@@ -104,6 +111,10 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 	if (live) {
 		DevRay ray = make_ray<PROJ>(f, px, py);
 		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
+		if constexpr (LIT == 2) { // (the camera's ray is dead too: from the surface above the hit point towards the sun)
+			ray.px = lit->hx; ray.py = lit->hy; ray.pz = lit->t;
+			ray.dx = sun.dir[0]; ray.dy = sun.dir[1]; ray.dz = sun.dir[2];
+		}
 		const double d_box = slab_distance(ray, f);
 		if (STATS && st.entry_d) st.entry_d[(int64_t)py * f.screen_w + px] = d_box;
 		double d = d_box;
@@ -129,9 +140,10 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 			y = y + f.nudge * ray.dy;
 			z = z + f.nudge * ray.dz;
 			// hmap.cpp:1037  step_dist * dir is the same three products every iteration
-			const double sx = f.step_dist * ray.dx;
-			const double sy = f.step_dist * ray.dy;
-			const double sz = f.step_dist * ray.dz;
+			const double step_dist = LIT == 2 ? sun.step_dist : f.step_dist;
+			const double sx = step_dist * ray.dx;
+			const double sy = step_dist * ray.dy;
+			const double sz = step_dist * ray.dz;
 			const double wlim = (double)f.map_w, hlim = (double)f.map_h;
 			const double c0x = f.c0[0], c0y = f.c0[1];
 			const bool pow2 = f.grid_pow2 != 0;
@@ -160,6 +172,7 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 					rgba = ((c >> 24) == 0) ? pack_rgba(f.bg[0], f.bg[1], f.bg[2]) : (c | 0xff000000u);
 					real_hit = true;
 					if constexpr (RAYS) { hx = x; hy = y; hz = z; hgx = gridx; hgy = gridy; }
+					if constexpr (LIT == 1) { lit->hx = x; lit->hy = y; lit->t = t; }
 					break;
 				}
 				x = x + sx;
@@ -186,6 +199,12 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 			sg.ended = my_cap != 0u && sg.ends;
 			my_cap = sg.ended ? 0u : my_cap;
 		}
+		if constexpr (LIT == 1) {
+			lit->primary_hit = real_hit;
+			lit->rgba = rgba;
+		} else if constexpr (LIT == 2) {
+			if (real_hit) lit->rgba = shade_shadowed(lit->rgba, sun.ambient); // (MISS, END and CAPPED leave the pixel lit)
+		} else
 		if constexpr (RAYS && SEG) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
 		else if constexpr (RAYS) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, d_box, (uint32_t)my_steps, rgba);
 		else if constexpr (AA) aa_rgba = rgba;
@@ -230,6 +249,20 @@ __global__ __launch_bounds__(kBlockThreads) void k_render_interior_literal(const
                                                                            uint32_t *__restrict__ out, int64_t out_stride_px,
                                                                            int tiles_y, StatsOut st, const SegRules seg) {
 	render_lane_literal<PROJ, false, false, true>(f, pixel_of_lane(f, rows, tiles_y), thr, cmap, out, out_stride_px, st, RayBatch{}, seg);
+}
+// A lit pixel (hmrm_render_lit with HMRM_KERNEL=simple): the literal loop twice, primary ray and shadow ray, one store.
+template <int PROJ>
+__global__ __launch_bounds__(kBlockThreads) void k_render_lit_literal(const DevFrame f, const RowMap rows,
+                                                                      const double *__restrict__ thr,
+                                                                      const uint32_t *__restrict__ cmap,
+                                                                      uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                      int tiles_y, StatsOut st, const SegRules seg, const SunRules sun) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, sun, &lt);
+	render_lane_literal<PROJ, false, false, true, 2>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
+	                                                 SegRules{nullptr, sun.max_steps, 1u}, sun, &lt);
+	if (pid.live) out[(int64_t)pid.lrow * out_stride_px + pid.px] = lt.rgba;
 }
 __global__ __launch_bounds__(kBlockThreads) void k_trace_segments_literal(const DevFrame f, const double *__restrict__ thr,
                                                                           const uint32_t *__restrict__ cmap, const RayBatch batch,
@@ -421,6 +454,23 @@ hipError_t launch_render_interior_literal(const DevFrame &f, const RowMap &rows,
 	case 1: hipLaunchKernelGGL(k_render_interior_literal<1>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
 	case 2: hipLaunchKernelGGL(k_render_interior_literal<2>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
 	default: hipLaunchKernelGGL(k_render_interior_literal<3>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_render_lit_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                     uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
+                                     bool primary_interior, hipStream_t stream) {
+	const int tiles_x = (f.screen_w + kTileW - 1) / kTileW;
+	const int tiles_y = (rows.local_rows + kTileH - 1) / kTileH;
+	if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
+	const dim3 grid((unsigned)tiles_x, (unsigned)(tiles_y < 32768 ? tiles_y : 32768), (unsigned)((tiles_y + 32767) / 32768)), block(kBlockThreads);
+	const StatsOut st{d_counters, nullptr, nullptr};
+	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
+	switch (f.projection) {
+	case 1: hipLaunchKernelGGL(k_render_lit_literal<1>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg, sun); break;
+	case 2: hipLaunchKernelGGL(k_render_lit_literal<2>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg, sun); break;
+	default: hipLaunchKernelGGL(k_render_lit_literal<3>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg, sun); break;
 	}
 	return hipGetLastError();
 }

@@ -63,6 +63,16 @@ hipError_t launch_render_interior(const DevFrame &f, const RowMap &rows, const d
 hipError_t launch_render_interior_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
                                           uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
                                           hipStream_t stream);
+// Frames with sun shadows (hmrm_render_lit; frame.hpp SunRules; render_lit.hip: the production kernels' instantiations that
+// march a hit pixel's shadow ray in the same launch, and the literal loop in render.hip).  `primary_interior`: the primary
+// rays are under the interior rule too.  d_counters[2] counts capped primary and capped shadow rays.  Never measured.
+hipError_t launch_render_lit(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
+                             const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                             FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
+                             hipStream_t stream);
+hipError_t launch_render_lit_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                     uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
+                                     bool primary_interior, hipStream_t stream);
 // The record table of the thr table: rec_row(map_w) x ceil(map_h / 4) WindowRecords.
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream);
 // thr32[i] = (float)thr[i], round to nearest (the "float heights" mode).

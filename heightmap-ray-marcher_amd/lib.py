@@ -116,6 +116,23 @@ class SegmentParams(C.Structure):
                    TRACE_INTERIOR if interior else 0, int(max_steps), 0)
 
 
+class Sun(C.Structure):
+    """hmrm_sun (48 bytes): the sun of Scene.render_lit"""
+    _fields_ = [("dir", C.c_double * 3), ("step_dist", C.c_double), ("max_steps", C.c_uint32), ("flags", C.c_uint32),
+                ("ambient", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+    @classmethod
+    def make(cls, dir, step_dist, max_steps=0, ambient=128, interior=False):
+        """dir: towards the sun, used as given (not normalised); step_dist in units of |dir|; max_steps: limit of every shadow
+        ray (0 = none); ambient 0..255: what a shadowed pixel keeps; interior: the primary rays under the interior rule too."""
+        if not 0 <= int(ambient) <= 255:
+            raise ValueError("ambient must be 0..255")
+        return cls((C.c_double * 3)(*(float(v) for v in dir)), float(step_dist), int(max_steps),
+                   TRACE_INTERIOR if interior else 0, int(ambient), (C.c_uint8 * 7)())
+
+
+assert C.sizeof(Sun) == 48
+
 # the same layouts as numpy structured dtypes (arrays of rays in, arrays of records out)
 RAY_DTYPE = np.dtype([("pos", np.float64, 3), ("dir", np.float64, 3)])
 RAY_HIT_DTYPE = np.dtype([("point", np.float64, 3), ("entry_d", np.float64), ("steps", np.uint32),
@@ -185,6 +202,7 @@ def _load():
         "hmrm_trace_segments": (C.c_int, [vp, C.POINTER(SegmentParams), vp, vp, C.c_int64, vp, C.POINTER(Stats)]),
         "hmrm_trace_segments_device": (C.c_int, [vp, C.POINTER(SegmentParams), vp, vp, C.c_int64, vp, vp]),
         "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
+        "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
         "hmrm_pick": (C.c_int, [vp, C.POINTER(Camera), i32, i32, C.POINTER(RayHit)]),
         "hmrm_debug_ray": (C.c_int, [vp, C.POINTER(Camera), i32, i32, dp, dp, dp]),
         "hmrm_debug_frame": (C.c_int, [C.POINTER(Camera), C.POINTER(SceneParams), i32, i32, vp, vp]),
@@ -200,6 +218,8 @@ def _load():
         "hmrm_config_devices": (i32, [vp]),
         "hmrm_config_antialias": (i32, [vp]),
         "hmrm_config_interior": (i32, [vp]),
+        "hmrm_config_shadows": (i32, [vp]),
+        "hmrm_config_get_sun": (None, [vp, C.POINTER(Sun)]),
         "hmrm_record_orbit_multi": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32]),
         "hmrm_record_orbit_flags": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
@@ -358,6 +378,16 @@ class Scene:
         self._sync_env()
         fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
         _check(lib.hmrm_render_interior(self._h, C.byref(cam), _ptr(fb), cam.width * 4),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
+    def render_lit(self, cam: Camera, sun: Sun, allow_capped=False) -> np.ndarray:
+        """One full frame with sun shadows (hmrm_render_lit): render()'s frame -- render_interior()'s with Sun.make(...,
+        interior=True) -- in which every pixel whose shadow ray hits keeps ambient / 255 of its colour -> HxWx4 uint8.  Capped
+        primary or shadow rays: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
+        _check(lib.hmrm_render_lit(self._h, C.byref(cam), C.byref(sun), _ptr(fb), cam.width * 4),
                allow=(HMRM_E_NOTERM,) if allow_capped else ())
         return fb
 
@@ -717,6 +747,16 @@ class Config:
     def interior(self) -> bool:
         """Additive `interior on|off`: the CLI renders its single frame with hmrm_render_interior."""
         return bool(lib.hmrm_config_interior(self._h))
+
+    def shadows(self) -> bool:
+        """Additive `shadows on|off`: the CLI renders its single frame with hmrm_render_lit."""
+        return bool(lib.hmrm_config_shadows(self._h))
+
+    def sun(self) -> Sun:
+        """The sun of the additive keys sun_dir, shadow_step_dist (absent: step_dist), shadow_max_steps, shadow_ambient, interior."""
+        out = Sun()
+        lib.hmrm_config_get_sun(self._h, C.byref(out))
+        return out
 
     @property
     def output_path(self) -> str:

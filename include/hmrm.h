@@ -349,6 +349,38 @@ int hmrm_trace_segments_device(const hmrm_scene *scene, const hmrm_segment_param
  * Not antialiased, no tickets, strips or recording: trace a batch for those. */
 int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes);
 
+/* ------------------------------------------------------------- sun shadows */
+/* hmrm_render with hard sun shadows (build-side addition), exact: every pixel first gets hmrm_render's value -- with
+ * HMRM_TRACE_INTERIOR in `flags` hmrm_render_interior's; the primary march is unchanged -- and every pixel whose primary ray
+ * HIT (hmap.cpp:1016 fired; a hit cell with alpha 0, which shows the background, :1020, counts) then casts one shadow ray.
+ * Misses, sky and primary rays stopped by the step cap cast none.
+ * The shadow ray is an hmrm_trace_segments ray: pos = (P.x, P.y, t), dir = sun->dir as given, sun->step_dist, sun->max_steps,
+ * the camera's sampling mode, HMRM_TRACE_INTERIOR always on.  P is the reference's int_point at the hit (hmrm_ray_hit.point),
+ * t the threshold the hitting load compared z with: heightmap_buf[c] + min_height (HMRM_NEAREST), the float entry of that
+ * table widened to double (HMRM_NEAREST_F32), the interpolated threshold at P (HMRM_BILINEAR) -- the ray starts on the
+ * surface above the hit point (P itself lies below it, z < t).  Nothing is special-cased: an origin with t >= max_height is
+ * not strictly inside and goes through distance() as written; a sun below the horizon, zero, infinite and NaN components and
+ * step_dist = 0 go through the same arithmetic.
+ * A pixel is SHADOWED when its shadow ray's status is HMRM_RAY_HIT; MISS, END and CAPPED leave it lit.  R, G and B of a
+ * shadowed pixel become (c * ambient + 127) / 255 in integers, A stays 255; ambient = 255 reproduces the frame without
+ * shadows (the shadow rays are marched all the same).
+ * Capped primary rays and capped shadow rays are counted together; either kind makes the call return HMRM_E_NOTERM with a
+ * valid frame.  END rays are never counted.  dir = (0, 0, 1) without max_steps never leaves the grid and runs to the cap.
+ * Refusals (HMRM_E_ARG) come before the scene is looked at: NULL sun, an undefined flag bit, reserved != 0.  Synchronous, on
+ * the scene's stream, launched the way hmrm_render_interior is: one launch renders the frame, never measured, never the
+ * scene's probe and not counted towards it, with the scene's current kernel (HMRM_KERNEL or the probe's verdict; the window
+ * records apply to HMRM_NEAREST).  All three projections and sampling modes.  Not antialiased, no tickets, strips or
+ * recording. */
+typedef struct hmrm_sun {        /* 48 bytes */
+	double   dir[3];     /* towards the sun; used as given, NOT normalised (like hmrm_ray.dir) */
+	double   step_dist;  /* of the shadow march, in units of |dir| */
+	uint32_t max_steps;  /* step limit L of every shadow ray, 0 = none (hmrm_trace_segments' rule) */
+	uint32_t flags;      /* HMRM_TRACE_INTERIOR: primary rays under the interior rule too; any other bit: HMRM_E_ARG */
+	uint8_t  ambient;    /* 0..255: what a shadowed pixel keeps; 255 = shadows change nothing */
+	uint8_t  reserved[7];/* must be 0 */
+} hmrm_sun;
+int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint8_t *rgba, size_t stride_bytes);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -489,7 +521,12 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * `output <path.png|.ppm>`, `record orbit|off`, `devices n`, `sampling nearest|bilinear`, `heights f64|f32`,
  * `antialias 1|2|4|8` (hmrm_render_aa's factor; another value warns "WARNING: Unknown antialias: v" and keeps the old one),
  * `interior on|off|1|0` (default off; the CLI renders its single frame with hmrm_render_interior; another value warns
- * "WARNING: Unknown interior: v" and keeps the old one).  Unknown key -> "WARNING: Unknown identifier: k". */
+ * "WARNING: Unknown interior: v" and keeps the old one),
+ * `shadows on|off|1|0` (default off; the CLI renders its single frame with hmrm_render_lit; another value warns "WARNING:
+ * Unknown shadows: v" and keeps the old one), `sun_dir x y z` (default 0.5 0.5 0.7071..., used as given), `shadow_ambient n`
+ * (0..255, default 128; another value warns "WARNING: shadow_ambient must be 0..255" and keeps the old one),
+ * `shadow_step_dist v` (absent: the camera's step_dist), `shadow_max_steps n` (default 0 = none; a value outside
+ * 0..4294967295 warns and keeps the old one).  Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
 /* Consume a whole stream; loads heightmap/colormap images when those keys
@@ -509,6 +546,10 @@ int32_t      hmrm_config_record_mode(const hmrm_config *cfg);   /* additive `rec
 int32_t      hmrm_config_devices(const hmrm_config *cfg);       /* additive `devices n`: GPUs for recording, 0 = all */
 int32_t      hmrm_config_antialias(const hmrm_config *cfg);     /* additive `antialias n`: 1 (default, off), 2, 4 or 8 */
 int32_t      hmrm_config_interior(const hmrm_config *cfg);      /* additive `interior on|off`: 1|0 */
+int32_t      hmrm_config_shadows(const hmrm_config *cfg);       /* additive `shadows on|off`: 1|0 */
+/* The sun of the additive keys: sun_dir, shadow_step_dist (the config's step_dist when the key was absent),
+ * shadow_max_steps, shadow_ambient; flags = HMRM_TRACE_INTERIOR when `interior on`. */
+void         hmrm_config_get_sun(const hmrm_config *cfg, hmrm_sun *out);
 /* Loaded maps (owned by cfg): RGB8 / RGBA8; NULL until the key was consumed. */
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *cfg, int32_t *w, int32_t *h);
 const uint8_t *hmrm_config_color_rgba(const hmrm_config *cfg, int32_t *w, int32_t *h);
