@@ -891,7 +891,7 @@ int run_update_heights(hmrm_scene *s) {
 	                                     s->params.lum_b, s->params.min_height, s->params.max_height,
 	                                     false, s->d_maxkey, s->stream));
 	HIP_TRY(hmrm::launch_thr_to_float(s->d_thr, s->d_thr32, n, s->stream)); // (float)thr, round to nearest
-	// window-maximum pyramid for the exact-leap traversal (render_fast.hip)
+	// window-maximum pyramid for the exact-leap traversal (march.hpp)
 	HIP_TRY(hmrm::launch_build_mip0(s->d_thr, s->map_w, s->map_h, s->plane(s->d_mipbuf, 0), s->mip_w[0], s->mip_h[0],
 	                                s->mip_row, s->stream));
 	for (int l = 1; l < hmrm::kMipLevels; ++l)

@@ -72,7 +72,7 @@ struct DevFrame {
 
 // Window sizes S = 4 * 2^(kLevelStep*l) cells, placed every S/2 cells.  kLevelStep 1 (the build): S = 4, 8, 16, 32,
 // 64, 128, 256 -- a ray moves two levels at a time (4, 16, 64, 256) until it has made a few jumps and then one at a time
-// (render_fast.hip kAdaptAfter); kLevelStep 2: only S = 4, 16, 64, 256 exist (round 2's pyramid, kept for A/B runs).
+// (march.hpp kAdaptAfter); kLevelStep 2: only S = 4, 16, 64, 256 exist (round 2's pyramid, kept for A/B runs).
 #ifndef HMRM_LEVEL_STEP
 #define HMRM_LEVEL_STEP 1
 #endif
@@ -108,7 +108,7 @@ __host__ __device__
 #endif
 inline unsigned mip_index(int ix, int iy, int pitch) { return (unsigned)(iy * pitch + ix); }
 
-// Window records (render_fast.hip, the record kernel): one per window of level kRecLevel (16 x 16 cells, one every 4
+// Window records (march.hpp, the record kernel; built by render_fast.hip): one per window of level kRecLevel (16 x 16 cells, one every 4
 // cells, row pitch rec_row(map_w)).  `max2` is the window's maximum with its kRecCells highest cells left out (rounded up
 // to float like the pyramid, NaN ignored), xs / ys the places of those cells inside the window, one byte each (255: slot
 // not used -- fewer than kRecCells cells stand above max2).  A ray at or above max2 crosses the window without a load if
@@ -143,7 +143,7 @@ struct RowMap {
 	int32_t seg_delta[4];  // pieces 0..3
 	// Calibration launch (api.cpp, launch order from measurement): when not null, every wave folds its duration, and
 	// a tile row's first wave its start time (s_memrealtime ticks, 10 ns), into the row's record: kMeasureStride words
-	// per tile row (render_fast.hip).  Scheduling aid only.
+	// per tile row (march_frame.hpp k_render_fast).  Scheduling aid only.
 	unsigned long long *measure;
 };
 constexpr int kMeasureStride = 33;

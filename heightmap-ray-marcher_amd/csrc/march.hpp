@@ -1,0 +1,786 @@
+// march.hpp -- the production march for gfx950: render_wave_tile, one wave's 8 x 8 pixels (or 64 batch rays), and its
+// tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
+// render_segments.hip, render_interior.hip and render_lit.hip, each with a __global__ kernel of its own.
+//
+// Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
+// the reference loop main/hmap.cpp:978-1058; two bit-preserving restructurings:
+//
+// (1) SPECULATIVE GROUPS.  The positions a ray visits do not depend on the heights
+//     it loads -- only the decision to stop does.  So U consecutive positions are
+//     produced with the reference's sequential adds (hmap.cpp:1037), their U height
+//     loads are issued together, and the tests (range :1006, hit :1016) are then
+//     resolved in order.  One memory latency per U steps instead of per step.
+//
+// (2) EXACT LEAPS.  While a coordinate p stays inside one binade [2^E, 2^(E+1)) every
+//     value is a multiple of u = 2^(E-52), and fl(p + s) = p + delta with the SAME
+//     delta = round_u(s) for every p of that binade (round-to-nearest; on an exact
+//     tie the increment is constant too once p has the steady parity: axis_refresh).  Hence the
+//     reference's sequential accumulation satisfies p_k = p_0 + k*delta EXACTLY, and
+//     both the product k*delta and the sum are exact in fp64.  A pyramid of window
+//     maxima over the hit thresholds then lets a ray jump over n steps at once when
+//     all n skipped positions provably (a) stay inside the window whose maximum was
+//     looked up and (b) stay at or above that maximum (no hit possible: hmap.cpp:1016
+//     needs z < threshold), with (c) all three coordinates inside their binades.
+//     (a) and (b): the jump length is only ESTIMATED (approximate reciprocals); the landing
+//     point is then VERIFIED with exact tests (cell inside the window, z >= max), and
+//     monotonicity of each coordinate in k extends the verification from the landing point to
+//     every skipped position.  A failed verification just means "no jump".
+//     (c): how many further steps stay strictly inside a coordinate's binade is established ONCE
+//     per binade (axis_refresh: estimate, shortened, verified at its far end) and counted down
+//     with every step leaped or marched (Axis::left): the multiplied part of a jump never exceeds the
+//     three counts.  A jump of n steps is n - 1 multiplied steps and then ONE real step fl(p + s) from that
+//     exact position (HMRM_CROSS): where a binade's end cut the jump short, that step is the one
+//     that carries the coordinate into its next binade -- otherwise a whole group of real steps would
+//     have to be marched at every binade boundary (half of all groups before this was done).  The
+//     end point after the real step is what (a) and (b) are verified for.
+//     Skipped positions are counted as steps: each was inside the grid, so the reference
+//     executed its height load there.
+//
+// Pyramid layout (built by k_build_mip*): level l holds maxima of S x S-cell windows,
+// S = 4, 8, 16, .. 256, placed every S/2 cells on the 4-cell level and every S/4 cells above it
+// (overlapping), so that a ray can always pick a window in which it has at least S/2 (3S/4) cells of
+// room ahead.  Values are floats rounded UP (a larger bound is always safe).  Above them: the whole
+// map, the one window of a top plane.  A ray moves two levels at a time until it has made kAdaptAfter
+// jumps, then one at a time (performance only: any level sequence gives the same pixels).
+#pragma once
+#include "device_common.hpp"
+#include "leap_common.hpp"
+#include "leap_diag.hpp"
+#include "launch_common.hpp"
+#include "march_dispatch.hpp"
+#include "render.hpp"
+
+#pragma clang fp contract(off)
+
+namespace hmrm {
+
+namespace {
+
+#ifndef HMRM_GROUP
+#define HMRM_GROUP 4
+#endif
+constexpr int kGroup = HMRM_GROUP; // U: positions per speculative group of the production kernel
+// ... and of the plain-groups instantiation (LEAP = false: no leaps, every height load of the reference is executed --
+// what the scene's probe picks on content that admits no jumps, and the kernel SURVEY 8(d)'s byte roofline is defined
+// for).  That kernel waits for its gathers 70 % of the time at 17 % VALU busy (profiles/r05_C3_group_rocprof.txt): more
+// loads in flight per lane pay until the registers cost resident waves -- C3 2.61 ms with 4, 2.37 with 6, 2.57 with 8
+// (profiles/r05_raw/group_len_ab.txt).  Deciding the hit test from a float copy of the table, doubles only where that is
+// unsafe, halves the bytes and changes little: the gathers are bound by lanes, not bytes (r05_experiments.txt section 4).
+#ifndef HMRM_GROUP_PLAIN
+#define HMRM_GROUP_PLAIN 6
+#endif
+constexpr int kGroupPlain = HMRM_GROUP_PLAIN;
+// ... and of the record kernel; the most refusals in a row its back-off counts (attempts every 2^n-th trip at most)
+#ifndef HMRM_GROUP_REC
+#define HMRM_GROUP_REC 6
+#endif
+constexpr int kGroupRec = HMRM_GROUP_REC;
+#ifndef HMRM_REC_BACKOFF
+#define HMRM_REC_BACKOFF 6
+#endif
+constexpr int kRecBackoff = HMRM_REC_BACKOFF;
+#ifndef HMRM_MIN_LEAP
+#define HMRM_MIN_LEAP 2
+#endif
+constexpr int kMinLeap = HMRM_MIN_LEAP; // a jump shorter than this is not worth its bookkeeping
+#ifndef HMRM_UP_RATIO
+#define HMRM_UP_RATIO (kLevelStep == 2 ? 4.0 : 2.0)
+#endif
+constexpr double kUpRatio = HMRM_UP_RATIO; // see the level policy in k_render_fast
+// Per-ray adaptive level spacing (pyramids with windows doubling per level, HMRM_LEVEL_STEP=1): a ray moves two
+// levels at a time -- windows of 4, 16, 64, 256 cells, which is what ordinary rays want (fewer level changes) --
+// until it has made more than HMRM_ADAPT_AFTER successful jumps; from then on one level at a time, so that the few
+// long rays skimming the terrain (the launch's tail) can use the 8-, 32- and 128-cell windows in between: where a
+// 16-cell window clears the ray and the 64-cell one does not, the 32-cell one often does and the jump doubles.
+// 0 = off (every ray one level at a time).  Performance only: any level sequence gives the same pixels.
+#ifndef HMRM_ADAPT_AFTER
+#define HMRM_ADAPT_AFTER 8
+#endif
+constexpr int kAdaptAfter = (kLevelStep == 1) ? HMRM_ADAPT_AFTER : 0;
+constexpr bool kAdaptive = kAdaptAfter > 0;
+
+// HMRM_EARLY_LOAD (default 1): order of an attempt -- the pyramid look-up is issued first, refreshes and lateral estimates
+// run while it is in flight (see the attempt block).  0 = refresh first and estimates after the load, for A/B runs.
+#ifndef HMRM_EARLY_LOAD
+#define HMRM_EARLY_LOAD 1
+#endif
+constexpr bool kEarlyLoad = HMRM_EARLY_LOAD != 0;
+
+// ---- bilinear quality mode (HMRM_BILINEAR; a build-side addition, not in the reference) ----
+// Same definition, operation for operation, as oracle/hmrm_oracle.c "bilinear quality mode":
+// values sit at cell centres; u = q - 0.5, t = u - floor(u), neighbours clamp(floor(u)) and
+// clamp(floor(u) + 1); f = a + ty*(b - a), a = f00 + tx*(f10 - f00), b = f01 + tx*(f11 - f01).
+struct Bil {
+	int c00, c10, c01, c11; // the four neighbour cells (linear indices)
+	double tx, ty;
+};
+__device__ __forceinline__ Bil bil_setup(double qx, double qy, int w, int h) {
+	const double u = qx - 0.5, v = qy - 0.5;
+	const double fu = __builtin_floor(u), fv = __builtin_floor(v);
+	Bil b;
+	b.tx = u - fu;
+	b.ty = v - fv;
+	const int iu = cvt_i32_sat(fu), iv = cvt_i32_sat(fv);
+	const int i0 = min(max(iu, 0), w - 1), i1 = min(max(iu + 1, 0), w - 1);
+	const int j0 = min(max(iv, 0), h - 1), j1 = min(max(iv + 1, 0), h - 1);
+	b.c00 = j0 * w + i0; b.c10 = j0 * w + i1;
+	b.c01 = j1 * w + i0; b.c11 = j1 * w + i1;
+	return b;
+}
+__device__ __forceinline__ double bil_mix(const Bil &b, double f00, double f10, double f01, double f11) {
+	const double a = f00 + b.tx * (f10 - f00);
+	const double c = f01 + b.tx * (f11 - f01);
+	return a + b.ty * (c - a);
+}
+// Colour at a hit: R,G,B interpolated and rounded with floor(f + 0.5); the alpha-0 rule
+// (hmap.cpp:1020) keeps looking at the nearest cell.
+__device__ __forceinline__ uint32_t shade_hit_bilinear(const DevFrame &f, const uint32_t *__restrict__ cmap,
+                                                       int nearest_cell, const Bil &b) {
+	const uint32_t tn = cmap[nearest_cell];
+	if ((tn >> 24) == 0) return pack_rgba(f.bg[0], f.bg[1], f.bg[2]);
+	const uint32_t t00 = cmap[b.c00], t10 = cmap[b.c10], t01 = cmap[b.c01], t11 = cmap[b.c11];
+	uint32_t ch[3];
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		const int sh = 8 * k;
+		double v = bil_mix(b, (double)((t00 >> sh) & 255u), (double)((t10 >> sh) & 255u),
+		                   (double)((t01 >> sh) & 255u), (double)((t11 >> sh) & 255u)) + 0.5;
+		if (v < 0.0) v = 0.0;
+		else if (v > 255.0) v = 255.0;
+		ch[k] = (uint32_t)(int)__builtin_floor(v);
+	}
+	return pack_rgba(ch[0], ch[1], ch[2]);
+}
+
+} // namespace
+
+#ifndef HMRM_MIN_WAVES
+#define HMRM_MIN_WAVES 1
+#endif
+#ifdef HMRM_WAVES_PER_EU
+#define HMRM_OCCUPANCY_ATTR __attribute__((amdgpu_waves_per_eu(HMRM_WAVES_PER_EU, HMRM_WAVES_PER_EU), amdgpu_num_vgpr(512 / HMRM_WAVES_PER_EU / 8 * 8)))
+#else
+#define HMRM_OCCUPANCY_ATTR
+#endif
+// SAMP: 0 nearest cell (the reference), 1 bilinear quality mode, 2 nearest cell with float thresholds
+// (`thr` then points at the float copy of the table).
+// One wave's 8 x 8 pixels: wave `wave` of the workgroup-sized tile (tile_x, grid row gy).  Returns the tile row rendered
+// (-1: the grid row does not exist).  k_render_fast calls it with the tile = blockIdx (one tile per workgroup); round 4's
+// persistent-tile experiment (resident waves pulling tiles from queue heads) called it in a loop and was 1.4-1.9 x slower:
+// profiles/r04_experiments.txt section 1, code at commit 80527e9.
+// AA: the antialiased epilogue (device_common.hpp store_box_filtered; instantiated in render_fast_aa.hip only).
+// PROJ 4 (instantiated in render_rays.hip only): a batch of caller-supplied rays (hmrm_trace_rays; frame.hpp RayBatch) -- the
+// lane's ray is loaded from `batch`, not made from a camera, and instead of a pixel the lane writes its hmrm_ray_hit record,
+// which wants distance()'s value for misses too and the ray's exact step count: the two things the instrumented
+// instantiation computes (COUNT below), without its diagnostics or its wave-wide counters.  `out` is not used then.
+// SEG (instantiated in render_segments.hip and render_interior.hip only; hmrm_trace_segments, hmrm_render_interior): the two
+// segment rules of frame.hpp SegRules -- a ray whose origin is strictly inside the box enters it at d = +0.0 instead of
+// missing, and a ray ends after its own number of height loads (HMRM_RAY_END) -- written like PROJ == 4, as `if constexpr`
+// statements beside the others' own.  The loop needs nothing new: it is position based and each lane has its budget.
+// LIT (instantiated in render_lit.hip only; hmrm_render_lit, frame.hpp SunRules; implies SEG): sun shadows.  "Entry, then the
+// march loop" runs a second time for the wave: a lane whose primary ray hit keeps its pixel and marches its shadow ray -- a
+// segment ray under the interior rule from (P.x, P.y, t) towards the sun -- through the SAME loop; the other lanes sit the
+// second pass out.  Nothing per pixel goes through memory between the two.  Again `if constexpr` statements beside the
+// others' own and a per-lane struct that is empty unless LIT (device_common.hpp LitState).
+template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false>
+__device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
+                                                const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
+                                                int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
+                                                int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{},
+                                                const SunRules &sun = SunRules{}) {
+	static_assert(!LIT || (SEG && PROJ != 4), "sun shadows: frames, under the segment rules");
+	constexpr bool BILINEAR = SAMP == 1, F32 = SAMP == 2;
+	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
+	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
+	static_assert(!SEG || (!AA && !STATS), "segment rules: production kernels only");
+	constexpr bool REC = LEAP == 2;                     // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
+	constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
+	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
+	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
+	const float *__restrict__ mip = BILINEAR ? f.mipbuf_bil : f.mipbuf; // the pyramid this sampling mode leaps on
+	PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, lane);
+	// (what a batch adds is written as `if constexpr (RAYS)` statements beside the frame kernels' own, which stay as they
+	// were: they must keep compiling to the same instructions)
+	int64_t ray_index = 0;
+	if constexpr (RAYS) {
+		ray_index = (int64_t)pid.py * kBatchW + pid.px;
+		pid.live = pid.live && ray_index < batch.n;
+	}
+	LoopDiag<STATS> diag; // (empty unless STATS: leap_diag.hpp)
+	diag.start();
+	unsigned long long my_steps = 0;
+	uint32_t my_hit = 0, my_cap = 0;
+	uint32_t aa_rgba = 0; // (AA: this lane's sample, filtered by the whole wave below)
+
+	if (pid.live) {
+		DevRay ray = make_ray<PROJ>(f, pid.px, pid.py);
+		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
+		// most rays of a frame never touch the box: prove the miss cheaply where possible (the instrumented
+		// variant reports d, so it takes no shortcut for misses); most of the others get their entry distance
+		// from one division instead of six (slab_classify: the instrumented variant uses that path too, so the
+		// parity tests compare its d with the oracle's bit for bit)
+		double d = __builtin_huge_val();
+		if (COUNT || !slab_points_away<PROJ>(ray, f)) {
+			const int verdict = slab_classify(ray, f, !COUNT, &d);
+			if (verdict == 0) d = slab_distance(ray, f);
+		}
+		if (STATS && st.entry_d) st.entry_d[(int64_t)pid.py * f.screen_w + pid.px] = d;
+		SegState<SEG> sg; // (empty unless SEG: device_common.hpp)
+		if constexpr (SEG) {
+			sg.d_record = d; // (a record keeps distance()'s own value, not the d that was used)
+			if (seg.interior != 0u && origin_strictly_inside(ray, f)) d = 0.0; // as if distance() had returned +0.0
+			sg.budget = segment_budget(seg, RAYS ? ray_index : 0, f.step_cap, &sg.ends);
+		}
+
+		uint32_t rgba = 0;
+		bool real_hit = false;
+		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired, and in which cell)
+		unsigned hcell = 0u;
+		LitState<LIT> lt; // (empty unless LIT: device_common.hpp)
+		bool again = false; // (LIT: the wave has shadow rays to march)
+
+		do { // (once; LIT: once more with the shadow rays)
+			if (!(d == __builtin_huge_val()) && !(d < 0.0)) { // intersection(), AABB.cpp:33-44
+				double x = ray.px + d * ray.dx;
+				double y = ray.py + d * ray.dy;
+				double z = ray.pz + d * ray.dz;
+				x = x + f.nudge * ray.dx; // hmap.cpp:998
+				y = y + f.nudge * ray.dy;
+				z = z + f.nudge * ray.dz;
+				double step_dist = f.step_dist;
+				if constexpr (LIT) step_dist = lt.phase ? sun.step_dist : step_dist; // (a shadow ray's own)
+				const double sx = step_dist * ray.dx; // hmap.cpp:1037, loop invariant
+				const double sy = step_dist * ray.dy;
+				const double sz = step_dist * ray.dz;
+				const unsigned wlim = (unsigned)f.map_w, hlim = (unsigned)f.map_h;
+				const int budget0 = f.step_cap > 0x7fffffff ? 0x7fffffff : (int)f.step_cap;
+				int budget = budget0; // every step taken or leaped comes off it: steps so far = budget0 - budget
+				if constexpr (SEG) budget = sg.budget; // (min(step cap, the ray's own limit): steps so far = sg.budget - budget)
+				// (int)NaN is INT_MIN on the reference's CPU: the first range test fails, the ray misses
+				const bool entry_nan = x != x || y != y;
+
+				// leap state
+				// First level to look at: a finer window has a lower maximum, so the finest level whose
+				// windows still leave the ray lateral room for its whole descent to the box floor is the
+				// best one (steep rays: the finest level at once, instead of walking down from the top);
+				// oblique rays start with the whole-map bound.  Performance only.
+				int lev = kTopLevel;
+				if (sz < 0.0) {
+					const double descent = (z - f.c0[2]) * __builtin_amdgcn_rcp(-sz); // steps down to min_height
+					const double lateral = descent * __builtin_fmax(__builtin_fabs(sx), __builtin_fabs(sy)) * (GWM == 0 ? 1.0 : f.inv_grid_width);
+#pragma unroll
+					for (int l = kMipLevels - 1; l >= 0; l -= (kAdaptive ? 2 : 1)) // windows every 1 << hs cells: at least that much room ahead
+						lev = (l >= f.min_level && lateral <= (double)((win_strides(l) - 1) << mip_stride_shift(l))) ? l : lev;
+				}
+				if (REC) lev = lev == kTopLevel ? kTopLevel : kRecLevel; // (the record kernel knows the whole-map bound and the record level)
+				int cooldown = 0, fails = 0;
+				unsigned trip_no = 0; // (REC)
+				int jumps = 0; // successful jumps so far (kAdaptive)
+				Axis ax, ay, az;
+				ax.key = ay.key = az.key = 0xfffffffeu; // never matches: forces the first refresh
+				ax.delta = ay.delta = az.delta = 0.0;
+				ax.lim = ay.lim = az.lim = 0.0;
+				ax.rdel = ay.rdel = az.rdel = 0.0;
+				ax.left = ay.left = az.left = -1; // (kStepsLeft: forces the first refresh)
+				// window choice: step back one half-window when the cell index decreases along the ray
+				const int offx = sx < 0.0 ? 1 : 0, offy = sy > 0.0 ? 1 : 0; // gy = trunc(-y/gw) falls when y grows
+				const double gwid = (GWM == 0) ? 1.0 : f.grid_width;
+
+				// The loop body is written branch-light on purpose: a wave executes every divergent
+				// branch any of its lanes takes, and exec-mask juggling per `if` costs as much as
+				// the arithmetic it guards.  Values are computed for all lanes and selected.
+				bool done = entry_nan;
+				while (!done) {
+					bool skip_group = false;
+					diag.begin_trip();
+					// ---------------------------------------------------------- leap
+					if (LEAP) {
+						// (REC: after `fails` refusals in a row a ray attempts on every 2^fails-th trip of the WAVE's count -- rays that
+						// back off do so in step, and on a map that admits no leaps the block is issued once in 64 trips)
+						const bool attempt = REC ? (trip_no & ((1u << fails) - 1u)) == 0u : cooldown == 0;
+						++trip_no;
+						cooldown -= attempt ? 0 : 1;
+						if (attempt) {
+							diag.on_attempt();
+							// Order of the block (HMRM_EARLY_LOAD): the window look-up depends on the position and the level only, so
+							// its load is issued FIRST; the refreshes of stale coordinates and the estimates of lateral room, which
+							// do not need the loaded maximum, then run while it is in flight.  For a wave alone on its SIMD -- the
+							// long waves at the end of a launch -- a trip is one chain of dependent instructions, and this takes
+							// the refreshes and ~20 instructions of the estimate out of the part that waits for the load.
+							auto refresh_stale = [&]() {
+								const bool stale_x = kStepsLeft ? ax.left < 0 : (hi32(x) >> 20) != ax.key;
+								const bool stale_y = kStepsLeft ? ay.left < 0 : (hi32(y) >> 20) != ay.key;
+								const bool stale_z = kStepsLeft ? az.left < 0 : (hi32(z) >> 20) != az.key;
+								diag.on_refresh_check(f, stale_x, stale_y, stale_z);
+								if (stale_x) axis_refresh(ax, x, sx);
+								if (stale_y) axis_refresh(ay, y, sy);
+								if (stale_z) axis_refresh(az, z, sz);
+							};
+							if (!kEarlyLoad) refresh_stale();
+							bool near0 = false;
+							const double qx = cell_coord_fast<GWM>(x, f, near0), qy = cell_coord_fast<GWM>(-y, f, near0);
+							// General grid widths: a start or landing point within 2^-20 of a cell boundary would need the true quotient
+							// to name its cell.  The START divides for real then (a rare, wave-uniform branch: a coordinate that never
+							// moves -- orthographic rays along an axis -- can sit that close to a boundary for a whole ray).  The LANDING
+							// point does not: its cell is gxn or gxn - 1 (below), and the jump is accepted when BOTH lie inside the window
+							// -- two inlined divisions and their temporaries less at the block's point of highest register pressure.
+							// (Refusing such landings outright is wrong for speed: with 1 / grid_width an integer -- 0.05, 0.01 -- every
+							// power of two is a cell boundary, the landing point of a binade-limited jump is the first position behind
+							// one, always the same whatever the start, and a ray whose crossing step ends within 2^-20 of it was
+							// refused again and again until it had MARCHED there: 175 groups instead of one, the launch's last wave.)
+							double qx2 = qx, qy2 = qy;
+							if (GWM == 2 && __builtin_amdgcn_ballot_w64(near0) != 0ull) {
+								qx2 = near0 ? x / f.grid_width : qx;
+								qy2 = near0 ? -y / f.grid_width : qy;
+							}
+							const int gx = cvt_i32_sat(qx2), gy = GWM == 0 ? cvt_i32_sat_neg(y) : cvt_i32_sat(qy2);
+							const bool inb0 = (unsigned)gx < wlim && (unsigned)gy < hlim;
+							const bool top = lev == kTopLevel;
+							// window (ix,iy) of level lev: S = 4 << lev cells wide, one every 1<<hs cells.  The whole map is
+							// the one window of the top plane: with hs = 28 every in-grid cell has ix = iy = 0 and the
+							// spans below come out as the map's, so nothing else treats that level specially.
+							// (levels below kDenseFrom: windows every half window, the others every quarter -- frame.hpp)
+							const bool sparse = lev < kDenseFrom;
+							const int hs = top ? 28 : kLevelStep * lev + (sparse ? 1 : 0);
+							const int back = sparse ? 1 : 3; // strides to step back when the cell index falls along the ray
+							int ix = (gx >> hs) - (offx ? back : 0), iy = (gy >> hs) - (offy ? back : 0);
+							ix = ix < 0 ? 0 : ix;
+							iy = iy < 0 ? 0 : iy;
+							const unsigned widx = ((unsigned)lev << f.mip_plane_shift) + (unsigned)index_2d(iy, f.mip_row, ix); // (= mip_index)
+							diag.load_begin(f, 17);
+#ifndef HMRM_WIDE_MIP
+#define HMRM_WIDE_MIP 1
+#endif
+							// (the element index fits 32 bits -- 8 planes of at most 2^28 floats, api.cpp's map limit -- the byte offset
+							// need not: a 64-bit offset, one v_lshl_add_u64 where the 32-bit form had a shift.  Measured equal within the
+							// run-to-run spread on C3 / C5 / C2 / C4, profiles/r05_raw/wide_mip_abn.txt; with HMRM_WIDE_MIP 0 -- round 4 --
+							// very oblong maps near the 2^29-cell limit, 16385 x 32766, had to be rendered by the literal loop, 85 x slower.)
+							float mf = HMRM_WIDE_MIP ? mip[(size_t)((REC ? inb0 && top : inb0) ? widx : 0u)]
+							                         : *(const float *)((const char *)mip + (size_t)((inb0 ? widx : 0u) * 4u));
+							uint32_t rec_xs0 = ~0u, rec_xs1 = ~0u, rec_ys0 = ~0u, rec_ys1 = ~0u;
+							if constexpr (REC) { // the window's record: two 16-byte loads of one 32-byte line
+								const WindowRecord *recs = reinterpret_cast<const WindowRecord *>(f.mipbuf_bil);
+								const unsigned ridx = (inb0 && !top) ? (unsigned)index_2d(iy, rec_row(f.map_w), ix) : 0u;
+								const uint4 r0 = *reinterpret_cast<const uint4 *>(recs + ridx);
+								const uint2 r1 = *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(recs + ridx) + 16);
+								mf = top ? mf : __uint_as_float(r0.x);
+								rec_xs0 = r0.z; rec_xs1 = r0.w; rec_ys0 = r1.x; rec_ys1 = r1.y;
+							}
+							diag.load_end(f, 17, mf);
+							if (kEarlyLoad) refresh_stale();
+							const bool exact = kStepsLeft ? (ax.left | ay.left | az.left) >= 0
+							                              : ax.key != 0xffffffffu && ay.key != 0xffffffffu && az.key != 0xffffffffu;
+							const int left_min = min(ax.left, min(ay.left, az.left)); // (kStepsLeft)
+							const int wx0 = ix << hs, wy0 = iy << hs;
+							// (the last windows of a row / column hang over the map's edge: the usable span ends at the edge)
+							const int wcells = top ? (1 << 30) : (4 << (kLevelStep * lev)); // window size S in cells
+							const int wspan_x = min(wcells, f.map_w - wx0), wspan_y = min(wcells, f.map_h - wy0);
+							// estimates of the steps left before each lateral constraint bites; rdel is signed like
+							// the motion, so every quotient is >= 0.  Only estimates: verified below.
+							// (a coordinate that does not move -- s == 0 or absorbed -- has rdel = 2^40 and is strictly inside
+							// of whichever edge it looks at: a huge quotient once its sign is dropped, which costs nothing -- an
+							// operand modifier -- and changes nothing for a moving coordinate.  No case distinction needed.)
+							const double ex = (double)(offx ? wx0 : wx0 + wspan_x) * gwid;  // x edge ahead
+							const double ey = -(double)(offy ? wy0 : wy0 + wspan_y) * gwid; // y edge ahead
+							double room_lat = 0.0;
+							if (kStepsLeft) {
+								room_lat = __builtin_fmin(__builtin_fabs((ex - x) * ax.rdel), __builtin_fabs((ey - y) * ay.rdel));
+								// (computed here, not sunk behind the wait for the load: the empty statement reads the estimate
+								// and stands between the load and the first use of its result)
+								if (kEarlyLoad) asm volatile("" : "+v"(mf) : "v"(room_lat));
+							}
+							const double m = (double)mf; // (floats rounded up: also bounds every float / interpolated threshold)
+							const bool above = z >= m;
+							// Nothing below can succeed unless the ray is above this window's maximum: when no
+							// lane of the wave is, skip the estimate and the verification (the usual case in
+							// the last, nearly empty waves of a launch, which set its duration).
+							double room = 0.0, room_b = 0x1p40, room_z = 0.0;
+							bool z_bound = false, ok = false, can = false, binade_bound = false;
+							int n = 0;
+							const bool cand = inb0 && exact && above;
+							if (__builtin_amdgcn_ballot_w64(cand) != 0ull) {
+								if (kStepsLeft) {
+									room = room_lat;
+								} else {
+									room = (ax.lim - x) * ax.rdel;
+									room = __builtin_fmin(room, (ay.lim - y) * ay.rdel);
+									room = __builtin_fmin(room, (az.lim - z) * az.rdel);
+									room_b = room; // steps left inside the three binades
+									room = __builtin_fmin(room, sx != 0.0 ? (ex - x) * ax.rdel : 0x1p40);
+									room = __builtin_fmin(room, sy != 0.0 ? (ey - y) * ay.rdel : 0x1p40);
+								}
+								room_z = sz < 0.0 ? (m - z) * az.rdel : 0x1p40;
+								z_bound = room_z < room;
+								// (a select on the compare just made: the same value as fmin for the lanes that use it -- neither
+								// is NaN there (z >= m, finite non-zero reciprocals) -- without fmin's canonicalising v_max)
+								room = STATS ? __builtin_fmin(room, room_z) : (z_bound ? room_z : room);
+								// (the saturating cast takes care of huge and negative estimates; the step budget caps the
+								// integer: a jump never takes more steps than the cap has left)
+								n = min(cvt_i32_sat(room * 0.998), budget) - 1;
+								if (kStepsLeft) { // (the binades' share is an exact count, not an estimate)
+									// (kCross: the jump's last step is a real one and may leave the binade)
+									const int left_lim = left_min + (kCross ? 1 : 0);
+									binade_bound = left_lim <= n;
+									z_bound = z_bound & !binade_bound;
+									n = min(n, left_lim);
+								} else {
+									binade_bound = room_b <= room;
+								}
+								can = cand && n >= kMinLeap;
+								// landing point and its exact verification
+								// (kCross: n - 1 steps by multiplication, all inside the three binades by count, then one real step
+								// from that exact position.  Coordinates move monotonically, so the tests of the end point below
+								// hold for every position before it.)
+								const double nn = (double)(kCross ? n - 1 : n);
+								const double xm = x + nn * ax.delta, ym = y + nn * ay.delta, zm = z + nn * az.delta;
+								const double xn = kCross ? xm + sx : xm, yn = kCross ? ym + sy : ym, zn = kCross ? zm + sz : zm;
+								bool nearn = false;
+								const double qxn = cell_coord_fast<GWM>(xn, f, nearn), qyn = cell_coord_fast<GWM>(-yn, f, nearn);
+								const int gxn = cvt_i32_sat(qxn), gyn = GWM == 0 ? cvt_i32_sat_neg(yn) : cvt_i32_sat(qyn);
+								const bool inbn = (unsigned)gxn < wlim && (unsigned)gyn < hlim; // (diagnostics only)
+								// (inside the window implies inside the grid: the spans were cut at the map's edge)
+								// (kStepsLeft: n <= left of every axis, so the landing point is inside the three binades by count)
+								// (general grid widths, nearn: q' + 2^-20 lies in [k, k + 2^-19), so the landing cell is k = gxn or k - 1;
+								// both are asked to be inside the window, on both axes -- one flag serves the two)
+								const unsigned nm = (GWM == 2 && nearn) ? 1u : 0u;
+								ok = can && (unsigned)(gxn - wx0) - nm < (unsigned)wspan_x - nm &&
+								     (unsigned)(gyn - wy0) - nm < (unsigned)wspan_y - nm && zn >= m &&
+								     (kStepsLeft || (axis_landing_ok(ax, xn) && axis_landing_ok(ay, yn) && axis_landing_ok(az, zn)));
+								diag.on_landing_refused(f, can && !ok, inbn,
+								                        (unsigned)(gxn - wx0) < (unsigned)wspan_x && (unsigned)(gyn - wy0) < (unsigned)wspan_y, zn >= m);
+								if constexpr (REC) {
+									// The positions leaped over are x + k delta, k = 0 .. n - 1 (kCross: up to (xm, ym); else up to the landing
+									// point): all ON the segment between the first and the last, inside the window, at heights >= max2.  None
+									// of them may lie in a recorded cell: segment against each cell's box, in cells relative to the window's
+									// corner, float -- values below 32, conversion and product errors below 2^-13 -- with the box grown by
+									// 2^-10 and the line test given 2^-9 of slack: conservative, never wrong.  (Separating axes: the
+									// segment's extent in x, in y, and the line through it against the box's four corners.)
+									const double bxd = kCross ? xm : xn, byd = kCross ? ym : yn;
+									const double qbx = GWM == 0 ? bxd : bxd * f.inv_grid_width, qby = GWM == 0 ? -byd : -byd * f.inv_grid_width;
+									const float pax = (float)(qx2 - (double)wx0), pay = (float)(qy2 - (double)wy0);
+									const float pbx = (float)(qbx - (double)wx0), pby = (float)(qby - (double)wy0);
+									constexpr float grow = 0x1p-10f;
+									const float ddx = pbx - pax, ddy = pby - pay;
+									const float x_lo = __builtin_fminf(pax, pbx) - (1.0f + grow), x_hi = __builtin_fmaxf(pax, pbx) + grow;
+									const float y_lo = __builtin_fminf(pay, pby) - (1.0f + grow), y_hi = __builtin_fmaxf(pay, pby) + grow;
+									const float reach = (0.5f + grow) * (__builtin_fabsf(ddx) + __builtin_fabsf(ddy)) + 0x1p-9f;
+									const float cax = pax - 0.5f, cay = pay - 0.5f; // (cell corner - this = cell centre - start)
+									bool touched = false;
+#pragma unroll
+									for (int k = 0; k < kRecCells; ++k) {
+										const uint32_t wxs = k < 4 ? rec_xs0 : rec_xs1, wys = k < 4 ? rec_ys0 : rec_ys1;
+										const float cx = (float)((wxs >> (8 * (k & 3))) & 0xffu), cy = (float)((wys >> (8 * (k & 3))) & 0xffu);
+										const float ex = cx - cax, ey = cy - cay;
+										const float cross = ex * ddy - ey * ddx;
+										const bool apart = cx > x_hi || cx < x_lo || cy > y_hi || cy < y_lo || __builtin_fabsf(cross) > reach;
+										touched = touched || !apart;
+									}
+									// (the reference truncates: a coordinate in (-1, 0) -- a ray on its way out through the map's low edge --
+									// still names cell 0, which no box says.  Such paths are marched.)
+									const bool floor_is_trunc = __builtin_fmin(qx2, qbx) >= 0.0 && __builtin_fmin(qy2, qby) >= 0.0;
+									ok = ok && (top || (!touched && floor_is_trunc));
+								}
+								x = ok ? xn : x;
+								y = ok ? yn : y;
+								z = ok ? zn : z;
+								budget -= ok ? n : 0;
+								if (kStepsLeft) {
+									const int took = ok ? n : 0;
+									ax.left -= took;
+									ay.left -= took;
+									az.left -= took;
+								}
+							}
+							diag.on_attempt_done(f, inb0, exact, above, n < kMinLeap, z_bound, can, ok, n, lev);
+							diag.on_bounds(ok, binade_bound);
+							// level policy (performance only; any policy gives the same pixels):
+							//   window crossed                    -> coarser next time, if the height bound of this
+							//                                        level left room for a window kUpRatio times
+							//                                        longer (a coarser maximum is no lower)
+							//   jump ended at a binade boundary   -> same level (without kCross: and march a group first)
+							//   height bound was the limit        -> finer; without a jump retry at once (the
+							//     (z < max, or z-room smallest)      level strictly decreases); at the finest
+							//                                        level march 1 + finest_pause groups first
+							//   no lateral/binade room, not exact -> coarser (a bigger window has more room),
+							//                                        growing pause while attempts keep failing
+							const bool height_limited = inb0 && exact && (!above || z_bound);
+							// levels per move: two while the ray is young (kAdaptive), then one
+							const bool young = kAdaptive && jumps <= kAdaptAfter;
+							const int lstep = kAdaptive ? (young ? 2 : 1) : 1;
+							if (kAdaptive) jumps += ok ? 1 : 0;
+							const int coarser = lev + lstep > kMipLevels - 1 ? kMipLevels - 1 : lev + lstep;
+							const int minlev = f.min_level;
+#ifndef HMRM_DOWN
+#define HMRM_DOWN 1
+#endif
+							// a failed height test drops HMRM_DOWN levels, a height-limited jump one
+							const int drop = (ok ? 1 : HMRM_DOWN) * lstep;
+							const int finer = top ? kMipLevels - 1 : (lev - drop > minlev ? lev - drop : minlev);
+							const bool at_finest = lev == minlev;
+							// (selects, not branches: the three cases are mutually exclusive)
+							const bool crossed = ok && !z_bound;
+							const bool hl = !crossed && height_limited;
+							const bool other = !crossed && !hl;
+							// (lane-mask logic: `a ? b : c` on booleans would be materialised in VGPRs)
+							// (a window lstep levels up is 2^lstep times as long: the scaling rides on the exponent)
+							const double room_up = kAdaptive ? __builtin_ldexp(room, lstep) : kUpRatio * room;
+							const bool go_up = (crossed & (room_z >= room_up) & !binade_bound) | other;
+							const int fails_before = fails;
+							lev = hl ? finer : (go_up ? coarser : lev);
+							fails = (crossed | (hl & ok)) ? 0 : fails + (other ? 1 : 0);
+							cooldown = (hl & !ok & at_finest) ? f.finest_pause : (other ? (fails_before < 3 ? fails_before : 3) : 0);
+							// retry one level down without marching; after a jump look at the next window straight
+							// away -- unless the jump stopped at a binade boundary: only real steps cross it,
+							// another attempt here would just fail
+							// (kCross: the jump's last step has crossed it)
+							skip_group = (hl & !ok & !at_finest) | (ok & (kCross | !binade_bound));
+							if constexpr (REC) {
+								// two levels only: the whole map while the ray is above everything, then the record level for good.
+								// A refusal there is followed by a group; refusals in a row thin the attempts out (see `attempt`).
+								lev = lev == kTopLevel ? kTopLevel : kRecLevel;
+								fails = (ok | top) ? 0 : (fails_before < kRecBackoff ? fails_before + 1 : kRecBackoff);
+								skip_group = (top & hl & !ok) | (ok & (kCross | !binade_bound));
+							}
+						}
+					}
+					diag.on_trip(f, LEAP, skip_group);
+					if (skip_group) continue;
+
+					// --------------------------------------------- speculative group
+					diag.on_group();
+					double X[U], Y[U], Z[U], T[U];
+					unsigned cell[U]; // (unsigned: the 64-bit address needs no sign extension)
+					bool inb[U];
+					X[0] = x; Y[0] = y; Z[0] = z;
+#pragma unroll
+					for (int j = 1; j < U; ++j) {
+						X[j] = X[j - 1] + sx;
+						Y[j] = Y[j - 1] + sy;
+						Z[j] = Z[j - 1] + sz;
+					}
+					// cells of the U positions.  Only the integers are kept: the general-grid-width quotient q' is needed for
+					// nothing but its truncation (and the test whether it is too close to an integer to be trusted), and holding
+					// U pairs of them cost the general instantiations 12 vector registers (76: 6 waves per SIMD).  The
+					// bilinear mode needs the exact quotients themselves (its weights) and keeps them.
+					double QX[BILINEAR ? U : 1], QY[BILINEAR ? U : 1];
+					bool near = false;
+#pragma unroll
+					for (int j = 0; j < U; ++j) {
+						int gx, gy;
+						if constexpr (BILINEAR && GWM != 0) { // (the exact q: true division unless the reciprocal is exact)
+							QX[j] = GWM == 2 ? X[j] / f.grid_width : X[j] * f.inv_grid_width;
+							QY[j] = GWM == 2 ? -Y[j] / f.grid_width : -Y[j] * f.inv_grid_width;
+							gx = cvt_i32_sat(QX[j]);
+							gy = cvt_i32_sat(QY[j]);
+						} else {
+							const double qx = cell_coord_fast<GWM>(X[j], f, near), qy = cell_coord_fast<GWM>(-Y[j], f, near);
+							if constexpr (BILINEAR) { QX[j] = qx; QY[j] = qy; }
+							gx = cvt_i32_sat(qx);                                       // hmap.cpp:1001-1004
+							gy = GWM == 0 ? cvt_i32_sat_neg(Y[j]) : cvt_i32_sat(qy);
+						}
+						inb[j] = (unsigned)gx < wlim && (unsigned)gy < hlim;      // hmap.cpp:1006-1011
+						cell[j] = inb[j] ? (unsigned)index_2d(gy, f.map_w, gx) : 0u;
+					}
+					if (GWM == 2 && !BILINEAR && near) { // some position is on a cell boundary to within 2^-20: divide for real
+#pragma unroll
+						for (int j = 0; j < U; ++j) {
+							// (one division at a time: interleaved, their temporaries set the kernel's register count)
+							__builtin_amdgcn_sched_barrier(0);
+							const int gx = cvt_i32_sat(X[j] / f.grid_width);
+							__builtin_amdgcn_sched_barrier(0);
+							const int gy = cvt_i32_sat(-Y[j] / f.grid_width);
+							inb[j] = (unsigned)gx < wlim && (unsigned)gy < hlim;
+							cell[j] = inb[j] ? (unsigned)index_2d(gy, f.map_w, gx) : 0u;
+						}
+						__builtin_amdgcn_sched_barrier(0);
+					}
+					diag.load_begin(f, 18);
+					if constexpr (BILINEAR) {
+#pragma unroll
+						for (int j = 0; j < U; ++j) {
+							const Bil b = bil_setup(inb[j] ? QX[j] : 0.0, inb[j] ? QY[j] : 0.0, f.map_w, f.map_h);
+							T[j] = bil_mix(b, thr[b.c00], thr[b.c10], thr[b.c01], thr[b.c11]);
+						}
+					} else {
+#pragma unroll
+						// (32-bit byte offsets from the table's base -- api.cpp caps maps at 2^29 cells -- so that the loads can
+						// take the base from scalar registers: no 64-bit address arithmetic per sample)
+						for (int j = 0; j < U; ++j)
+							T[j] = F32 ? (double)*(const float *)((const char *)thr32 + (size_t)(cell[j] * 4u))
+							           : *(const double *)((const char *)thr + (size_t)(cell[j] * 8u)); // hmap.cpp:1013-1014 (+ c0.z)
+					}
+					if constexpr (U == 4) diag.load_end(f, 18, T[0], T[1], T[2], T[3]);
+					if (budget >= U) {
+						// in order: the first position that leaves the grid (:1006) or hits (:1016) ends the ray
+						int first = U, hit_j = 0;
+						unsigned hit_cell = 0u;
+						bool hit = false, stop = false;
+#pragma unroll
+						for (int j = U - 1; j >= 0; --j) { // (selects, last write = earliest position)
+							const bool h = inb[j] && Z[j] < T[j];
+							const bool s = !inb[j] || h;
+							if (COUNT) first = s ? j : first;
+							stop = stop | s; // (lane masks: no VGPR select)
+							hit = s ? h : hit;
+							hit_cell = s ? cell[j] : hit_cell;
+							hit_j = s ? j : hit_j;
+						}
+						// loads the reference executed in this group: U unless the ray ends in it.  Only the instrumented kernel
+						// and the ray batches read the budget of a ray that has ended (its step count), so only they count the exact
+						// share of the last group; the others need the budget of rays that go on, and first + hit = U for those.
+						budget -= COUNT ? first + (hit ? 1 : 0) : U;
+						done = stop;
+						if (hit) {
+							if constexpr (BILINEAR) {
+								// (the weights are rebuilt for the one position that hit: cheaper than keeping
+								// U sets of them alive)
+								double qxh = QX[0], qyh = QY[0];
+#pragma unroll
+								for (int j = 1; j < U; ++j) {
+									qxh = hit_j == j ? QX[j] : qxh;
+									qyh = hit_j == j ? QY[j] : qyh;
+								}
+								rgba = shade_hit_bilinear(f, cmap, (int)hit_cell, bil_setup(qxh, qyh, f.map_w, f.map_h));
+							} else {
+								rgba = shade_hit(f, cmap[hit_cell]);
+							}
+							real_hit = true;
+							if constexpr (RAYS) {
+								hx = X[0]; hy = Y[0]; hz = Z[0];
+#pragma unroll
+								for (int j = 1; j < U; ++j) {
+									hx = hit_j == j ? X[j] : hx;
+									hy = hit_j == j ? Y[j] : hy;
+									hz = hit_j == j ? Z[j] : hz;
+								}
+								hcell = hit_cell;
+							}
+							if constexpr (LIT) {
+								// The shadow ray's origin (P.x, P.y, t): int_point's x and y where :1016 fired and the threshold z was
+								// below.  The lane leaves the loop with it in x, y, z, which nothing else reads after a hit, so no
+								// register is held across the loop for it; and X[hit_j] is made again from the group's start with
+								// the same sequential adds (the same bits) so that X[1 .. U-2] need not outlive the cell indices.
+								double ox = x, oy = y, ot = T[0];
+#pragma unroll
+								for (int j = 1; j < U; ++j) {
+									ox = hit_j >= j ? ox + sx : ox;
+									oy = hit_j >= j ? oy + sy : oy;
+									ot = hit_j == j ? T[j] : ot;
+								}
+								x = ox; y = oy; z = ot;
+							}
+						}
+					} else {
+						// (almost never) close to the step cap: the literal loop, one position at a time, cap
+						// checked per step; a real loop over scalars so that none of the group's arrays is
+						// indexed dynamically
+						double xs = x, ys = y, zs = z;
+#pragma unroll 1
+						for (int j = 0; j < U; ++j) {
+							const double qx = (GWM == 0) ? xs : xs / f.grid_width, qy = (GWM == 0) ? -ys : -ys / f.grid_width;
+							const int gx = cvt_i32_sat(qx), gy = cvt_i32_sat(qy);
+							if (!((unsigned)gx < wlim && (unsigned)gy < hlim)) { done = true; break; }
+							if (budget <= 0) { my_cap = 1; done = true; break; }
+							--budget;
+							const int c = gy * f.map_w + gx;
+							Bil b{};
+							double t;
+							if (BILINEAR) {
+								b = bil_setup(qx, qy, f.map_w, f.map_h);
+								t = bil_mix(b, thr[b.c00], thr[b.c10], thr[b.c01], thr[b.c11]);
+							} else {
+								t = F32 ? (double)thr32[c] : thr[c];
+							}
+							if (zs < t) { // hmap.cpp:1016
+								rgba = BILINEAR ? shade_hit_bilinear(f, cmap, c, b) : shade_hit(f, cmap[c]);
+								real_hit = true;
+								if constexpr (RAYS) { hx = xs; hy = ys; hz = zs; hcell = (unsigned)c; }
+								if constexpr (LIT) { x = xs; y = ys; z = t; } // (as above)
+								done = true;
+								break;
+							}
+							xs += sx;
+							ys += sy;
+							zs += sz;
+						}
+					}
+					if constexpr (LIT) { // (a lane that hit keeps what the hit left in x, y, z)
+						x = real_hit ? x : X[U - 1] + sx;
+						y = real_hit ? y : Y[U - 1] + sy;
+						z = real_hit ? z : Z[U - 1] + sz;
+					} else {
+						x = X[U - 1] + sx;
+						y = Y[U - 1] + sy;
+						z = Z[U - 1] + sz;
+					}
+					if (LEAP && kStepsLeft) { // U real steps further inside (or out of) the binades
+						ax.left -= U;
+						ay.left -= U;
+						az.left -= U;
+					}
+				}
+				if (COUNT) my_steps = (unsigned long long)(unsigned)(budget0 - budget);
+				if constexpr (SEG && COUNT) my_steps = (unsigned long long)(unsigned)(sg.budget - budget);
+				if constexpr (LIT) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
+			}
+			if constexpr (LIT) {
+				// After the primary rays: the lanes that hit keep their pixel and become their shadow rays -- the ray, its d, its step
+				// (above) and its budget min(step cap, L) are replaced, everything derived from them is computed again by the second
+				// pass -- the others get d = inf and sit it out.  A wave without a hit is finished.  After the shadow rays: real_hit
+				// says SHADOWED for the lanes that marched one.
+				again = false;
+				if (lt.phase == 0) {
+					lt.primary_hit = real_hit;
+					lt.rgba = rgba;
+					if (__builtin_amdgcn_ballot_w64(real_hit) != 0ull) {
+						lt.phase = 1;
+						again = true;
+						// (every lane takes the new ray -- a lane that keeps its old one would hold it in registers through the
+						// second march for nothing -- and only its dz, for the miss shade, is put aside)
+						lt.dz = ray.dz;
+						ray = shadow_ray(lt, sun);
+						d = __builtin_huge_val();
+						if (real_hit) {
+							d = shadow_entry(ray, f);
+							sg.budget = segment_budget(SegRules{nullptr, sun.max_steps, 1u}, 0, f.step_cap, &sg.ends);
+						}
+						real_hit = false;
+					}
+				}
+			}
+		} while (LIT && again);
+		if constexpr (LIT) {
+			if (lt.primary_hit) { // MISS, END and CAPPED shadow rays leave the pixel lit
+				rgba = real_hit ? shade_shadowed(lt.rgba, sun.ambient) : lt.rgba;
+				real_hit = true;
+			}
+			ray.dz = lt.phase ? lt.dz : ray.dz; // (the primary ray's, for the miss shade)
+		}
+
+		if (real_hit) my_hit = 1;
+		else rgba = shade_miss(f, ray.dz);
+		if constexpr (SEG) { // an END ray is not a capped one: not counted, never HMRM_E_NOTERM
+			sg.ended = my_cap != 0u && sg.ends;
+			my_cap = sg.ended ? 0u : my_cap;
+		}
+		// (row and pitch are below 2^31, api.cpp: one 32 x 32 -> 64-bit multiply-add)
+		if constexpr (RAYS) {
+			const unsigned cy = hcell / (unsigned)f.map_w; // (gridx, gridy of hmap.cpp:1001-1004 from gridx + gridy * W)
+			if constexpr (SEG) {
+				store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy,
+				                sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
+			} else
+			store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy, d,
+			                (uint32_t)my_steps, rgba);
+		} else if constexpr (AA) aa_rgba = rgba;
+		else out[(uint64_t)(uint32_t)pid.lrow * (uint32_t)out_stride_px + (uint32_t)pid.px] = rgba;
+		if (STATS && st.steps_per_pixel)
+			st.steps_per_pixel[(int64_t)pid.py * f.screen_w + pid.px] = diag.pixel_value(f, my_steps);
+	}
+	if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, lane, pid.px, pid.lrow, pid.live, aa_rgba);
+	publish_counters<STATS>(st, my_steps, my_hit, my_cap);
+	diag.publish(st, f);
+	return pid.tile_y;
+}
+
+} // namespace hmrm

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "device_common.hpp"
+#include "launch_common.hpp"
 #include "render.hpp"
 
 #pragma clang fp contract(off)
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 // The literal loop for the pixel (or, PROJ 4, the batch ray: hmrm_trace_rays, frame.hpp RayBatch) of one lane.
 // AA: the antialiased epilogue (device_common.hpp store_box_filtered, f.aa_shift); the plain instantiations store per lane.
 // PROJ 4: the lane's ray comes from `batch` and its hmrm_ray_hit record goes there; `out` is not used.
-// SEG: the segment rules (frame.hpp SegRules; hmrm_trace_segments, hmrm_render_interior), as in render_fast.hip.
+// SEG: the segment rules (frame.hpp SegRules; hmrm_trace_segments, hmrm_render_interior), as in march.hpp.
 // LIT (hmrm_render_lit; frame.hpp SunRules; implies SEG): one of the two passes of a lit pixel, which hand each other `lit` in
 // registers and write no pixel themselves.  1: the primary ray -- its pixel, whether it hit, and where and under which
 // threshold, go to *lit.  2: the shadow ray of a lane whose primary ray hit, made from *lit and `sun` with the sun's step
@@ -398,22 +399,21 @@ template <bool STATS, bool AA>
 static hipError_t launch_render_t(const DevFrame &f, const RowMap &rows, const double *d_thr,
                                   const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
                                   StatsOut st, hipStream_t stream) {
-	const int tiles_x = (f.screen_w + kTileW - 1) / kTileW;
-	const int tiles_y = (rows.local_rows + kTileH - 1) / kTileH;
-	if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
-	const dim3 grid((unsigned)tiles_x, (unsigned)(tiles_y < 32768 ? tiles_y : 32768), (unsigned)((tiles_y + 32767) / 32768)), block(kBlockThreads);
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	const dim3 block(kBlockThreads);
 	switch (f.projection) {
 	case 1:
-		hipLaunchKernelGGL((k_render<1, STATS, AA>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
-		                   out_stride_px, tiles_y, st);
+		hipLaunchKernelGGL((k_render<1, STATS, AA>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
+		                   out_stride_px, g.tiles_y, st);
 		break;
 	case 2:
-		hipLaunchKernelGGL((k_render<2, STATS, AA>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
-		                   out_stride_px, tiles_y, st);
+		hipLaunchKernelGGL((k_render<2, STATS, AA>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
+		                   out_stride_px, g.tiles_y, st);
 		break;
 	default:
-		hipLaunchKernelGGL((k_render<3, STATS, AA>), grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
-		                   out_stride_px, tiles_y, st);
+		hipLaunchKernelGGL((k_render<3, STATS, AA>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
+		                   out_stride_px, g.tiles_y, st);
 		break;
 	}
 	return hipGetLastError();
@@ -421,22 +421,18 @@ static hipError_t launch_render_t(const DevFrame &f, const RowMap &rows, const d
 
 hipError_t launch_trace_rays_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
                                      unsigned long long *d_counters, hipStream_t stream) {
-	if (batch.n <= 0) return hipSuccess;
-	if (batch.n > ((int64_t)1 << 29) || f.screen_w != kBatchW || (int64_t)f.screen_h * kBatchW < batch.n) return hipErrorInvalidValue;
-	const int tiles_y = (f.screen_h + kTileH - 1) / kTileH;
-	const dim3 grid((unsigned)(tiles_y < 32768 ? tiles_y : 32768), 1u, (unsigned)((tiles_y + 32767) / 32768));
-	hipLaunchKernelGGL(k_trace_rays_literal, grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_cmap, batch, tiles_y,
+	const LaunchGrid g = batch_grid(f, batch);
+	if (g.tiles_y == 0) return g.err;
+	hipLaunchKernelGGL(k_trace_rays_literal, g.grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_cmap, batch, g.tiles_y,
 	                   StatsOut{d_counters, nullptr, nullptr});
 	return hipGetLastError();
 }
 
 hipError_t launch_trace_segments_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
                                          const SegRules &seg, unsigned long long *d_counters, hipStream_t stream) {
-	if (batch.n <= 0) return hipSuccess;
-	if (batch.n > ((int64_t)1 << 29) || f.screen_w != kBatchW || (int64_t)f.screen_h * kBatchW < batch.n) return hipErrorInvalidValue;
-	const int tiles_y = (f.screen_h + kTileH - 1) / kTileH;
-	const dim3 grid((unsigned)(tiles_y < 32768 ? tiles_y : 32768), 1u, (unsigned)((tiles_y + 32767) / 32768));
-	hipLaunchKernelGGL(k_trace_segments_literal, grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_cmap, batch, seg, tiles_y,
+	const LaunchGrid g = batch_grid(f, batch);
+	if (g.tiles_y == 0) return g.err;
+	hipLaunchKernelGGL(k_trace_segments_literal, g.grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_cmap, batch, seg, g.tiles_y,
 	                   StatsOut{d_counters, nullptr, nullptr});
 	return hipGetLastError();
 }
@@ -444,16 +440,15 @@ hipError_t launch_trace_segments_literal(const DevFrame &f, const double *d_thr,
 hipError_t launch_render_interior_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
                                           uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
                                           hipStream_t stream) {
-	const int tiles_x = (f.screen_w + kTileW - 1) / kTileW;
-	const int tiles_y = (rows.local_rows + kTileH - 1) / kTileH;
-	if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
-	const dim3 grid((unsigned)tiles_x, (unsigned)(tiles_y < 32768 ? tiles_y : 32768), (unsigned)((tiles_y + 32767) / 32768)), block(kBlockThreads);
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	const dim3 block(kBlockThreads);
 	const StatsOut st{d_counters, nullptr, nullptr};
 	const SegRules seg{nullptr, 0u, 1u};
 	switch (f.projection) {
-	case 1: hipLaunchKernelGGL(k_render_interior_literal<1>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
-	case 2: hipLaunchKernelGGL(k_render_interior_literal<2>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
-	default: hipLaunchKernelGGL(k_render_interior_literal<3>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg); break;
+	case 1: hipLaunchKernelGGL(k_render_interior_literal<1>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg); break;
+	case 2: hipLaunchKernelGGL(k_render_interior_literal<2>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg); break;
+	default: hipLaunchKernelGGL(k_render_interior_literal<3>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg); break;
 	}
 	return hipGetLastError();
 }
@@ -461,16 +456,15 @@ hipError_t launch_render_interior_literal(const DevFrame &f, const RowMap &rows,
 hipError_t launch_render_lit_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
                                      uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
                                      bool primary_interior, hipStream_t stream) {
-	const int tiles_x = (f.screen_w + kTileW - 1) / kTileW;
-	const int tiles_y = (rows.local_rows + kTileH - 1) / kTileH;
-	if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
-	const dim3 grid((unsigned)tiles_x, (unsigned)(tiles_y < 32768 ? tiles_y : 32768), (unsigned)((tiles_y + 32767) / 32768)), block(kBlockThreads);
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	const dim3 block(kBlockThreads);
 	const StatsOut st{d_counters, nullptr, nullptr};
 	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
 	switch (f.projection) {
-	case 1: hipLaunchKernelGGL(k_render_lit_literal<1>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg, sun); break;
-	case 2: hipLaunchKernelGGL(k_render_lit_literal<2>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg, sun); break;
-	default: hipLaunchKernelGGL(k_render_lit_literal<3>, grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg, sun); break;
+	case 1: hipLaunchKernelGGL(k_render_lit_literal<1>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	case 2: hipLaunchKernelGGL(k_render_lit_literal<2>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	default: hipLaunchKernelGGL(k_render_lit_literal<3>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
 	}
 	return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "frame.hpp"
+#include "march_dispatch.hpp" // (enum FastKernel)
 
 namespace hmrm {
 
@@ -23,11 +24,10 @@ hipError_t launch_render(const DevFrame &f, const RowMap &rows, const double *d_
                          unsigned long long *d_counters, uint32_t *d_steps, double *d_entry,
                          bool stats, hipStream_t stream);
 
-// Production kernel (render_fast.hip): speculative step groups (kPlainGroups), plus exact leaps over empty pyramid
+// Production kernel (march.hpp; the frame launchers in render_fast.hip): speculative step groups (kPlainGroups), plus exact leaps over empty pyramid
 // windows (kLeaps), or over windows of the record level that are empty but for a few recorded cells the ray's path
 // misses (kRecords: nearest sampling only, `d_records` from launch_build_records).  Same outputs as launch_render.
 // f.sampling == 2 reads the float copy of the table (d_thr32, launch_thr_to_float) instead of d_thr.
-enum FastKernel { kPlainGroups = 0, kLeaps = 1, kRecords = 2 };
 hipError_t launch_render_fast(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
                               const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
                               unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
@@ -77,9 +77,9 @@ hipError_t launch_render_lit_literal(const DevFrame &f, const RowMap &rows, cons
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream);
 // thr32[i] = (float)thr[i], round to nearest (the "float heights" mode).
 hipError_t launch_thr_to_float(const double *d_thr, float *d_thr32, int64_t n, hipStream_t stream);
-// 3x3 maximum filter of the thr table (bounds every bilinear interpolation, render_fast.hip).
+// 3x3 maximum filter of the thr table (bounds every bilinear interpolation: render_fast.hip k_dilate3x3).
 hipError_t launch_dilate3x3(const double *d_thr, int w, int h, double *d_dst, hipStream_t stream);
-// Window-maximum pyramid (see render_fast.hip): level 0 from the thr table, level l+1 from level l.
+// Window-maximum pyramid (see march.hpp): level 0 from the thr table, level l+1 from level l.
 // `pitch` = row pitch (floats) of every plane of the pyramid buffer (DevFrame::mip_row).
 hipError_t launch_build_mip0(const double *d_thr, int map_w, int map_h, float *d_dst, int dst_w, int dst_h,
                              int pitch, hipStream_t stream);

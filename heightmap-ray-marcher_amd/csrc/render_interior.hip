@@ -4,9 +4,7 @@
 // projections, three grid modes, leaps and plain groups in the three sampling modes, window records for nearest sampling; no
 // instrumented and no antialiased ones -- in a translation unit of their own, as render_fast_aa.hip and render_rays.hip are:
 // the existing frame kernels keep their argument lists and their instructions.
-#undef HMRM_TIMELINE
-#define HMRM_RENDER_INTERIOR 1
-#include "render_fast.hip"
+#include "march.hpp"
 
 namespace hmrm {
 
@@ -23,71 +21,21 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
 	                                                                   (int)(threadIdx.x & 63), RayBatch{}, seg);
 }
 
-namespace {
-struct Launch {
-	const DevFrame &f;
-	const RowMap &rows;
-	const double *d_thr;
-	const uint32_t *d_cmap;
-	uint32_t *d_out;
-	int64_t out_stride_px;
-	StatsOut st;
-	SegRules seg;
-	dim3 grid;
-	int tiles_y;
-	hipStream_t stream;
-};
-
-template <int PROJ, int GWM, int LEAP, int SAMP>
-void launch_one(const Launch &l) {
-	hipLaunchKernelGGL((k_render_interior<PROJ, GWM, LEAP, SAMP>), l.grid, dim3(kBlockThreads), 0, l.stream, l.f, l.rows, l.d_thr,
-	                   l.d_cmap, l.d_out, l.out_stride_px, l.tiles_y, l.st, l.seg);
-}
-
-template <int PROJ, int GWM>
-void launch_kind(FastKernel kernel, const Launch &l) {
-	if (kernel == kRecords) { // (nearest sampling only: launch_render_interior has checked)
-		launch_one<PROJ, GWM, kRecords, 0>(l);
-	} else if (kernel == kLeaps) {
-		if (l.f.sampling == 1) launch_one<PROJ, GWM, kLeaps, 1>(l);
-		else if (l.f.sampling == 2) launch_one<PROJ, GWM, kLeaps, 2>(l); // (d_thr is the float table here)
-		else launch_one<PROJ, GWM, kLeaps, 0>(l);
-	} else {
-		if (l.f.sampling == 1) launch_one<PROJ, GWM, kPlainGroups, 1>(l);
-		else if (l.f.sampling == 2) launch_one<PROJ, GWM, kPlainGroups, 2>(l);
-		else launch_one<PROJ, GWM, kPlainGroups, 0>(l);
-	}
-}
-
-template <int PROJ>
-void launch_gwm(FastKernel kernel, const Launch &l) {
-	switch (l.f.grid_mode) {
-	case 0: launch_kind<PROJ, 0>(kernel, l); break;
-	case 1: launch_kind<PROJ, 1>(kernel, l); break;
-	default: launch_kind<PROJ, 2>(kernel, l); break;
-	}
-}
-} // namespace
-
 hipError_t launch_render_interior(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
                                   const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
                                   FastKernel kernel, const WindowRecord *d_records, hipStream_t stream) {
-	if (kernel == kRecords && (f.sampling != 0 || !d_records)) return hipErrorInvalidValue;
 	if (f.aa_shift != 0 || rows.measure != nullptr) return hipErrorInvalidValue;
 	DevFrame fr = f;
-	if (kernel == kRecords) fr.mipbuf_bil = reinterpret_cast<const float *>(d_records); // (as launch_fast does)
-	const double *d_thr = f.sampling == 2 ? reinterpret_cast<const double *>(d_thr32) : d_thr_f64;
-	const int tiles_x = (f.screen_w + kTileW - 1) / kTileW;
-	const int tiles_y = (rows.local_rows + kTileH - 1) / kTileH;
-	if (tiles_x <= 0 || tiles_y <= 0) return hipSuccess;
-	const dim3 grid((unsigned)tiles_x, (unsigned)(tiles_y < 32768 ? tiles_y : 32768), (unsigned)((tiles_y + 32767) / 32768));
-	const Launch l{fr, rows, d_thr, d_cmap, d_out, out_stride_px, StatsOut{d_counters, nullptr, nullptr}, SegRules{nullptr, 0u, 1u},
-	               grid, tiles_y, stream};
-	switch (f.projection) {
-	case 1: launch_gwm<1>(kernel, l); break;
-	case 2: launch_gwm<2>(kernel, l); break;
-	default: launch_gwm<3>(kernel, l); break;
-	}
+	const double *d_thr = nullptr;
+	if (const hipError_t e = select_tables(&fr, kernel, d_thr_f64, d_thr32, d_records, &d_thr); e != hipSuccess) return e;
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	const StatsOut st{d_counters, nullptr, nullptr};
+	const SegRules seg{nullptr, 0u, 1u};
+	dispatch_march(f.projection, f.grid_mode, kernel, f.sampling, [&](auto proj, auto gwm, auto leap, auto samp) {
+		hipLaunchKernelGGL((k_render_interior<proj(), gwm(), leap(), samp()>), g.grid, dim3(kBlockThreads), 0, stream, fr, rows, d_thr, d_cmap,
+		                   d_out, out_stride_px, g.tiles_y, st, seg);
+	});
 	return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-"""Seeded fuzz aimed at binade crossings (csrc/render_fast.hip HMRM_CROSS: a jump ends with one real step that carries a
+"""Seeded fuzz aimed at binade crossings (csrc/march.hpp HMRM_CROSS: a jump ends with one real step that carries a
 coordinate into its next binade): long, low maps crossed end to end by shallow rays -- a dozen binades of x or y towards
 the map's origin or away from it, several of z on the way down -- with step sizes that include exact rounding ties,
 power-of-two and general grid widths.  GPU vs CPU oracle on frames, per-ray step counts and distance() bits.

@@ -1,5 +1,5 @@
 """Seeded fuzz aimed at CELL BOUNDARIES under general grid widths (csrc/leap_common.hpp cell_coord_fast<2>, the attempt
-block of csrc/render_fast.hip): grid widths whose reciprocal rounds to an integer (0.05, 0.01, 0.2, 0.1, 1e-3: every
+block of csrc/march.hpp): grid widths whose reciprocal rounds to an integer (0.05, 0.01, 0.2, 0.1, 1e-3: every
 power of two is then a cell boundary to the last bit) and ones where it does not, with rays that run ALONG cell
 boundaries (orthographic cameras looking down an axis, columns a fraction of a cell apart from a corner that is a multiple
 of the cell), rays whose steps are exact fractions of a cell (positions ON a boundary every few steps), and perspective /

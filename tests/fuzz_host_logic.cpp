@@ -6,7 +6,9 @@
 //   row_cost.cpp      estimate_row_costs for degenerate and non-finite cameras (W = 1, H = 1, NaN angles, huge positions);
 //   launch_order.cpp  orders from measured records -- which the DEVICE writes, so nothing about them may be trusted:
 //                     every RowMap they lead to must hand every tile row to exactly one grid row, whatever the records
-//                     hold -- and the calibration's state machine under random event sequences.
+//                     hold -- and the calibration's state machine under random event sequences;
+//   march_dispatch.hpp  the ladder from (projection, grid mode, kernel kind, sampling) to the march kernels' template
+//                     arguments: every combination reaches its callable exactly once, with exactly those constants.
 //
 // usage: fuzz_host_logic <rounds> ; prints "host logic ok: ..." and returns 0, or aborts under the sanitizers.
 #include <cmath>
@@ -22,6 +24,7 @@
 #include "config.hpp"
 #include "frame.hpp"
 #include "launch_order.hpp"
+#include "march_dispatch.hpp"
 
 namespace {
 
@@ -300,6 +303,45 @@ int fuzz_calibration(int rounds) {
 	return settled;
 }
 
+// ---- the march kernels' dispatch ladder -------------------------------------------------------------------------------
+// What the ladder must hand over for run-time values (projection, grid_mode, kernel, sampling): out-of-range grid modes and
+// projections land where the launchers' `default:` branches sent them (GWM 2, PROJ 3), and the record kernel exists for
+// nearest sampling only (the launchers refuse it with another sampling before they come to the ladder).
+int check_dispatch() {
+	int calls_checked = 0;
+	for (int projection = -1; projection <= 5; ++projection)
+		for (int grid_mode = -1; grid_mode <= 4; ++grid_mode)
+			for (int kernel = 0; kernel <= 2; ++kernel)
+				for (int sampling = 0; sampling <= 2; ++sampling) {
+					const int want_proj = projection == 1 || projection == 2 ? projection : 3;
+					const int want_gwm = grid_mode == 0 || grid_mode == 1 ? grid_mode : 2;
+					const int want_samp = kernel == hmrm::kRecords ? 0 : sampling;
+					int calls = 0, got[4] = {-1, -1, -1, -1};
+					hmrm::dispatch_march(projection, grid_mode, kernel, sampling, [&](auto proj, auto gwm, auto leap, auto samp) {
+						++calls;
+						got[0] = decltype(proj)::value; got[1] = decltype(gwm)::value; got[2] = decltype(leap)::value; got[3] = decltype(samp)::value;
+					});
+					if (calls != 1 || got[0] != want_proj || got[1] != want_gwm || got[2] != kernel || got[3] != want_samp) {
+						fprintf(stderr, "dispatch: (%d, %d, %d, %d) -> %d calls, <%d, %d, %d, %d>\n", projection, grid_mode, kernel, sampling, calls,
+						        got[0], got[1], got[2], got[3]);
+						return -1;
+					}
+					if (projection != 1) continue; // (the variant without a projection: once per (grid_mode, kernel, sampling))
+					calls = 0;
+					got[1] = got[2] = got[3] = -1;
+					hmrm::dispatch_march(grid_mode, kernel, sampling, [&](auto gwm, auto leap, auto samp) {
+						++calls;
+						got[1] = decltype(gwm)::value; got[2] = decltype(leap)::value; got[3] = decltype(samp)::value;
+					});
+					if (calls != 1 || got[1] != want_gwm || got[2] != kernel || got[3] != want_samp) {
+						fprintf(stderr, "dispatch: (%d, %d, %d) -> %d calls, <%d, %d, %d>\n", grid_mode, kernel, sampling, calls, got[1], got[2], got[3]);
+						return -1;
+					}
+					calls_checked += 2;
+				}
+	return calls_checked;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -318,6 +360,7 @@ int main(int argc, char **argv) {
 	if (o < 0) return 1;
 	const int s = fuzz_calibration(rounds);
 	if (s < 0) return 1;
+	if (check_dispatch() < 0) return 1;
 	printf("host logic ok: %d config streams (%d accepted), %d cameras, %d launch orders, %d calibration runs (%d settled)\n", rounds, a, f,
 	       o, rounds, s);
 	return 0;

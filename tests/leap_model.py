@@ -1,4 +1,4 @@
-"""Pure-Python model of the exact-leap arithmetic of csrc/render_fast.hip
+"""Pure-Python model of the exact-leap arithmetic of csrc/march.hpp
 (axis_refresh / axis_landing_ok), used by CPU tests to check the claim the GPU
 kernel relies on:
 

@@ -1,5 +1,5 @@
 """CPU property tests of the general-grid-width cell rule of the production kernel (csrc/leap_common.hpp
-cell_coord_fast<2>, csrc/render_fast.hip): the reference computes (int)((x - c0.x) / grid_width)
+cell_coord_fast<2>, csrc/march.hpp): the reference computes (int)((x - c0.x) / grid_width)
 (main/hmap.cpp:1001-1004); the kernel computes q'' = fma(v, fl(1 / gw), 2^-20) and
 
   (1) off the neighbourhood of an integer -- fract(q'') >= 2^-19 -- trunc(q'') equals the reference's cell;

@@ -1,5 +1,5 @@
 """CPU property tests of the arithmetic the production kernel's exact leaps rely on
-(csrc/render_fast.hip, modelled in tests/leap_model.py):
+(csrc/march.hpp, modelled in tests/leap_model.py):
 
   whenever axis_refresh accepts (p, s) and axis_landing_ok accepts p + n*delta, the
   value p + n*delta computed with ONE multiply and ONE add equals the reference's n
@@ -175,7 +175,7 @@ def test_steps_left_count_is_a_safe_bound(short):
 
 
 def test_jumps_ending_in_a_real_step_cross_binades_exactly():
-    """HMRM_CROSS (csrc/render_fast.hip): a jump is `left` multiplied steps and then one real step fl(p + s).  A ray
+    """HMRM_CROSS (csrc/march.hpp): a jump is `left` multiplied steps and then one real step fl(p + s).  A ray
     that only ever moves that way -- refresh, jump to the binade's end, cross with the real step, refresh ... -- visits
     positions of the reference's sequence p += s, bit for bit, through many binades in either direction; and the
     real step after the counted ones does leave the binade nearly always (else the next refresh fails and a group

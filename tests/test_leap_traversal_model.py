@@ -1,4 +1,4 @@
-"""CPU model of the production kernel's traversal (csrc/render_fast.hip) against plain sequential marching
+"""CPU model of the production kernel's traversal (csrc/march.hpp) against plain sequential marching
 (main/hmap.cpp:1000-1038): window maxima, estimated jump lengths, exact verification of the end point, binade stays
 counted by tests/leap_model.py, jumps that end in one real step (HMRM_CROSS), groups of real steps otherwise.
 Same hit cell, same step count and the same final position (bit for bit) for every ray -- with ANY level policy, which is why the policy here is a crude one.

@@ -532,7 +532,7 @@ def test_exact_tie_steps_and_many_binades(gpu, oracle):
 
 
 def test_jumps_cross_binade_boundaries_themselves(gpu, oracle, monkeypatch):
-    """csrc/render_fast.hip (HMRM_CROSS): a jump ends with one real step, so a jump that a binade's end cut short
+    """csrc/march.hpp (HMRM_CROSS): a jump ends with one real step, so a jump that a binade's end cut short
     carries its coordinate into the next binade itself.  The instrumented kernel counts what came before each group of
     real steps (diagnostic mode 20): none may follow such a jump any more -- before, half of all groups did.  Pixels and
     step counts against the oracle as everywhere; a general grid width, whose binade boundaries fall inside windows."""

@@ -1,6 +1,6 @@
 """Offline model (no GPU) of COOPERATIVE TRAVERSAL for the production kernel's tail: once a wave has
 few live rays, the idle lanes take over disjoint step ranges [k_j, k_j+1) of the live rays -- inside a binade
-p_k = p_0 + k * delta exactly (render_fast.hip header), so a helper lane can start k_j steps down the ray without having
+p_k = p_0 + k * delta exactly (march.hpp header), so a helper lane can start k_j steps down the ray without having
 walked there -- and the lowest range that finds a hit / the grid's edge decides.
 
 The kernel's traversal (level policy, windows, 4-step groups; binade stays as exact step counts) is ported to Python;

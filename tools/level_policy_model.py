@@ -1,4 +1,4 @@
-"""Offline estimate: trips per ray under (a) the kernel's level policy (ported from render_fast.hip), (b) the same with the best of
+"""Offline estimate: trips per ray under (a) the kernel's level policy (ported from march.hpp), (b) the same with the best of
 {finer, lev, coarser} looked up in one attempt, (c) the best of all levels (oracle)."""
 import importlib, sys, math
 import numpy as np

@@ -3,7 +3,7 @@
 
 Every instruction of the march loop of one k_render_fast instantiation (default: the C3 headline's, spherical, leaps,
 nearest cell) is attributed to a purpose -- start cell, window geometry, refresh, estimate, landing, policy, group, ...
--- by the source line it was compiled from.  The lines come from a second compile of render_fast.hip with
+-- by the source line of march.hpp it was compiled from.  The lines come from a second compile of render_fast.hip with
 -gline-tables-only and otherwise the flags of `make asm`; the tool first checks that this compile emits exactly the
 instruction stream of the plain one (line tables must not change the code they describe), else it stops.  Inlined
 helpers (cvt_i32_sat, axis_refresh, ...) are attributed to the line of render_wave_tile they were inlined into.
@@ -32,7 +32,9 @@ import isa_cost  # noqa: E402
 DEFAULT_CSRC = os.path.join(os.path.dirname(HERE), "heightmap-ray-marcher_amd", "csrc")
 C3 = "ILi2ELb0ELi0ELi1ELi0ELb0E"
 
-# A line of render_fast.hip gets the purpose of the last marker at or above it (markers in source order).
+MARCH_SRC = "march.hpp"  # the file that holds render_wave_tile
+
+# A line of it gets the purpose of the last marker at or above it (markers in source order).
 MARKERS = [
     ("bool done = entry_nan;", "loop control"),
     ("const bool attempt = REC", "attempt decision"),
@@ -56,7 +58,7 @@ MARKERS = [
     ("if (budget >= U) {", "group: tests, advance"),
     ("// (almost never) close to the step cap", "cap path"),
     ("x = X[U - 1] + sx;", "group: tests, advance"),
-    ("if (STATS) my_steps =", "epilogue"),
+    ("if (COUNT) my_steps =", "epilogue"),
 ]
 KIND = {"loop control": "control", "attempt decision": "control", "refresh": "refresh", "cap path": "cap",
         "epilogue": "control"}
@@ -122,12 +124,12 @@ def instructions(text):
 
 
 def source_line(loc, lo, hi):
-    """The innermost render_fast.hip line of an inline chain ('a.hpp:12:3 @[ render_fast.hip:283:5 @[ ... ] ]')
+    """The innermost march.hpp line of an inline chain ('a.hpp:12:3 @[ march.hpp:283:5 @[ ... ] ]')
     that lies inside render_wave_tile's body [lo, hi]."""
     if not loc:
         return None
     for f, ln in re.findall(r'([\w./-]+):(\d+):\d+', loc):
-        if os.path.basename(f) == "render_fast.hip" and lo <= int(ln) <= hi:
+        if os.path.basename(f) == MARCH_SRC and lo <= int(ln) <= hi:
             return int(ln)
     return None
 
@@ -140,7 +142,7 @@ def marker_lines(src_path):
     for text, purpose in MARKERS:
         ln = next((i for i, l in enumerate(src, 1) if i >= start and text in l), None)
         if ln is None:
-            sys.exit(f"marker not found in render_fast.hip: {text!r}")
+            sys.exit(f"marker not found in {MARCH_SRC}: {text!r}")
         marks.append((ln, purpose))
         start = ln
     return marks, body_lo, body_hi
@@ -176,7 +178,7 @@ def main():
         sys.exit(f"the -gline-tables-only build differs from `make asm` at instruction {k}: "
                  f"{plain[k][2] if k < len(plain) else '(end)'!r} vs {tagged[k][2] if k < len(tagged) else '(end)'!r}")
 
-    marks, lo, hi = marker_lines(os.path.join(a.csrc, "render_fast.hip"))
+    marks, lo, hi = marker_lines(os.path.join(a.csrc, MARCH_SRC))
     # purposes per instruction: own line, else the previous attributed instruction of the block
     rows, last = [], {}
     for blk, loop, ins, loc in tagged:

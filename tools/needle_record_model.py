@@ -103,7 +103,7 @@ def record(level, wx0, wy0, K):
 
 
 def window(level, gx, gy, sx, sy):
-    """the kernel's window for a ray at cell (gx, gy): quarter-stride placement, >= 3/4 of the window ahead (render_fast.hip)"""
+    """the kernel's window for a ray at cell (gx, gy): quarter-stride placement, >= 3/4 of the window ahead (march.hpp)"""
     Sz = 4 << level
     st = 2 if level == 0 else Sz // 4
     back = 1 if level == 0 else 3
