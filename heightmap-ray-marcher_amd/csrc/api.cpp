@@ -644,7 +644,15 @@ int launch_shadow_probe(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, co
 struct LitFrame {
 	hmrm::SunRules sun;
 	bool primary_interior; // HMRM_TRACE_INTERIOR: the primary rays under the interior rule too
+	uint32_t shade_flags;  // hmrm_render_shaded's HMRM_SHADE_*; 0: hmrm_render_lit's frame, by its kernels
 };
+// (hmrm_render_shaded) Without HMRM_SHADE_DIFFUSE a pixel that is not shadowed has the weight 255: the kernels without shadow
+// rays get that from ambient = 255, whatever the level.
+hmrm::SunRules shade_sun(const LitFrame &lit) {
+	hmrm::SunRules sun = lit.sun;
+	if (!(lit.shade_flags & HMRM_SHADE_DIFFUSE)) sun.ambient = 255u;
+	return sun;
+}
 int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hmrm::RowMap &rows_in_order, uint32_t *d_out,
                   int64_t out_stride_px, uint32_t *d_steps, double *d_entry, bool stats, bool use_group, bool interior = false,
                   const LitFrame *lit = nullptr) {
@@ -652,6 +660,12 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 	if (huge_side && f.sampling != 0)
 		return fail(HMRM_E_ARG, "maps with a side of 2^24 cells or more support nearest sampling only");
 	if ((s->knobs.kernel == 2 || huge_side) && f.sampling == 0) { // (the literal loop only knows the reference's sampling)
+		if (lit && lit->shade_flags) {
+			const bool shadows = !(lit->shade_flags & HMRM_SHADE_NO_SHADOWS);
+			HIP_TRY(hmrm::launch_render_shaded_literal(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters,
+			                                           shadows ? lit->sun : shade_sun(*lit), lit->primary_interior, shadows, c->stream));
+			return HMRM_OK;
+		}
 		if (lit) {
 			HIP_TRY(hmrm::launch_render_lit_literal(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters, lit->sun,
 			                                        lit->primary_interior, c->stream));
@@ -669,6 +683,21 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		if (k == hmrm::kRecords) {
 			const int rc_r = ensure_records(s);
 			if (rc_r) return rc_r;
+		}
+		// (HMRM_SHADE_NO_SHADOWS without HMRM_SHADE_DIFFUSE is hmrm_render's frame by definition.  It goes through the shaded kernel
+		// with every weight 255 all the same, not through launch_render_interior / launch_render_fast: the interior launcher always
+		// sets the interior rule, which this frame has only with HMRM_TRACE_INTERIOR, and the plain one belongs to frames that may
+		// be measured or be the probe, which no frame of this entry point is.  The levels it computes for nothing are the price
+		// of one route; the combination is an identity for tests, not something to render with.)
+		if (lit && (lit->shade_flags & HMRM_SHADE_NO_SHADOWS)) {
+			HIP_TRY(hmrm::launch_render_shaded(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px, c->d_counters, k,
+			                                   s->d_records, shade_sun(*lit), lit->primary_interior, c->stream));
+			return HMRM_OK;
+		}
+		if (lit && lit->shade_flags) { // (HMRM_SHADE_DIFFUSE alone)
+			HIP_TRY(hmrm::launch_render_lit_shaded(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px, c->d_counters, k,
+			                                       s->d_records, lit->sun, lit->primary_interior, c->stream));
+			return HMRM_OK;
 		}
 		if (lit) {
 			HIP_TRY(hmrm::launch_render_lit(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px, c->d_counters, k,
@@ -1335,14 +1364,32 @@ int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_
 }
 
 // Sun shadows: hmrm_render's frame (hmrm_render_interior's with HMRM_TRACE_INTERIOR), the hit pixels' shadow rays marched
-// by the same launch.  The sun is checked before anything else is looked at.
-int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint8_t *rgba, size_t stride_bytes) {
+// by the same launch.  The sun is checked before anything else is looked at (check_sun: hmrm_render_lit's three refusals,
+// hmrm_render_shaded's too).
+static int check_sun(const hmrm_sun *sun) {
 	if (!sun) return fail(HMRM_E_ARG, "NULL sun");
 	if (sun->flags & ~HMRM_TRACE_INTERIOR) return fail(HMRM_E_ARG, "hmrm_sun.flags: undefined bit");
 	for (uint8_t r : sun->reserved)
 		if (r) return fail(HMRM_E_ARG, "hmrm_sun.reserved must be 0");
-	const LitFrame lit{hmrm::SunRules{{sun->dir[0], sun->dir[1], sun->dir[2]}, sun->step_dist, sun->max_steps, sun->ambient},
-	                   (sun->flags & HMRM_TRACE_INTERIOR) != 0u};
+	return HMRM_OK;
+}
+static LitFrame make_lit_frame(const hmrm_sun *sun, uint32_t shade_flags) {
+	return LitFrame{hmrm::SunRules{{sun->dir[0], sun->dir[1], sun->dir[2]}, sun->step_dist, sun->max_steps, sun->ambient},
+	                (sun->flags & HMRM_TRACE_INTERIOR) != 0u, shade_flags};
+}
+int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint8_t *rgba, size_t stride_bytes) {
+	if (const int rc = check_sun(sun)) return rc;
+	const LitFrame lit = make_lit_frame(sun, 0u);
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, nullptr, nullptr, nullptr, false, 1, false, &lit);
+}
+
+// Diffuse sun shading: the lit frame whose hit pixels are weighted by their diffuse level, with or without the shadow rays.
+// shade_flags = 0 is hmrm_render_lit itself, launch for launch.
+int hmrm_render_shaded(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags, uint8_t *rgba,
+                       size_t stride_bytes) {
+	if (const int rc = check_sun(sun)) return rc;
+	if (shade_flags & ~(HMRM_SHADE_DIFFUSE | HMRM_SHADE_NO_SHADOWS)) return fail(HMRM_E_ARG, "shade_flags: undefined bit");
+	const LitFrame lit = make_lit_frame(sun, shade_flags);
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, nullptr, nullptr, nullptr, false, 1, false, &lit);
 }
 
@@ -1834,6 +1881,7 @@ int32_t hmrm_config_devices(const hmrm_config *c) { return c->cfg.devices; }
 int32_t hmrm_config_antialias(const hmrm_config *c) { return c->cfg.antialias; }
 int32_t hmrm_config_interior(const hmrm_config *c) { return c->cfg.interior; }
 int32_t hmrm_config_shadows(const hmrm_config *c) { return c->cfg.shadows; }
+int32_t hmrm_config_shading(const hmrm_config *c) { return c->cfg.shading; }
 void hmrm_config_get_sun(const hmrm_config *c, hmrm_sun *out) {
 	const hmrm::Config &g = c->cfg;
 	memset(out, 0, sizeof *out);

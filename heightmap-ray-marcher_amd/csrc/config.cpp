@@ -14,6 +14,7 @@
 //   output <path>                                   (.png or .ppm)
 //   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8, interior on|off,
 //   shadows on|off, sun_dir x y z, shadow_ambient n, shadow_step_dist v, shadow_max_steps n
+//   shading on|off
 #include "config.hpp"
 
 #include <cmath>
@@ -204,6 +205,14 @@ void shadows_key(Config &c, std::istream &in, const char *key, std::string *) {
 	c.log << key << " " << (c.shadows ? "on" : "off") << "\n";
 }
 
+// diffuse sun shading of the single frame (hmrm_render_shaded)
+void shading_key(Config &c, std::istream &in, const char *key, std::string *) {
+	static const Word words[] = {{"on", 1}, {"1", 1}, {"off", 0}, {"0", 0}};
+	std::string seen;
+	if (!pick(in, words, &c.shading, &seen)) c.warn << "WARNING: Unknown shading: " << seen << "\n";
+	c.log << key << " " << (c.shading ? "on" : "off") << "\n";
+}
+
 void sun_dir_key(Config &c, std::istream &in, const char *key, std::string *) { // towards the sun, used as given
 	in >> c.sun_dir[0] >> c.sun_dir[1] >> c.sun_dir[2];
 	c.log << key << " " << c.sun_dir[0] << " " << c.sun_dir[1] << " " << c.sun_dir[2] << "\n";
@@ -271,6 +280,7 @@ const Row kGrammar[] = {
 	{"antialias", antialias_key},
 	{"interior", interior_key},
 	{"shadows", shadows_key},
+	{"shading", shading_key},
 	{"sun_dir", sun_dir_key},
 	{"shadow_ambient", shadow_ambient_key},
 	{"shadow_step_dist", shadow_step_dist_key},

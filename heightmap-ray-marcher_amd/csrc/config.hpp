@@ -45,6 +45,9 @@ struct Config {
 	// additive: sun shadows of the CLI's single frame (hmrm_render_lit): `shadows on|off|1|0`, `sun_dir x y z` (towards the sun,
 	// used as given), `shadow_ambient 0..255`, `shadow_step_dist v` (absent: the camera's step_dist), `shadow_max_steps n`
 	int shadows = 0;
+	// additive: `shading on|off|1|0` -- diffuse sun shading of that frame (hmrm_render_shaded), with the shadow rays when
+	// `shadows on`; the sun is the same
+	int shading = 0;
 	double sun_dir[3] = {0.5, 0.5, 0.70710678118654757};
 	int shadow_ambient = 128;
 	double shadow_step_dist = 0.0;

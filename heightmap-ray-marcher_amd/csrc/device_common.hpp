@@ -124,6 +124,48 @@ __device__ __forceinline__ uint32_t shade_shadowed(uint32_t rgba, uint32_t ambie
 	return r | (g << 8) | (b << 16) | (rgba & 0xff000000u);
 }
 
+// Diffuse sun shading (hmrm_render_shaded, hmrm.h; SHADE in the kernels): what a lane keeps of its primary hit until the
+// epilogue computes its level -- the hit cell for the nearest-cell modes; for the bilinear mode, where no LitState holds the
+// hit point, the point's x and y (plain groups) or its exact cell coordinates (leaps: march.hpp KEEP_P / KEEP_Q).  Empty in
+// every other instantiation, as SegState is.
+template <bool SHADE, bool BILINEAR, bool LIT> struct ShadeState {};
+template <bool LIT> struct ShadeState<true, false, LIT> { unsigned cell = 0u; };
+template <> struct ShadeState<true, true, false> { double px = 0.0, py = 0.0; };
+// The diffuse level q in 0..255 of a surface with the gradient (gx, gy) -- gy along the rows, which grow towards decreasing
+// world y -- under the sun direction s as given: n = (-gx, gy, 1), q = round(255 * clamp(n.s / (|n| |s|), 0, 1)), every
+// operation a plain IEEE double one in the order of hmrm.h, NaN -> 0.  Nothing is special-cased.
+__device__ __forceinline__ uint32_t diffuse_level(double gx, double gy, const double (&s)[3]) {
+	const double nx = -gx, ny = gy;
+	const double dot = (nx * s[0] + ny * s[1]) + s[2];
+	const double len = __builtin_sqrt(((nx * nx + ny * ny) + 1.0) * ((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]));
+	double k = dot / len;
+	k = k > 0.0 ? (k < 1.0 ? k : 1.0) : 0.0;
+	return (uint32_t)(k * 255.0 + 0.5);
+}
+// ... of the hit cell `cell` for the nearest-cell modes: central differences of the threshold table the march reads (F32: its
+// float copy, widened), one-sided on the map's border, 0 along a side of one cell.
+template <bool F32>
+__device__ __forceinline__ uint32_t diffuse_level_nearest(const DevFrame &f, const double *__restrict__ thr, unsigned cell,
+                                                          const double (&s)[3]) {
+	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
+	const int w = f.map_w, h = f.map_h;
+	const int cy = (int)(cell / (unsigned)w), cx = (int)(cell - (unsigned)cy * (unsigned)w);
+	const int xm = max(cx - 1, 0), xp = min(cx + 1, w - 1), ym = max(cy - 1, 0), yp = min(cy + 1, h - 1);
+	const size_t row = (size_t)cy * (size_t)w, ixm = row + (size_t)xm, ixp = row + (size_t)xp;
+	const size_t iym = (size_t)ym * (size_t)w + (size_t)cx, iyp = (size_t)yp * (size_t)w + (size_t)cx;
+	const double txm = F32 ? (double)thr32[ixm] : thr[ixm], txp = F32 ? (double)thr32[ixp] : thr[ixp];
+	const double tym = F32 ? (double)thr32[iym] : thr[iym], typ = F32 ? (double)thr32[iyp] : thr[iyp];
+	const double gx = xp > xm ? (txp - txm) / ((double)(xp - xm) * f.grid_width) : 0.0;
+	const double gy = yp > ym ? (typ - tym) / ((double)(yp - ym) * f.grid_width) : 0.0;
+	return diffuse_level(gx, gy, s);
+}
+// The weight w in 0..255 of a hit pixel that is not shadowed, from its level, and the pixel under a weight:
+// (c * w + 127) / 255 per channel (w = ambient for a shadowed pixel; w = 255 gives c back).
+__device__ __forceinline__ uint32_t shade_weight(uint32_t ambient, uint32_t q) {
+	return ambient + ((255u - ambient) * q + 127u) / 255u;
+}
+__device__ __forceinline__ uint32_t shade_weighted(uint32_t rgba, uint32_t w) { return shade_shadowed(rgba, w); }
+
 // AABB.cpp:49-77, axis order x,y,z, same comparisons (NaN => every test false).
 __device__ __forceinline__ double slab_distance(const DevRay &r, const DevFrame &f) {
 	const double inf = __builtin_huge_val();

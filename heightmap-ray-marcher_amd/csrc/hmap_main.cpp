@@ -10,7 +10,9 @@
 // n x n box-filtered samples per pixel (hmrm_render_aa).  `interior on` renders the single frame under the interior rule
 // (hmrm_render_interior: a camera inside the box sees the terrain); it is ignored, with a warning, together with
 // `antialias` > 1, `devices` > 1 or `record orbit`.  `shadows on` renders the single frame with sun shadows (hmrm_render_lit;
-// under the interior rule too when `interior on`), and is ignored, with a warning, in the same three cases.
+// under the interior rule too when `interior on`), and is ignored, with a warning, in the same three cases.  `shading on`
+// renders it with diffuse sun shading (hmrm_render_shaded with HMRM_SHADE_DIFFUSE, and HMRM_SHADE_NO_SHADOWS unless
+// `shadows on`; the sun is the same), and is ignored, with a warning, in those three cases too.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -66,6 +68,7 @@ int main(int argc, char *argv[]) {
 	const int32_t aa = hmrm_config_antialias(cfg);
 	const bool interior = hmrm_config_interior(cfg) != 0;
 	const bool shadows = hmrm_config_shadows(cfg) != 0;
+	const bool shading = hmrm_config_shading(cfg) != 0;
 	hmrm_scene *scene = NULL;
 	if (hmrm_config_create_scene(cfg, &scene) != HMRM_OK) {
 		std::cerr << hmrm_last_error() << "\n";
@@ -75,6 +78,7 @@ int main(int argc, char *argv[]) {
 	if (hmrm_config_record_mode(cfg) == 1) {
 		if (interior) std::cerr << "WARNING: interior is ignored with record orbit\n";
 		if (shadows) std::cerr << "WARNING: shadows is ignored with record orbit\n";
+		if (shading) std::cerr << "WARNING: shading is ignored with record orbit\n";
 		// `record orbit`: recording_frame_count frames on a circle around the map centre through
 		// the configured camera position, always looking at the centre;
 		// files screenshots/hmap_<epoch>_<n>.png as hmap.cpp:1131-1144.
@@ -125,7 +129,21 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: interior is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
 	if (shadows && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: shadows is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (shadows && want_dev <= 1 && aa == 1) {
+	if (shading && (want_dev > 1 || aa > 1))
+		std::cerr << "WARNING: shading is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
+	if (shading && want_dev <= 1 && aa == 1) {
+		hmrm_sun sun;
+		hmrm_config_get_sun(cfg, &sun);
+		rc = hmrm_render_shaded(scene, &cam, &sun, HMRM_SHADE_DIFFUSE | (shadows ? 0u : HMRM_SHADE_NO_SHADOWS), framebuf.data(),
+		                        (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height << " rays with sun shading" << (shadows ? " and sun shadows" : "")
+		          << (interior ? " under the interior rule" : "") << " in " << hmrm_last_kernel_ms() << " ms (kernel)\n";
+	} else if (shadows && want_dev <= 1 && aa == 1) {
 		hmrm_sun sun;
 		hmrm_config_get_sun(cfg, &sun);
 		rc = hmrm_render_lit(scene, &cam, &sun, framebuf.data(), (size_t)cam.width * 4);

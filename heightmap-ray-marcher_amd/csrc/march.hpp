@@ -132,6 +132,17 @@ __device__ __forceinline__ double bil_mix(const Bil &b, double f00, double f10, 
 	const double c = f01 + b.tx * (f11 - f01);
 	return a + b.ty * (c - a);
 }
+// Diffuse level (device_common.hpp diffuse_level) of the interpolated surface at a hit point whose neighbours and weights are
+// `b`: the gradient of bil_mix's surface there, a = f10 - f00, b = f11 - f01 mixed along y, c = f01 - f00, d = f11 - f10 along x.
+__device__ __forceinline__ uint32_t diffuse_level_bilinear(const DevFrame &f, const double *__restrict__ thr, const Bil &b,
+                                                           const double (&s)[3]) {
+	const double t00 = thr[b.c00], t10 = thr[b.c10], t01 = thr[b.c01], t11 = thr[b.c11];
+	const double ax = t10 - t00, bx = t11 - t01;
+	const double gx = (ax + b.ty * (bx - ax)) / f.grid_width;
+	const double cy = t01 - t00, dy = t11 - t10;
+	const double gy = (cy + b.tx * (dy - cy)) / f.grid_width;
+	return diffuse_level(gx, gy, s);
+}
 // Colour at a hit: R,G,B interpolated and rounded with floor(f + 0.5); the alpha-0 rule
 // (hmap.cpp:1020) keeps looking at the nearest cell.
 __device__ __forceinline__ uint32_t shade_hit_bilinear(const DevFrame &f, const uint32_t *__restrict__ cmap,
@@ -182,14 +193,27 @@ __device__ __forceinline__ uint32_t shade_hit_bilinear(const DevFrame &f, const 
 // segment ray under the interior rule from (P.x, P.y, t) towards the sun -- through the SAME loop; the other lanes sit the
 // second pass out.  Nothing per pixel goes through memory between the two.  Again `if constexpr` statements beside the
 // others' own and a per-lane struct that is empty unless LIT (device_common.hpp LitState).
-template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false>
+// SHADE (instantiated in render_shaded.hip and render_lit_shaded.hip only; hmrm_render_shaded; implies SEG): diffuse sun
+// shading.  An epilogue: a lane whose primary ray hit -- and, LIT, whose shadow ray did not -- computes its diffuse level from
+// the threshold table (device_common.hpp diffuse_level) and keeps a weighted pixel; `sun` brings the direction and the
+// ambient level.  Across the loop it keeps the hit's cell index (nearest-cell modes) or the hit point (bilinear: LitState's,
+// or its cell coordinates): device_common.hpp ShadeState, empty unless SHADE.  (LIT: computing the level at the phase
+// switch instead and carrying it through the shadow march in the saved pixel's alpha byte holds no cell index, but the
+// compiler then keeps more across the march, not less: DESIGN.md 5.12.)
+template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false, bool SHADE = false>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
                                                 int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{},
                                                 const SunRules &sun = SunRules{}) {
 	static_assert(!LIT || (SEG && PROJ != 4), "sun shadows: frames, under the segment rules");
+	static_assert(!SHADE || (SEG && PROJ != 4), "sun shading: frames, under the segment rules");
 	constexpr bool BILINEAR = SAMP == 1, F32 = SAMP == 2;
+	// KEEP_P: a lane that hit leaves the loop with its hit point in x, y (LIT: and t in z).  SHADE with bilinear sampling wants
+	// the point too; without LIT the plain groups take it that way, the leap kernels keep the hit's exact cell coordinates
+	// instead (KEEP_Q) -- each the cheaper of the two in registers for its family, DESIGN.md 5.12.
+	constexpr bool KEEP_Q = SHADE && BILINEAR && !LIT && LEAP != 0;
+	constexpr bool KEEP_P = LIT || (SHADE && BILINEAR && !KEEP_Q);
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || (!AA && !STATS), "segment rules: production kernels only");
@@ -237,6 +261,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired, and in which cell)
 		unsigned hcell = 0u;
 		LitState<LIT> lt; // (empty unless LIT: device_common.hpp)
+		ShadeState<SHADE, SAMP == 1, LIT> sh; // (empty unless SHADE)
 		bool again = false; // (LIT: the wave has shadow rays to march)
 
 		do { // (once; LIT: once more with the shadow rays)
@@ -641,8 +666,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 									qyh = hit_j == j ? QY[j] : qyh;
 								}
 								rgba = shade_hit_bilinear(f, cmap, (int)hit_cell, bil_setup(qxh, qyh, f.map_w, f.map_h));
+								if constexpr (KEEP_Q) { sh.px = qxh; sh.py = qyh; }
 							} else {
 								rgba = shade_hit(f, cmap[hit_cell]);
+								if constexpr (SHADE && LIT) sh.cell = lt.phase ? sh.cell : hit_cell; // (the primary ray's)
+								else if constexpr (SHADE) sh.cell = hit_cell;
 							}
 							real_hit = true;
 							if constexpr (RAYS) {
@@ -655,7 +683,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								}
 								hcell = hit_cell;
 							}
-							if constexpr (LIT) {
+							if constexpr (KEEP_P) {
 								// The shadow ray's origin (P.x, P.y, t): int_point's x and y where :1016 fired and the threshold z was
 								// below.  The lane leaves the loop with it in x, y, z, which nothing else reads after a hit, so no
 								// register is held across the loop for it; and X[hit_j] is made again from the group's start with
@@ -694,8 +722,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							if (zs < t) { // hmap.cpp:1016
 								rgba = BILINEAR ? shade_hit_bilinear(f, cmap, c, b) : shade_hit(f, cmap[c]);
 								real_hit = true;
+								if constexpr (KEEP_Q) { sh.px = qx; sh.py = qy; }
+								if constexpr (SHADE && !BILINEAR && LIT) sh.cell = lt.phase ? sh.cell : (unsigned)c;
+								else if constexpr (SHADE && !BILINEAR) sh.cell = (unsigned)c;
 								if constexpr (RAYS) { hx = xs; hy = ys; hz = zs; hcell = (unsigned)c; }
-								if constexpr (LIT) { x = xs; y = ys; z = t; } // (as above)
+								if constexpr (KEEP_P) { x = xs; y = ys; z = t; } // (as above)
 								done = true;
 								break;
 							}
@@ -704,7 +735,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							zs += sz;
 						}
 					}
-					if constexpr (LIT) { // (a lane that hit keeps what the hit left in x, y, z)
+					if constexpr (KEEP_P) { // (a lane that hit keeps what the hit left in x, y, z)
 						x = real_hit ? x : X[U - 1] + sx;
 						y = real_hit ? y : Y[U - 1] + sy;
 						z = real_hit ? z : Z[U - 1] + sz;
@@ -721,7 +752,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				}
 				if (COUNT) my_steps = (unsigned long long)(unsigned)(budget0 - budget);
 				if constexpr (SEG && COUNT) my_steps = (unsigned long long)(unsigned)(sg.budget - budget);
+				if constexpr (LIT && SHADE && BILINEAR) { // (the primary hit's point outlives the shadow march: the gradient is taken there)
+					if (lt.phase == 0) { lt.hx = x; lt.hy = y; lt.t = z; }
+				} else
 				if constexpr (LIT) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
+				else if constexpr (KEEP_P) { sh.px = x; sh.py = y; } // (SHADE, bilinear: the same two, for the gradient at P)
 			}
 			if constexpr (LIT) {
 				// After the primary rays: the lanes that hit keep their pixel and become their shadow rays -- the ray, its d, its step
@@ -751,10 +786,36 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		} while (LIT && again);
 		if constexpr (LIT) {
 			if (lt.primary_hit) { // MISS, END and CAPPED shadow rays leave the pixel lit
+				if constexpr (SHADE) { // ... at the weight of its diffuse level; a shadowed pixel keeps the ambient weight
+					uint32_t w = sun.ambient;
+					if (!real_hit) {
+						if constexpr (BILINEAR) {
+							const double qxh = GWM == 0 ? lt.hx : (GWM == 2 ? lt.hx / f.grid_width : lt.hx * f.inv_grid_width);
+							const double qyh = GWM == 0 ? -lt.hy : (GWM == 2 ? -lt.hy / f.grid_width : -lt.hy * f.inv_grid_width);
+							w = shade_weight(sun.ambient, diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), sun.dir));
+						} else {
+							w = shade_weight(sun.ambient, diffuse_level_nearest<F32>(f, thr, sh.cell, sun.dir));
+						}
+					}
+					// (nearest-cell modes: the pixel is made again from the cell index, which is kept anyway, instead of being held
+					// across the shadow march beside it -- one load per hit pixel for one register)
+					if constexpr (BILINEAR) rgba = shade_weighted(lt.rgba, w);
+					else rgba = shade_weighted(shade_hit(f, cmap[sh.cell]), w);
+				} else
 				rgba = real_hit ? shade_shadowed(lt.rgba, sun.ambient) : lt.rgba;
 				real_hit = true;
 			}
 			ray.dz = lt.phase ? lt.dz : ray.dz; // (the primary ray's, for the miss shade)
+		} else if constexpr (SHADE) { // (no shadow rays: every hit pixel at the weight of its level)
+			if (real_hit) {
+				uint32_t q;
+				if constexpr (BILINEAR) {
+					const double qxh = (KEEP_Q || GWM == 0) ? sh.px : (GWM == 2 ? sh.px / f.grid_width : sh.px * f.inv_grid_width);
+					const double qyh = KEEP_Q ? sh.py : (GWM == 0 ? -sh.py : (GWM == 2 ? -sh.py / f.grid_width : -sh.py * f.inv_grid_width));
+					q = diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), sun.dir);
+				} else q = diffuse_level_nearest<F32>(f, thr, sh.cell, sun.dir);
+				rgba = shade_weighted(rgba, shade_weight(sun.ambient, q));
+			}
 		}
 
 		if (real_hit) my_hit = 1;

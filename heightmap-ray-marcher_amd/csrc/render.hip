@@ -84,12 +84,14 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 // registers and write no pixel themselves.  1: the primary ray -- its pixel, whether it hit, and where and under which
 // threshold, go to *lit.  2: the shadow ray of a lane whose primary ray hit, made from *lit and `sun` with the sun's step
 // (`seg` holds the sun's limit and the interior rule); a hit darkens lit->rgba.  The other lanes sit that pass out.
+// 3 (hmrm_render_shaded): pass 2, but a hit leaves lit->rgba alone and says SHADOWED in lit->phase -- the caller weights the pixel;
+// `hit_cell` (pass 1, may be null): where the primary hit's cell index gridx + gridy * W goes, for that caller.
 template <int PROJ, bool STATS, bool AA, bool SEG = false, int LIT = 0>
 __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId pid, const double *__restrict__ thr,
                                                     const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                     int64_t out_stride_px, const StatsOut &st, const RayBatch &batch,
                                                     const SegRules &seg = SegRules{}, const SunRules &sun = SunRules{},
-                                                    LitState<true> *lit = nullptr) {
+                                                    LitState<true> *lit = nullptr, unsigned *hit_cell = nullptr) {
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	static_assert(LIT == 0 || (SEG && !RAYS), "sun shadows: frames, under the segment rules");
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
@@ -101,7 +103,7 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 		ray_index = (int64_t)pid.py * kBatchW + pid.px;
 		pid.live = pid.live && ray_index < batch.n;
 	}
-	if constexpr (LIT == 2) pid.live = pid.live && lit->primary_hit;
+	if constexpr (LIT >= 2) pid.live = pid.live && lit->primary_hit;
 	const int px = pid.px, py = pid.py, lrow = pid.lrow;
 	const bool live = pid.live;
 
@@ -112,7 +114,7 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 	if (live) {
 		DevRay ray = make_ray<PROJ>(f, px, py);
 		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
-		if constexpr (LIT == 2) { // (the camera's ray is dead too: from the surface above the hit point towards the sun)
+		if constexpr (LIT >= 2) { // (the camera's ray is dead too: from the surface above the hit point towards the sun)
 			ray.px = lit->hx; ray.py = lit->hy; ray.pz = lit->t;
 			ray.dx = sun.dir[0]; ray.dy = sun.dir[1]; ray.dz = sun.dir[2];
 		}
@@ -141,7 +143,7 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 			y = y + f.nudge * ray.dy;
 			z = z + f.nudge * ray.dz;
 			// hmap.cpp:1037  step_dist * dir is the same three products every iteration
-			const double step_dist = LIT == 2 ? sun.step_dist : f.step_dist;
+			const double step_dist = LIT >= 2 ? sun.step_dist : f.step_dist;
 			const double sx = step_dist * ray.dx;
 			const double sy = step_dist * ray.dy;
 			const double sz = step_dist * ray.dz;
@@ -173,7 +175,10 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 					rgba = ((c >> 24) == 0) ? pack_rgba(f.bg[0], f.bg[1], f.bg[2]) : (c | 0xff000000u);
 					real_hit = true;
 					if constexpr (RAYS) { hx = x; hy = y; hz = z; hgx = gridx; hgy = gridy; }
-					if constexpr (LIT == 1) { lit->hx = x; lit->hy = y; lit->t = t; }
+					if constexpr (LIT == 1) {
+						lit->hx = x; lit->hy = y; lit->t = t;
+						if (hit_cell) *hit_cell = (unsigned)cell; // (maps hold at most 2^29 cells)
+					}
 					break;
 				}
 				x = x + sx;
@@ -205,6 +210,8 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 			lit->rgba = rgba;
 		} else if constexpr (LIT == 2) {
 			if (real_hit) lit->rgba = shade_shadowed(lit->rgba, sun.ambient); // (MISS, END and CAPPED leave the pixel lit)
+		} else if constexpr (LIT == 3) {
+			if (real_hit) lit->phase = 1;
 		} else
 		if constexpr (RAYS && SEG) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
 		else if constexpr (RAYS) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, d_box, (uint32_t)my_steps, rgba);
@@ -264,6 +271,30 @@ __global__ __launch_bounds__(kBlockThreads) void k_render_lit_literal(const DevF
 	render_lane_literal<PROJ, false, false, true, 2>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
 	                                                 SegRules{nullptr, sun.max_steps, 1u}, sun, &lt);
 	if (pid.live) out[(int64_t)pid.lrow * out_stride_px + pid.px] = lt.rgba;
+}
+// A hill-shaded pixel (hmrm_render_shaded with HMRM_KERNEL=simple): the primary ray, SHADOWS: its shadow ray, then the weight --
+// the ambient level for a shadowed pixel, else that of the diffuse level of the hit cell, which pass 1 hands over.
+template <int PROJ, bool SHADOWS>
+__global__ __launch_bounds__(kBlockThreads) void k_render_shaded_literal(const DevFrame f, const RowMap rows,
+                                                                         const double *__restrict__ thr,
+                                                                         const uint32_t *__restrict__ cmap,
+                                                                         uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                         int tiles_y, StatsOut st, const SegRules seg, const SunRules sun) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	unsigned cell = 0u;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, sun, &lt, &cell);
+	if constexpr (SHADOWS)
+		render_lane_literal<PROJ, false, false, true, 3>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
+		                                                 SegRules{nullptr, sun.max_steps, 1u}, sun, &lt);
+	if (!pid.live) return;
+	uint32_t rgba = lt.rgba;
+	if (lt.primary_hit) {
+		uint32_t w = sun.ambient;
+		if (lt.phase == 0) w = shade_weight(sun.ambient, diffuse_level_nearest<false>(f, thr, cell, sun.dir));
+		rgba = shade_weighted(rgba, w);
+	}
+	out[(int64_t)pid.lrow * out_stride_px + pid.px] = rgba;
 }
 __global__ __launch_bounds__(kBlockThreads) void k_trace_segments_literal(const DevFrame f, const double *__restrict__ thr,
                                                                           const uint32_t *__restrict__ cmap, const RayBatch batch,
@@ -467,6 +498,29 @@ hipError_t launch_render_lit_literal(const DevFrame &f, const RowMap &rows, cons
 	default: hipLaunchKernelGGL(k_render_lit_literal<3>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
 	}
 	return hipGetLastError();
+}
+
+template <bool SHADOWS>
+static hipError_t launch_render_shaded_literal_t(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                                 uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                                 const SunRules &sun, bool primary_interior, hipStream_t stream) {
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	const dim3 block(kBlockThreads);
+	const StatsOut st{d_counters, nullptr, nullptr};
+	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
+	switch (f.projection) {
+	case 1: hipLaunchKernelGGL((k_render_shaded_literal<1, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	case 2: hipLaunchKernelGGL((k_render_shaded_literal<2, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	default: hipLaunchKernelGGL((k_render_shaded_literal<3, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	}
+	return hipGetLastError();
+}
+hipError_t launch_render_shaded_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                        uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
+                                        bool primary_interior, bool shadows, hipStream_t stream) {
+	return shadows ? launch_render_shaded_literal_t<true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream)
+	               : launch_render_shaded_literal_t<false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream);
 }
 
 hipError_t launch_render(const DevFrame &f, const RowMap &rows, const double *d_thr,

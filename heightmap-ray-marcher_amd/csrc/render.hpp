@@ -73,6 +73,21 @@ hipError_t launch_render_lit(const DevFrame &f, const RowMap &rows, const double
 hipError_t launch_render_lit_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
                                      uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
                                      bool primary_interior, hipStream_t stream);
+// Hill-shaded frames (hmrm_render_shaded; `sun` brings the direction and the ambient level): launch_render_shaded
+// (render_shaded.hip) marches no shadow rays and looks at neither sun.step_dist nor sun.max_steps -- every hit pixel at the
+// weight of its diffuse level; launch_render_lit_shaded (render_lit_shaded.hip) is launch_render_lit whose lit pixels get that
+// weight; the literal loop (render.hip) does either.  Counters and launches as launch_render_lit.
+hipError_t launch_render_shaded(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
+                                const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
+                                hipStream_t stream);
+hipError_t launch_render_lit_shaded(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
+                                    const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                    FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
+                                    hipStream_t stream);
+hipError_t launch_render_shaded_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                        uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
+                                        bool primary_interior, bool shadows, hipStream_t stream);
 // The record table of the thr table: rec_row(map_w) x ceil(map_h / 4) WindowRecords.
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream);
 // thr32[i] = (float)thr[i], round to nearest (the "float heights" mode).

@@ -1,0 +1,44 @@
+// render_lit_shaded.hip -- hill-shaded frames with sun shadows (hmrm_render_shaded with HMRM_SHADE_DIFFUSE, hmrm.h): the lit
+// kernels of render_lit.hip instantiated once more with SHADE (march.hpp render_wave_tile): after the shadow march a pixel
+// that hit and is not shadowed takes its diffuse level from the neighbours of its primary hit in the threshold table and
+// keeps a weighted pixel; a shadowed one keeps the ambient weight as before.  The hit's cell index (the hit point for
+// bilinear sampling) is what survives the second pass for it.  A translation unit of its own: the existing kernels keep
+// their argument lists and their instructions.
+#include "march.hpp"
+
+namespace hmrm {
+
+// k_render_lit's launch shape and arguments; never a calibration launch.
+template <int PROJ, int GWM, int LEAP, int SAMP>
+__global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR void k_render_lit_shaded(const DevFrame f, const RowMap rows,
+                                                                                                          const double *__restrict__ thr,
+                                                                                                          const uint32_t *__restrict__ cmap,
+                                                                                                          uint32_t *__restrict__ out,
+                                                                                                          int64_t out_stride_px, int tiles_y,
+                                                                                                          StatsOut st, const SegRules seg, const SunRules sun) {
+	(void)render_wave_tile<PROJ, false, GWM, LEAP, SAMP, false, true, true, true>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
+	                                                                         blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
+	                                                                         (int)(threadIdx.x & 63), RayBatch{}, seg, sun);
+}
+
+// `primary_interior`: the primary rays are under the interior rule too (HMRM_TRACE_INTERIOR; the kernel tests each origin).
+hipError_t launch_render_lit_shaded(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
+                                    const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                    FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
+                                    hipStream_t stream) {
+	if (f.aa_shift != 0 || rows.measure != nullptr) return hipErrorInvalidValue;
+	DevFrame fr = f;
+	const double *d_thr = nullptr;
+	if (const hipError_t e = select_tables(&fr, kernel, d_thr_f64, d_thr32, d_records, &d_thr); e != hipSuccess) return e;
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	const StatsOut st{d_counters, nullptr, nullptr};
+	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
+	dispatch_march(f.projection, f.grid_mode, kernel, f.sampling, [&](auto proj, auto gwm, auto leap, auto samp) {
+		hipLaunchKernelGGL((k_render_lit_shaded<proj(), gwm(), leap(), samp()>), g.grid, dim3(kBlockThreads), 0, stream, fr, rows, d_thr, d_cmap,
+		                   d_out, out_stride_px, g.tiles_y, st, seg, sun);
+	});
+	return hipGetLastError();
+}
+
+} // namespace hmrm

@@ -80,6 +80,7 @@ class Stats(C.Structure):
 RAY_MISS, RAY_HIT, RAY_CAPPED = 0, 1, 2  # hmrm_ray_hit.status (HMRM_RAY_*)
 RAY_END = 3  # ... of hmrm_trace_segments: ended by the ray's own step limit, inside the grid
 TRACE_INTERIOR = 1  # hmrm_segment_params.flags (HMRM_TRACE_INTERIOR)
+SHADE_DIFFUSE, SHADE_NO_SHADOWS = 1, 2  # hmrm_render_shaded's shade_flags (HMRM_SHADE_*)
 MAX_RAYS = 1 << 29  # rays per batch
 
 
@@ -203,6 +204,7 @@ def _load():
         "hmrm_trace_segments_device": (C.c_int, [vp, C.POINTER(SegmentParams), vp, vp, C.c_int64, vp, vp]),
         "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
+        "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
         "hmrm_pick": (C.c_int, [vp, C.POINTER(Camera), i32, i32, C.POINTER(RayHit)]),
         "hmrm_debug_ray": (C.c_int, [vp, C.POINTER(Camera), i32, i32, dp, dp, dp]),
         "hmrm_debug_frame": (C.c_int, [C.POINTER(Camera), C.POINTER(SceneParams), i32, i32, vp, vp]),
@@ -219,6 +221,7 @@ def _load():
         "hmrm_config_antialias": (i32, [vp]),
         "hmrm_config_interior": (i32, [vp]),
         "hmrm_config_shadows": (i32, [vp]),
+        "hmrm_config_shading": (i32, [vp]),
         "hmrm_config_get_sun": (None, [vp, C.POINTER(Sun)]),
         "hmrm_record_orbit_multi": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32]),
@@ -388,6 +391,17 @@ class Scene:
         self._sync_env()
         fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
         _check(lib.hmrm_render_lit(self._h, C.byref(cam), C.byref(sun), _ptr(fb), cam.width * 4),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
+    def render_shaded(self, cam: Camera, sun: Sun, diffuse=True, shadows=True, allow_capped=False) -> np.ndarray:
+        """One full frame with diffuse sun shading (hmrm_render_shaded): render_lit()'s frame in which every hit pixel that is
+        not shadowed is weighted by the diffuse level of its hit (`diffuse`; include/hmrm.h has the arithmetic); shadows=False
+        marches no shadow rays (HMRM_SHADE_NO_SHADOWS) -> HxWx4 uint8.  Capped rays: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
+        flags = (SHADE_DIFFUSE if diffuse else 0) | (0 if shadows else SHADE_NO_SHADOWS)
+        _check(lib.hmrm_render_shaded(self._h, C.byref(cam), C.byref(sun), flags, _ptr(fb), cam.width * 4),
                allow=(HMRM_E_NOTERM,) if allow_capped else ())
         return fb
 
@@ -751,6 +765,10 @@ class Config:
     def shadows(self) -> bool:
         """Additive `shadows on|off`: the CLI renders its single frame with hmrm_render_lit."""
         return bool(lib.hmrm_config_shadows(self._h))
+
+    def shading(self) -> bool:
+        """Additive `shading on|off`: the CLI renders its single frame with hmrm_render_shaded."""
+        return bool(lib.hmrm_config_shading(self._h))
 
     def sun(self) -> Sun:
         """The sun of the additive keys sun_dir, shadow_step_dist (absent: step_dist), shadow_max_steps, shadow_ambient, interior."""

@@ -381,6 +381,50 @@ typedef struct hmrm_sun {        /* 48 bytes */
 } hmrm_sun;
 int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint8_t *rgba, size_t stride_bytes);
 
+/* ------------------------------------------------------- diffuse sun shading */
+/* hmrm_render_lit with diffuse (hill) shading, with or without the shadow rays (build-side addition), exact.
+ * Every pixel first gets hmrm_render's value (hmrm_render_interior's with HMRM_TRACE_INTERIOR in sun->flags; the primary
+ * march is unchanged).  Every pixel whose primary ray HIT (alpha-0 cells count, as in hmrm_render_lit) gets a weight w in
+ * 0..255, and its R, G and B become (c * w + 127) / 255 in integers; A stays 255.  Misses, sky and capped primary rays are
+ * untouched.
+ * Without HMRM_SHADE_NO_SHADOWS every hit pixel casts exactly hmrm_render_lit's shadow ray -- origin (P.x, P.y, t), dir =
+ * sun->dir, sun->step_dist, sun->max_steps, the interior rule always on -- and a pixel whose shadow ray's status is
+ * HMRM_RAY_HIT is SHADOWED: w = ambient.  With it no shadow ray is marched, no pixel is shadowed, and step_dist and
+ * max_steps are not looked at.
+ * A pixel that is not shadowed has w = 255 without HMRM_SHADE_DIFFUSE, and with it
+ *   w = ambient + ((255 - ambient) * q + 127) / 255   in integers,
+ * q in 0..255 the diffuse level of the hit: q = 255 gives the texel back, q = 0 what a shadowed pixel gets.
+ * THE LEVEL q.  Plain IEEE double operations in this order, no contraction.  T is the threshold table of the camera's
+ * sampling mode (heightmap_buf[i] + min_height for HMRM_NEAREST, its float entry widened to double for HMRM_NEAREST_F32),
+ * gw = grid_width, s = sun->dir as given, W x H the map.
+ *   HMRM_NEAREST, HMRM_NEAREST_F32: (cx, cy) = the hit's cell_x, cell_y (hmrm_ray_hit);
+ *     xm = max(cx - 1, 0), xp = min(cx + 1, W - 1), ym = max(cy - 1, 0), yp = min(cy + 1, H - 1);
+ *     gx = xp > xm ? (T[xp, cy] - T[xm, cy]) / ((double)(xp - xm) * gw) : 0.0;
+ *     gy = yp > ym ? (T[cx, yp] - T[cx, ym]) / ((double)(yp - ym) * gw) : 0.0.
+ *   HMRM_BILINEAR: the gradient of the interpolated surface at P: the four cells c00, c10, c01, c11 and the weights tx, ty of
+ *     the bilinear mode at ((P.x - c0.x) / gw, -(P.y - c0.y) / gw);
+ *     a = T[c10] - T[c00], b = T[c11] - T[c01], gx = (a + ty * (b - a)) / gw;
+ *     c = T[c01] - T[c00], d = T[c11] - T[c10], gy = (c + tx * (d - c)) / gw.
+ *   n = (-gx, gy, 1)  (rows grow towards decreasing world y: gy is minus the y slope);
+ *   dot = (n.x * s.x + n.y * s.y) + s.z;
+ *   len = sqrt(((n.x * n.x + n.y * n.y) + 1.0) * ((s.x * s.x + s.y * s.y) + s.z * s.z)), correctly rounded;
+ *   k = dot / len;  k = k > 0 ? (k < 1 ? k : 1) : 0  (NaN gives 0);  q = (uint32_t)(k * 255.0 + 0.5).
+ * Nothing is special-cased: a zero, infinite or NaN sun gives q = 0 through this arithmetic; a sun below the horizon lights
+ * the slopes that face it.
+ * Consequences: shade_flags = 0 is hmrm_render_lit byte for byte (its kernels run); HMRM_SHADE_NO_SHADOWS alone is
+ * hmrm_render / hmrm_render_interior byte for byte; ambient = 255 is the frame without shading under any flags.
+ * Refusals (HMRM_E_ARG) come before the scene is looked at: hmrm_render_lit's three (NULL sun, an undefined bit in
+ * sun->flags, reserved != 0) and an undefined bit in shade_flags.  Capped rays are counted and reported as in
+ * hmrm_render_lit; with HMRM_SHADE_NO_SHADOWS only primary rays can be capped.  Synchronous, on the scene's stream, launched
+ * the way a lit frame is: one launch, never measured, never the scene's probe and not counted towards it, with the scene's
+ * current kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST).  All three projections and
+ * sampling modes.  Not antialiased, no tickets, strips or recording.  The shading arithmetic is tested at unit world scale
+ * only: world scales far beyond a unit-scale scene (the 2^-900 .. 2^900 of the parity tests) are not tested for it. */
+#define HMRM_SHADE_DIFFUSE    1u
+#define HMRM_SHADE_NO_SHADOWS 2u
+int hmrm_render_shaded(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun,
+                       uint32_t shade_flags, uint8_t *rgba, size_t stride_bytes);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -526,7 +570,9 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * Unknown shadows: v" and keeps the old one), `sun_dir x y z` (default 0.5 0.5 0.7071..., used as given), `shadow_ambient n`
  * (0..255, default 128; another value warns "WARNING: shadow_ambient must be 0..255" and keeps the old one),
  * `shadow_step_dist v` (absent: the camera's step_dist), `shadow_max_steps n` (default 0 = none; a value outside
- * 0..4294967295 warns and keeps the old one).  Unknown key -> "WARNING: Unknown identifier: k". */
+ * 0..4294967295 warns and keeps the old one), `shading on|off|1|0` (default off; the CLI renders its single frame with
+ * hmrm_render_shaded, HMRM_SHADE_DIFFUSE, plus HMRM_SHADE_NO_SHADOWS unless `shadows on`; another value warns "WARNING:
+ * Unknown shading: v" and keeps the old one).  Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
 /* Consume a whole stream; loads heightmap/colormap images when those keys
@@ -547,6 +593,7 @@ int32_t      hmrm_config_devices(const hmrm_config *cfg);       /* additive `dev
 int32_t      hmrm_config_antialias(const hmrm_config *cfg);     /* additive `antialias n`: 1 (default, off), 2, 4 or 8 */
 int32_t      hmrm_config_interior(const hmrm_config *cfg);      /* additive `interior on|off`: 1|0 */
 int32_t      hmrm_config_shadows(const hmrm_config *cfg);       /* additive `shadows on|off`: 1|0 */
+int32_t      hmrm_config_shading(const hmrm_config *cfg);       /* additive `shading on|off`: 1|0 */
 /* The sun of the additive keys: sun_dir, shadow_step_dist (the config's step_dist when the key was absent),
  * shadow_max_steps, shadow_ambient; flags = HMRM_TRACE_INTERIOR when `interior on`. */
 void         hmrm_config_get_sun(const hmrm_config *cfg, hmrm_sun *out);
