@@ -640,7 +640,8 @@ int launch_shadow_probe(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, co
 // kernel indexes cells and windows with 24-bit multiplies, leap_common.hpp index_2d), else the production kernel or the other one (the plain groups,
 // with leaps over window records where the frame's sampling allows them).
 // `interior` (hmrm_render_interior): the same choice among the kernels built with the interior rule (render_interior.hip).
-// `lit` (hmrm_render_lit): ... among the kernels that march the shadow rays too (render_lit.hip).
+// `lit` (hmrm_render_lit): ... among the kernels that march the shadow rays too (render_lit.hip); with f.aa_shift != 0
+// (hmrm_render_shaded_aa and the lit tickets) among their antialiased counterparts.
 struct LitFrame {
 	hmrm::SunRules sun;
 	bool primary_interior; // HMRM_TRACE_INTERIOR: the primary rays under the interior rule too
@@ -662,8 +663,18 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 	if ((s->knobs.kernel == 2 || huge_side) && f.sampling == 0) { // (the literal loop only knows the reference's sampling)
 		if (lit && lit->shade_flags) {
 			const bool shadows = !(lit->shade_flags & HMRM_SHADE_NO_SHADOWS);
+			if (f.aa_shift) {
+				HIP_TRY(hmrm::launch_render_shaded_literal_aa(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters,
+				                                              shadows ? lit->sun : shade_sun(*lit), lit->primary_interior, shadows, c->stream));
+				return HMRM_OK;
+			}
 			HIP_TRY(hmrm::launch_render_shaded_literal(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters,
 			                                           shadows ? lit->sun : shade_sun(*lit), lit->primary_interior, shadows, c->stream));
+			return HMRM_OK;
+		}
+		if (lit && f.aa_shift) {
+			HIP_TRY(hmrm::launch_render_lit_literal_aa(f, rows_in_order, s->d_thr, s->d_cmap, d_out, out_stride_px, c->d_counters, lit->sun,
+			                                           lit->primary_interior, c->stream));
 			return HMRM_OK;
 		}
 		if (lit) {
@@ -689,6 +700,15 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		// sets the interior rule, which this frame has only with HMRM_TRACE_INTERIOR, and the plain one belongs to frames that may
 		// be measured or be the probe, which no frame of this entry point is.  The levels it computes for nothing are the price
 		// of one route; the combination is an identity for tests, not something to render with.)
+		// (an antialiased lit frame, hmrm_render_shaded_aa: the same three choices among the kernels with the AA epilogue)
+		if (lit && f.aa_shift) {
+			const auto launch = (lit->shade_flags & HMRM_SHADE_NO_SHADOWS) ? hmrm::launch_render_shaded_aa
+			                    : lit->shade_flags                         ? hmrm::launch_render_lit_shaded_aa
+			                                                               : hmrm::launch_render_lit_aa;
+			HIP_TRY(launch(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px, c->d_counters, k, s->d_records,
+			               (lit->shade_flags & HMRM_SHADE_NO_SHADOWS) ? shade_sun(*lit) : lit->sun, lit->primary_interior, c->stream));
+			return HMRM_OK;
+		}
 		if (lit && (lit->shade_flags & HMRM_SHADE_NO_SHADOWS)) {
 			HIP_TRY(hmrm::launch_render_shaded(f, rows_in_order, s->d_thr, s->d_thr32, s->d_cmap, d_out, out_stride_px, c->d_counters, k,
 			                                   s->d_records, shade_sun(*lit), lit->primary_interior, c->stream));
@@ -1383,14 +1403,29 @@ int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, nullptr, nullptr, nullptr, false, 1, false, &lit);
 }
 
+// hmrm_render_lit's three refusals and hmrm_render_shaded's own, in the header's order.
+static int check_shaded(const hmrm_sun *sun, uint32_t shade_flags) {
+	if (const int rc = check_sun(sun)) return rc;
+	if (shade_flags & ~(HMRM_SHADE_DIFFUSE | HMRM_SHADE_NO_SHADOWS)) return fail(HMRM_E_ARG, "shade_flags: undefined bit");
+	return HMRM_OK;
+}
+
 // Diffuse sun shading: the lit frame whose hit pixels are weighted by their diffuse level, with or without the shadow rays.
 // shade_flags = 0 is hmrm_render_lit itself, launch for launch.
 int hmrm_render_shaded(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags, uint8_t *rgba,
                        size_t stride_bytes) {
-	if (const int rc = check_sun(sun)) return rc;
-	if (shade_flags & ~(HMRM_SHADE_DIFFUSE | HMRM_SHADE_NO_SHADOWS)) return fail(HMRM_E_ARG, "shade_flags: undefined bit");
+	if (const int rc = check_shaded(sun, shade_flags)) return rc;
 	const LitFrame lit = make_lit_frame(sun, shade_flags);
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, nullptr, nullptr, nullptr, false, 1, false, &lit);
+}
+
+// The antialiased lit frame: hmrm_render_shaded's of the super camera, box-filtered in the launch.  Factor 1 is
+// hmrm_render_shaded, launch for launch.
+int hmrm_render_shaded_aa(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags, int32_t factor,
+                          uint8_t *rgba, size_t stride_bytes) {
+	if (const int rc = check_shaded(sun, shade_flags)) return rc;
+	const LitFrame lit = make_lit_frame(sun, shade_flags);
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, nullptr, nullptr, nullptr, false, factor, false, &lit);
 }
 
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
@@ -1580,7 +1615,8 @@ int hmrm_render_begin(const hmrm_scene *scene, const hmrm_camera *cam, int32_t *
 	return hmrm_render_begin_flags(scene, cam, 0u, ticket);
 }
 
-int hmrm_render_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket) {
+// `lit` (hmrm_render_shaded_begin): the ticket's frame is a lit one -- launched the way a lit frame is (launch_frame), on the lane.
+static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket, const LitFrame *lit) {
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	int rc = check_camera(cam);
 	if (rc) return rc;
@@ -1636,7 +1672,7 @@ int hmrm_render_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, uin
 	if ((rc = prepare_frame(s, c, &super, &f, &slot))) return rc;
 	f.aa_shift = aa_shift;
 	hmrm::RowMap rows{0, super.height, 0, 0, 1, {}, {}, nullptr};
-	if ((rc = launch_frame(s, c, f, slot, rows, r->d_frame, (int64_t)W, nullptr, nullptr, false, (flags & HMRM_NO_PROBE) != 0))) return rc;
+	if ((rc = launch_frame(s, c, f, slot, rows, r->d_frame, (int64_t)W, nullptr, nullptr, false, (flags & HMRM_NO_PROBE) != 0, 0, lit))) return rc;
 	r->ctx = c;
 	HIP_TRY(hipEventRecord(r->kernel_done, c->stream));
 	HIP_TRY(hipStreamWaitEvent(s->copy_stream, r->kernel_done, 0));
@@ -1649,6 +1685,18 @@ int hmrm_render_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, uin
 	r->busy = true;
 	*ticket = idx;
 	return HMRM_OK;
+}
+
+int hmrm_render_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket) {
+	return begin_common(scene, cam, flags, ticket, nullptr);
+}
+
+// (the sun goes into the launch by value -- SunRules is a kernel argument -- so the caller's hmrm_sun need not outlive the call)
+int hmrm_render_shaded_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags, uint32_t flags,
+                             int32_t *ticket) {
+	if (const int rc = check_shaded(sun, shade_flags)) return rc;
+	const LitFrame lit = make_lit_frame(sun, shade_flags);
+	return begin_common(scene, cam, flags, ticket, &lit);
 }
 
 int hmrm_render_wait(const hmrm_scene *scene, int32_t ticket, const uint8_t **rgba, size_t *stride_bytes) {
@@ -1694,8 +1742,8 @@ int hmrm_render_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, vo
 	return hmrm_render_device_begin_flags(scene, cam, d_rgba, stride_bytes, 0u, ticket);
 }
 
-int hmrm_render_device_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba, size_t stride_bytes, uint32_t flags,
-                                   int32_t *ticket) {
+static int device_begin_common(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba, size_t stride_bytes, uint32_t flags,
+                               int32_t *ticket, const LitFrame *lit) {
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	int rc = check_camera(cam);
 	if (rc) return rc;
@@ -1737,13 +1785,25 @@ int hmrm_render_device_begin_flags(const hmrm_scene *scene, const hmrm_camera *c
 	if ((rc = prepare_frame(s, c, &super, &f, &slot))) return rc;
 	f.aa_shift = aa_shift;
 	hmrm::RowMap rows{0, super.height, 0, 0, 1, {}, {}, nullptr};
-	if ((rc = launch_frame(s, c, f, slot, rows, (uint32_t *)d_rgba, (int64_t)(stride_bytes / 4), nullptr, nullptr, false, (flags & HMRM_NO_PROBE) != 0))) return rc;
+	if ((rc = launch_frame(s, c, f, slot, rows, (uint32_t *)d_rgba, (int64_t)(stride_bytes / 4), nullptr, nullptr, false, (flags & HMRM_NO_PROBE) != 0, 0, lit))) return rc;
 	HIP_TRY(hipMemcpyAsync(t->h_capped, c->d_counters + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipEventRecord(t->done, c->stream));
 	t->ctx = c;
 	t->busy = true;
 	*ticket = idx;
 	return HMRM_OK;
+}
+
+int hmrm_render_device_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba, size_t stride_bytes, uint32_t flags,
+                                   int32_t *ticket) {
+	return device_begin_common(scene, cam, d_rgba, stride_bytes, flags, ticket, nullptr);
+}
+
+int hmrm_render_shaded_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags,
+                                    void *d_rgba, size_t stride_bytes, uint32_t flags, int32_t *ticket) {
+	if (const int rc = check_shaded(sun, shade_flags)) return rc;
+	const LitFrame lit = make_lit_frame(sun, shade_flags);
+	return device_begin_common(scene, cam, d_rgba, stride_bytes, flags, ticket, &lit);
 }
 
 int hmrm_render_device_wait(const hmrm_scene *scene, int32_t ticket) {
@@ -1882,6 +1942,7 @@ int32_t hmrm_config_antialias(const hmrm_config *c) { return c->cfg.antialias; }
 int32_t hmrm_config_interior(const hmrm_config *c) { return c->cfg.interior; }
 int32_t hmrm_config_shadows(const hmrm_config *c) { return c->cfg.shadows; }
 int32_t hmrm_config_shading(const hmrm_config *c) { return c->cfg.shading; }
+int32_t hmrm_config_sun_scope(const hmrm_config *c) { return c->cfg.sun_scope; }
 void hmrm_config_get_sun(const hmrm_config *c, hmrm_sun *out) {
 	const hmrm::Config &g = c->cfg;
 	memset(out, 0, sizeof *out);
@@ -2296,3 +2357,7 @@ int32_t hmrm_band_local_rows(int32_t height, int32_t band_rows, int32_t band_ind
 }
 
 } // extern "C"
+
+namespace hmrm {
+int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags) { return check_shaded(sun, shade_flags); } // (record.cpp)
+} // namespace hmrm

@@ -14,7 +14,7 @@
 //   output <path>                                   (.png or .ppm)
 //   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8, interior on|off,
 //   shadows on|off, sun_dir x y z, shadow_ambient n, shadow_step_dist v, shadow_max_steps n
-//   shading on|off
+//   shading on|off, sun_scope single|all
 #include "config.hpp"
 
 #include <cmath>
@@ -213,6 +213,14 @@ void shading_key(Config &c, std::istream &in, const char *key, std::string *) {
 	c.log << key << " " << (c.shading ? "on" : "off") << "\n";
 }
 
+// which frames shadows / shading apply to: the plain single frame, or antialiased and recorded ones too
+void sun_scope_key(Config &c, std::istream &in, const char *key, std::string *) {
+	static const Word words[] = {{"single", 0}, {"all", 1}};
+	std::string seen;
+	if (!pick(in, words, &c.sun_scope, &seen)) c.warn << "WARNING: Unknown sun_scope: " << seen << "\n";
+	c.log << key << " " << (c.sun_scope ? "all" : "single") << "\n";
+}
+
 void sun_dir_key(Config &c, std::istream &in, const char *key, std::string *) { // towards the sun, used as given
 	in >> c.sun_dir[0] >> c.sun_dir[1] >> c.sun_dir[2];
 	c.log << key << " " << c.sun_dir[0] << " " << c.sun_dir[1] << " " << c.sun_dir[2] << "\n";
@@ -281,6 +289,7 @@ const Row kGrammar[] = {
 	{"interior", interior_key},
 	{"shadows", shadows_key},
 	{"shading", shading_key},
+	{"sun_scope", sun_scope_key},
 	{"sun_dir", sun_dir_key},
 	{"shadow_ambient", shadow_ambient_key},
 	{"shadow_step_dist", shadow_step_dist_key},

@@ -48,6 +48,9 @@ struct Config {
 	// additive: `shading on|off|1|0` -- diffuse sun shading of that frame (hmrm_render_shaded), with the shadow rays when
 	// `shadows on`; the sun is the same
 	int shading = 0;
+	// additive: `sun_scope single|all` -- 0: shadows / shading apply to the plain single frame only; 1: also with `antialias n` > 1
+	// (hmrm_render_shaded_aa) and to `record orbit` (hmrm_record_orbit_shaded)
+	int sun_scope = 0;
 	double sun_dir[3] = {0.5, 0.5, 0.70710678118654757};
 	int shadow_ambient = 128;
 	double shadow_step_dist = 0.0;

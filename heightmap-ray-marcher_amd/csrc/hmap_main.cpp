@@ -12,7 +12,11 @@
 // `antialias` > 1, `devices` > 1 or `record orbit`.  `shadows on` renders the single frame with sun shadows (hmrm_render_lit;
 // under the interior rule too when `interior on`), and is ignored, with a warning, in the same three cases.  `shading on`
 // renders it with diffuse sun shading (hmrm_render_shaded with HMRM_SHADE_DIFFUSE, and HMRM_SHADE_NO_SHADOWS unless
-// `shadows on`; the sun is the same), and is ignored, with a warning, in those three cases too.
+// `shadows on`; the sun is the same), and is ignored, with a warning, in those three cases too.  `sun_scope all` lifts two of
+// the three for shadows and shading: with `antialias n` > 1 the single frame is the antialiased lit frame
+// (hmrm_render_shaded_aa), and `record orbit` records lit frames (hmrm_record_orbit_shaded, antialiased with `antialias n`,
+// over `devices n`); `interior on` then reaches those frames as the sun's HMRM_TRACE_INTERIOR.  A single frame over
+// `devices` > 1 stays plain.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -69,6 +73,9 @@ int main(int argc, char *argv[]) {
 	const bool interior = hmrm_config_interior(cfg) != 0;
 	const bool shadows = hmrm_config_shadows(cfg) != 0;
 	const bool shading = hmrm_config_shading(cfg) != 0;
+	// `sun_scope all`: shadows / shading also apply to antialiased and recorded frames
+	const bool sun_all = hmrm_config_sun_scope(cfg) != 0 && (shadows || shading);
+	const uint32_t shade_flags = shading ? (HMRM_SHADE_DIFFUSE | (shadows ? 0u : HMRM_SHADE_NO_SHADOWS)) : 0u;
 	hmrm_scene *scene = NULL;
 	if (hmrm_config_create_scene(cfg, &scene) != HMRM_OK) {
 		std::cerr << hmrm_last_error() << "\n";
@@ -76,9 +83,11 @@ int main(int argc, char *argv[]) {
 	}
 
 	if (hmrm_config_record_mode(cfg) == 1) {
-		if (interior) std::cerr << "WARNING: interior is ignored with record orbit\n";
-		if (shadows) std::cerr << "WARNING: shadows is ignored with record orbit\n";
-		if (shading) std::cerr << "WARNING: shading is ignored with record orbit\n";
+		if (!sun_all) {
+			if (interior) std::cerr << "WARNING: interior is ignored with record orbit\n";
+			if (shadows) std::cerr << "WARNING: shadows is ignored with record orbit\n";
+			if (shading) std::cerr << "WARNING: shading is ignored with record orbit\n";
+		}
 		// `record orbit`: recording_frame_count frames on a circle around the map centre through
 		// the configured camera position, always looking at the centre;
 		// files screenshots/hmap_<epoch>_<n>.png as hmap.cpp:1131-1144.
@@ -109,7 +118,13 @@ int main(int argc, char *argv[]) {
 			if (rc == HMRM_OK) rc = hmrm_config_create_scene(cfg, &extra);
 			if (rc == HMRM_OK) scenes.push_back(extra);
 		}
-		if (rc == HMRM_OK)
+		if (rc == HMRM_OK && sun_all) {
+			hmrm_sun sun;
+			hmrm_config_get_sun(cfg, &sun);
+			rc = hmrm_record_orbit_shaded(scenes.data(), (int32_t)scenes.size(), &cam, cx, cy, radius, hang0,
+			                              hmrm_config_recording_frame_count(cfg), dir.c_str(), (long long)id, 0, 1,
+			                              aa > 1 ? HMRM_AA(aa) : 0u, &sun, shade_flags);
+		} else if (rc == HMRM_OK)
 			rc = hmrm_record_orbit_flags(scenes.data(), (int32_t)scenes.size(), &cam, cx, cy, radius, hang0,
 			                             hmrm_config_recording_frame_count(cfg), dir.c_str(), (long long)id, 0, 1,
 			                             aa > 1 ? HMRM_AA(aa) : 0u);
@@ -125,13 +140,26 @@ int main(int argc, char *argv[]) {
 	const int want_dev = wanted_devices(cfg, &visible_dev);
 	if (want_dev > 1 && aa > 1)
 		std::cerr << "WARNING: antialias " << aa << " renders the single frame on one device (devices " << want_dev << " ignored)\n";
-	if (interior && (want_dev > 1 || aa > 1))
+	const bool lit_aa = sun_all && want_dev <= 1 && aa > 1; // (the antialiased lit single frame)
+	if (interior && !lit_aa && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: interior is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (shadows && (want_dev > 1 || aa > 1))
+	if (shadows && !lit_aa && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: shadows is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (shading && (want_dev > 1 || aa > 1))
+	if (shading && !lit_aa && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: shading is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (shading && want_dev <= 1 && aa == 1) {
+	if (lit_aa) {
+		hmrm_sun sun;
+		hmrm_config_get_sun(cfg, &sun);
+		rc = hmrm_render_shaded_aa(scene, &cam, &sun, shade_flags, aa, framebuf.data(), (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height * aa * aa << " rays at antialias " << aa
+		          << (shading ? (shadows ? " with sun shading and sun shadows" : " with sun shading") : " with sun shadows")
+		          << (interior ? " under the interior rule" : "") << " in " << hmrm_last_kernel_ms() << " ms (kernel)\n";
+	} else if (shading && want_dev <= 1 && aa == 1) {
 		hmrm_sun sun;
 		hmrm_config_get_sun(cfg, &sun);
 		rc = hmrm_render_shaded(scene, &cam, &sun, HMRM_SHADE_DIFFUSE | (shadows ? 0u : HMRM_SHADE_NO_SHADOWS), framebuf.data(),

@@ -1,6 +1,7 @@
 // march.hpp -- the production march for gfx950: render_wave_tile, one wave's 8 x 8 pixels (or 64 batch rays), and its
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
-// render_segments.hip, render_interior.hip and render_lit.hip, each with a __global__ kernel of its own.
+// render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip and their antialiased
+// counterparts (march_lit_aa.hpp), each with a __global__ kernel of its own.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
 // the reference loop main/hmap.cpp:978-1058; two bit-preserving restructurings:
@@ -179,7 +180,10 @@ __device__ __forceinline__ uint32_t shade_hit_bilinear(const DevFrame &f, const 
 // (-1: the grid row does not exist).  k_render_fast calls it with the tile = blockIdx (one tile per workgroup); round 4's
 // persistent-tile experiment (resident waves pulling tiles from queue heads) called it in a loop and was 1.4-1.9 x slower:
 // profiles/r04_experiments.txt section 1, code at commit 80527e9.
-// AA: the antialiased epilogue (device_common.hpp store_box_filtered; instantiated in render_fast_aa.hip only).
+// AA: the antialiased epilogue (device_common.hpp store_box_filtered; instantiated in render_fast_aa.hip and, with LIT and / or
+// SHADE, in the three render_*_aa.hip units of march_lit_aa.hpp).  It comes after the LIT / SHADE epilogues -- a sample is lit and
+// shaded on its own, then filtered -- and outside `if (pid.live)`: every lane of the wave reaches it together, whatever the
+// lanes did in the LIT loop, whose ballot only the live lanes take part in.
 // PROJ 4 (instantiated in render_rays.hip only): a batch of caller-supplied rays (hmrm_trace_rays; frame.hpp RayBatch) -- the
 // lane's ray is loaded from `batch`, not made from a camera, and instead of a pixel the lane writes its hmrm_ray_hit record,
 // which wants distance()'s value for misses too and the ray's exact step count: the two things the instrumented
@@ -216,7 +220,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	constexpr bool KEEP_P = LIT || (SHADE && BILINEAR && !KEEP_Q);
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
-	static_assert(!SEG || (!AA && !STATS), "segment rules: production kernels only");
+	static_assert(!SEG || !STATS, "segment rules: production kernels only");
+	static_assert(!SEG || !AA || LIT || SHADE, "segment rules: antialiased for the sun-lit frames only");
 	constexpr bool REC = LEAP == 2;                     // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
 	constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
 	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
@@ -838,7 +843,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		if (STATS && st.steps_per_pixel)
 			st.steps_per_pixel[(int64_t)pid.py * f.screen_w + pid.px] = diag.pixel_value(f, my_steps);
 	}
-	if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, lane, pid.px, pid.lrow, pid.live, aa_rgba);
+	// (the sun-lit families make the lane's number again instead of holding it across their marches)
+	if constexpr (AA && SEG)
+		store_box_filtered(out, out_stride_px, f.aa_shift, (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), pid.px,
+		                   pid.lrow, pid.live, aa_rgba);
+	else if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, lane, pid.px, pid.lrow, pid.live, aa_rgba);
 	publish_counters<STATS>(st, my_steps, my_hit, my_cap);
 	diag.publish(st, f);
 	return pid.tile_y;

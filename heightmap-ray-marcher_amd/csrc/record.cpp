@@ -31,6 +31,7 @@
 
 namespace hmrm {
 int set_error(int code, const char *msg);
+int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags); // (api.cpp: the refusals of hmrm_render_shaded_begin's sun)
 }
 
 extern "C" {
@@ -55,10 +56,17 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices) {
 }
 
 // `flags` go to every ticketed render (hmrm_render_begin_flags): HMRM_AA(n) records antialiased frames -- still W x H
-// in the ring and in the files.
-int hmrm_record_orbit_flags(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
-                            double centre_y, double radius, double hang0, int32_t frames, const char *dir,
-                            long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags) {
+// in the ring and in the files.  `sun` (may be NULL: plain frames, `shade_flags` must be 0 then): every frame is a lit ticket
+// (hmrm_render_shaded_begin) with that sun and those shade_flags; the sun is copied, the caller's need not outlive the call.
+int hmrm_record_orbit_shaded(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
+                             double centre_y, double radius, double hang0, int32_t frames, const char *dir,
+                             long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags, const hmrm_sun *sun,
+                             uint32_t shade_flags) {
+	if (!sun && shade_flags != 0u) return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit_shaded: shade_flags without a sun");
+	if (sun)
+		if (const int rc_sun = hmrm::check_shaded_args(sun, shade_flags)) return rc_sun;
+	const bool lit = sun != nullptr;
+	const hmrm_sun the_sun = lit ? *sun : hmrm_sun{};
 	if (!scenes || n_scenes <= 0 || !base || !dir || frames <= 0)
 		return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit: bad argument");
 	for (int i = 0; i < n_scenes; ++i)
@@ -176,7 +184,8 @@ int hmrm_record_orbit_flags(hmrm_scene *const *scenes, int32_t n_scenes, const h
 					hmrm_camera cam;
 					hmrm_orbit_camera(base, centre_x, centre_y, radius, hang0, next, frames, &cam);
 					int32_t ticket = -1;
-					const int rc = hmrm_render_begin_flags(scenes[i], &cam, flags, &ticket);
+					const int rc = lit ? hmrm_render_shaded_begin(scenes[i], &cam, &the_sun, shade_flags, flags, &ticket)
+					                   : hmrm_render_begin_flags(scenes[i], &cam, flags, &ticket);
 					if (rc != HMRM_OK) {
 						note_error(rc);
 						break;
@@ -216,6 +225,13 @@ int hmrm_record_orbit_flags(hmrm_scene *const *scenes, int32_t n_scenes, const h
 	if (failures.load() > 0) return hmrm::set_error(HMRM_E_IO, "Failed to write one or more recording frames");
 	if (verbose) std::printf("Done recording.\n"); // hmap.cpp:1142
 	return HMRM_OK;
+}
+
+int hmrm_record_orbit_flags(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
+                            double centre_y, double radius, double hang0, int32_t frames, const char *dir,
+                            long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags) {
+	return hmrm_record_orbit_shaded(scenes, n_scenes, base, centre_x, centre_y, radius, hang0, frames, dir, id, encoder_threads,
+	                                verbose, flags, nullptr, 0u);
 }
 
 int hmrm_record_orbit_multi(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,

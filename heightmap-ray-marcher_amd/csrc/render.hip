@@ -296,6 +296,46 @@ __global__ __launch_bounds__(kBlockThreads) void k_render_shaded_literal(const D
 	}
 	out[(int64_t)pid.lrow * out_stride_px + pid.px] = rgba;
 }
+// The antialiased lit and hill-shaded pixels (hmrm_render_shaded_aa with HMRM_KERNEL=simple): the same passes per sample of the
+// super frame; the lane's final sample goes to the wave's box filter (store_box_filtered: every lane of the wave calls it,
+// so no lane returns before) and not to memory.  Kernels of their own: the two above keep their instructions.
+template <int PROJ>
+__global__ __launch_bounds__(kBlockThreads) void k_render_lit_literal_aa(const DevFrame f, const RowMap rows,
+                                                                         const double *__restrict__ thr,
+                                                                         const uint32_t *__restrict__ cmap,
+                                                                         uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                         int tiles_y, StatsOut st, const SegRules seg, const SunRules sun) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, sun, &lt);
+	render_lane_literal<PROJ, false, false, true, 2>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
+	                                                 SegRules{nullptr, sun.max_steps, 1u}, sun, &lt);
+	store_box_filtered(out, out_stride_px, f.aa_shift, (int)(threadIdx.x & 63), pid.px, pid.lrow, pid.live, pid.live ? lt.rgba : 0u);
+}
+template <int PROJ, bool SHADOWS>
+__global__ __launch_bounds__(kBlockThreads) void k_render_shaded_literal_aa(const DevFrame f, const RowMap rows,
+                                                                            const double *__restrict__ thr,
+                                                                            const uint32_t *__restrict__ cmap,
+                                                                            uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                            int tiles_y, StatsOut st, const SegRules seg, const SunRules sun) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	unsigned cell = 0u;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, sun, &lt, &cell);
+	if constexpr (SHADOWS)
+		render_lane_literal<PROJ, false, false, true, 3>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
+		                                                 SegRules{nullptr, sun.max_steps, 1u}, sun, &lt);
+	uint32_t rgba = 0u;
+	if (pid.live) {
+		rgba = lt.rgba;
+		if (lt.primary_hit) {
+			uint32_t w = sun.ambient;
+			if (lt.phase == 0) w = shade_weight(sun.ambient, diffuse_level_nearest<false>(f, thr, cell, sun.dir));
+			rgba = shade_weighted(rgba, w);
+		}
+	}
+	store_box_filtered(out, out_stride_px, f.aa_shift, (int)(threadIdx.x & 63), pid.px, pid.lrow, pid.live, rgba);
+}
 __global__ __launch_bounds__(kBlockThreads) void k_trace_segments_literal(const DevFrame f, const double *__restrict__ thr,
                                                                           const uint32_t *__restrict__ cmap, const RayBatch batch,
                                                                           const SegRules seg, int tiles_y, StatsOut st) {
@@ -521,6 +561,47 @@ hipError_t launch_render_shaded_literal(const DevFrame &f, const RowMap &rows, c
                                         bool primary_interior, bool shadows, hipStream_t stream) {
 	return shadows ? launch_render_shaded_literal_t<true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream)
 	               : launch_render_shaded_literal_t<false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream);
+}
+
+// The antialiased ones: f is the super frame, d_out the filtered frame's.
+hipError_t launch_render_lit_literal_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                        uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
+                                        bool primary_interior, hipStream_t stream) {
+	if (f.aa_shift == 0 || rows.measure != nullptr) return hipErrorInvalidValue;
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	const dim3 block(kBlockThreads);
+	const StatsOut st{d_counters, nullptr, nullptr};
+	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
+	switch (f.projection) {
+	case 1: hipLaunchKernelGGL(k_render_lit_literal_aa<1>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	case 2: hipLaunchKernelGGL(k_render_lit_literal_aa<2>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	default: hipLaunchKernelGGL(k_render_lit_literal_aa<3>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	}
+	return hipGetLastError();
+}
+template <bool SHADOWS>
+static hipError_t launch_render_shaded_literal_aa_t(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                                    uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                                    const SunRules &sun, bool primary_interior, hipStream_t stream) {
+	if (f.aa_shift == 0 || rows.measure != nullptr) return hipErrorInvalidValue;
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	const dim3 block(kBlockThreads);
+	const StatsOut st{d_counters, nullptr, nullptr};
+	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
+	switch (f.projection) {
+	case 1: hipLaunchKernelGGL((k_render_shaded_literal_aa<1, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	case 2: hipLaunchKernelGGL((k_render_shaded_literal_aa<2, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	default: hipLaunchKernelGGL((k_render_shaded_literal_aa<3, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	}
+	return hipGetLastError();
+}
+hipError_t launch_render_shaded_literal_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                           uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
+                                           bool primary_interior, bool shadows, hipStream_t stream) {
+	return shadows ? launch_render_shaded_literal_aa_t<true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream)
+	               : launch_render_shaded_literal_aa_t<false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream);
 }
 
 hipError_t launch_render(const DevFrame &f, const RowMap &rows, const double *d_thr,

@@ -88,6 +88,28 @@ hipError_t launch_render_lit_shaded(const DevFrame &f, const RowMap &rows, const
 hipError_t launch_render_shaded_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
                                         uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
                                         bool primary_interior, bool shadows, hipStream_t stream);
+// The antialiased counterparts (hmrm_render_shaded_aa; march_lit_aa.hpp and the three render_*_aa.hip units; the literal loop in
+// render.hip): f is the super frame with f.aa_shift != 0, every sample is lit and shaded on its own and the launch writes the
+// box-filtered frame, (f.screen_w >> f.aa_shift) pixels wide, into d_out.  They refuse f.aa_shift == 0, as the ones above
+// refuse the opposite.  Counters as above, per sample.
+hipError_t launch_render_lit_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
+                                const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
+                                hipStream_t stream);
+hipError_t launch_render_shaded_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
+                                   const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                   FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
+                                   hipStream_t stream);
+hipError_t launch_render_lit_shaded_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
+                                       const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
+                                       FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
+                                       hipStream_t stream);
+hipError_t launch_render_lit_literal_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                        uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
+                                        bool primary_interior, hipStream_t stream);
+hipError_t launch_render_shaded_literal_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
+                                           uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
+                                           bool primary_interior, bool shadows, hipStream_t stream);
 // The record table of the thr table: rec_row(map_w) x ceil(map_h / 4) WindowRecords.
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream);
 // thr32[i] = (float)thr[i], round to nearest (the "float heights" mode).

@@ -205,6 +205,10 @@ def _load():
         "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
+        "hmrm_render_shaded_aa": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, i32, vp, C.c_size_t]),
+        "hmrm_render_shaded_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, C.c_uint32, C.POINTER(i32)]),
+        "hmrm_render_shaded_device_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t, C.c_uint32,
+                                                      C.POINTER(i32)]),
         "hmrm_pick": (C.c_int, [vp, C.POINTER(Camera), i32, i32, C.POINTER(RayHit)]),
         "hmrm_debug_ray": (C.c_int, [vp, C.POINTER(Camera), i32, i32, dp, dp, dp]),
         "hmrm_debug_frame": (C.c_int, [C.POINTER(Camera), C.POINTER(SceneParams), i32, i32, vp, vp]),
@@ -222,11 +226,15 @@ def _load():
         "hmrm_config_interior": (i32, [vp]),
         "hmrm_config_shadows": (i32, [vp]),
         "hmrm_config_shading": (i32, [vp]),
+        "hmrm_config_sun_scope": (i32, [vp]),
         "hmrm_config_get_sun": (None, [vp, C.POINTER(Sun)]),
         "hmrm_record_orbit_multi": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32]),
         "hmrm_record_orbit_flags": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32, C.c_uint32]),
+        "hmrm_record_orbit_shaded": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
+                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32, C.c_uint32, C.POINTER(Sun),
+                                               C.c_uint32]),
         "hmrm_orbit_frame_owner": (i32, [i32, i32]),
         "hmrm_render_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(i32)]),
         "hmrm_render_begin_flags": (C.c_int, [vp, C.POINTER(Camera), C.c_uint32, C.POINTER(i32)]),
@@ -315,6 +323,11 @@ def set_device(i: int):
 _ENV_KNOBS = ("HMRM_KERNEL", "HMRM_STEP_CAP", "HMRM_TILE_ORDER", "HMRM_DIAG_ITERS", "HMRM_MIN_LEVEL", "HMRM_FINEST_PAUSE", "HMRM_TILE_SEGMENTS", "HMRM_ORDER_VERBOSE", "HMRM_TRY_GROUP")
 
 
+def shade_flags(diffuse=True, shadows=True) -> int:
+    """hmrm_render_shaded's shade_flags (HMRM_SHADE_*)."""
+    return (SHADE_DIFFUSE if diffuse else 0) | (0 if shadows else SHADE_NO_SHADOWS)
+
+
 def _env_snapshot():
     return tuple(os.environ.get(k) for k in _ENV_KNOBS)
 
@@ -384,26 +397,53 @@ class Scene:
                allow=(HMRM_E_NOTERM,) if allow_capped else ())
         return fb
 
-    def render_lit(self, cam: Camera, sun: Sun, allow_capped=False) -> np.ndarray:
+    def render_lit(self, cam: Camera, sun: Sun, allow_capped=False, aa=1) -> np.ndarray:
         """One full frame with sun shadows (hmrm_render_lit): render()'s frame -- render_interior()'s with Sun.make(...,
         interior=True) -- in which every pixel whose shadow ray hits keeps ambient / 255 of its colour -> HxWx4 uint8.  Capped
-        primary or shadow rays: HMRM_E_NOTERM unless allow_capped."""
+        primary or shadow rays: HMRM_E_NOTERM unless allow_capped.  aa > 1: the antialiased lit frame (hmrm_render_shaded_aa
+        with shade_flags = 0)."""
+        if aa != 1:
+            return self.render_shaded(cam, sun, diffuse=False, shadows=True, allow_capped=allow_capped, aa=aa)
         self._sync_env()
         fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
         _check(lib.hmrm_render_lit(self._h, C.byref(cam), C.byref(sun), _ptr(fb), cam.width * 4),
                allow=(HMRM_E_NOTERM,) if allow_capped else ())
         return fb
 
-    def render_shaded(self, cam: Camera, sun: Sun, diffuse=True, shadows=True, allow_capped=False) -> np.ndarray:
+    def render_shaded(self, cam: Camera, sun: Sun, diffuse=True, shadows=True, allow_capped=False, aa=1) -> np.ndarray:
         """One full frame with diffuse sun shading (hmrm_render_shaded): render_lit()'s frame in which every hit pixel that is
         not shadowed is weighted by the diffuse level of its hit (`diffuse`; include/hmrm.h has the arithmetic); shadows=False
-        marches no shadow rays (HMRM_SHADE_NO_SHADOWS) -> HxWx4 uint8.  Capped rays: HMRM_E_NOTERM unless allow_capped."""
+        marches no shadow rays (HMRM_SHADE_NO_SHADOWS) -> HxWx4 uint8.  Capped rays: HMRM_E_NOTERM unless allow_capped.
+        aa > 1: the antialiased lit frame (hmrm_render_shaded_aa): every sample of the aa x aa times larger frame is shaded and
+        shadowed on its own, then box-filtered."""
         self._sync_env()
         fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
-        flags = (SHADE_DIFFUSE if diffuse else 0) | (0 if shadows else SHADE_NO_SHADOWS)
-        _check(lib.hmrm_render_shaded(self._h, C.byref(cam), C.byref(sun), flags, _ptr(fb), cam.width * 4),
-               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        flags = shade_flags(diffuse, shadows)
+        if aa == 1:
+            rc = lib.hmrm_render_shaded(self._h, C.byref(cam), C.byref(sun), flags, _ptr(fb), cam.width * 4)
+        else:
+            rc = lib.hmrm_render_shaded_aa(self._h, C.byref(cam), C.byref(sun), flags, int(aa), _ptr(fb), cam.width * 4)
+        _check(rc, allow=(HMRM_E_NOTERM,) if allow_capped else ())
         return fb
+
+    def render_shaded_begin(self, cam: Camera, sun: Sun, diffuse=True, shadows=True, aa=1, no_probe=False) -> int:
+        """render_begin for a lit frame (hmrm_render_shaded_begin) -> ticket of the same ring: render_wait / render_release.
+        diffuse=False, shadows=True is render_lit's frame.  no_probe is accepted and has no effect."""
+        self._sync_env()
+        t = C.c_int32()
+        _check(lib.hmrm_render_shaded_begin(self._h, C.byref(cam), C.byref(sun), shade_flags(diffuse, shadows),
+                                            (NO_PROBE if no_probe else 0) | aa_flags(aa), C.byref(t)))
+        return int(t.value)
+
+    def render_shaded_device_begin(self, cam: Camera, sun: Sun, d_ptr: int, stride_bytes: int, diffuse=True, shadows=True, aa=1,
+                                   no_probe=False) -> int:
+        """render_device_begin for a lit frame (hmrm_render_shaded_device_begin) -> ticket for render_device_wait."""
+        self._sync_env()
+        t = C.c_int32()
+        _check(lib.hmrm_render_shaded_device_begin(self._h, C.byref(cam), C.byref(sun), shade_flags(diffuse, shadows),
+                                                   C.c_void_p(d_ptr), stride_bytes, (NO_PROBE if no_probe else 0) | aa_flags(aa),
+                                                   C.byref(t)))
+        return int(t.value)
 
     def render_cycle(self, cam: Camera, framebuf: np.ndarray, cycle: int, cycle_period: int):
         """Progressive refresh (hmap.cpp:976-983): rewrites pixels p = cycle (mod cycle_period) in place."""
@@ -672,6 +712,20 @@ def record_orbit_multi(scenes, base: Camera, centre_x, centre_y, radius, hang0, 
                allow=(HMRM_E_NOTERM,))
 
 
+def record_orbit_shaded(scenes, base: Camera, centre_x, centre_y, radius, hang0, frames, directory, rec_id, sun,
+                        diffuse=True, shadows=True, aa=1, encoder_threads=0, verbose=False):
+    """record_orbit_multi whose frames are lit ones (hmrm_record_orbit_shaded): `sun` with diffuse / shadows as in
+    Scene.render_shaded, aa the antialias factor.  sun=None records plain frames (diffuse and shadows are not looked at)."""
+    for s in scenes:
+        s._sync_env()
+    arr = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    _check(lib.hmrm_record_orbit_shaded(arr, len(scenes), C.byref(base), centre_x, centre_y, radius, hang0, frames,
+                                        os.fsencode(directory), rec_id, encoder_threads, int(verbose), aa_flags(aa),
+                                        C.byref(sun) if sun is not None else None,
+                                        shade_flags(diffuse, shadows) if sun is not None else 0),
+           allow=(HMRM_E_NOTERM,))
+
+
 def render_multi(scenes, cam: Camera, allow_capped=False) -> np.ndarray:
     """One frame over several scenes (one per GPU): scene i renders the cyclic 16-row bands i, i+n, ..."""
     for s in scenes:
@@ -769,6 +823,10 @@ class Config:
     def shading(self) -> bool:
         """Additive `shading on|off`: the CLI renders its single frame with hmrm_render_shaded."""
         return bool(lib.hmrm_config_shading(self._h))
+
+    def sun_scope(self) -> int:
+        """Additive `sun_scope single|all`: 0 | 1 -- whether shadows / shading also apply to antialiased and recorded frames."""
+        return int(lib.hmrm_config_sun_scope(self._h))
 
     def sun(self) -> Sun:
         """The sun of the additive keys sun_dir, shadow_step_dist (absent: step_dist), shadow_max_steps, shadow_ambient, interior."""

@@ -346,7 +346,8 @@ int hmrm_trace_segments_device(const hmrm_scene *scene, const hmrm_segment_param
  * probe, not counted towards it.  A perspective or spherical camera that is not strictly inside the box gives hmrm_render's
  * frame byte for byte (the ordinary kernel runs); orthographic origins are tested per pixel.  HMRM_E_NOTERM as hmrm_render:
  * an interior ray with dir.x = dir.y = 0 that never hits (straight up) never leaves the grid and runs to the step cap.
- * Not antialiased, no tickets, strips or recording: trace a batch for those. */
+ * Not antialiased, no tickets, strips or recording by itself: hmrm_render_shaded_aa, hmrm_render_shaded_begin and
+ * hmrm_record_orbit_shaded with HMRM_SHADE_NO_SHADOWS and HMRM_TRACE_INTERIOR give this frame all of those; or trace a batch. */
 int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes);
 
 /* ------------------------------------------------------------- sun shadows */
@@ -369,8 +370,9 @@ int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_
  * Refusals (HMRM_E_ARG) come before the scene is looked at: NULL sun, an undefined flag bit, reserved != 0.  Synchronous, on
  * the scene's stream, launched the way hmrm_render_interior is: one launch renders the frame, never measured, never the
  * scene's probe and not counted towards it, with the scene's current kernel (HMRM_KERNEL or the probe's verdict; the window
- * records apply to HMRM_NEAREST).  All three projections and sampling modes.  Not antialiased, no tickets, strips or
- * recording. */
+ * records apply to HMRM_NEAREST).  All three projections and sampling modes.  Antialiased, ticketed and recorded lit
+ * frames: hmrm_render_shaded_aa, hmrm_render_shaded_begin, hmrm_render_shaded_device_begin and hmrm_record_orbit_shaded below
+ * with shade_flags = 0.  Still no row strips or bands, no multi-GPU single frame, no cycle, no statistics. */
 typedef struct hmrm_sun {        /* 48 bytes */
 	double   dir[3];     /* towards the sun; used as given, NOT normalised (like hmrm_ray.dir) */
 	double   step_dist;  /* of the shadow march, in units of |dir| */
@@ -418,12 +420,42 @@ int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_
  * hmrm_render_lit; with HMRM_SHADE_NO_SHADOWS only primary rays can be capped.  Synchronous, on the scene's stream, launched
  * the way a lit frame is: one launch, never measured, never the scene's probe and not counted towards it, with the scene's
  * current kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST).  All three projections and
- * sampling modes.  Not antialiased, no tickets, strips or recording.  The shading arithmetic is tested at unit world scale
+ * sampling modes.  Antialiased, ticketed and recorded: the entry points below.  Still no row strips or bands
+ * (hmrm_render_rows_device), no hmrm_render_multi, no hmrm_render_cycle, no statistics.  The shading arithmetic is tested at unit world scale
  * only: world scales far beyond a unit-scale scene (the 2^-900 .. 2^900 of the parity tests) are not tested for it. */
 #define HMRM_SHADE_DIFFUSE    1u
 #define HMRM_SHADE_NO_SHADOWS 2u
 int hmrm_render_shaded(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun,
                        uint32_t shade_flags, uint8_t *rgba, size_t stride_bytes);
+
+/* -------------------------------------- antialiased, ticketed and recorded sun-lit frames */
+/* THE ANTIALIASED LIT FRAME with factor n (1, 2, 4, 8) of a W x H camera is the frame hmrm_render_shaded returns for the super
+ * camera (n*W) x (n*H) -- hmrm_render_aa's super frame -- with the same sun and shade_flags: every sample is shaded and
+ * shadowed on its own.  That frame is then box-filtered with hmrm_render_aa's formula: per channel (S + n*n/2) >> (2 log2 n),
+ * A = 255.  The samples are marched, lit and reduced inside one launch: no buffer of n*n*W*H pixels exists.
+ * Consequences, all byte for byte: factor 1 is hmrm_render_shaded (its kernels run); HMRM_SHADE_NO_SHADOWS alone is
+ * hmrm_render_aa's frame -- with HMRM_TRACE_INTERIOR and a camera inside the box the box-filtered hmrm_render_interior frame,
+ * which is how an unlit interior fly-through reaches tickets and recording; ambient = 255 is hmrm_render_aa's frame under any
+ * flags; shade_flags = 0 is the antialiased hmrm_render_lit frame.
+ * Capped samples (primary and shadow rays together) are counted as in hmrm_render_lit and make the call -- or the wait --
+ * return HMRM_E_NOTERM with a valid frame; END rays never do.
+ * Refusals (HMRM_E_ARG) come before the scene is looked at, in this order: NULL sun, an undefined bit in sun->flags, reserved
+ * != 0, an undefined bit in shade_flags; then those of hmrm_render_aa (hmrm_render_begin_flags for the tickets): the camera,
+ * the flag bits, the factor, the super frame's size.
+ * hmrm_render_shaded_aa is synchronous, on the scene's stream, launched the way a lit frame is. */
+int hmrm_render_shaded_aa(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags,
+                          int32_t factor, uint8_t *rgba, size_t stride_bytes);
+/* Lit tickets: hmrm_render_begin_flags / hmrm_render_device_begin_flags for the lit frame above.  flags: HMRM_AA(n), and
+ * HMRM_NO_PROBE, which is accepted and has no effect -- a lit frame is never the scene's probe, never measured and not counted
+ * towards the probe; hmrm_debug_kernel_choice and every later plain frame are as they would have been without it.  The
+ * tickets come from the same rings as plain ones and are waited for and released with hmrm_render_wait, hmrm_render_release
+ * and hmrm_render_device_wait; the lane rotation and the per-lane accounting of capped rays are the same; plain and lit
+ * tickets with different factors may be in flight together on one scene; hmrm_scene_update waits for them as for any ticket
+ * (they finish with the old heights).  *sun is copied into the launch: it need not outlive the call. */
+int hmrm_render_shaded_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags,
+                             uint32_t flags, int32_t *ticket);
+int hmrm_render_shaded_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun,
+                                    uint32_t shade_flags, void *d_rgba, size_t stride_bytes, uint32_t flags, int32_t *ticket);
 
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
@@ -554,6 +586,14 @@ int hmrm_record_orbit_multi(hmrm_scene *const *scenes, int32_t n_scenes, const h
 int hmrm_record_orbit_flags(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base,
                             double centre_x, double centre_y, double radius, double hang0, int32_t frames,
                             const char *dir, long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags);
+/* hmrm_record_orbit_flags whose frames are lit tickets (hmrm_render_shaded_begin with `sun`, `shade_flags` and `flags`): a
+ * shaded, shadowed, antialiased orbit as PNGs.  sun = NULL with shade_flags = 0 is hmrm_record_orbit_flags, which calls it so:
+ * the same ticketed renders, the same files; sun = NULL with shade_flags != 0 is HMRM_E_ARG, and so is a sun or a shade_flags
+ * word that hmrm_render_shaded_begin refuses -- before any scene is looked at.  *sun is copied. */
+int hmrm_record_orbit_shaded(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base,
+                             double centre_x, double centre_y, double radius, double hang0, int32_t frames,
+                             const char *dir, long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags,
+                             const hmrm_sun *sun, uint32_t shade_flags);
 int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
 
 /* ------------------------------------------------------------------- config */
@@ -572,7 +612,10 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * `shadow_step_dist v` (absent: the camera's step_dist), `shadow_max_steps n` (default 0 = none; a value outside
  * 0..4294967295 warns and keeps the old one), `shading on|off|1|0` (default off; the CLI renders its single frame with
  * hmrm_render_shaded, HMRM_SHADE_DIFFUSE, plus HMRM_SHADE_NO_SHADOWS unless `shadows on`; another value warns "WARNING:
- * Unknown shading: v" and keeps the old one).  Unknown key -> "WARNING: Unknown identifier: k". */
+ * Unknown shading: v" and keeps the old one), `sun_scope single|all` (default single: shadows / shading apply to the plain
+ * single frame only, as before; all: they also apply with `antialias n` > 1 -- hmrm_render_shaded_aa -- and to `record orbit`
+ * -- hmrm_record_orbit_shaded; another value warns "WARNING: Unknown sun_scope: v" and keeps the old one).
+ * Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
 /* Consume a whole stream; loads heightmap/colormap images when those keys
@@ -594,6 +637,7 @@ int32_t      hmrm_config_antialias(const hmrm_config *cfg);     /* additive `ant
 int32_t      hmrm_config_interior(const hmrm_config *cfg);      /* additive `interior on|off`: 1|0 */
 int32_t      hmrm_config_shadows(const hmrm_config *cfg);       /* additive `shadows on|off`: 1|0 */
 int32_t      hmrm_config_shading(const hmrm_config *cfg);       /* additive `shading on|off`: 1|0 */
+int32_t      hmrm_config_sun_scope(const hmrm_config *cfg);     /* additive `sun_scope single|all`: 0|1 */
 /* The sun of the additive keys: sun_dir, shadow_step_dist (the config's step_dist when the key was absent),
  * shadow_max_steps, shadow_ambient; flags = HMRM_TRACE_INTERIOR when `interior on`. */
 void         hmrm_config_get_sun(const hmrm_config *cfg, hmrm_sun *out);
