@@ -231,6 +231,8 @@ struct hmrm_scene {
 	size_t batch_cap = 0;
 	uint32_t *d_limits = nullptr; // ... and of hmrm_trace_segments' per-ray limits
 	size_t limits_cap = 0;
+	uint8_t *d_cells = nullptr; // ... and of hmrm_cell_map: the rect's bytes, rows packed
+	size_t cells_cap = 0;
 	// launch state per stream; `mu` guards the list and the slot choice (launches themselves are
 	// asynchronous), so that threads driving different streams of one scene do not collide
 	std::mutex mu;
@@ -274,6 +276,11 @@ static_assert(sizeof(hmrm_ray) == sizeof(hmrm::BatchRay) && sizeof(hmrm_ray_hit)
                   sizeof(hmrm_segment_params) == 24 && offsetof(hmrm_segment_params, flags) == 12 &&
                   offsetof(hmrm_segment_params, max_steps) == 16 && offsetof(hmrm_segment_params, reserved) == 20,
               "the kernels' mirrors of hmrm_ray / hmrm_ray_hit (frame.hpp)");
+static_assert(sizeof(hmrm_cell_map_params) == 56 && offsetof(hmrm_cell_map_params, max_steps) == 40 &&
+                  offsetof(hmrm_cell_map_params, sampling) == 48 && sizeof(hmrm_cell_rect) == 16 &&
+                  HMRM_MAP_TOWARDS_POINT == hmrm::kMapTowardsPoint && HMRM_MAP_WEIGHT == hmrm::kMapWeight &&
+                  HMRM_MAP_DIFFUSE == hmrm::kMapDiffuse && HMRM_MAP_NO_SHADOWS == hmrm::kMapNoShadows,
+              "hmrm_cell_map_params and the kernels' flag bits (frame.hpp CellRules)");
 // cached records and settled launch orders are looked up with memcmp on these two: no padding bytes allowed
 static_assert(sizeof(hmrm_sun) == 48, "hmrm_sun has padding");
 static_assert(sizeof(hmrm_camera) == 3 * sizeof(int32_t) + 4 + 8 * sizeof(double), "hmrm_camera has padding");
@@ -1011,15 +1018,11 @@ int ensure_batch(hmrm_scene *s, size_t n) {
 	return HMRM_OK;
 }
 
-// One batch on the context's stream.  The DevFrame has no camera: a zeroed record plus the scene's box, grid and pyramid,
-// laid out as a frame kBatchW pixels wide (frame.hpp RayBatch).  A batch is not a frame: it takes no cached record, is
-// never measured, never probes and does not count towards the scene's probe; it only READS the scene's kernel choice
-// (HMRM_KERNEL or the probe's verdict), and waits -- in stream order -- for a measured launch in flight like any launch.
-// The leap policy's hints come from a camera's step length in cells for frames (camera.cpp); a batch's directions have
+// The DevFrame of a launch without a camera (ray batches, cell maps): a zeroed record plus the scene's box, grid and pyramid.
+// The leap policy's hints come from a camera's step length in cells for frames (camera.cpp); such a launch's directions have
 // any length, so it gets the fine-step defaults: windows from 4 cells on, no pause (HMRM_MIN_LEVEL / HMRM_FINEST_PAUSE apply).
-// `seg` (hmrm_trace_segments; null: hmrm_trace_rays): the segment rules, run by the segment kernels (render_segments.hip).
-int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg[3], int sampling, const hmrm::BatchRay *d_rays,
-                 int64_t n, hmrm::BatchHit *d_hits, const hmrm::SegRules *seg = nullptr) {
+// The caller sets projection and the "frame" (screen_w x screen_h).  Refuses what no kernel of the sampling mode can render.
+int cameraless_frame(hmrm_scene *s, double step_dist, int sampling, hmrm::DevFrame *out) {
 	const bool huge_side = s->map_w >= (1 << 24) || s->map_h >= (1 << 24);
 	if (huge_side && sampling != 0) return fail(HMRM_E_ARG, "maps with a side of 2^24 cells or more support nearest sampling only");
 	if (sampling == HMRM_BILINEAR) {
@@ -1028,12 +1031,6 @@ int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg
 	}
 	hmrm::DevFrame f = hmrm::DevFrame();
 	hmrm::fill_scene_fields(s->map_w, s->map_h, s->params.min_height, s->params.max_height, s->params.grid_width, step_dist, &f);
-	f.screen_w = hmrm::kBatchW;
-	f.screen_h = (int32_t)((n + hmrm::kBatchW - 1) / hmrm::kBatchW);
-	f.projection = 4;
-	f.bg[0] = bg[0];
-	f.bg[1] = bg[1];
-	f.bg[2] = bg[2];
 	f.bg[3] = 255;
 	f.sampling = sampling;
 	f.thr_max = sampling == HMRM_BILINEAR ? s->thr_max_bil : s->thr_max;
@@ -1045,19 +1042,105 @@ int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg
 	f.min_window = 4;
 	f.min_level = s->knobs.min_level >= 0 ? s->knobs.min_level : 0;
 	f.finest_pause = s->knobs.finest_pause >= 0 ? s->knobs.finest_pause : 0;
-	const hmrm::RayBatch batch{d_rays, d_hits, n};
-	int rc = wait_for_measure_fence(s, c);
+	*out = f;
+	return HMRM_OK;
+}
+// ... and the kernel such a launch runs: the scene's choice is only READ (HMRM_KERNEL or the probe's verdict, never a probe).
+// *literal: the literal loop (HMRM_KERNEL=simple, or a side of 2^24 cells), which only knows the reference's sampling.
+int cameraless_kernel(hmrm_scene *s, int sampling, bool *literal, hmrm::FastKernel *k) {
+	const bool huge_side = s->map_w >= (1 << 24) || s->map_h >= (1 << 24);
+	*literal = (s->knobs.kernel == 2 || huge_side) && sampling == 0;
+	*k = hmrm::kLeaps;
+	if (*literal) return HMRM_OK;
+	const bool use_other = s->knobs.kernel == 0 && s->knobs.try_group && s->choice.use_group;
+	*k = (hmrm::FastKernel)hmrm::pick_fast_kernel(s->knobs.kernel, use_other, sampling == 0 && s->d_records, s->choice);
+	return *k == hmrm::kRecords ? ensure_records(s) : HMRM_OK;
+}
+
+// One batch on the context's stream.  The DevFrame has no camera: a zeroed record plus the scene's box, grid and pyramid,
+// laid out as a frame kBatchW pixels wide (frame.hpp RayBatch).  A batch is not a frame: it takes no cached record, is
+// never measured, never probes and does not count towards the scene's probe; it only READS the scene's kernel choice
+// (HMRM_KERNEL or the probe's verdict), and waits -- in stream order -- for a measured launch in flight like any launch.
+// `seg` (hmrm_trace_segments; null: hmrm_trace_rays): the segment rules, run by the segment kernels (render_segments.hip).
+int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg[3], int sampling, const hmrm::BatchRay *d_rays,
+                 int64_t n, hmrm::BatchHit *d_hits, const hmrm::SegRules *seg = nullptr) {
+	hmrm::DevFrame f;
+	int rc = cameraless_frame(s, step_dist, sampling, &f);
 	if (rc) return rc;
-	if ((s->knobs.kernel == 2 || huge_side) && sampling == 0) { // (the literal loop only knows the reference's sampling)
+	f.screen_w = hmrm::kBatchW;
+	f.screen_h = (int32_t)((n + hmrm::kBatchW - 1) / hmrm::kBatchW);
+	f.projection = 4;
+	f.bg[0] = bg[0];
+	f.bg[1] = bg[1];
+	f.bg[2] = bg[2];
+	const hmrm::RayBatch batch{d_rays, d_hits, n};
+	if ((rc = wait_for_measure_fence(s, c))) return rc;
+	bool literal = false;
+	hmrm::FastKernel k;
+	if ((rc = cameraless_kernel(s, sampling, &literal, &k))) return rc;
+	if (literal) {
 		if (seg) HIP_TRY(hmrm::launch_trace_segments_literal(f, s->d_thr, s->d_cmap, batch, *seg, c->d_counters, c->stream));
 		else HIP_TRY(hmrm::launch_trace_rays_literal(f, s->d_thr, s->d_cmap, batch, c->d_counters, c->stream));
 	} else {
-		const bool use_other = s->knobs.kernel == 0 && s->knobs.try_group && s->choice.use_group; // (the verdict, never a probe)
-		const hmrm::FastKernel k = (hmrm::FastKernel)hmrm::pick_fast_kernel(s->knobs.kernel, use_other, sampling == 0 && s->d_records, s->choice);
-		if (k == hmrm::kRecords && (rc = ensure_records(s))) return rc;
 		if (seg) HIP_TRY(hmrm::launch_trace_segments(f, s->d_thr, s->d_thr32, s->d_cmap, batch, *seg, c->d_counters, k, s->d_records, c->stream));
 		else HIP_TRY(hmrm::launch_trace_rays(f, s->d_thr, s->d_thr32, s->d_cmap, batch, c->d_counters, k, s->d_records, c->stream));
 	}
+	return note_launch(s, c);
+}
+
+// ---- cell maps (hmrm_cell_map, hmrm_cell_map_device) ----
+// Needs no scene and no device, in hmrm.h's order.
+int check_cell_map(const hmrm_cell_map_params *p, const void *out) {
+	if (!p) return fail(HMRM_E_ARG, "cell map: NULL params");
+	constexpr uint32_t known = HMRM_MAP_TOWARDS_POINT | HMRM_MAP_WEIGHT | HMRM_MAP_DIFFUSE | HMRM_MAP_NO_SHADOWS;
+	if (p->flags & ~known)
+		return fail(HMRM_E_ARG, "cell map: unknown flag bits (defined: HMRM_MAP_TOWARDS_POINT, _WEIGHT, _DIFFUSE, _NO_SHADOWS)");
+	for (uint8_t r : p->reserved)
+		if (r != 0) return fail(HMRM_E_ARG, "cell map: hmrm_cell_map_params.reserved must be 0");
+	if (p->sampling > HMRM_NEAREST_F32)
+		return fail(HMRM_E_ARG, "cell map: sampling must be 0 (nearest), 1 (bilinear) or 2 (nearest, float heights)");
+	if ((p->flags & (HMRM_MAP_DIFFUSE | HMRM_MAP_NO_SHADOWS)) && !(p->flags & HMRM_MAP_WEIGHT))
+		return fail(HMRM_E_ARG, "cell map: HMRM_MAP_DIFFUSE and HMRM_MAP_NO_SHADOWS need HMRM_MAP_WEIGHT");
+	if (!out) return fail(HMRM_E_ARG, "cell map: NULL out");
+	return HMRM_OK;
+}
+
+// ... and what needs the scene's size: the rect (null: the whole map) and the stride.
+int check_cell_rect(const hmrm_scene *s, const hmrm_cell_rect *rect, size_t stride_bytes, hmrm_cell_rect *r) {
+	*r = rect ? *rect : hmrm_cell_rect{0, 0, s->map_w, s->map_h};
+	if (r->w <= 0 || r->h <= 0 || r->x0 < 0 || r->y0 < 0 || (int64_t)r->x0 + r->w > s->map_w || (int64_t)r->y0 + r->h > s->map_h)
+		return fail(HMRM_E_ARG, "cell map: the rect must be non-empty and inside the map");
+	if (stride_bytes < (size_t)r->w) return fail(HMRM_E_ARG, "cell map: stride_bytes is below the rect's width");
+	return HMRM_OK;
+}
+
+int ensure_cells(hmrm_scene *s, size_t n) {
+	if (n <= s->cells_cap) return HMRM_OK;
+	if (s->d_cells) (void)hipFree(s->d_cells);
+	s->d_cells = nullptr;
+	s->cells_cap = 0;
+	HIP_TRY(hipMalloc((void **)&s->d_cells, n));
+	s->cells_cap = n;
+	return HMRM_OK;
+}
+
+// One cell map on the context's stream: launch_batch's recipe -- a DevFrame without a camera whose "frame" is the rect, the
+// fine-step leap hints, no cached record, never measured, never a probe and not counted towards it; it only READS the scene's
+// kernel choice and waits, in stream order, for a measured launch in flight.
+int launch_cells(hmrm_scene *s, StreamCtx *c, const hmrm_cell_map_params *p, const hmrm_cell_rect &r, uint8_t *d_out, size_t stride_bytes) {
+	hmrm::DevFrame f;
+	int rc = cameraless_frame(s, p->step_dist, p->sampling, &f);
+	if (rc) return rc;
+	f.screen_w = r.w;
+	f.screen_h = r.h;
+	f.projection = 5;
+	const hmrm::CellRules cells{{p->target[0], p->target[1], p->target[2]}, p->lift, r.x0, r.y0, p->max_steps, p->flags, p->ambient};
+	if ((rc = wait_for_measure_fence(s, c))) return rc;
+	bool literal = false;
+	hmrm::FastKernel k;
+	if ((rc = cameraless_kernel(s, p->sampling, &literal, &k))) return rc;
+	if (literal) HIP_TRY(hmrm::launch_cell_map_literal(f, s->d_thr, d_out, (int64_t)stride_bytes, cells, c->d_counters, c->stream));
+	else HIP_TRY(hmrm::launch_cell_map(f, s->d_thr, s->d_thr32, d_out, (int64_t)stride_bytes, cells, c->d_counters, k, s->d_records, c->stream));
 	return note_launch(s, c);
 }
 
@@ -1224,6 +1307,7 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	if (s->d_rays) (void)hipFree(s->d_rays);
 	if (s->d_hits) (void)hipFree(s->d_hits);
 	if (s->d_limits) (void)hipFree(s->d_limits);
+	if (s->d_cells) (void)hipFree(s->d_cells);
 	if (s->ev0) (void)hipEventDestroy(s->ev0);
 	if (s->ev1) (void)hipEventDestroy(s->ev1);
 	if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -1943,6 +2027,8 @@ int32_t hmrm_config_interior(const hmrm_config *c) { return c->cfg.interior; }
 int32_t hmrm_config_shadows(const hmrm_config *c) { return c->cfg.shadows; }
 int32_t hmrm_config_shading(const hmrm_config *c) { return c->cfg.shading; }
 int32_t hmrm_config_sun_scope(const hmrm_config *c) { return c->cfg.sun_scope; }
+const char *hmrm_config_sun_map_path(const hmrm_config *c) { return c->cfg.sun_map_path.c_str(); }
+double hmrm_config_sun_map_lift(const hmrm_config *c) { return c->cfg.sun_map_lift; }
 void hmrm_config_get_sun(const hmrm_config *c, hmrm_sun *out) {
 	const hmrm::Config &g = c->cfg;
 	memset(out, 0, sizeof *out);
@@ -2127,6 +2213,43 @@ int hmrm_trace_segments_device(const hmrm_scene *scene, const hmrm_segment_param
 	const hmrm::SegRules seg{static_cast<const uint32_t *>(d_max_steps), p->max_steps, p->flags & HMRM_TRACE_INTERIOR};
 	return launch_batch(s, c, p->step_dist, bg, p->sampling, static_cast<const hmrm::BatchRay *>(d_rays), n,
 	                    static_cast<hmrm::BatchHit *>(d_hits), &seg);
+}
+
+int hmrm_cell_map(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect, uint8_t *out, size_t stride_bytes) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	int rc = check_cell_map(p, out);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	hmrm_cell_rect r;
+	if ((rc = check_cell_rect(s, rect, stride_bytes, &r))) return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	if ((rc = ensure_cells(s, (size_t)r.w * (size_t)r.h))) return rc;
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, s->stream, &c))) return rc;
+	if ((rc = launch_cells(s, c, p, r, s->d_cells, (size_t)r.w))) return rc;
+	HIP_TRY(hipMemcpy2DAsync(out, stride_bytes, s->d_cells, (size_t)r.w, (size_t)r.w, (size_t)r.h, hipMemcpyDeviceToHost, s->stream));
+	unsigned long long capped_now = 0;
+	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	const unsigned long long capped = capped_now - c->capped_seen;
+	c->capped_seen = capped_now;
+	return capped ? noterm(capped) : HMRM_OK;
+}
+
+int hmrm_cell_map_device(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect, void *d_out,
+                         size_t stride_bytes, void *hip_stream) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	int rc = check_cell_map(p, d_out);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	hmrm_cell_rect r;
+	if ((rc = check_cell_rect(s, rect, stride_bytes, &r))) return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
+	return launch_cells(s, c, p, r, static_cast<uint8_t *>(d_out), stride_bytes);
 }
 
 // Picking: GetRay of one pixel on the device (k_probe, as hmrm_debug_ray) and that ray traced as a batch of one.  Like a

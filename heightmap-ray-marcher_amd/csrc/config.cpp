@@ -15,6 +15,7 @@
 //   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8, interior on|off,
 //   shadows on|off, sun_dir x y z, shadow_ambient n, shadow_step_dist v, shadow_max_steps n
 //   shading on|off, sun_scope single|all
+//   sun_map <path.png>, sun_map_lift v                (the whole map's light map, hmrm_cell_map, written by the CLI)
 #include "config.hpp"
 
 #include <cmath>
@@ -294,6 +295,8 @@ const Row kGrammar[] = {
 	{"shadow_ambient", shadow_ambient_key},
 	{"shadow_step_dist", shadow_step_dist_key},
 	{"shadow_max_steps", shadow_max_steps_key},
+	{"sun_map", scalar<&Config::sun_map_path>},
+	{"sun_map_lift", scalar<&Config::sun_map_lift>},
 };
 
 } // namespace

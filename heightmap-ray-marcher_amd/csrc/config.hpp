@@ -56,6 +56,10 @@ struct Config {
 	double shadow_step_dist = 0.0;
 	bool have_shadow_step_dist = false;
 	long long shadow_max_steps = 0;
+	// additive: `sun_map <path.png>` -- the CLI also writes the whole map's light map (hmrm_cell_map with HMRM_MAP_WEIGHT under the
+	// same sun) there, one byte per cell; `sun_map_lift v` -- how far above the surface its rays start
+	std::string sun_map_path;
+	double sun_map_lift = 0.0;
 
 	bool heightmap_dirty = false; // should_update_heightmap, sticky until taken
 	std::ostringstream log;       // what the reference prints to stdout

@@ -201,6 +201,25 @@ __device__ __forceinline__ double shadow_entry(const DevRay &r, const DevFrame &
 	return origin_strictly_inside(r, f) ? 0.0 : slab_distance(r, f);
 }
 
+// Cell maps (hmrm_cell_map; frame.hpp CellRules): the ray of cell (cx, cy) whose threshold is t -- from `lift` above the
+// surface at the cell's centre towards the target, a direction used as given or a point -- hmrm.h's operations in hmrm.h's order.
+__device__ __forceinline__ DevRay cell_ray(const CellRules &c, const DevFrame &f, int cx, int cy, double t) {
+	DevRay r;
+	r.px = ((double)cx + 0.5) * f.grid_width;
+	r.py = -(((double)cy + 0.5) * f.grid_width);
+	r.pz = t + c.lift;
+	const bool point = (c.flags & kMapTowardsPoint) != 0u; // (uniform)
+	r.dx = point ? c.target[0] - r.px : c.target[0];
+	r.dy = point ? c.target[1] - r.py : c.target[1];
+	r.dz = point ? c.target[2] - r.pz : c.target[2];
+	return r;
+}
+// ... and the byte of a cell whose ray ended with `status` (HMRM_RAY_*): the status itself, or with HMRM_MAP_WEIGHT the weight
+// of hmrm_render_shaded -- ambient for a shadowed cell (status HIT), else 255 or, HMRM_MAP_DIFFUSE, that of the level q.
+__device__ __forceinline__ uint32_t cell_weight(const CellRules &c, bool shadowed, uint32_t q) {
+	return shadowed ? c.ambient : ((c.flags & kMapDiffuse) != 0u ? shade_weight(c.ambient, q) : 255u);
+}
+
 // Relative error of the hardware reciprocal.  MEASURED on gfx950 (tools/rcp_accuracy.py over 1.6e11 inputs: the
 // leading 32 mantissa bits exhaustively in six binades, hashed mantissas / signs / exponents 2^-1000..2^1000, and the
 // product n * rcp(d) against n / d; profiles/r03_rcp_accuracy.txt): |rcp(x) * x - 1| <= 2^-24.36 everywhere, the same

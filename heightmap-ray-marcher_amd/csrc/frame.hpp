@@ -202,6 +202,23 @@ struct SunRules {
 	uint32_t ambient; // 0..255
 };
 
+// ---- cell maps (hmrm_cell_map; PROJ == 5 in the kernels) ----
+// A lane owns one map cell of the rect instead of a pixel: cell (x0 + px, y0 + py) of the launch's "frame", which is the
+// rect (DevFrame::screen_w x screen_h = the rect's w x h, no camera).  Its ray starts `lift` above the cell's threshold, at the
+// cell's centre, towards `target` (flags & 1: a point, else a direction as given) -- a segment ray under the interior rule with
+// DevFrame::step_dist and the limit max_steps -- and the lane writes ONE BYTE: the ray's status, or (flags & 2) the weight of
+// hmrm_render_shaded.  flags are hmrm.h's HMRM_MAP_*.  An extra argument of the cell kernels' own __global__ entry points,
+// like SegRules.
+struct CellRules {
+	double target[3];
+	double lift;
+	int32_t x0, y0;
+	uint32_t max_steps;
+	uint32_t flags;
+	uint32_t ambient; // 0..255
+};
+constexpr uint32_t kMapTowardsPoint = 1u, kMapWeight = 2u, kMapDiffuse = 4u, kMapNoShadows = 8u;
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

@@ -16,7 +16,9 @@
 // the three for shadows and shading: with `antialias n` > 1 the single frame is the antialiased lit frame
 // (hmrm_render_shaded_aa), and `record orbit` records lit frames (hmrm_record_orbit_shaded, antialiased with `antialias n`,
 // over `devices n`); `interior on` then reaches those frames as the sun's HMRM_TRACE_INTERIOR.  A single frame over
-// `devices` > 1 stays plain.
+// `devices` > 1 stays plain.  `sun_map <path.png>`: after its frames the whole map's light map (hmrm_cell_map with HMRM_MAP_WEIGHT:
+// one byte per cell under the config's sun, the camera's sampling, `sun_map_lift` above the surface; diffuse levels with
+// `shading on`, shadow rays unless `shading on` stands without `shadows on`) is written there as a one-component PNG.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -46,6 +48,38 @@ static int wanted_devices(hmrm_config *cfg, int *visible_out) {
 static bool ends_with(const std::string &s, const char *suffix) {
 	const size_t n = strlen(suffix);
 	return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+// `sun_map <path>`: the whole map's light map, one byte per cell.  Returns false when it could not be made or written.
+static bool write_sun_map(hmrm_config *cfg, hmrm_scene *scene, const hmrm_camera &cam, bool shading, bool shadows) {
+	const std::string path = hmrm_config_sun_map_path(cfg);
+	if (path.empty()) return true;
+	int32_t mw = 0, mh = 0;
+	hmrm_config_height_rgb(cfg, &mw, &mh);
+	hmrm_sun sun;
+	hmrm_config_get_sun(cfg, &sun);
+	hmrm_cell_map_params p;
+	memset(&p, 0, sizeof p);
+	for (int k = 0; k < 3; ++k) p.target[k] = sun.dir[k];
+	p.step_dist = sun.step_dist;
+	p.lift = hmrm_config_sun_map_lift(cfg);
+	p.max_steps = sun.max_steps;
+	p.flags = HMRM_MAP_WEIGHT | (shading ? HMRM_MAP_DIFFUSE : 0u) | (shading && !shadows ? HMRM_MAP_NO_SHADOWS : 0u);
+	p.sampling = cam.sampling;
+	p.ambient = sun.ambient;
+	std::vector<uint8_t> map((size_t)mw * mh);
+	const int rc = hmrm_cell_map(scene, &p, NULL, map.data(), (size_t)mw);
+	if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+		std::cerr << hmrm_last_error() << "\n";
+		return false;
+	}
+	if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+	if (hmrm_write_png(path.c_str(), mw, mh, 1, map.data(), (size_t)mw) != HMRM_OK) {
+		std::cerr << "Failed to write sun map to " << path << "\n";
+		return false;
+	}
+	std::cout << "Saved sun map at " << path << "\n";
+	return true;
 }
 
 int main(int argc, char *argv[]) {
@@ -130,6 +164,7 @@ int main(int argc, char *argv[]) {
 			                             aa > 1 ? HMRM_AA(aa) : 0u);
 		if (rc != HMRM_OK) std::cerr << hmrm_last_error() << "\n";
 		for (size_t i = 1; i < scenes.size(); ++i) hmrm_scene_destroy(scenes[i]);
+		if (rc == HMRM_OK && !write_sun_map(cfg, scene, cam, shading, shadows)) rc = HMRM_E_IO;
 		hmrm_scene_destroy(scene);
 		hmrm_config_destroy(cfg);
 		return rc == HMRM_OK ? 0 : 1;
@@ -241,6 +276,7 @@ int main(int argc, char *argv[]) {
 		std::cerr << "Failed to write screenshot to " << path << "\n";
 	else
 		std::cout << "Saved screenshot at " << path << "\n";
+	if (wrc == HMRM_OK && !write_sun_map(cfg, scene, cam, shading, shadows)) wrc = HMRM_E_IO;
 
 	hmrm_scene_destroy(scene);
 	hmrm_config_destroy(cfg);

@@ -1,7 +1,7 @@
 // march.hpp -- the production march for gfx950: render_wave_tile, one wave's 8 x 8 pixels (or 64 batch rays), and its
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
-// render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip and their antialiased
-// counterparts (march_lit_aa.hpp), each with a __global__ kernel of its own.
+// render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
+// counterparts (march_lit_aa.hpp) and render_cells.hip, each with a __global__ kernel of its own.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
 // the reference loop main/hmap.cpp:978-1058; two bit-preserving restructurings:
@@ -164,6 +164,16 @@ __device__ __forceinline__ uint32_t shade_hit_bilinear(const DevFrame &f, const 
 	return pack_rgba(ch[0], ch[1], ch[2]);
 }
 
+// Cell maps: the ray of cell (x0 + px, y0 + py) of the rect, made from the cell's entry of the table the sampling mode's
+// march reads (`thr`: the float copy for SAMP 2, else the doubles -- the bilinear mode's origin sits on the cell's own value).
+template <int SAMP>
+__device__ __forceinline__ DevRay cell_ray_of(const CellRules &c, const DevFrame &f, const double *__restrict__ thr, int px, int py) {
+	const int cx = c.x0 + px, cy = c.y0 + py;
+	const size_t i = (size_t)cy * (size_t)f.map_w + (size_t)cx;
+	const double t = SAMP == 2 ? (double)reinterpret_cast<const float *>(thr)[i] : thr[i];
+	return cell_ray(c, f, cx, cy, t);
+}
+
 } // namespace
 
 #ifndef HMRM_MIN_WAVES
@@ -204,12 +214,20 @@ __device__ __forceinline__ uint32_t shade_hit_bilinear(const DevFrame &f, const 
 // or its cell coordinates): device_common.hpp ShadeState, empty unless SHADE.  (LIT: computing the level at the phase
 // switch instead and carrying it through the shadow march in the saved pixel's alpha byte holds no cell index, but the
 // compiler then keeps more across the march, not less: DESIGN.md 5.12.)
+// PROJ 5 (instantiated in render_cells.hip only; hmrm_cell_map, frame.hpp CellRules; needs SEG): a cell map.  The "frame" is the
+// rect, a lane owns one map cell, a wave 8 x 8 of them; the lane's ray is made from the cell index and the cell's own entry of
+// `thr` (device_common.hpp cell_ray), enters the loop like a shadow ray (shadow_entry: the interior rule is always on), and the
+// epilogue stores ONE BYTE -- the ray's status, or the weight of SHADE's arithmetic -- through `out`, which points at bytes then
+// (`out_stride_px` counts bytes).  HMRM_MAP_NO_SHADOWS gives every lane d = inf: the wave skips the loop.  Again `if constexpr`
+// statements beside the others' own; the ray is made again in the epilogue rather than held across the march.
 template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false, bool SHADE = false>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
                                                 int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{},
-                                                const SunRules &sun = SunRules{}) {
+                                                const SunRules &sun = SunRules{}, const CellRules &cells = CellRules{}) {
+	constexpr bool CELLS = PROJ == 5;
+	static_assert(!CELLS || (SEG && !STATS && !AA && !LIT && !SHADE), "cell maps: segment rays, one byte per cell");
 	static_assert(!LIT || (SEG && PROJ != 4), "sun shadows: frames, under the segment rules");
 	static_assert(!SHADE || (SEG && PROJ != 4), "sun shading: frames, under the segment rules");
 	constexpr bool BILINEAR = SAMP == 1, F32 = SAMP == 2;
@@ -244,11 +262,15 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	if (pid.live) {
 		DevRay ray = make_ray<PROJ>(f, pid.px, pid.py);
 		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
+		if constexpr (CELLS) ray = cell_ray_of<SAMP>(cells, f, thr, pid.px, pid.py); // (make_ray<5>'s too)
 		// most rays of a frame never touch the box: prove the miss cheaply where possible (the instrumented
 		// variant reports d, so it takes no shortcut for misses); most of the others get their entry distance
 		// from one division instead of six (slab_classify: the instrumented variant uses that path too, so the
 		// parity tests compare its d with the oracle's bit for bit)
 		double d = __builtin_huge_val();
+		if constexpr (CELLS) { // (most origins are strictly inside: no slab test unless one is not; no ray at all without shadows)
+			if ((cells.flags & kMapNoShadows) == 0u) d = shadow_entry(ray, f);
+		} else
 		if (COUNT || !slab_points_away<PROJ>(ray, f)) {
 			const int verdict = slab_classify(ray, f, !COUNT, &d);
 			if (verdict == 0) d = slab_distance(ray, f);
@@ -257,6 +279,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		SegState<SEG> sg; // (empty unless SEG: device_common.hpp)
 		if constexpr (SEG) {
 			sg.d_record = d; // (a record keeps distance()'s own value, not the d that was used)
+			if constexpr (!CELLS) // (shadow_entry has applied the rule)
 			if (seg.interior != 0u && origin_strictly_inside(ray, f)) d = 0.0; // as if distance() had returned +0.0
 			sg.budget = segment_budget(seg, RAYS ? ray_index : 0, f.step_cap, &sg.ends);
 		}
@@ -670,9 +693,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 									qxh = hit_j == j ? QX[j] : qxh;
 									qyh = hit_j == j ? QY[j] : qyh;
 								}
+								if constexpr (!CELLS) // (a cell map has no colours: `cmap` is null)
 								rgba = shade_hit_bilinear(f, cmap, (int)hit_cell, bil_setup(qxh, qyh, f.map_w, f.map_h));
 								if constexpr (KEEP_Q) { sh.px = qxh; sh.py = qyh; }
 							} else {
+								if constexpr (!CELLS)
 								rgba = shade_hit(f, cmap[hit_cell]);
 								if constexpr (SHADE && LIT) sh.cell = lt.phase ? sh.cell : hit_cell; // (the primary ray's)
 								else if constexpr (SHADE) sh.cell = hit_cell;
@@ -725,6 +750,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								t = F32 ? (double)thr32[c] : thr[c];
 							}
 							if (zs < t) { // hmap.cpp:1016
+								if constexpr (!CELLS)
 								rgba = BILINEAR ? shade_hit_bilinear(f, cmap, c, b) : shade_hit(f, cmap[c]);
 								real_hit = true;
 								if constexpr (KEEP_Q) { sh.px = qx; sh.py = qy; }
@@ -823,6 +849,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			}
 		}
 
+		// (CELLS: a cell map has no pixel and counts no hits -- `rgba`, the miss shade and my_hit are dead there and compile to
+		// nothing; the family's entry passes SegRules::interior = 1 for the record, the rule itself is shadow_entry's above)
 		if (real_hit) my_hit = 1;
 		else rgba = shade_miss(f, ray.dz);
 		if constexpr (SEG) { // an END ray is not a capped one: not counted, never HMRM_E_NOTERM
@@ -830,6 +858,25 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			my_cap = sg.ended ? 0u : my_cap;
 		}
 		// (row and pitch are below 2^31, api.cpp: one 32 x 32 -> 64-bit multiply-add)
+		if constexpr (CELLS) {
+			uint32_t v = real_hit ? 1u : (my_cap != 0u ? 2u : (sg.ended ? 3u : 0u)); // HMRM_RAY_*
+			if ((cells.flags & kMapWeight) != 0u) {
+				uint32_t q = 0u;
+				if ((cells.flags & kMapDiffuse) != 0u && !real_hit) { // the level of the cell under its own direction
+					const DevRay own = cell_ray_of<SAMP>(cells, f, thr, pid.px, pid.py);
+					const double s[3] = {own.dx, own.dy, own.dz};
+					if constexpr (BILINEAR) {
+						const double qxc = GWM == 0 ? own.px : (GWM == 2 ? own.px / f.grid_width : own.px * f.inv_grid_width);
+						const double qyc = GWM == 0 ? -own.py : (GWM == 2 ? -own.py / f.grid_width : -own.py * f.inv_grid_width);
+						q = diffuse_level_bilinear(f, thr, bil_setup(qxc, qyc, f.map_w, f.map_h), s);
+					} else {
+						q = diffuse_level_nearest<F32>(f, thr, (unsigned)index_2d(cells.y0 + pid.py, f.map_w, cells.x0 + pid.px), s);
+					}
+				}
+				v = cell_weight(cells, real_hit, q);
+			}
+			reinterpret_cast<uint8_t *>(out)[(uint64_t)(uint32_t)pid.lrow * (uint64_t)out_stride_px + (uint32_t)pid.px] = (uint8_t)v;
+		} else
 		if constexpr (RAYS) {
 			const unsigned cy = hcell / (unsigned)f.map_w; // (gridx, gridy of hmap.cpp:1001-1004 from gridx + gridy * W)
 			if constexpr (SEG) {

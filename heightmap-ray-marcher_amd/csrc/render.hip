@@ -86,6 +86,7 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 // (`seg` holds the sun's limit and the interior rule); a hit darkens lit->rgba.  The other lanes sit that pass out.
 // 3 (hmrm_render_shaded): pass 2, but a hit leaves lit->rgba alone and says SHADOWED in lit->phase -- the caller weights the pixel;
 // `hit_cell` (pass 1, may be null): where the primary hit's cell index gridx + gridy * W goes, for that caller.
+// 4 (hmrm_cell_map): pass 3 for a ray the caller put into *lit itself; the ray's status (HMRM_RAY_*) comes back in lit->phase.
 template <int PROJ, bool STATS, bool AA, bool SEG = false, int LIT = 0>
 __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId pid, const double *__restrict__ thr,
                                                     const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
@@ -171,8 +172,10 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 				const double t = thr[cell]; // hmap.cpp:1013-1014 (+ c0.z folded in)
 				if (COUNT) my_steps += 1;
 				if (z < t) { // hmap.cpp:1016
+					if constexpr (LIT != 4) { // (a cell map has no colours: `cmap` is null)
 					const uint32_t c = cmap[cell];
 					rgba = ((c >> 24) == 0) ? pack_rgba(f.bg[0], f.bg[1], f.bg[2]) : (c | 0xff000000u);
+					}
 					real_hit = true;
 					if constexpr (RAYS) { hx = x; hy = y; hz = z; hgx = gridx; hgy = gridy; }
 					if constexpr (LIT == 1) {
@@ -212,6 +215,8 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 			if (real_hit) lit->rgba = shade_shadowed(lit->rgba, sun.ambient); // (MISS, END and CAPPED leave the pixel lit)
 		} else if constexpr (LIT == 3) {
 			if (real_hit) lit->phase = 1;
+		} else if constexpr (LIT == 4) {
+			lit->phase = real_hit ? 1 : (my_cap != 0u ? 2 : (sg.ended ? 3 : 0));
 		} else
 		if constexpr (RAYS && SEG) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
 		else if constexpr (RAYS) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, d_box, (uint32_t)my_steps, rgba);
@@ -343,6 +348,38 @@ __global__ __launch_bounds__(kBlockThreads) void k_trace_segments_literal(const 
 	const PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, 0, blockIdx.z * 32768u + blockIdx.x, (int)(threadIdx.x >> 6),
 	                                       (int)(threadIdx.x & 63));
 	render_lane_literal<4, false, false, true>(f, pid, thr, cmap, nullptr, 0, st, batch, seg);
+}
+
+// A cell of a cell map (hmrm_cell_map with HMRM_KERNEL=simple, or on a map with a side of 2^24 cells; frame.hpp CellRules):
+// the cell's ray (device_common.hpp cell_ray) through the literal loop as a shadow ray is, then the byte.  The "frame" is the
+// rect, tiled like a frame; nearest sampling only, like every literal kernel.
+__global__ __launch_bounds__(kBlockThreads) void k_cell_map_literal(const DevFrame f, const double *__restrict__ thr,
+                                                                    uint8_t *__restrict__ out, int64_t stride_bytes,
+                                                                    const CellRules cells, int tiles_y, StatsOut st) {
+	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	DevRay ray{};
+	size_t cell = 0; // (gridx + gridy * W of the lane's cell)
+	if (pid.live) {
+		const int cx = cells.x0 + pid.px, cy = cells.y0 + pid.py;
+		cell = (size_t)cy * (size_t)f.map_w + (size_t)cx;
+		ray = cell_ray(cells, f, cx, cy, thr[cell]);
+	}
+	const SunRules sun{{ray.dx, ray.dy, ray.dz}, f.step_dist, cells.max_steps, cells.ambient};
+	lt.hx = ray.px; lt.hy = ray.py; lt.t = ray.pz;
+	lt.primary_hit = (cells.flags & kMapNoShadows) == 0u; // (without shadows no lane marches)
+	render_lane_literal<3, false, false, true, 4>(f, pid, thr, nullptr, nullptr, 0, st, RayBatch{}, SegRules{nullptr, cells.max_steps, 1u},
+	                                              sun, &lt);
+	if (!pid.live) return;
+	uint32_t v = (uint32_t)lt.phase;
+	if ((cells.flags & kMapWeight) != 0u) {
+		uint32_t q = 0u;
+		if ((cells.flags & kMapDiffuse) != 0u && lt.phase != 1)
+			q = diffuse_level_nearest<false>(f, thr, (unsigned)cell, sun.dir); // (maps hold at most 2^29 cells)
+		v = cell_weight(cells, lt.phase == 1, q);
+	}
+	out[(int64_t)pid.lrow * stride_bytes + pid.px] = (uint8_t)v;
 }
 
 // Per-ray parity hook: GetRay + distance() of one pixel -> out[0..2] pos, [3..5] dir, [6] d.
@@ -504,6 +541,16 @@ hipError_t launch_trace_segments_literal(const DevFrame &f, const double *d_thr,
 	const LaunchGrid g = batch_grid(f, batch);
 	if (g.tiles_y == 0) return g.err;
 	hipLaunchKernelGGL(k_trace_segments_literal, g.grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_cmap, batch, seg, g.tiles_y,
+	                   StatsOut{d_counters, nullptr, nullptr});
+	return hipGetLastError();
+}
+
+hipError_t launch_cell_map_literal(const DevFrame &f, const double *d_thr, uint8_t *d_out, int64_t stride_bytes, const CellRules &cells,
+                                   unsigned long long *d_counters, hipStream_t stream) {
+	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	hipLaunchKernelGGL(k_cell_map_literal, g.grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_out, stride_bytes, cells, g.tiles_y,
 	                   StatsOut{d_counters, nullptr, nullptr});
 	return hipGetLastError();
 }

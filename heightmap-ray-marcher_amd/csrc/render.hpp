@@ -55,6 +55,15 @@ hipError_t launch_trace_segments(const DevFrame &f, const double *d_thr, const f
                                  const WindowRecord *d_records, hipStream_t stream);
 hipError_t launch_trace_segments_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
                                          const SegRules &seg, unsigned long long *d_counters, hipStream_t stream);
+// Cell maps (hmrm_cell_map; frame.hpp CellRules; render_cells.hip: the segment march with a lane per map cell, and the literal
+// loop in render.hip, nearest sampling only).  `f` is a DevFrame without a camera whose "frame" is the rect: projection 5,
+// screen_w x screen_h = the rect's w x h, step_dist the rays'.  One byte per cell at d_out[row * stride_bytes + column] (no
+// alignment asked); d_counters[2] counts CAPPED rays only.
+hipError_t launch_cell_map(const DevFrame &f, const double *d_thr, const float *d_thr32, uint8_t *d_out, int64_t stride_bytes,
+                           const CellRules &cells, unsigned long long *d_counters, FastKernel kernel, const WindowRecord *d_records,
+                           hipStream_t stream);
+hipError_t launch_cell_map_literal(const DevFrame &f, const double *d_thr, uint8_t *d_out, int64_t stride_bytes, const CellRules &cells,
+                                   unsigned long long *d_counters, hipStream_t stream);
 // Frames under the interior rule (hmrm_render_interior; render_interior.hip: the production kernels' instantiations with the
 // rule, a translation unit of its own, and the literal loop in render.hip).  Not instrumented, not antialiased, never measured.
 hipError_t launch_render_interior(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,

@@ -134,6 +134,32 @@ class Sun(C.Structure):
 
 assert C.sizeof(Sun) == 48
 
+MAP_TOWARDS_POINT, MAP_WEIGHT, MAP_DIFFUSE, MAP_NO_SHADOWS = 1, 2, 4, 8  # hmrm_cell_map_params.flags (HMRM_MAP_*)
+
+
+class CellMapParams(C.Structure):
+    """hmrm_cell_map_params (56 bytes): the rays and the byte of Scene.cell_map"""
+    _fields_ = [("target", C.c_double * 3), ("step_dist", C.c_double), ("lift", C.c_double), ("max_steps", C.c_uint32),
+                ("flags", C.c_uint32), ("sampling", C.c_uint8), ("ambient", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+    @classmethod
+    def make(cls, target, step_dist, lift=0.0, max_steps=0, flags=0, sampling=NEAREST, ambient=128):
+        """target: the direction towards the sun, used as given -- with MAP_TOWARDS_POINT in flags the point O; step_dist in
+        units of |dir|; lift: how far above its cell's surface a ray starts; max_steps: limit of every ray (0 = none); flags:
+        MAP_*; ambient 0..255: the weight of a shadowed cell."""
+        if not 0 <= int(ambient) <= 255:
+            raise ValueError("ambient must be 0..255")
+        return cls((C.c_double * 3)(*(float(v) for v in target)), float(step_dist), float(lift), int(max_steps), int(flags),
+                   int(sampling), int(ambient), (C.c_uint8 * 6)())
+
+
+class CellRect(C.Structure):
+    """hmrm_cell_rect: cells [x0, x0 + w) x [y0, y0 + h)"""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+assert C.sizeof(CellMapParams) == 56 and C.sizeof(CellRect) == 16
+
 # the same layouts as numpy structured dtypes (arrays of rays in, arrays of records out)
 RAY_DTYPE = np.dtype([("pos", np.float64, 3), ("dir", np.float64, 3)])
 RAY_HIT_DTYPE = np.dtype([("point", np.float64, 3), ("entry_d", np.float64), ("steps", np.uint32),
@@ -202,6 +228,8 @@ def _load():
         "hmrm_trace_rays_device": (C.c_int, [vp, C.POINTER(TraceParams), vp, C.c_int64, vp, vp]),
         "hmrm_trace_segments": (C.c_int, [vp, C.POINTER(SegmentParams), vp, vp, C.c_int64, vp, C.POINTER(Stats)]),
         "hmrm_trace_segments_device": (C.c_int, [vp, C.POINTER(SegmentParams), vp, vp, C.c_int64, vp, vp]),
+        "hmrm_cell_map": (C.c_int, [vp, C.POINTER(CellMapParams), C.POINTER(CellRect), vp, C.c_size_t]),
+        "hmrm_cell_map_device": (C.c_int, [vp, C.POINTER(CellMapParams), C.POINTER(CellRect), vp, C.c_size_t, vp]),
         "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
@@ -227,6 +255,8 @@ def _load():
         "hmrm_config_shadows": (i32, [vp]),
         "hmrm_config_shading": (i32, [vp]),
         "hmrm_config_sun_scope": (i32, [vp]),
+        "hmrm_config_sun_map_path": (C.c_char_p, [vp]),
+        "hmrm_config_sun_map_lift": (C.c_double, [vp]),
         "hmrm_config_get_sun": (None, [vp, C.POINTER(Sun)]),
         "hmrm_record_orbit_multi": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32]),
@@ -326,6 +356,19 @@ _ENV_KNOBS = ("HMRM_KERNEL", "HMRM_STEP_CAP", "HMRM_TILE_ORDER", "HMRM_DIAG_ITER
 def shade_flags(diffuse=True, shadows=True) -> int:
     """hmrm_render_shaded's shade_flags (HMRM_SHADE_*)."""
     return (SHADE_DIFFUSE if diffuse else 0) | (0 if shadows else SHADE_NO_SHADOWS)
+
+
+def map_flags(point=False, weight=False, diffuse=False, shadows=True) -> int:
+    """hmrm_cell_map_params.flags (HMRM_MAP_*)."""
+    return ((MAP_TOWARDS_POINT if point else 0) | (MAP_WEIGHT if weight else 0) | (MAP_DIFFUSE if diffuse else 0)
+            | (0 if shadows else MAP_NO_SHADOWS))
+
+
+def _as_rect(rect):
+    if rect is None or isinstance(rect, CellRect):
+        return rect
+    x0, y0, w, h = (int(v) for v in rect)
+    return CellRect(x0, y0, w, h)
 
 
 def _env_snapshot():
@@ -574,6 +617,34 @@ class Scene:
         _check(lib.hmrm_trace_segments_device(self._h, C.byref(p), C.c_void_p(d_rays_ptr),
                                               C.c_void_p(d_max_steps_ptr) if d_max_steps_ptr else None, int(n),
                                               C.c_void_p(d_hits_ptr), C.c_void_p(stream)))
+
+    def cell_map(self, target, step_dist, lift=0.0, max_steps=0, point=False, weight=False, diffuse=False, shadows=True,
+                 sampling=NEAREST, ambient=128, rect=None, allow_capped=False, stride_bytes=None) -> np.ndarray:
+        """One byte per map cell (hmrm_cell_map): every cell of `rect` ((x0, y0, w, h) or a CellRect; None = the whole map)
+        casts one segment ray from `lift` above its surface towards `target` -- a direction used as given, or with point=True
+        the point O -- and gets the ray's status (RAY_MISS / HIT / CAPPED / END) or, with weight=True, the light weight of
+        render_shaded (diffuse: the diffuse level of an unshadowed cell; shadows=False: no ray is marched) -> (h, w) uint8.
+        stride_bytes > w: the rows are written into a wider buffer (returned whole, untouched bytes are 0xA5).  Capped rays:
+        HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        p = CellMapParams.make(target, step_dist, lift, max_steps, map_flags(point, weight, diffuse, shadows), sampling, ambient)
+        r = _as_rect(rect)
+        w, h = (r.w, r.h) if r is not None else (self.map_w, self.map_h)
+        stride = w if stride_bytes is None else int(stride_bytes)
+        out = np.full((max(h, 0), max(stride, 0)), 0xA5, dtype=np.uint8)
+        _check(lib.hmrm_cell_map(self._h, C.byref(p), C.byref(r) if r is not None else None, _ptr(out), stride),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return out
+
+    def cell_map_device(self, d_ptr: int, stride_bytes: int, target, step_dist, lift=0.0, max_steps=0, point=False, weight=False,
+                        diffuse=False, shadows=True, sampling=NEAREST, ambient=128, rect=None, stream: int = 0):
+        """hmrm_cell_map_device: the same bytes into device memory (no alignment asked), enqueued on `stream` without a host
+        sync; take_capped(stream) reports the capped rays."""
+        self._sync_env()
+        p = CellMapParams.make(target, step_dist, lift, max_steps, map_flags(point, weight, diffuse, shadows), sampling, ambient)
+        r = _as_rect(rect)
+        _check(lib.hmrm_cell_map_device(self._h, C.byref(p), C.byref(r) if r is not None else None, C.c_void_p(d_ptr),
+                                        int(stride_bytes), C.c_void_p(stream)))
 
     def pick(self, cam: Camera, px: int, py: int, allow_capped=False) -> np.ndarray:
         """hmrm_pick: the record (RAY_HIT_DTYPE scalar) of the ray of pixel (px, py) of `cam`."""
@@ -827,6 +898,14 @@ class Config:
     def sun_scope(self) -> int:
         """Additive `sun_scope single|all`: 0 | 1 -- whether shadows / shading also apply to antialiased and recorded frames."""
         return int(lib.hmrm_config_sun_scope(self._h))
+
+    def sun_map_path(self) -> str:
+        """Additive `sun_map <path.png>`: where the CLI writes the whole map's light map (Scene.cell_map with weight=True)."""
+        return lib.hmrm_config_sun_map_path(self._h).decode()
+
+    def sun_map_lift(self) -> float:
+        """Additive `sun_map_lift v`: how far above the surface the rays of that map start."""
+        return float(lib.hmrm_config_sun_map_lift(self._h))
 
     def sun(self) -> Sun:
         """The sun of the additive keys sun_dir, shadow_step_dist (absent: step_dist), shadow_max_steps, shadow_ambient, interior."""

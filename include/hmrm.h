@@ -457,6 +457,63 @@ int hmrm_render_shaded_begin(const hmrm_scene *scene, const hmrm_camera *cam, co
 int hmrm_render_shaded_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun,
                                     uint32_t shade_flags, void *d_rgba, size_t stride_bytes, uint32_t flags, int32_t *ticket);
 
+/* ---------------------------------------------------------------- cell maps */
+/* The lighting model asked of the terrain itself (build-side addition), exact: one byte per map cell -- which cells a sun
+ * reaches and how bright each one is (a light map, a hillshade map, baked lighting), which cells see a point (a viewshed).  It is
+ * the terrain-space counterpart of hmrm_render_lit / hmrm_render_shaded: every cell casts ONE segment ray, made on the device
+ * from the cell index and the threshold table; no ray is read from memory and no record is written.
+ * THE RAY OF CELL (cx, cy), 0 <= cx < W, 0 <= cy < H, gw = grid_width, T the threshold table of p->sampling
+ * (heightmap_buf[i] + min_height for HMRM_NEAREST and HMRM_BILINEAR, the float entry of that table widened to double for
+ * HMRM_NEAREST_F32).  Plain IEEE double operations in this order, no contraction:
+ *   pos.x = ((double)cx + 0.5) * gw
+ *   pos.y = -(((double)cy + 0.5) * gw)
+ *   pos.z = T[cx, cy] + lift
+ *   dir = target                                                      (direction mode)
+ *   dir = (target.x - pos.x, target.y - pos.y, target.z - pos.z)      (HMRM_MAP_TOWARDS_POINT)
+ * The ray is an hmrm_trace_segments ray: step_dist and max_steps from the struct, the struct's sampling mode,
+ * HMRM_TRACE_INTERIOR always on.  Its `status` is the cell's status s.  Nothing is special-cased, as in hmrm_render_lit: a cell
+ * whose origin is not strictly inside the box (T + lift >= max_height, or T + lift <= min_height: a zero-height cell with lift
+ * 0) goes through distance() as written; a sun below the horizon, a zero, infinite or NaN target and step_dist = 0 go through
+ * the same arithmetic.  With lift 0 a ray may hit its own cell's neighbourhood in its first loads: the slope shadowing itself.
+ * THE BYTE OF A CELL.  Without HMRM_MAP_WEIGHT: s, one of HMRM_RAY_MISS, HIT, CAPPED, END.  (Point mode with step_dist = 1/N and
+ * max_steps = N: the ray ends at about O; HIT means hidden from O, END and MISS mean visible.)  With HMRM_MAP_WEIGHT: the
+ * weight w of hmrm_render_shaded.  A cell is SHADOWED when s == HIT -- never with HMRM_MAP_NO_SHADOWS, and then no ray is
+ * marched and step_dist and max_steps are not looked at, nor is lift in direction mode -- and gets w = ambient.  A cell that is not shadowed gets
+ * w = 255 without HMRM_MAP_DIFFUSE, and with it w = ambient + ((255 - ambient) * q + 127) / 255, q the diffuse level above
+ * ("THE LEVEL q"), operation for operation, with s = the cell's `dir` (in point mode the cell's own direction as made above, lift
+ * included); nearest modes: (cx, cy) is the cell; HMRM_BILINEAR: the gradient of the interpolated surface at P = pos.
+ * out[(cy - y0) * stride_bytes + (cx - x0)] is the byte; bytes between rows are not touched.
+ * Refusals (HMRM_E_ARG) before the scene is looked at, in this order: NULL p, an undefined flag bit, reserved != 0, a sampling
+ * outside the enum, DIFFUSE or NO_SHADOWS without WEIGHT, NULL out.  Then: a NULL scene, a rect that is empty, negative or not
+ * inside the map, stride_bytes below the rect's width, a map with a side of 2^24 cells or more with a sampling other than
+ * nearest (as for ray batches).
+ * Capped rays make hmrm_cell_map return HMRM_E_NOTERM with a valid map; END rays never do.  hmrm_cell_map_device reports them
+ * through hmrm_scene_take_capped for its stream -- hmrm_trace_rays_device's contract: no host sync; d_out needs no alignment.
+ * hmrm_cell_map is synchronous on the scene's stream, one such call at a time per scene.  A cell map is not a frame: no
+ * calibration, no probe, not counted towards the probe; hmrm_debug_kernel_choice and every later frame are as they would have
+ * been.  It runs the scene's current kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST);
+ * every kernel writes the same bytes, the literal loop too (HMRM_KERNEL=simple, maps with a side >= 2^24).  The shading
+ * arithmetic is tested at unit world scale only, as for hmrm_render_shaded. */
+#define HMRM_MAP_TOWARDS_POINT 1u  /* target is a point O, not a direction: a viewshed, a point light */
+#define HMRM_MAP_WEIGHT        2u  /* write the light weight w (0..255) instead of the ray's status */
+#define HMRM_MAP_DIFFUSE       4u  /* with WEIGHT: an unshadowed cell gets its diffuse level */
+#define HMRM_MAP_NO_SHADOWS    8u  /* with WEIGHT: march no ray, no cell is shadowed (pure hillshade) */
+typedef struct hmrm_cell_map_params {   /* 56 bytes */
+	double   target[3];  /* direction towards the sun, used as given, NOT normalised; TOWARDS_POINT: the point O */
+	double   step_dist;  /* in units of |dir| */
+	double   lift;       /* the ray starts this far above the cell's surface (an observer's eye height; 0 = on it) */
+	uint32_t max_steps;  /* step limit L of every ray, 0 = none (hmrm_trace_segments' rule) */
+	uint32_t flags;
+	uint8_t  sampling;   /* HMRM_NEAREST | HMRM_BILINEAR | HMRM_NEAREST_F32 */
+	uint8_t  ambient;    /* as hmrm_sun.ambient */
+	uint8_t  reserved[6];/* must be 0 */
+} hmrm_cell_map_params;
+typedef struct hmrm_cell_rect { int32_t x0, y0, w, h; } hmrm_cell_rect;  /* cells [x0, x0+w) x [y0, y0+h) */
+int hmrm_cell_map(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect /* NULL: the map */,
+                  uint8_t *out, size_t stride_bytes);
+int hmrm_cell_map_device(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect,
+                         void *d_out, size_t stride_bytes, void *hip_stream);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -614,7 +671,10 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * hmrm_render_shaded, HMRM_SHADE_DIFFUSE, plus HMRM_SHADE_NO_SHADOWS unless `shadows on`; another value warns "WARNING:
  * Unknown shading: v" and keeps the old one), `sun_scope single|all` (default single: shadows / shading apply to the plain
  * single frame only, as before; all: they also apply with `antialias n` > 1 -- hmrm_render_shaded_aa -- and to `record orbit`
- * -- hmrm_record_orbit_shaded; another value warns "WARNING: Unknown sun_scope: v" and keeps the old one).
+ * -- hmrm_record_orbit_shaded; another value warns "WARNING: Unknown sun_scope: v" and keeps the old one),
+ * `sun_map <path.png>` (echoed like `output`; after its frames the CLI writes the whole map's HMRM_MAP_WEIGHT cell map as a
+ * one-component PNG: the config's sun, the camera's sampling, HMRM_MAP_DIFFUSE with `shading on`, HMRM_MAP_NO_SHADOWS only for
+ * `shading on` without `shadows on`), `sun_map_lift v` (default 0: hmrm_cell_map_params.lift of that map).
  * Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
@@ -638,6 +698,8 @@ int32_t      hmrm_config_interior(const hmrm_config *cfg);      /* additive `int
 int32_t      hmrm_config_shadows(const hmrm_config *cfg);       /* additive `shadows on|off`: 1|0 */
 int32_t      hmrm_config_shading(const hmrm_config *cfg);       /* additive `shading on|off`: 1|0 */
 int32_t      hmrm_config_sun_scope(const hmrm_config *cfg);     /* additive `sun_scope single|all`: 0|1 */
+const char  *hmrm_config_sun_map_path(const hmrm_config *cfg);  /* additive `sun_map <path.png>`: "" = none */
+double       hmrm_config_sun_map_lift(const hmrm_config *cfg);  /* additive `sun_map_lift v` */
 /* The sun of the additive keys: sun_dir, shadow_step_dist (the config's step_dist when the key was absent),
  * shadow_max_steps, shadow_ambient; flags = HMRM_TRACE_INTERIOR when `interior on`. */
 void         hmrm_config_get_sun(const hmrm_config *cfg, hmrm_sun *out);
