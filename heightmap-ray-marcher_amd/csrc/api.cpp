@@ -2446,6 +2446,24 @@ int hmrm_debug_read_records(const hmrm_scene *cs, void *records_out, double *thr
 	return HMRM_OK;
 }
 
+// Test hook (no GPU): the level state byte of frame.hpp unpacked, and the policy's level moves from that level.
+int hmrm_debug_level_state(int32_t level, int32_t young, int32_t min_level, int32_t out[8]) {
+	if (!out || level < 0 || level > hmrm::kMipLevels || min_level < 0 || min_level >= hmrm::kMipLevels)
+		return fail(HMRM_E_ARG, "hmrm_debug_level_state: bad argument");
+	const uint32_t b = (uint32_t)(hmrm::level_state_table() >> (8 * level)) & 0xffu;
+	const int hs = (int)(b & 31u), back = (int)(b >> 5);
+	const int lstep = hmrm::level_step(young ? 0 : -1);
+	out[0] = hs;
+	out[1] = back;
+	out[2] = (back + 1) << hs;
+	out[3] = lstep;
+	out[4] = hmrm::level_coarser(level, lstep);
+	out[5] = hmrm::level_finer(level, lstep, min_level);
+	out[6] = level == min_level ? 1 : 0;
+	out[7] = (int32_t)b;
+	return hmrm::kMipLevels;
+}
+
 // Test hook (no GPU): the calibration's state machine (launch_order.hpp OrderCalibration / KernelChoice) driven through a
 // sequence of full-frame launches of one camera; the measurement of a launch arrives before the next launch.
 int hmrm_debug_calibrate(const uint64_t *records, int32_t launches, int32_t tile_rows, int32_t rot, int32_t may_probe,

@@ -72,7 +72,7 @@ struct DevFrame {
 
 // Window sizes S = 4 * 2^(kLevelStep*l) cells, placed every S/2 cells.  kLevelStep 1 (the build): S = 4, 8, 16, 32,
 // 64, 128, 256 -- a ray moves two levels at a time (4, 16, 64, 256) until it has made a few jumps and then one at a time
-// (march.hpp kAdaptAfter); kLevelStep 2: only S = 4, 16, 64, 256 exist (round 2's pyramid, kept for A/B runs).
+// (kAdaptAfter below); kLevelStep 2: only S = 4, 16, 64, 256 exist (round 2's pyramid, kept for A/B runs).
 #ifndef HMRM_LEVEL_STEP
 #define HMRM_LEVEL_STEP 1
 #endif
@@ -101,6 +101,63 @@ constexpr int win_cells(int l) { return 4 << (kLevelStep * l); }                
 __host__ __device__
 #endif
 constexpr int mip_stride_shift(int l) { return kLevelStep * l + (l < kDenseFrom ? 1 : 0); } // log2(S / strides per window)
+// Level state byte (leap_common.hpp level_state): mip_stride_shift in bits 0-4, win_strides - 1 in bits 5-6.  The whole map,
+// level kMipLevels, is the one window of its plane: shift 28 and 4 strides, a window of 1 << 30 cells that no level treats specially.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr uint32_t level_state_byte(int l) {
+	return l >= kMipLevels ? (28u | (3u << 5)) : ((uint32_t)mip_stride_shift(l) | ((uint32_t)(win_strides(l) - 1) << 5));
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr uint64_t level_state_table() {
+	uint64_t k = 0;
+	for (int l = 0; l <= kMipLevels; ++l) k |= (uint64_t)level_state_byte(l) << (8 * l);
+	return k;
+}
+static_assert(kMipLevels + 1 <= 8 && mip_stride_shift(kMipLevels - 1) < 28, "level state: one byte per level, eight levels");
+// (the sweep: every level's byte against the formulas above, at whatever HMRM_LEVEL_STEP / HMRM_DENSE_FROM this is compiled with)
+constexpr bool level_state_table_ok() {
+	for (int l = 0; l <= kMipLevels; ++l) {
+		const uint32_t b = (uint32_t)(level_state_table() >> (8 * l)) & 0xffu;
+		const int hs = (int)(b & 31u), back = (int)(b >> 5);
+		if (l < kMipLevels && (hs != mip_stride_shift(l) || back + 1 != win_strides(l) || ((back + 1) << hs) != win_cells(l))) return false;
+		if (l == kMipLevels && (hs != 28 || ((back + 1) << hs) != (1 << 30))) return false;
+	}
+	return true;
+}
+static_assert(level_state_table_ok(), "level state bytes disagree with win_strides / win_cells / mip_stride_shift");
+
+// Per-ray adaptive level spacing (pyramids with windows doubling per level, HMRM_LEVEL_STEP=1): a ray moves two
+// levels at a time -- windows of 4, 16, 64, 256 cells, which is what ordinary rays want (fewer level changes) --
+// until it has made more than HMRM_ADAPT_AFTER successful jumps; from then on one level at a time, so that the few
+// long rays skimming the terrain (the launch's tail) can use the 8-, 32- and 128-cell windows in between: where a
+// 16-cell window clears the ray and the 64-cell one does not, the 32-cell one often does and the jump doubles.
+// 0 = off (every ray one level at a time).  Performance only: any level sequence gives the same pixels.
+#ifndef HMRM_ADAPT_AFTER
+#define HMRM_ADAPT_AFTER 8
+#endif
+constexpr int kAdaptAfter = (kLevelStep == 1) ? HMRM_ADAPT_AFTER : 0;
+constexpr bool kAdaptive = kAdaptAfter > 0;
+// The level moves of the policy (march.hpp): levels per move -- two while the ray is young, `young_left` = kAdaptAfter - its
+// jumps so far not negative -- and the targets of a move up and of a move down by `drop` levels, clamped at the coarsest
+// pyramid level and at the frame's finest; the whole map (level kMipLevels) always steps down to the coarsest level.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr int level_step(int young_left) { return kAdaptive ? 2 + (young_left >> 31) : 1; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr int level_coarser(int lev, int lstep) { return lev + lstep > kMipLevels - 1 ? kMipLevels - 1 : lev + lstep; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr int level_finer(int lev, int drop, int minlev) {
+	return lev == kMipLevels ? kMipLevels - 1 : (lev - drop > minlev ? lev - drop : minlev);
+}
 // Element of window (ix, iy) inside a plane (row-major with level 0's pitch; 8 x 4-window tiles per
 // 128-byte line were tried and change nothing, profiles/r02_experiments.txt).
 #if defined(__HIPCC__)

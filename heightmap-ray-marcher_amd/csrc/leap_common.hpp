@@ -16,6 +16,17 @@ __device__ __forceinline__ uint32_t hi32(double v) { return (uint32_t)((unsigned
 __device__ __forceinline__ uint32_t lo32(double v) { return (uint32_t)(unsigned long long)__double_as_longlong(v); }
 __device__ __forceinline__ double f64_from_hi(uint32_t hi) { return __longlong_as_double((long long)((unsigned long long)hi << 32)); }
 
+// Level state: what an attempt reads of its level, one byte per level in a wave-uniform 64-bit constant (frame.hpp
+// level_state_table: the stride shift hs in bits 0-4, the strides to step back above them).  PERM: fetched with one byte
+// permute (selector 0x0c: a zero byte), which holds half the constant in a vector register; else with a 64-bit shift of the
+// constant in scalar registers and a mask -- an instruction more, no register.
+template <bool PERM>
+__device__ __forceinline__ uint32_t level_state(int lev) {
+	constexpr uint64_t k = level_state_table();
+	if constexpr (PERM) return __builtin_amdgcn_perm((uint32_t)(k >> 32), (uint32_t)k, (uint32_t)lev | 0x0c0c0c00u);
+	else return (uint32_t)(k >> (8 * lev)) & 0xffu;
+}
+
 // Cell coordinate q with trunc(q) == trunc(v / grid_width); v is x - c0.x or -(y - c0.y) with
 // c0.x = c0.y = 0.0 (hmap.cpp:968: v - 0.0 == v for every v, so the subtraction is elided).
 //   GWM 0: grid_width == 1.0   -> q = v
@@ -91,9 +102,9 @@ constexpr bool kCross = kStepsLeft && HMRM_CROSS != 0;
 // Exact-stepping state of one coordinate inside its current binade.
 struct Axis {
 	double delta;  // p_{k+1} - p_k for every p of the binade (valid iff key matches)
-	double lim;    // binade boundary the coordinate is moving towards
+	double lim;    // binade boundary the coordinate is moving towards (!kStepsLeft only: not stored otherwise)
 	double rdel;   // ~1/delta (signed); (lim - p) * rdel estimates the steps left
-	uint32_t key;  // sign+exponent bits (hi32 >> 20) the above was measured for
+	uint32_t key;  // sign+exponent bits (hi32 >> 20) the above was measured for (!kStepsLeft only: not stored otherwise)
 	int left;      // kStepsLeft: further steps certain to stay strictly inside the binade; < 0: refresh needed
 };
 
@@ -117,7 +128,7 @@ __device__ __forceinline__ void axis_refresh(Axis &a, double p, double s) {
 	uint32_t moved = (hp ^ hp1) | (hp ^ hp2), dsign = hi32(d) ^ hp;
 	asm("" : "+v"(moved), "+v"(dsign));
 	const int ok = (int)(moved < (1u << 20)) & (int)(e - 128u <= 1772u) & (int)((p2 - p1) == d);
-	a.key = ok ? (hp >> 20) : 0xffffffffu;
+	if (!kStepsLeft) a.key = ok ? (hp >> 20) : 0xffffffffu;
 	a.delta = d;
 	// |p| grows (d has p's sign): the limit is 2^(E+1), else 2^E; either way with p's sign.
 	// One integer add on the high word (E <= 1900, no overflow into the sign).
@@ -125,7 +136,7 @@ __device__ __forceinline__ void axis_refresh(Axis &a, double p, double s) {
 	asm("" : "+v"(lim_hi));
 	const double lim = f64_from_hi(lim_hi);
 	const bool still = d == 0.0;              // the coordinate never moves (s == 0 or absorbed): unlimited room
-	a.lim = still ? p + 1.0 : lim;
+	if (!kStepsLeft) a.lim = still ? p + 1.0 : lim;
 	a.rdel = still ? 0x1p40 : __builtin_amdgcn_rcp(d);
 	if (kStepsLeft) {
 		// steps that stay inside: the estimate (the reciprocal is good to 2^-24: shortened by 2^-22 of itself, so it is

@@ -88,17 +88,7 @@ constexpr int kMinLeap = HMRM_MIN_LEAP; // a jump shorter than this is not worth
 #define HMRM_UP_RATIO (kLevelStep == 2 ? 4.0 : 2.0)
 #endif
 constexpr double kUpRatio = HMRM_UP_RATIO; // see the level policy in k_render_fast
-// Per-ray adaptive level spacing (pyramids with windows doubling per level, HMRM_LEVEL_STEP=1): a ray moves two
-// levels at a time -- windows of 4, 16, 64, 256 cells, which is what ordinary rays want (fewer level changes) --
-// until it has made more than HMRM_ADAPT_AFTER successful jumps; from then on one level at a time, so that the few
-// long rays skimming the terrain (the launch's tail) can use the 8-, 32- and 128-cell windows in between: where a
-// 16-cell window clears the ray and the 64-cell one does not, the 32-cell one often does and the jump doubles.
-// 0 = off (every ray one level at a time).  Performance only: any level sequence gives the same pixels.
-#ifndef HMRM_ADAPT_AFTER
-#define HMRM_ADAPT_AFTER 8
-#endif
-constexpr int kAdaptAfter = (kLevelStep == 1) ? HMRM_ADAPT_AFTER : 0;
-constexpr bool kAdaptive = kAdaptAfter > 0;
+// (per-ray adaptive level spacing, kAdaptAfter: frame.hpp, beside the policy's level moves)
 
 // HMRM_EARLY_LOAD (default 1): order of an attempt -- the pyramid look-up is issued first, refreshes and lateral estimates
 // run while it is in flight (see the attempt block).  0 = refresh first and estimates after the load, for A/B runs.
@@ -241,6 +231,9 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	static_assert(!SEG || !STATS, "segment rules: production kernels only");
 	static_assert(!SEG || !AA || LIT || SHADE, "segment rules: antialiased for the sun-lit frames only");
 	constexpr bool REC = LEAP == 2;                     // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
+	// CARRY: a ray holds its level state in a register (see the leap state below).  The cell maps, the sun shadows, the ray batches
+	// and the shaded record kernels sit on a register granule: a register more would cost them a resident wave per SIMD.
+	constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !RAYS && !(SHADE && REC);
 	constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
 	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
 	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
@@ -326,13 +319,19 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 						lev = (l >= f.min_level && lateral <= (double)((win_strides(l) - 1) << mip_stride_shift(l))) ? l : lev;
 				}
 				if (REC) lev = lev == kTopLevel ? kTopLevel : kRecLevel; // (the record kernel knows the whole-map bound and the record level)
+				// Level state (leap_common.hpp level_state): what an attempt reads of its level besides the number, one word per ray,
+				// made again where lev is assigned -- the first level above, the policy's and the record kernel's choice below.
+				// (CARRY false: the families a register more would cost a wave per SIMD read the same word off lev at the attempt.)
+				uint32_t ls = level_state<CARRY>(lev);
 				int cooldown = 0, fails = 0;
 				unsigned trip_no = 0; // (REC)
-				int jumps = 0; // successful jumps so far (kAdaptive)
+				int young_left = kAdaptAfter; // kAdaptAfter - successful jumps so far (kAdaptive): negative once the ray moves one level at a time
 				Axis ax, ay, az;
-				ax.key = ay.key = az.key = 0xfffffffeu; // never matches: forces the first refresh
 				ax.delta = ay.delta = az.delta = 0.0;
-				ax.lim = ay.lim = az.lim = 0.0;
+				if (!kStepsLeft) { // (the counted scheme neither stores nor reads the two)
+					ax.key = ay.key = az.key = 0xfffffffeu; // never matches: forces the first refresh
+					ax.lim = ay.lim = az.lim = 0.0;
+				}
 				ax.rdel = ay.rdel = az.rdel = 0.0;
 				ax.left = ay.left = az.left = -1; // (kStepsLeft: forces the first refresh)
 				// window choice: step back one half-window when the cell index decreases along the ray
@@ -352,7 +351,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 						// back off do so in step, and on a map that admits no leaps the block is issued once in 64 trips)
 						const bool attempt = REC ? (trip_no & ((1u << fails) - 1u)) == 0u : cooldown == 0;
 						++trip_no;
-						cooldown -= attempt ? 0 : 1;
+						if constexpr (REC) cooldown -= attempt ? 0 : 1;
+						else cooldown = (int)__builtin_elementwise_sub_sat((unsigned)cooldown, 1u); // (never negative: 0 stays, the others count down)
 						if (attempt) {
 							diag.on_attempt();
 							// Order of the block (HMRM_EARLY_LOAD): the window look-up depends on the position and the level only, so
@@ -393,12 +393,12 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							// the one window of the top plane: with hs = 28 every in-grid cell has ix = iy = 0 and the
 							// spans below come out as the map's, so nothing else treats that level specially.
 							// (levels below kDenseFrom: windows every half window, the others every quarter -- frame.hpp)
-							const bool sparse = lev < kDenseFrom;
-							const int hs = top ? 28 : kLevelStep * lev + (sparse ? 1 : 0);
-							const int back = sparse ? 1 : 3; // strides to step back when the cell index falls along the ray
-							int ix = (gx >> hs) - (offx ? back : 0), iy = (gy >> hs) - (offy ? back : 0);
-							ix = ix < 0 ? 0 : ix;
-							iy = iy < 0 ? 0 : iy;
+							const uint32_t lsa = CARRY ? ls : level_state<false>(lev);
+							const int hs = (int)(lsa & 31u);
+							const int back = (int)(lsa >> 5); // strides to step back when the cell index falls along the ray
+							// (a cell inside the grid is not negative: the unsigned difference saturates at window 0)
+							const int ix = (int)__builtin_elementwise_sub_sat((unsigned)(gx >> hs), (unsigned)(offx ? back : 0));
+							const int iy = (int)__builtin_elementwise_sub_sat((unsigned)(gy >> hs), (unsigned)(offy ? back : 0));
 							const unsigned widx = ((unsigned)lev << f.mip_plane_shift) + (unsigned)index_2d(iy, f.mip_row, ix); // (= mip_index)
 							diag.load_begin(f, 17);
 #ifndef HMRM_WIDE_MIP
@@ -426,7 +426,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							const int left_min = min(ax.left, min(ay.left, az.left)); // (kStepsLeft)
 							const int wx0 = ix << hs, wy0 = iy << hs;
 							// (the last windows of a row / column hang over the map's edge: the usable span ends at the edge)
-							const int wcells = top ? (1 << 30) : (4 << (kLevelStep * lev)); // window size S in cells
+							const int wcells = (back + 1) << hs; // window size S in cells: its strides, each 1 << hs cells
 							const int wspan_x = min(wcells, f.map_w - wx0), wspan_y = min(wcells, f.map_h - wy0);
 							// estimates of the steps left before each lateral constraint bites; rdel is signed like
 							// the motion, so every quotient is >= 0.  Only estimates: verified below.
@@ -451,7 +451,12 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							bool z_bound = false, ok = false, can = false, binade_bound = false;
 							int n = 0;
 							const bool cand = inb0 && exact && above;
-							if (__builtin_amdgcn_ballot_w64(cand) != 0ull) {
+							// (the wave asks for `above` alone: the ballot of one compare is the compare's own lane mask, that of the
+							// conjunction a select and a compare more.  A wave whose only lanes above their maximum are no candidates
+							// -- outside the grid: a ray's last trip on its way out; or not exact -- now runs the block for nothing
+							// where it used to skip it.  How often that happens has not been counted: the headline A/B carries it,
+							// DESIGN.md 5.2.  Per lane nothing changes: `can` and `ok` start from `cand`.)
+							if (__builtin_amdgcn_ballot_w64(above) != 0ull) {
 								if (kStepsLeft) {
 									room = room_lat;
 								} else {
@@ -558,17 +563,16 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							//                                        growing pause while attempts keep failing
 							const bool height_limited = inb0 && exact && (!above || z_bound);
 							// levels per move: two while the ray is young (kAdaptive), then one
-							const bool young = kAdaptive && jumps <= kAdaptAfter;
-							const int lstep = kAdaptive ? (young ? 2 : 1) : 1;
-							if (kAdaptive) jumps += ok ? 1 : 0;
-							const int coarser = lev + lstep > kMipLevels - 1 ? kMipLevels - 1 : lev + lstep;
+							const int lstep = level_step(young_left);
+							if (kAdaptive) young_left -= ok ? 1 : 0;
+							const int coarser = level_coarser(lev, lstep);
 							const int minlev = f.min_level;
 #ifndef HMRM_DOWN
 #define HMRM_DOWN 1
 #endif
 							// a failed height test drops HMRM_DOWN levels, a height-limited jump one
 							const int drop = (ok ? 1 : HMRM_DOWN) * lstep;
-							const int finer = top ? kMipLevels - 1 : (lev - drop > minlev ? lev - drop : minlev);
+							const int finer = level_finer(lev, drop, minlev);
 							const bool at_finest = lev == minlev;
 							// (selects, not branches: the three cases are mutually exclusive)
 							const bool crossed = ok && !z_bound;
@@ -581,12 +585,13 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							const int fails_before = fails;
 							lev = hl ? finer : (go_up ? coarser : lev);
 							fails = (crossed | (hl & ok)) ? 0 : fails + (other ? 1 : 0);
-							cooldown = (hl & !ok & at_finest) ? f.finest_pause : (other ? (fails_before < 3 ? fails_before : 3) : 0);
+							const bool hl_fail = hl & !ok, pause_now = hl_fail & at_finest;
+							cooldown = pause_now ? f.finest_pause : (other ? (fails_before < 3 ? fails_before : 3) : 0);
 							// retry one level down without marching; after a jump look at the next window straight
 							// away -- unless the jump stopped at a binade boundary: only real steps cross it,
 							// another attempt here would just fail
 							// (kCross: the jump's last step has crossed it)
-							skip_group = (hl & !ok & !at_finest) | (ok & (kCross | !binade_bound));
+							skip_group = (hl_fail ^ pause_now) | (ok & (kCross | !binade_bound));
 							if constexpr (REC) {
 								// two levels only: the whole map while the ray is above everything, then the record level for good.
 								// A refusal there is followed by a group; refusals in a row thin the attempts out (see `attempt`).
@@ -594,6 +599,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								fails = (ok | top) ? 0 : (fails_before < kRecBackoff ? fails_before + 1 : kRecBackoff);
 								skip_group = (top & hl & !ok) | (ok & (kCross | !binade_bound));
 							}
+							if constexpr (CARRY) ls = level_state<true>(lev);
 						}
 					}
 					diag.on_trip(f, LEAP, skip_group);

@@ -221,6 +221,7 @@ def _load():
         "hmrm_debug_pick_kernel": (C.c_int, [i32, i32, i32, i32, i32, C.POINTER(i32)]),
         "hmrm_debug_calibrate": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "hmrm_debug_mip_layout": (C.c_int, [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "hmrm_debug_level_state": (C.c_int, [i32, i32, i32, C.POINTER(i32)]),
         "hmrm_band_local_rows": (i32, [i32, i32, i32, i32]),
         "hmrm_render_stats": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t, C.POINTER(Stats), vp, vp]),
         "hmrm_render_aa": (C.c_int, [vp, C.POINTER(Camera), i32, vp, C.c_size_t, C.POINTER(Stats)]),
@@ -705,6 +706,16 @@ def mip_layout(map_w: int, map_h: int):
     if rc < 0:
         raise HmrmError(rc, last_error())
     return row.value, shift.value, levels.value, bool(rc)
+
+
+def level_state(level: int, young: bool, min_level: int):
+    """hmrm_debug_level_state (no GPU) -> (dict of the level's unpacked state and the policy's moves from it, pyramid levels)."""
+    out = (C.c_int32 * 8)()
+    rc = lib.hmrm_debug_level_state(int(level), int(bool(young)), int(min_level), out)
+    if rc < 0:
+        raise HmrmError(rc, last_error())
+    keys = ("stride_shift", "back", "cells", "lstep", "coarser", "finer", "at_finest", "byte")
+    return dict(zip(keys, (int(v) for v in out))), int(rc)
 
 
 def pick_kernel(forced=0, use_other=False, records_ok=True, verdict=False, verdict_with_records=False):

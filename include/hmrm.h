@@ -555,6 +555,14 @@ int hmrm_debug_calibrate(const uint64_t *records, int32_t launches, int32_t tile
                          int32_t *group_kernel, int32_t *n_trials, int32_t *best, int32_t *scene_use_group,
                          int32_t *settled_at_launch);
 
+/* Host-only test hook (no GPU, no reference counterpart): what the march kernels read of pyramid level `level` (0 .. levels - 1,
+ * or `levels` = the whole map), unpacked from the per-level byte they fetch it from, and where the level policy moves from
+ * there for a ray that is `young` (non-zero: it moves two levels at a time) in a frame whose finest level is min_level.
+ * out: [0] log2 of the window stride in cells, [1] strides a ray steps back when its cell index falls (strides per window
+ * - 1), [2] window size in cells, [3] levels per move, [4] the level a move up goes to, [5] the level a move down goes to,
+ * [6] 1 when level == min_level, [7] the byte itself.  Returns the number of pyramid levels; negative = HMRM_E_ARG. */
+int hmrm_debug_level_state(int32_t level, int32_t young, int32_t min_level, int32_t out[8]);
+
 /* Accuracy of the hardware reciprocal v_rcp_f64 on the current device (test hook; no reference counterpart:
  * the reference divides, AABB.cpp:62-63, and the kernel's one-division shortcut through distance() must prove
  * from approximate quotients which exact quotient is the result).  mode 0: the leading 32 mantissa bits
