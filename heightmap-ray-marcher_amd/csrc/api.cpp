@@ -113,7 +113,7 @@ using hmrm::kCostRows;
 constexpr int kFrameSlots = 64;  // cached per-frame records (and spherical tables) per stream: a 64-frame orbit fits
 constexpr int kMaxMeasRows = 512;  // tile rows (8192 frame rows) a launch order is calibrated for; taller frames keep the rotation
 constexpr int kProbeAfterFrames = 6; // full frames of never-repeating cameras before the scene's shadow probe
-constexpr int kMaxStreamCtx = 32; // streams a scene keeps launch state for (more: the least recently used one is recycled, with a stream sync)
+constexpr int kMaxStreamCtx = 32; // streams a scene keeps launch state for (more: the least recently used one is recycled, behind a device sync)
 
 // One cached per-frame record: the result of the host set-up (camera.cpp) for one camera, and for
 // spherical cameras its sin/cos tables on the device.  A pure function of (camera, scene params,
@@ -156,9 +156,6 @@ struct StreamCtx {
 	unsigned long long *d_counters = nullptr;
 	bool probe_in_flight = false; // the scene's shadow probe uses this context's calibration records
 	unsigned long long capped_seen = 0; // value of [2] the host has already reported
-	// recorded behind every launch: what a recycled context waits for (the caller's stream handle may be gone by then)
-	hipEvent_t last_launch = nullptr;
-	bool launched = false; // ... has been recorded at least once
 };
 
 // One slot of the asynchronous read-back ring (hmrm_render_begin/_wait/_release): a device frame
@@ -304,12 +301,11 @@ void destroy_ctx(StreamCtx *c) {
 	if (c->d_arena) (void)hipFree(c->d_arena);
 	if (c->h_arena) (void)hipHostFree(c->h_arena);
 	if (c->d_counters) (void)hipFree(c->d_counters);
-	if (c->last_launch) (void)hipEventDestroy(c->last_launch);
 	delete c;
 }
 
 // The launch state of `stream` (created on first use; the least recently used one is dropped, after
-// its last launch has finished, when a scene is driven from more than kMaxStreamCtx streams).
+// the device has drained, when a scene is driven from more than kMaxStreamCtx streams).
 int ctx_for(hmrm_scene *s, hipStream_t stream, StreamCtx **out) {
 	for (StreamCtx *c : s->ctxs)
 		if (c->stream == stream) {
@@ -323,8 +319,9 @@ int ctx_for(hmrm_scene *s, hipStream_t stream, StreamCtx **out) {
 			if (!s->ctxs[i]->scene_owned && (victim == 0 || s->ctxs[i]->stamp < s->ctxs[victim]->stamp)) victim = i;
 		if (victim == 0) return fail(HMRM_E_ARG, "too many streams");
 		// its kernels may still read the tables / counters about to be freed.  The stream belongs to the caller and
-		// may have been destroyed since (no call may name it any more): wait on the context's own event instead
-		(void)hipEventSynchronize(s->ctxs[victim]->last_launch);
+		// may have been destroyed since (no call may name it any more), and nothing is recorded behind a frame for
+		// this rare path to wait on: wait for the device (the hipFrees of destroy_ctx would anyway)
+		(void)hipDeviceSynchronize();
 		if (s->probe_ctx == s->ctxs[victim]) s->probe_ctx = nullptr;
 		if (s->measure_fence_ctx == s->ctxs[victim]) s->measure_fence_ctx = nullptr;
 		destroy_ctx(s->ctxs[victim]);
@@ -337,7 +334,6 @@ int ctx_for(hmrm_scene *s, hipStream_t stream, StreamCtx **out) {
 	for (hipStream_t lane : s->lanes) c->scene_owned = c->scene_owned || (lane && stream == lane);
 	c->stamp = ++s->clock;
 	hipError_t e = hipMalloc((void **)&c->d_counters, 16 * sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipEventCreateWithFlags(&c->last_launch, hipEventDisableTiming);
 	// (zeroed on the scene's stream and waited for: the caller's stream may be anything)
 	if (e == hipSuccess) e = hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), s->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
@@ -551,9 +547,15 @@ int ensure_meas(StreamCtx *c) {
 
 // ---- measured launches: the HIP side of launch_order.hpp's calibration ----
 // Is nothing of the scene running on another of its own streams?  (A measured launch wants the chip to itself.)
+// The scene owns those streams, so it asks them directly: nothing has to be recorded behind a frame for this.
 bool others_idle(hmrm_scene *s, StreamCtx *c) {
-	for (StreamCtx *o : s->ctxs)
-		if (o != c && o->scene_owned && o->launched && hipEventQuery(o->last_launch) != hipSuccess) return false;
+	for (StreamCtx *o : s->ctxs) {
+		if (o == c || !o->scene_owned) continue;
+		const hipError_t e = hipStreamQuery(o->stream);
+		if (e == hipSuccess) continue;
+		if (e == hipErrorNotReady) (void)hipGetLastError(); // (busy is no error: not left behind for the caller's next check)
+		return false;
+	}
 	return true;
 }
 
@@ -742,15 +744,6 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 	return HMRM_OK;
 }
 
-// Behind every launch on a stream other than the scene's own: the event a recycled context waits for (ctx_for) and a measured
-// launch on another of the scene's streams looks at (others_idle).
-int note_launch(hmrm_scene *s, StreamCtx *c) {
-	if (c->scene_owned && c->stream == s->stream) return HMRM_OK;
-	HIP_TRY(hipEventRecord(c->last_launch, c->stream));
-	c->launched = true;
-	return HMRM_OK;
-}
-
 // The kernel launch -- bracketed, when it is a measured one, by the set-up of the records in front of it and their read-back,
 // the record's event and the scene's fence behind it.
 int launch_maybe_measured(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot *slot, hmrm::RowMap &rows_in_order, int tiles_y,
@@ -817,8 +810,7 @@ int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot
 		measure_now = p.measure;
 		if (!measure_now && probe_open && quiet && slot->cal.in_flight < 0 && ++s->choice.unprobed_frames >= (unsigned)kProbeAfterFrames) {
 			hmrm::set_tile_order(&rows_in_order, tiles_y, rot, order.n, order.b, order.c);
-			if ((rc = launch_shadow_probe(s, c, f, rows_in_order, tiles_y, d_out, out_stride_px))) return rc;
-			return note_launch(s, c);
+			return launch_shadow_probe(s, c, f, rows_in_order, tiles_y, d_out, out_stride_px);
 		}
 	}
 	hmrm::set_tile_order(&rows_in_order, tiles_y, rot, order.n, order.b, order.c);
@@ -828,7 +820,7 @@ int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot
 		if (measure_now) slot->cal.drop_in_flight();
 		return rc;
 	}
-	return note_launch(s, c);
+	return HMRM_OK;
 }
 
 // Pyramid layout of a map (DevFrame): windows per level, the common row pitch (level 0's) and the log2 of the
@@ -1085,7 +1077,7 @@ int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg
 		if (seg) HIP_TRY(hmrm::launch_trace_segments(f, s->d_thr, s->d_thr32, s->d_cmap, batch, *seg, c->d_counters, k, s->d_records, c->stream));
 		else HIP_TRY(hmrm::launch_trace_rays(f, s->d_thr, s->d_thr32, s->d_cmap, batch, c->d_counters, k, s->d_records, c->stream));
 	}
-	return note_launch(s, c);
+	return HMRM_OK;
 }
 
 // ---- cell maps (hmrm_cell_map, hmrm_cell_map_device) ----
@@ -1141,7 +1133,7 @@ int launch_cells(hmrm_scene *s, StreamCtx *c, const hmrm_cell_map_params *p, con
 	if ((rc = cameraless_kernel(s, p->sampling, &literal, &k))) return rc;
 	if (literal) HIP_TRY(hmrm::launch_cell_map_literal(f, s->d_thr, d_out, (int64_t)stride_bytes, cells, c->d_counters, c->stream));
 	else HIP_TRY(hmrm::launch_cell_map(f, s->d_thr, s->d_thr32, d_out, (int64_t)stride_bytes, cells, c->d_counters, k, s->d_records, c->stream));
-	return note_launch(s, c);
+	return HMRM_OK;
 }
 
 // The host-memory half of hmrm_trace_rays / hmrm_pick: the records of the scene's staging buffer and the stream's capped-ray

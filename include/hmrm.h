@@ -19,7 +19,8 @@
  * be used from several host threads.  Everything a launch mutates -- spherical tables, counters, the
  * cache of per-frame records -- is kept per HIP stream, so hmrm_render_rows_device calls on different
  * streams run concurrently on the device (a scene keeps that state for the 32 most recently used streams;
- * driving it from more makes every launch wait for the stream whose state it takes over); the host-side
+ * driving it from more makes every launch that takes over another stream's state wait for the DEVICE -- nothing is
+ * recorded behind a frame on a caller's stream, so recycling a stream's state waits for all work on the device); the host-side
  * set-up of a call is serialised per scene.  The
  * entry points that return pixels in host memory (hmrm_render, _stats, _cycle, _multi) use the scene's own
  * stream and scratch frame: one such call at a time per scene.  hmrm_render_begin may be called while
