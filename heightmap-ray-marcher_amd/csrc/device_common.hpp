@@ -124,13 +124,6 @@ __device__ __forceinline__ uint32_t shade_shadowed(uint32_t rgba, uint32_t ambie
 	return r | (g << 8) | (b << 16) | (rgba & 0xff000000u);
 }
 
-// Diffuse sun shading (hmrm_render_shaded, hmrm.h; SHADE in the kernels): what a lane keeps of its primary hit until the
-// epilogue computes its level -- the hit cell for the nearest-cell modes; for the bilinear mode, where no LitState holds the
-// hit point, the point's x and y (plain groups) or its exact cell coordinates (leaps: march.hpp KEEP_P / KEEP_Q).  Empty in
-// every other instantiation, as SegState is.
-template <bool SHADE, bool BILINEAR, bool LIT> struct ShadeState {};
-template <bool LIT> struct ShadeState<true, false, LIT> { unsigned cell = 0u; };
-template <> struct ShadeState<true, true, false> { double px = 0.0, py = 0.0; };
 // The diffuse level q in 0..255 of a surface with the gradient (gx, gy) -- gy along the rows, which grow towards decreasing
 // world y -- under the sun direction s as given: n = (-gx, gy, 1), q = round(255 * clamp(n.s / (|n| |s|), 0, 1)), every
 // operation a plain IEEE double one in the order of hmrm.h, NaN -> 0.  Nothing is special-cased.

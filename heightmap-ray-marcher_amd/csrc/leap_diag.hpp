@@ -20,6 +20,7 @@ struct LoopDiag<false> {
 	__device__ __forceinline__ void on_trip(const DevFrame &, bool, bool) {}
 	__device__ __forceinline__ void on_bounds(bool, bool) {}
 	__device__ __forceinline__ void on_group() {}
+	__device__ __forceinline__ void on_group_done(const DevFrame &, bool) {}
 	__device__ __forceinline__ void load_begin(const DevFrame &, int) {}
 	__device__ __forceinline__ void load_end(const DevFrame &, int, float &) {}
 	__device__ __forceinline__ void load_end(const DevFrame &, int, double &, double &, double &, double &) {}
@@ -143,6 +144,19 @@ struct LoopDiag<true> {
 		}
 	}
 	__device__ __forceinline__ void on_group() { ++groups; }
+	// mode 24: how often does a WAVE run a group block in which a lane hits, and how many lanes hit in it?  (Each such trip of
+	// the production kernel fetched the hit lanes' colour, and waited for it, before round 9 moved the fetch behind the loop.)
+	__device__ __forceinline__ void on_group_done(const DevFrame &f, bool hit) {
+		if (f.diag_mode != 24) return;
+		const unsigned long long act = __ballot(true);
+		const unsigned long long bh = __ballot(hit);
+		if (wave_leader(act)) {
+			x0 += 1u;                     // group blocks run by waves
+			x1 += bh ? 1u : 0u;           // ... in which at least one lane hit
+			x2 += (unsigned)__popcll(bh); // lanes that hit in them
+			x3 += (unsigned)__popcll(act); // lanes in the group blocks
+		}
+	}
 	// modes 17 (pyramid look-up) / 18 (the group's height loads): cycles a wave waits for the data, per pixel
 	// (the wait is forced right after the load: the instrumented kernel then overlaps nothing with it)
 	__device__ __forceinline__ void load_begin(const DevFrame &f, int mode) {

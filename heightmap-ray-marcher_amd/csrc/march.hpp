@@ -200,10 +200,10 @@ __device__ __forceinline__ DevRay cell_ray_of(const CellRules &c, const DevFrame
 // SHADE (instantiated in render_shaded.hip and render_lit_shaded.hip only; hmrm_render_shaded; implies SEG): diffuse sun
 // shading.  An epilogue: a lane whose primary ray hit -- and, LIT, whose shadow ray did not -- computes its diffuse level from
 // the threshold table (device_common.hpp diffuse_level) and keeps a weighted pixel; `sun` brings the direction and the
-// ambient level.  Across the loop it keeps the hit's cell index (nearest-cell modes) or the hit point (bilinear: LitState's,
-// or its cell coordinates): device_common.hpp ShadeState, empty unless SHADE.  (LIT: computing the level at the phase
-// switch instead and carrying it through the shadow march in the saved pixel's alpha byte holds no cell index, but the
-// compiler then keeps more across the march, not less: DESIGN.md 5.12.)
+// ambient level.  Across the loop it keeps the hit's cell index (nearest-cell modes: hcell, which every family keeps for the
+// colour) or the hit point (bilinear: LitState's, or hqx / hqy, which the leap kernels keep for the colour too).  (LIT:
+// computing the level at the phase switch instead and carrying it through the shadow march in the saved pixel's alpha byte
+// holds no cell index, but the compiler then keeps more across the march, not less: DESIGN.md 5.12.)
 // PROJ 5 (instantiated in render_cells.hip only; hmrm_cell_map, frame.hpp CellRules; needs SEG): a cell map.  The "frame" is the
 // rect, a lane owns one map cell, a wave 8 x 8 of them; the lane's ray is made from the cell index and the cell's own entry of
 // `thr` (device_common.hpp cell_ray), enters the loop like a shadow ray (shadow_entry: the interior rule is always on), and the
@@ -223,10 +223,17 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	constexpr bool BILINEAR = SAMP == 1, F32 = SAMP == 2;
 	// KEEP_P: a lane that hit leaves the loop with its hit point in x, y (LIT: and t in z).  SHADE with bilinear sampling wants
 	// the point too; without LIT the plain groups take it that way, the leap kernels keep the hit's exact cell coordinates
-	// instead (KEEP_Q) -- each the cheaper of the two in registers for its family, DESIGN.md 5.12.
-	constexpr bool KEEP_Q = SHADE && BILINEAR && !LIT && LEAP != 0;
+	// instead (KEEP_Q) -- each the cheaper of the two in registers for its family, DESIGN.md 5.12 -- and from them they also
+	// mix the pixel behind the loop (DEFER), shaded or not.
+	constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && LEAP != 0;
 	constexpr bool KEEP_P = LIT || (SHADE && BILINEAR && !KEEP_Q);
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
+	// DEFER: a hit lane's colour is fetched behind the march loop, from the hit cell it leaves the loop with (hcell below; the
+	// bilinear mode: and from the hit point, KEEP_P / KEEP_Q), not inside it.  Two exceptions keep the in-loop form.  The record
+	// kernels of the interior and the shaded frames without shadow rays: two of them sit on the scalar registers' limit and the
+	// epilogue's load costs them a spill slot (profiles/r09_registers.txt).  And the bilinear mode of the plain groups: leaving
+	// the loop with the hit point made that kernel 20 % SLOWER where it was measured (0.263 -> 0.316 ms, profiles/r09_ab.txt).
+	constexpr bool DEFER = !CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0);
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || !STATS, "segment rules: production kernels only");
 	static_assert(!SEG || !AA || LIT || SHADE, "segment rules: antialiased for the sun-lit frames only");
@@ -279,11 +286,24 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 
 		uint32_t rgba = 0;
 		bool real_hit = false;
-		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired, and in which cell)
+		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired)
+		// The cell hmap.cpp:1016 fired in (LIT: for the primary ray).  The one thing a hit lane of the nearest-cell modes carries out
+		// of the march loop: its colour (below the loop: one load for all hit lanes of the wave, where the loop had one, and a wait
+		// for it, in every trip in which any lane hit), SHADE's diffuse level and the ray batches' record are all made from it.
 		unsigned hcell = 0u;
 		LitState<LIT> lt; // (empty unless LIT: device_common.hpp)
-		ShadeState<SHADE, SAMP == 1, LIT> sh; // (empty unless SHADE)
+		double hqx = 0.0, hqy = 0.0; // (bilinear, no LIT: the hit's exact cell coordinates, KEEP_Q, or SHADE's copy of its x and y, KEEP_P)
 		bool again = false; // (LIT: the wave has shadow rays to march)
+		// Bilinear mode, behind the march: the exact cell coordinates of a hit point -- the very expressions the group made its
+		// QX, QY with (the true division for general grid widths; the literal path's division by a power of two is the same
+		// product), so the weights keep their bits -- and the pixel there, with the alpha-0 rule looked up in the hit cell.
+		auto cell_coords_of = [&](double px, double py, double &qx, double &qy) {
+			qx = GWM == 0 ? px : (GWM == 2 ? px / f.grid_width : px * f.inv_grid_width);
+			qy = GWM == 0 ? -py : (GWM == 2 ? -py / f.grid_width : -py * f.inv_grid_width);
+		};
+		auto bilinear_pixel = [&](double qx, double qy) {
+			return shade_hit_bilinear(f, cmap, (int)hcell, bil_setup(qx, qy, f.map_w, f.map_h));
+		};
 
 		do { // (once; LIT: once more with the shadow rays)
 			if (!(d == __builtin_huge_val()) && !(d < 0.0)) { // intersection(), AABB.cpp:33-44
@@ -669,6 +689,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							           : *(const double *)((const char *)thr + (size_t)(cell[j] * 8u)); // hmap.cpp:1013-1014 (+ c0.z)
 					}
 					if constexpr (U == 4) diag.load_end(f, 18, T[0], T[1], T[2], T[3]);
+					const bool hit_before = real_hit; // (diagnostics only)
 					if (budget >= U) {
 						// in order: the first position that leaves the grid (:1006) or hits (:1016) ends the ray
 						int first = U, hit_j = 0;
@@ -699,15 +720,15 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 									qxh = hit_j == j ? QX[j] : qxh;
 									qyh = hit_j == j ? QY[j] : qyh;
 								}
-								if constexpr (!CELLS) // (a cell map has no colours: `cmap` is null)
+								// (DEFER: the colour's five loads, its weights and mixes come behind the loop, bilinear_pixel below)
+								if constexpr (!DEFER && !CELLS) // (a cell map has no colours: `cmap` is null)
 								rgba = shade_hit_bilinear(f, cmap, (int)hit_cell, bil_setup(qxh, qyh, f.map_w, f.map_h));
-								if constexpr (KEEP_Q) { sh.px = qxh; sh.py = qyh; }
-							} else {
-								if constexpr (!CELLS)
-								rgba = shade_hit(f, cmap[hit_cell]);
-								if constexpr (SHADE && LIT) sh.cell = lt.phase ? sh.cell : hit_cell; // (the primary ray's)
-								else if constexpr (SHADE) sh.cell = hit_cell;
+								if constexpr (KEEP_Q) { hqx = qxh; hqy = qyh; }
 							}
+							// (DEFER: no colour here, nothing reads it before the pixel is stored -- see hcell)
+							if constexpr (!DEFER && !BILINEAR && !CELLS) rgba = shade_hit(f, cmap[hit_cell]);
+							if constexpr (LIT) hcell = lt.phase ? hcell : hit_cell; // (the primary ray's)
+							else hcell = hit_cell;
 							real_hit = true;
 							if constexpr (RAYS) {
 								hx = X[0]; hy = Y[0]; hz = Z[0];
@@ -717,7 +738,6 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 									hy = hit_j == j ? Y[j] : hy;
 									hz = hit_j == j ? Z[j] : hz;
 								}
-								hcell = hit_cell;
 							}
 							if constexpr (KEEP_P) {
 								// The shadow ray's origin (P.x, P.y, t): int_point's x and y where :1016 fired and the threshold z was
@@ -756,13 +776,12 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								t = F32 ? (double)thr32[c] : thr[c];
 							}
 							if (zs < t) { // hmap.cpp:1016
-								if constexpr (!CELLS)
-								rgba = BILINEAR ? shade_hit_bilinear(f, cmap, c, b) : shade_hit(f, cmap[c]);
+								if constexpr (!DEFER && !CELLS) rgba = BILINEAR ? shade_hit_bilinear(f, cmap, c, b) : shade_hit(f, cmap[c]);
 								real_hit = true;
-								if constexpr (KEEP_Q) { sh.px = qx; sh.py = qy; }
-								if constexpr (SHADE && !BILINEAR && LIT) sh.cell = lt.phase ? sh.cell : (unsigned)c;
-								else if constexpr (SHADE && !BILINEAR) sh.cell = (unsigned)c;
-								if constexpr (RAYS) { hx = xs; hy = ys; hz = zs; hcell = (unsigned)c; }
+								if constexpr (KEEP_Q) { hqx = qx; hqy = qy; }
+								if constexpr (LIT) hcell = lt.phase ? hcell : (unsigned)c; // (as in the group: the colour comes behind the loop)
+								else hcell = (unsigned)c;
+								if constexpr (RAYS) { hx = xs; hy = ys; hz = zs; }
 								if constexpr (KEEP_P) { x = xs; y = ys; z = t; } // (as above)
 								done = true;
 								break;
@@ -772,6 +791,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							zs += sz;
 						}
 					}
+					diag.on_group_done(f, real_hit && !hit_before);
 					if constexpr (KEEP_P) { // (a lane that hit keeps what the hit left in x, y, z)
 						x = real_hit ? x : X[U - 1] + sx;
 						y = real_hit ? y : Y[U - 1] + sy;
@@ -793,7 +813,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					if (lt.phase == 0) { lt.hx = x; lt.hy = y; lt.t = z; }
 				} else
 				if constexpr (LIT) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
-				else if constexpr (KEEP_P) { sh.px = x; sh.py = y; } // (SHADE, bilinear: the same two, for the gradient at P)
+				else if constexpr (KEEP_P) { hqx = x; hqy = y; } // (SHADE, bilinear: the same two, for the gradient at P)
 			}
 			if constexpr (LIT) {
 				// After the primary rays: the lanes that hit keep their pixel and become their shadow rays -- the ray, its d, its step
@@ -803,6 +823,13 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				again = false;
 				if (lt.phase == 0) {
 					lt.primary_hit = real_hit;
+					if constexpr (BILINEAR && DEFER) { // (the primary pixel, between the two marches: the point is at hand, and LitState::rgba holds it)
+						if (real_hit) {
+							double qxp, qyp;
+							cell_coords_of(lt.hx, lt.hy, qxp, qyp);
+							rgba = bilinear_pixel(qxp, qyp);
+						}
+					}
 					lt.rgba = rgba;
 					if (__builtin_amdgcn_ballot_w64(real_hit) != 0ull) {
 						lt.phase = 1;
@@ -821,25 +848,29 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				}
 			}
 		} while (LIT && again);
+		// The hit lanes' colour: fetched here, once, behind the march (LIT, nearest-cell modes: behind both marches).
+		double qxh = hqx, qyh = hqy; // (bilinear: the hit's cell coordinates, for the colour and SHADE's gradient)
+		if constexpr (BILINEAR && KEEP_P && !LIT) cell_coords_of(hqx, hqy, qxh, qyh);
+		if constexpr (DEFER && !LIT) {
+			if (real_hit) rgba = BILINEAR ? bilinear_pixel(qxh, qyh) : shade_hit(f, cmap[hcell]);
+		}
 		if constexpr (LIT) {
 			if (lt.primary_hit) { // MISS, END and CAPPED shadow rays leave the pixel lit
+				uint32_t lit_rgba = lt.rgba;
+				if constexpr (DEFER && !BILINEAR) lit_rgba = shade_hit(f, cmap[hcell]);
 				if constexpr (SHADE) { // ... at the weight of its diffuse level; a shadowed pixel keeps the ambient weight
 					uint32_t w = sun.ambient;
 					if (!real_hit) {
 						if constexpr (BILINEAR) {
-							const double qxh = GWM == 0 ? lt.hx : (GWM == 2 ? lt.hx / f.grid_width : lt.hx * f.inv_grid_width);
-							const double qyh = GWM == 0 ? -lt.hy : (GWM == 2 ? -lt.hy / f.grid_width : -lt.hy * f.inv_grid_width);
+							cell_coords_of(lt.hx, lt.hy, qxh, qyh);
 							w = shade_weight(sun.ambient, diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), sun.dir));
 						} else {
-							w = shade_weight(sun.ambient, diffuse_level_nearest<F32>(f, thr, sh.cell, sun.dir));
+							w = shade_weight(sun.ambient, diffuse_level_nearest<F32>(f, thr, hcell, sun.dir));
 						}
 					}
-					// (nearest-cell modes: the pixel is made again from the cell index, which is kept anyway, instead of being held
-					// across the shadow march beside it -- one load per hit pixel for one register)
-					if constexpr (BILINEAR) rgba = shade_weighted(lt.rgba, w);
-					else rgba = shade_weighted(shade_hit(f, cmap[sh.cell]), w);
+					rgba = shade_weighted(lit_rgba, w);
 				} else
-				rgba = real_hit ? shade_shadowed(lt.rgba, sun.ambient) : lt.rgba;
+				rgba = real_hit ? shade_shadowed(lit_rgba, sun.ambient) : lit_rgba;
 				real_hit = true;
 			}
 			ray.dz = lt.phase ? lt.dz : ray.dz; // (the primary ray's, for the miss shade)
@@ -847,10 +878,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			if (real_hit) {
 				uint32_t q;
 				if constexpr (BILINEAR) {
-					const double qxh = (KEEP_Q || GWM == 0) ? sh.px : (GWM == 2 ? sh.px / f.grid_width : sh.px * f.inv_grid_width);
-					const double qyh = KEEP_Q ? sh.py : (GWM == 0 ? -sh.py : (GWM == 2 ? -sh.py / f.grid_width : -sh.py * f.inv_grid_width));
 					q = diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), sun.dir);
-				} else q = diffuse_level_nearest<F32>(f, thr, sh.cell, sun.dir);
+				} else q = diffuse_level_nearest<F32>(f, thr, hcell, sun.dir);
 				rgba = shade_weighted(rgba, shade_weight(sun.ambient, q));
 			}
 		}

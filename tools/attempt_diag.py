@@ -1,4 +1,4 @@
-"""Why leap attempts fail and at which pyramid level (instrumented kernel, HMRM_DIAG_ITERS=4..20)."""
+"""Why leap attempts fail and at which pyramid level (instrumented kernel, HMRM_DIAG_ITERS=4..24)."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 hm = importlib.import_module("heightmap-ray-marcher_amd")
@@ -31,6 +31,7 @@ for name in sys.argv[1:] or ["C3", "C5"]:
                          (21, ("jumps limited by the window maximum", "jumps limited otherwise", "steps of the former", "steps of the latter")),
                          (22, ("z-limited jumps L0", "L1", "L2", "L3+")),
                          (23, ("attempts L3-4", "L5-6", "whole map", "steps jumped at whole-map level")),
+                         (24, ("wave trips with a group block", "of them with a hit", "lanes that hit in them", "lanes in the group blocks")),
                          (20, ("groups after a jump to a binade's end", "after an attempt without binade room", "without an attempt", "after other attempts"))):
         os.environ["HMRM_DIAG_ITERS"] = str(mode)
         cam.bg_r = mode  # defeat the frame cache
