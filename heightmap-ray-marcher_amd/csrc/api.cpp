@@ -230,6 +230,8 @@ struct hmrm_scene {
 	size_t limits_cap = 0;
 	uint8_t *d_cells = nullptr; // ... and of hmrm_cell_map: the rect's bytes, rows packed
 	size_t cells_cap = 0;
+	double *d_targets = nullptr; // ... and of hmrm_cell_map_sum's targets (its words go through d_cells)
+	size_t targets_cap = 0;
 	// launch state per stream; `mu` guards the list and the slot choice (launches themselves are
 	// asynchronous), so that threads driving different streams of one scene do not collide
 	std::mutex mu;
@@ -1136,6 +1138,53 @@ int launch_cells(hmrm_scene *s, StreamCtx *c, const hmrm_cell_map_params *p, con
 	return HMRM_OK;
 }
 
+// ---- accumulated cell maps (hmrm_cell_map_sum, hmrm_cell_map_sum_device) ----
+// Needs no scene and no device, in hmrm.h's order: hmrm_cell_map's own refusals first.
+int check_cell_map_sum(const hmrm_cell_map_params *p, const void *targets, int32_t n_targets, const void *out) {
+	if (const int rc = check_cell_map(p, out)) return rc;
+	if (!targets) return fail(HMRM_E_ARG, "cell map sum: NULL targets");
+	if (n_targets < 1 || n_targets > hmrm::kMaxSumTargets) return fail(HMRM_E_ARG, "cell map sum: n_targets must be 1..256");
+	return HMRM_OK;
+}
+
+// ... and what needs the scene's size: the rect (null: the whole map) and the stride of its rows of 16-bit words.
+int check_cell_sum_rect(const hmrm_scene *s, const hmrm_cell_rect *rect, size_t stride_bytes, hmrm_cell_rect *r) {
+	if (const int rc = check_cell_rect(s, rect, (size_t)-1, r)) return rc; // (the rect's own test; the stride's is below)
+	if (stride_bytes < 2 * (size_t)r->w) return fail(HMRM_E_ARG, "cell map sum: stride_bytes is below twice the rect's width");
+	if (stride_bytes & 1u) return fail(HMRM_E_ARG, "cell map sum: stride_bytes must be even");
+	return HMRM_OK;
+}
+
+int ensure_targets(hmrm_scene *s, size_t n) {
+	if (n <= s->targets_cap) return HMRM_OK;
+	if (s->d_targets) (void)hipFree(s->d_targets);
+	s->d_targets = nullptr;
+	s->targets_cap = 0;
+	HIP_TRY(hipMalloc((void **)&s->d_targets, n * 3 * sizeof(double)));
+	s->targets_cap = n;
+	return HMRM_OK;
+}
+
+// One accumulated cell map on the context's stream: launch_cells' recipe with the list of targets beside the rules.
+int launch_cell_sums(hmrm_scene *s, StreamCtx *c, const hmrm_cell_map_params *p, const double *d_targets, int32_t n_targets,
+                     const hmrm_cell_rect &r, uint16_t *d_out, size_t stride_bytes) {
+	hmrm::DevFrame f;
+	int rc = cameraless_frame(s, p->step_dist, p->sampling, &f);
+	if (rc) return rc;
+	f.screen_w = r.w;
+	f.screen_h = r.h;
+	f.projection = 5;
+	const hmrm::CellRules cells{{0.0, 0.0, 0.0}, p->lift, r.x0, r.y0, p->max_steps, p->flags, p->ambient}; // (p->target is not looked at)
+	const hmrm::CellSums sums{d_targets, n_targets};
+	if ((rc = wait_for_measure_fence(s, c))) return rc;
+	bool literal = false;
+	hmrm::FastKernel k;
+	if ((rc = cameraless_kernel(s, p->sampling, &literal, &k))) return rc;
+	if (literal) HIP_TRY(hmrm::launch_cell_map_sum_literal(f, s->d_thr, d_out, (int64_t)stride_bytes, cells, sums, c->d_counters, c->stream));
+	else HIP_TRY(hmrm::launch_cell_map_sum(f, s->d_thr, s->d_thr32, d_out, (int64_t)stride_bytes, cells, sums, c->d_counters, k, s->d_records, c->stream));
+	return HMRM_OK;
+}
+
 // The host-memory half of hmrm_trace_rays / hmrm_pick: the records of the scene's staging buffer and the stream's capped-ray
 // count come back, the stream is drained.  (s->mu held.)
 int finish_batch(hmrm_scene *s, StreamCtx *c, hmrm_ray_hit *hits, int64_t n, hmrm_stats *stats) {
@@ -1300,6 +1349,7 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	if (s->d_hits) (void)hipFree(s->d_hits);
 	if (s->d_limits) (void)hipFree(s->d_limits);
 	if (s->d_cells) (void)hipFree(s->d_cells);
+	if (s->d_targets) (void)hipFree(s->d_targets);
 	if (s->ev0) (void)hipEventDestroy(s->ev0);
 	if (s->ev1) (void)hipEventDestroy(s->ev1);
 	if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -2021,6 +2071,11 @@ int32_t hmrm_config_shading(const hmrm_config *c) { return c->cfg.shading; }
 int32_t hmrm_config_sun_scope(const hmrm_config *c) { return c->cfg.sun_scope; }
 const char *hmrm_config_sun_map_path(const hmrm_config *c) { return c->cfg.sun_map_path.c_str(); }
 double hmrm_config_sun_map_lift(const hmrm_config *c) { return c->cfg.sun_map_lift; }
+const char *hmrm_config_sky_map_path(const hmrm_config *c) { return c->cfg.sky_map_path.c_str(); }
+void hmrm_config_sky_map_rings(const hmrm_config *c, int32_t *rings, int32_t *per_ring) {
+	if (rings) *rings = c->cfg.sky_map_rings;
+	if (per_ring) *per_ring = c->cfg.sky_map_per_ring;
+}
 void hmrm_config_get_sun(const hmrm_config *c, hmrm_sun *out) {
 	const hmrm::Config &g = c->cfg;
 	memset(out, 0, sizeof *out);
@@ -2242,6 +2297,68 @@ int hmrm_cell_map_device(const hmrm_scene *scene, const hmrm_cell_map_params *p,
 	StreamCtx *c = nullptr;
 	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
 	return launch_cells(s, c, p, r, static_cast<uint8_t *>(d_out), stride_bytes);
+}
+
+int hmrm_cell_map_sum(const hmrm_scene *scene, const hmrm_cell_map_params *p, const double *targets, int32_t n_targets,
+                      const hmrm_cell_rect *rect, uint16_t *out, size_t stride_bytes) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	int rc = check_cell_map_sum(p, targets, n_targets, out);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	hmrm_cell_rect r;
+	if ((rc = check_cell_sum_rect(s, rect, stride_bytes, &r))) return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	const size_t row_bytes = 2 * (size_t)r.w;
+	if ((rc = ensure_cells(s, row_bytes * (size_t)r.h))) return rc;
+	if ((rc = ensure_targets(s, (size_t)n_targets))) return rc;
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, s->stream, &c))) return rc;
+	HIP_TRY(hipMemcpyAsync(s->d_targets, targets, (size_t)n_targets * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+	if ((rc = launch_cell_sums(s, c, p, s->d_targets, n_targets, r, reinterpret_cast<uint16_t *>(s->d_cells), row_bytes))) return rc;
+	HIP_TRY(hipMemcpy2DAsync(out, stride_bytes, s->d_cells, row_bytes, row_bytes, (size_t)r.h, hipMemcpyDeviceToHost, s->stream));
+	unsigned long long capped_now = 0;
+	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	const unsigned long long capped = capped_now - c->capped_seen;
+	c->capped_seen = capped_now;
+	return capped ? noterm(capped) : HMRM_OK;
+}
+
+int hmrm_cell_map_sum_device(const hmrm_scene *scene, const hmrm_cell_map_params *p, const void *d_targets, int32_t n_targets,
+                             const hmrm_cell_rect *rect, void *d_out, size_t stride_bytes, void *hip_stream) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	int rc = check_cell_map_sum(p, d_targets, n_targets, d_out);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	hmrm_cell_rect r;
+	if ((rc = check_cell_sum_rect(s, rect, stride_bytes, &r))) return rc;
+	if ((uintptr_t)d_out & 1u) return fail(HMRM_E_ARG, "cell map sum: d_out must be 2-byte aligned");
+	if ((uintptr_t)d_targets & 7u) return fail(HMRM_E_ARG, "cell map sum: d_targets must be 8-byte aligned");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
+	return launch_cell_sums(s, c, p, static_cast<const double *>(d_targets), n_targets, r, static_cast<uint16_t *>(d_out), stride_bytes);
+}
+
+int hmrm_sky_directions(int32_t rings, int32_t per_ring, double *out_xyz) {
+	if (!out_xyz) return fail(HMRM_E_ARG, "sky directions: NULL out_xyz");
+	if (rings < 1 || per_ring < 1 || (int64_t)rings * per_ring > hmrm::kMaxSumTargets)
+		return fail(HMRM_E_ARG, "sky directions: rings * per_ring must be 1..256");
+	const double two_pi = 6.283185307179586476925286766559;
+	for (int32_t i = 0; i < rings; ++i) {
+		const double u = ((double)i + 0.5) / (double)rings;
+		const double z = std::sqrt(u), rad = std::sqrt(1.0 - u);
+		for (int32_t j = 0; j < per_ring; ++j) {
+			const double a = two_pi * ((double)j + 0.5 * (double)(i & 1)) / (double)per_ring;
+			double *o = out_xyz + 3 * ((size_t)i * (size_t)per_ring + (size_t)j);
+			o[0] = rad * std::cos(a);
+			o[1] = rad * std::sin(a);
+			o[2] = z;
+		}
+	}
+	return rings * per_ring;
 }
 
 // Picking: GetRay of one pixel on the device (k_probe, as hmrm_debug_ray) and that ray traced as a batch of one.  Like a

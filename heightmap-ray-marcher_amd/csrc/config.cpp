@@ -16,6 +16,7 @@
 //   shadows on|off, sun_dir x y z, shadow_ambient n, shadow_step_dist v, shadow_max_steps n
 //   shading on|off, sun_scope single|all
 //   sun_map <path.png>, sun_map_lift v                (the whole map's light map, hmrm_cell_map, written by the CLI)
+//   sky_map <path.png>, sky_map_rings r n             (the whole map's sky-view map, hmrm_cell_map_sum, written by the CLI)
 #include "config.hpp"
 
 #include <cmath>
@@ -249,6 +250,17 @@ void shadow_max_steps_key(Config &c, std::istream &in, const char *key, std::str
 	c.log << key << " " << c.shadow_max_steps << "\n";
 }
 
+void sky_map_rings_key(Config &c, std::istream &in, const char *key, std::string *) { // rings x directions per ring of the sky map
+	long long r = 0, n = 0;
+	in >> r >> n;
+	if (!in || r < 1 || n < 1 || r > 256 || n > 256 || r * n > 256) c.warn << "WARNING: sky_map_rings must give 1..256 directions\n";
+	else {
+		c.sky_map_rings = (int)r;
+		c.sky_map_per_ring = (int)n;
+	}
+	c.log << key << " " << c.sky_map_rings << " " << c.sky_map_per_ring << "\n";
+}
+
 struct Row { const char *key; Handler apply; };
 const Row kGrammar[] = {
 	// the reference's 27 keys (main/hmap.cpp:314-488)
@@ -297,6 +309,8 @@ const Row kGrammar[] = {
 	{"shadow_max_steps", shadow_max_steps_key},
 	{"sun_map", scalar<&Config::sun_map_path>},
 	{"sun_map_lift", scalar<&Config::sun_map_lift>},
+	{"sky_map", scalar<&Config::sky_map_path>},
+	{"sky_map_rings", sky_map_rings_key},
 };
 
 } // namespace

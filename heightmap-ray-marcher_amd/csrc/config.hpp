@@ -60,6 +60,10 @@ struct Config {
 	// same sun) there, one byte per cell; `sun_map_lift v` -- how far above the surface its rays start
 	std::string sun_map_path;
 	double sun_map_lift = 0.0;
+	// additive: `sky_map <path.png>` -- the CLI also writes the whole map's sky-view map there (hmrm_cell_map_sum in status mode
+	// over hmrm_sky_directions(r, n), scaled to a byte); `sky_map_rings r n` -- the directions, r * n in 1 .. 256
+	std::string sky_map_path;
+	int sky_map_rings = 4, sky_map_per_ring = 16;
 
 	bool heightmap_dirty = false; // should_update_heightmap, sticky until taken
 	std::ostringstream log;       // what the reference prints to stdout

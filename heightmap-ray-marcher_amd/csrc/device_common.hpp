@@ -212,6 +212,22 @@ __device__ __forceinline__ DevRay cell_ray(const CellRules &c, const DevFrame &f
 __device__ __forceinline__ uint32_t cell_weight(const CellRules &c, bool shadowed, uint32_t q) {
 	return shadowed ? c.ambient : ((c.flags & kMapDiffuse) != 0u ? shade_weight(c.ambient, q) : 255u);
 }
+// Accumulated cell maps (hmrm_cell_map_sum; frame.hpp CellSums): what a lane keeps across its passes; empty in every other
+// instantiation, as SegState is.  `rules` is the launch's CellRules with the current target in place; it and `k` are the same
+// for a whole wave.
+template <bool SUM> struct SumState {};
+template <> struct SumState<true> {
+	CellRules rules;
+	int k = 0;         // the pass = the target's index
+	uint32_t acc = 0;  // v_0 + .. + v_{k-1} (at most 256 * 255) + 2^16 * the passes of this lane that the step cap stopped (at most 256)
+};
+// Target k of the list, for every lane of the wave: the index is made a scalar so that the three doubles are scalar loads.
+__device__ __forceinline__ void sum_target(const CellSums &sums, int k, CellRules *rules) {
+	const double *__restrict__ t = sums.targets + 3 * (size_t)(unsigned)__builtin_amdgcn_readfirstlane(k);
+	rules->target[0] = t[0];
+	rules->target[1] = t[1];
+	rules->target[2] = t[2];
+}
 
 // Relative error of the hardware reciprocal.  MEASURED on gfx950 (tools/rcp_accuracy.py over 1.6e11 inputs: the
 // leading 32 mantissa bits exhaustively in six binades, hashed mantissas / signs / exponents 2^-1000..2^1000, and the

@@ -276,6 +276,17 @@ struct CellRules {
 };
 constexpr uint32_t kMapTowardsPoint = 1u, kMapWeight = 2u, kMapDiffuse = 4u, kMapNoShadows = 8u;
 
+// ---- accumulated cell maps (hmrm_cell_map_sum; PROJ == 5 with SUM in the kernels) ----
+// The cell kernels' march run n times per lane over a list of targets (device memory, n x 3 doubles, the same for every lane:
+// the index is wave-uniform) -- CellRules::target is not looked at, target k takes its place for pass k -- with the lane's
+// values summed in a register and ONE 16-bit word stored at the end: n * 255 <= 65280 for n <= 256.  A sibling of CellRules in
+// the sum kernels' own __global__ entry points: k_cell_map's arguments do not change.
+struct CellSums {
+	const double *targets;
+	int32_t n; // 1 .. 256
+};
+constexpr int kMaxSumTargets = 256;
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

@@ -19,6 +19,7 @@
 // `devices` > 1 stays plain.  `sun_map <path.png>`: after its frames the whole map's light map (hmrm_cell_map with HMRM_MAP_WEIGHT:
 // one byte per cell under the config's sun, the camera's sampling, `sun_map_lift` above the surface; diffuse levels with
 // `shading on`, shadow rays unless `shading on` stands without `shadows on`) is written there as a one-component PNG.
+// `sky_map <path.png>`: after that, the whole map's sky-view map (hmrm_cell_map_sum over `sky_map_rings r n` sky directions).
 #include <sys/stat.h>
 
 #include <cmath>
@@ -79,6 +80,46 @@ static bool write_sun_map(hmrm_config *cfg, hmrm_scene *scene, const hmrm_camera
 		return false;
 	}
 	std::cout << "Saved sun map at " << path << "\n";
+	return true;
+}
+
+// `sky_map <path>`: the whole map's sky-view map -- how many of the K = r * n cosine-weighted sky directions of `sky_map_rings`
+// are open above each cell (hmrm_cell_map_sum in status mode), scaled to a byte.  Returns false when it could not be made or written.
+static bool write_sky_map(hmrm_config *cfg, hmrm_scene *scene, const hmrm_camera &cam) {
+	const std::string path = hmrm_config_sky_map_path(cfg);
+	if (path.empty()) return true;
+	int32_t mw = 0, mh = 0, rings = 0, per_ring = 0;
+	hmrm_config_height_rgb(cfg, &mw, &mh);
+	hmrm_config_sky_map_rings(cfg, &rings, &per_ring);
+	std::vector<double> dirs((size_t)3 * rings * per_ring);
+	const int K = hmrm_sky_directions(rings, per_ring, dirs.data());
+	if (K < 1) {
+		std::cerr << hmrm_last_error() << "\n";
+		return false;
+	}
+	hmrm_sun sun;
+	hmrm_config_get_sun(cfg, &sun);
+	hmrm_cell_map_params p;
+	memset(&p, 0, sizeof p);
+	p.step_dist = sun.step_dist;
+	p.lift = hmrm_config_sun_map_lift(cfg);
+	p.max_steps = sun.max_steps;
+	p.sampling = cam.sampling;
+	p.ambient = sun.ambient;
+	std::vector<uint16_t> counts((size_t)mw * mh);
+	const int rc = hmrm_cell_map_sum(scene, &p, dirs.data(), K, NULL, counts.data(), 2 * (size_t)mw);
+	if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+		std::cerr << hmrm_last_error() << "\n";
+		return false;
+	}
+	if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+	std::vector<uint8_t> map(counts.size());
+	for (size_t i = 0; i < counts.size(); ++i) map[i] = (uint8_t)(((uint32_t)counts[i] * 255u + (uint32_t)K / 2u) / (uint32_t)K);
+	if (hmrm_write_png(path.c_str(), mw, mh, 1, map.data(), (size_t)mw) != HMRM_OK) {
+		std::cerr << "Failed to write sky map to " << path << "\n";
+		return false;
+	}
+	std::cout << "Saved sky map at " << path << "\n";
 	return true;
 }
 
@@ -165,6 +206,7 @@ int main(int argc, char *argv[]) {
 		if (rc != HMRM_OK) std::cerr << hmrm_last_error() << "\n";
 		for (size_t i = 1; i < scenes.size(); ++i) hmrm_scene_destroy(scenes[i]);
 		if (rc == HMRM_OK && !write_sun_map(cfg, scene, cam, shading, shadows)) rc = HMRM_E_IO;
+		if (rc == HMRM_OK && !write_sky_map(cfg, scene, cam)) rc = HMRM_E_IO;
 		hmrm_scene_destroy(scene);
 		hmrm_config_destroy(cfg);
 		return rc == HMRM_OK ? 0 : 1;
@@ -277,6 +319,7 @@ int main(int argc, char *argv[]) {
 	else
 		std::cout << "Saved screenshot at " << path << "\n";
 	if (wrc == HMRM_OK && !write_sun_map(cfg, scene, cam, shading, shadows)) wrc = HMRM_E_IO;
+	if (wrc == HMRM_OK && !write_sky_map(cfg, scene, cam)) wrc = HMRM_E_IO;
 
 	hmrm_scene_destroy(scene);
 	hmrm_config_destroy(cfg);

@@ -1,7 +1,7 @@
 // march.hpp -- the production march for gfx950: render_wave_tile, one wave's 8 x 8 pixels (or 64 batch rays), and its
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
 // render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
-// counterparts (march_lit_aa.hpp) and render_cells.hip, each with a __global__ kernel of its own.
+// counterparts (march_lit_aa.hpp), render_cells.hip and render_cell_sums.hip, each with a __global__ kernel of its own.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
 // the reference loop main/hmap.cpp:978-1058; two bit-preserving restructurings:
@@ -210,13 +210,20 @@ __device__ __forceinline__ DevRay cell_ray_of(const CellRules &c, const DevFrame
 // epilogue stores ONE BYTE -- the ray's status, or the weight of SHADE's arithmetic -- through `out`, which points at bytes then
 // (`out_stride_px` counts bytes).  HMRM_MAP_NO_SHADOWS gives every lane d = inf: the wave skips the loop.  Again `if constexpr`
 // statements beside the others' own; the ray is made again in the epilogue rather than held across the march.
-template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false, bool SHADE = false>
+// SUM (instantiated in render_cell_sums.hip only; hmrm_cell_map_sum, frame.hpp CellSums; needs PROJ 5): an accumulated cell map.
+// LIT's "entry, then the march loop, once more" generalised: the wave runs it once per target of a wave-uniform list, the lane
+// folds each pass's value -- k_cell_map's byte for that target, or 1 for a ray that did not hit -- into a register, and the
+// epilogue stores ONE 16-bit WORD through `out` (`out_stride_px` counts bytes).  Capped rays are counted per pass.
+template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false, bool SHADE = false,
+          bool SUM = false>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
                                                 int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{},
-                                                const SunRules &sun = SunRules{}, const CellRules &cells = CellRules{}) {
+                                                const SunRules &sun = SunRules{}, const CellRules &cells = CellRules{},
+                                                const CellSums &sums = CellSums{}) {
 	constexpr bool CELLS = PROJ == 5;
+	static_assert(!SUM || CELLS, "accumulated cell maps: the cell kernels' march, once per target");
 	static_assert(!CELLS || (SEG && !STATS && !AA && !LIT && !SHADE), "cell maps: segment rays, one byte per cell");
 	static_assert(!LIT || (SEG && PROJ != 4), "sun shadows: frames, under the segment rules");
 	static_assert(!SHADE || (SEG && PROJ != 4), "sun shading: frames, under the segment rules");
@@ -258,11 +265,17 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	unsigned long long my_steps = 0;
 	uint32_t my_hit = 0, my_cap = 0;
 	uint32_t aa_rgba = 0; // (AA: this lane's sample, filtered by the whole wave below)
+	SumState<SUM> sm; // (empty unless SUM: device_common.hpp)
 
 	if (pid.live) {
 		DevRay ray = make_ray<PROJ>(f, pid.px, pid.py);
 		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
 		if constexpr (CELLS) ray = cell_ray_of<SAMP>(cells, f, thr, pid.px, pid.py); // (make_ray<5>'s too)
+		if constexpr (SUM) { // (... towards the list's first target, not CellRules' own)
+			sm.rules = cells;
+			sum_target(sums, 0, &sm.rules);
+			ray = cell_ray_of<SAMP>(sm.rules, f, thr, pid.px, pid.py);
+		}
 		// most rays of a frame never touch the box: prove the miss cheaply where possible (the instrumented
 		// variant reports d, so it takes no shortcut for misses); most of the others get their entry distance
 		// from one division instead of six (slab_classify: the instrumented variant uses that path too, so the
@@ -293,7 +306,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		unsigned hcell = 0u;
 		LitState<LIT> lt; // (empty unless LIT: device_common.hpp)
 		double hqx = 0.0, hqy = 0.0; // (bilinear, no LIT: the hit's exact cell coordinates, KEEP_Q, or SHADE's copy of its x and y, KEEP_P)
-		bool again = false; // (LIT: the wave has shadow rays to march)
+		bool again = false; // (LIT: the wave has shadow rays to march; SUM: targets)
 		// Bilinear mode, behind the march: the exact cell coordinates of a hit point -- the very expressions the group made its
 		// QX, QY with (the true division for general grid widths; the literal path's division by a power of two is the same
 		// product), so the weights keep their bits -- and the pixel there, with the alpha-0 rule looked up in the hit cell.
@@ -305,7 +318,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			return shade_hit_bilinear(f, cmap, (int)hcell, bil_setup(qx, qy, f.map_w, f.map_h));
 		};
 
-		do { // (once; LIT: once more with the shadow rays)
+		do { // (once; LIT: once more with the shadow rays; SUM: once per target)
 			if (!(d == __builtin_huge_val()) && !(d < 0.0)) { // intersection(), AABB.cpp:33-44
 				double x = ray.px + d * ray.dx;
 				double y = ray.py + d * ray.dy;
@@ -847,7 +860,52 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					}
 				}
 			}
-		} while (LIT && again);
+			if constexpr (SUM) {
+				// After a pass: the lane folds the value of this target's ray into its sum -- the very byte k_cell_map's epilogue below
+				// would store for it, or 1 for a ray that did not hit -- and counts the pass if the step cap stopped it (an END ray is
+				// not a capped one).  While targets are left the wave then takes the next one: the cell's ray is made again from the
+				// cell index, as the epilogue makes it, and d, the budget, real_hit and the cap state start over; everything derived
+				// from them is computed again by the next pass.  The target's index is the same for the whole wave.
+				// (The lane's cell is made again per pass from its number in the wave, which goes through an empty statement: what
+				// is made from it -- the cell's position, its threshold, its gradient -- does not depend on the target, and the
+				// compiler would otherwise make all that once, before the first pass, and hold it in vector registers across every
+				// march: 104 instead of 73 of them in the production instantiation.)
+				int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+				asm volatile("" : "+v"(ln));
+				const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, ln);
+				const int spx = me.px, spy = me.py;
+				const bool capped = my_cap != 0u && !sg.ends;
+				sm.acc += capped ? 0x10000u : 0u; // (the sum is below 2^16: the passes the step cap stopped are counted above it)
+				my_cap = 0u;
+				uint32_t v = real_hit ? 0u : 1u;
+				if ((cells.flags & kMapWeight) != 0u) {
+					uint32_t q = 0u;
+					if ((cells.flags & kMapDiffuse) != 0u && !real_hit) { // the level of the cell under its direction towards this target
+						const DevRay own = cell_ray_of<SAMP>(sm.rules, f, thr, spx, spy);
+						const double s[3] = {own.dx, own.dy, own.dz};
+						if constexpr (BILINEAR) {
+							double qxc, qyc;
+							cell_coords_of(own.px, own.py, qxc, qyc);
+							q = diffuse_level_bilinear(f, thr, bil_setup(qxc, qyc, f.map_w, f.map_h), s);
+						} else {
+							q = diffuse_level_nearest<F32>(f, thr, (unsigned)index_2d(cells.y0 + spy, f.map_w, cells.x0 + spx), s);
+						}
+					}
+					v = cell_weight(cells, real_hit, q);
+				}
+				sm.acc += v;
+				++sm.k;
+				again = sm.k < sums.n;
+				if (again) {
+					sum_target(sums, sm.k, &sm.rules);
+					ray = cell_ray_of<SAMP>(sm.rules, f, thr, spx, spy);
+					d = __builtin_huge_val();
+					if ((cells.flags & kMapNoShadows) == 0u) d = shadow_entry(ray, f);
+					sg.budget = segment_budget(seg, 0, f.step_cap, &sg.ends);
+					real_hit = false;
+				}
+			}
+		} while ((LIT || SUM) && again);
 		// The hit lanes' colour: fetched here, once, behind the march (LIT, nearest-cell modes: behind both marches).
 		double qxh = hqx, qyh = hqy; // (bilinear: the hit's cell coordinates, for the colour and SHADE's gradient)
 		if constexpr (BILINEAR && KEEP_P && !LIT) cell_coords_of(hqx, hqy, qxh, qyh);
@@ -893,6 +951,12 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			my_cap = sg.ended ? 0u : my_cap;
 		}
 		// (row and pitch are below 2^31, api.cpp: one 32 x 32 -> 64-bit multiply-add)
+		if constexpr (SUM) { // (one 16-bit store per lane: hmrm.h fixes the alignment at 2 bytes, so a wave's row is not widened further)
+			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave,
+			                                      (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+			uint8_t *row = reinterpret_cast<uint8_t *>(out) + (uint64_t)(uint32_t)me.lrow * (uint64_t)out_stride_px;
+			reinterpret_cast<uint16_t *>(row)[(uint32_t)me.px] = (uint16_t)sm.acc;
+		} else
 		if constexpr (CELLS) {
 			uint32_t v = real_hit ? 1u : (my_cap != 0u ? 2u : (sg.ended ? 3u : 0u)); // HMRM_RAY_*
 			if ((cells.flags & kMapWeight) != 0u) {
@@ -930,6 +994,10 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		store_box_filtered(out, out_stride_px, f.aa_shift, (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), pid.px,
 		                   pid.lrow, pid.live, aa_rgba);
 	else if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, lane, pid.px, pid.lrow, pid.live, aa_rgba);
+	// (SUM: capped rays are counted per ray, up to n per lane -- publish_counters' production path adds one per lane)
+	if constexpr (SUM) {
+		if ((sm.acc >> 16) != 0u) atomicAdd(&st.counters[2], (unsigned long long)(sm.acc >> 16));
+	} else
 	publish_counters<STATS>(st, my_steps, my_hit, my_cap);
 	diag.publish(st, f);
 	return pid.tile_y;

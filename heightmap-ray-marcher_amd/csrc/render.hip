@@ -382,6 +382,44 @@ __global__ __launch_bounds__(kBlockThreads) void k_cell_map_literal(const DevFra
 	out[(int64_t)pid.lrow * stride_bytes + pid.px] = (uint8_t)v;
 }
 
+// A cell of an accumulated cell map (hmrm_cell_map_sum; frame.hpp CellSums): the loop over the targets around the same pass --
+// the cell's ray towards target k through the literal loop, the value k_cell_map_literal would have stored for it (or 1 for a
+// ray that did not hit) added up -- and one 16-bit word at the end.  Every pass publishes its own capped ray.
+__global__ __launch_bounds__(kBlockThreads) void k_cell_map_sum_literal(const DevFrame f, const double *__restrict__ thr,
+                                                                        uint16_t *__restrict__ out, int64_t stride_bytes,
+                                                                        const CellRules cells, const CellSums sums, int tiles_y,
+                                                                        StatsOut st) {
+	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	const int cx = cells.x0 + pid.px, cy = cells.y0 + pid.py;
+	const size_t cell = pid.live ? (size_t)cy * (size_t)f.map_w + (size_t)cx : 0; // (gridx + gridy * W of the lane's cell)
+	uint32_t acc = 0u;
+	for (int k = 0; k < sums.n; ++k) {
+		CellRules rules = cells;
+		rules.target[0] = sums.targets[3 * k];
+		rules.target[1] = sums.targets[3 * k + 1];
+		rules.target[2] = sums.targets[3 * k + 2];
+		LitState<true> lt;
+		DevRay ray{};
+		if (pid.live) ray = cell_ray(rules, f, cx, cy, thr[cell]);
+		const SunRules sun{{ray.dx, ray.dy, ray.dz}, f.step_dist, cells.max_steps, cells.ambient};
+		lt.hx = ray.px; lt.hy = ray.py; lt.t = ray.pz;
+		lt.primary_hit = (cells.flags & kMapNoShadows) == 0u; // (without shadows no lane marches)
+		render_lane_literal<3, false, false, true, 4>(f, pid, thr, nullptr, nullptr, 0, st, RayBatch{},
+		                                              SegRules{nullptr, cells.max_steps, 1u}, sun, &lt);
+		uint32_t v = lt.phase != 1 ? 1u : 0u;
+		if ((cells.flags & kMapWeight) != 0u) {
+			uint32_t q = 0u;
+			if ((cells.flags & kMapDiffuse) != 0u && lt.phase != 1 && pid.live)
+				q = diffuse_level_nearest<false>(f, thr, (unsigned)cell, sun.dir); // (maps hold at most 2^29 cells)
+			v = cell_weight(cells, lt.phase == 1, q);
+		}
+		acc += v;
+	}
+	if (!pid.live) return;
+	*reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(out) + (int64_t)pid.lrow * stride_bytes + 2 * (int64_t)pid.px) = (uint16_t)acc;
+}
+
 // Per-ray parity hook: GetRay + distance() of one pixel -> out[0..2] pos, [3..5] dir, [6] d.
 template <int PROJ>
 __global__ void k_probe(const DevFrame f, int px, int py, double *__restrict__ out) {
@@ -552,6 +590,16 @@ hipError_t launch_cell_map_literal(const DevFrame &f, const double *d_thr, uint8
 	if (g.tiles_y == 0) return g.err;
 	hipLaunchKernelGGL(k_cell_map_literal, g.grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_out, stride_bytes, cells, g.tiles_y,
 	                   StatsOut{d_counters, nullptr, nullptr});
+	return hipGetLastError();
+}
+
+hipError_t launch_cell_map_sum_literal(const DevFrame &f, const double *d_thr, uint16_t *d_out, int64_t stride_bytes,
+                                       const CellRules &cells, const CellSums &sums, unsigned long long *d_counters, hipStream_t stream) {
+	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const LaunchGrid g = tile_grid(f, rows);
+	if (g.tiles_y == 0) return g.err;
+	hipLaunchKernelGGL(k_cell_map_sum_literal, g.grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_out, stride_bytes, cells, sums,
+	                   g.tiles_y, StatsOut{d_counters, nullptr, nullptr});
 	return hipGetLastError();
 }
 

@@ -64,6 +64,15 @@ hipError_t launch_cell_map(const DevFrame &f, const double *d_thr, const float *
                            hipStream_t stream);
 hipError_t launch_cell_map_literal(const DevFrame &f, const double *d_thr, uint8_t *d_out, int64_t stride_bytes, const CellRules &cells,
                                    unsigned long long *d_counters, hipStream_t stream);
+// Accumulated cell maps (hmrm_cell_map_sum; frame.hpp CellSums; render_cell_sums.hip, and the literal loop in render.hip, nearest
+// sampling only): the same launch with the march run once per target of sums.targets (device memory) and one uint16 per cell at
+// (char *)d_out + row * stride_bytes + 2 * column (2-byte aligned); cells.target is not looked at.  d_counters[2] counts CAPPED
+// rays, one per ray: up to sums.n per cell.
+hipError_t launch_cell_map_sum(const DevFrame &f, const double *d_thr, const float *d_thr32, uint16_t *d_out, int64_t stride_bytes,
+                               const CellRules &cells, const CellSums &sums, unsigned long long *d_counters, FastKernel kernel,
+                               const WindowRecord *d_records, hipStream_t stream);
+hipError_t launch_cell_map_sum_literal(const DevFrame &f, const double *d_thr, uint16_t *d_out, int64_t stride_bytes,
+                                       const CellRules &cells, const CellSums &sums, unsigned long long *d_counters, hipStream_t stream);
 // Frames under the interior rule (hmrm_render_interior; render_interior.hip: the production kernels' instantiations with the
 // rule, a translation unit of its own, and the literal loop in render.hip).  Not instrumented, not antialiased, never measured.
 hipError_t launch_render_interior(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,

@@ -231,6 +231,9 @@ def _load():
         "hmrm_trace_segments_device": (C.c_int, [vp, C.POINTER(SegmentParams), vp, vp, C.c_int64, vp, vp]),
         "hmrm_cell_map": (C.c_int, [vp, C.POINTER(CellMapParams), C.POINTER(CellRect), vp, C.c_size_t]),
         "hmrm_cell_map_device": (C.c_int, [vp, C.POINTER(CellMapParams), C.POINTER(CellRect), vp, C.c_size_t, vp]),
+        "hmrm_cell_map_sum": (C.c_int, [vp, C.POINTER(CellMapParams), dp, i32, C.POINTER(CellRect), vp, C.c_size_t]),
+        "hmrm_cell_map_sum_device": (C.c_int, [vp, C.POINTER(CellMapParams), vp, i32, C.POINTER(CellRect), vp, C.c_size_t, vp]),
+        "hmrm_sky_directions": (C.c_int, [i32, i32, dp]),
         "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
@@ -258,6 +261,8 @@ def _load():
         "hmrm_config_sun_scope": (i32, [vp]),
         "hmrm_config_sun_map_path": (C.c_char_p, [vp]),
         "hmrm_config_sun_map_lift": (C.c_double, [vp]),
+        "hmrm_config_sky_map_path": (C.c_char_p, [vp]),
+        "hmrm_config_sky_map_rings": (None, [vp, C.POINTER(i32), C.POINTER(i32)]),
         "hmrm_config_get_sun": (None, [vp, C.POINTER(Sun)]),
         "hmrm_record_orbit_multi": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32]),
@@ -364,6 +369,17 @@ def map_flags(point=False, weight=False, diffuse=False, shadows=True) -> int:
     """hmrm_cell_map_params.flags (HMRM_MAP_*)."""
     return ((MAP_TOWARDS_POINT if point else 0) | (MAP_WEIGHT if weight else 0) | (MAP_DIFFUSE if diffuse else 0)
             | (0 if shadows else MAP_NO_SHADOWS))
+
+
+def sky_directions(rings: int, per_ring: int) -> np.ndarray:
+    """hmrm_sky_directions: rings * per_ring (1 .. 256) cosine-weighted directions of the upper hemisphere -> (K, 3) float64.
+    A plain count over them (Scene.cell_map_sum in status mode) is a sky-view factor.  Host only."""
+    n = int(rings) * int(per_ring)
+    out = np.zeros((max(min(n, 256), 1), 3), dtype=np.float64)
+    rc = lib.hmrm_sky_directions(int(rings), int(per_ring), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc < 0:
+        raise HmrmError(rc, last_error())
+    return out[:rc]
 
 
 def _as_rect(rect):
@@ -648,6 +664,38 @@ class Scene:
         _check(lib.hmrm_cell_map_device(self._h, C.byref(p), C.byref(r) if r is not None else None, C.c_void_p(d_ptr),
                                         int(stride_bytes), C.c_void_p(stream)))
 
+    def cell_map_sum(self, targets, step_dist, lift=0.0, max_steps=0, point=False, weight=False, diffuse=False, shadows=True,
+                     sampling=NEAREST, ambient=128, rect=None, allow_capped=False, stride_bytes=None) -> np.ndarray:
+        """One uint16 per map cell (hmrm_cell_map_sum): cell_map's ray towards each of the K = 1 .. 256 `targets` ((K, 3):
+        directions, or with point=True points) in ONE launch, and the sum of the K values -- with weight=True the bytes
+        cell_map would write, else 1 per target whose ray did not hit (reached by that sun / sky direction, seen by that
+        observer) -> (h, w) uint16.  stride_bytes > 2 * w: the rows are written into a wider buffer (returned whole,
+        untouched words are 0xA5A5).  Capped rays, counted per ray: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        t = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1, 3)
+        p = CellMapParams.make((0.0, 0.0, 0.0), step_dist, lift, max_steps, map_flags(point, weight, diffuse, shadows), sampling, ambient)
+        r = _as_rect(rect)
+        w, h = (r.w, r.h) if r is not None else (self.map_w, self.map_h)
+        stride = 2 * w if stride_bytes is None else int(stride_bytes)
+        out = np.full((max(h, 0), max((stride + 1) // 2, 0)), 0xA5A5, dtype=np.uint16)
+        _check(lib.hmrm_cell_map_sum(self._h, C.byref(p), t.ctypes.data_as(C.POINTER(C.c_double)), len(t),
+                                     C.byref(r) if r is not None else None, _ptr(out), stride),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return out
+
+    def cell_map_sum_device(self, d_ptr: int, stride_bytes: int, d_targets: int, n_targets: int, step_dist, lift=0.0, max_steps=0,
+                            point=False, weight=False, diffuse=False, shadows=True, sampling=NEAREST, ambient=128, rect=None,
+                            stream: int = 0):
+        """hmrm_cell_map_sum_device: the same words into device memory (2-byte aligned), the targets read from device memory
+        (n_targets x 3 float64, 8-byte aligned), enqueued on `stream` without a host sync; take_capped(stream) reports the
+        capped rays."""
+        self._sync_env()
+        p = CellMapParams.make((0.0, 0.0, 0.0), step_dist, lift, max_steps, map_flags(point, weight, diffuse, shadows), sampling, ambient)
+        r = _as_rect(rect)
+        _check(lib.hmrm_cell_map_sum_device(self._h, C.byref(p), C.c_void_p(d_targets), int(n_targets),
+                                            C.byref(r) if r is not None else None, C.c_void_p(d_ptr), int(stride_bytes),
+                                            C.c_void_p(stream)))
+
     def pick(self, cam: Camera, px: int, py: int, allow_capped=False) -> np.ndarray:
         """hmrm_pick: the record (RAY_HIT_DTYPE scalar) of the ray of pixel (px, py) of `cam`."""
         self._sync_env()
@@ -914,6 +962,16 @@ class Config:
     def sun_map_path(self) -> str:
         """Additive `sun_map <path.png>`: where the CLI writes the whole map's light map (Scene.cell_map with weight=True)."""
         return lib.hmrm_config_sun_map_path(self._h).decode()
+
+    def sky_map_path(self) -> str:
+        """Additive `sky_map <path.png>`: where the CLI writes the whole map's sky-view map (Scene.cell_map_sum over sky_directions)."""
+        return lib.hmrm_config_sky_map_path(self._h).decode()
+
+    def sky_map_rings(self):
+        """Additive `sky_map_rings r n`: (rings, per_ring) of that map's sky_directions."""
+        r, n = C.c_int32(0), C.c_int32(0)
+        lib.hmrm_config_sky_map_rings(self._h, C.byref(r), C.byref(n))
+        return int(r.value), int(n.value)
 
     def sun_map_lift(self) -> float:
         """Additive `sun_map_lift v`: how far above the surface the rays of that map start."""

@@ -515,6 +515,41 @@ int hmrm_cell_map(const hmrm_scene *scene, const hmrm_cell_map_params *p, const 
 int hmrm_cell_map_device(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect,
                          void *d_out, size_t stride_bytes, void *hip_stream);
 
+/* ACCUMULATED CELL MAPS: many suns, sky directions or observers in one launch (sun hours, a sky-view factor / ambient
+ * occlusion, a soft shadow from samples on the sun's disc, a cumulative viewshed).  For target k, 0 <= k < n_targets, the ray
+ * of cell (cx, cy) is hmrm_cell_map's ray above with p->target replaced by targets[3k .. 3k+2]; p->flags (HMRM_MAP_TOWARDS_POINT
+ * applies to every target), step_dist, lift, max_steps, sampling and ambient are p's, the interior rule stays always on and
+ * nothing is special-cased (a NaN, infinite or zero target goes through the same arithmetic).  p->target itself is not looked at.
+ * THE VALUE v_k, s_k the ray's status: with HMRM_MAP_WEIGHT exactly the byte hmrm_cell_map would write for target k (ambient
+ * for a shadowed cell, else 255 or HMRM_MAP_DIFFUSE's weight of the level under THIS target's direction, in point mode the
+ * cell's own direction with lift; HMRM_MAP_NO_SHADOWS marches no ray); without it v_k = 1 when s_k != HMRM_RAY_HIT, else 0 --
+ * MISS, END and CAPPED count as reached / visible, the rule that decides SHADOWED everywhere else.
+ * THE WORD OF A CELL: the native uint16 sum of v_0 .. v_{K-1}, K = n_targets in 1 .. 256 (at most 256 * 255 = 65280), at
+ * (char *)out + (cy - y0) * stride_bytes + 2 * (cx - x0); bytes between rows are not touched.  Byte for byte: K = 1 with WEIGHT
+ * is hmrm_cell_map's map widened to 16 bits, any K is the integer sum of K hmrm_cell_map maps, the order of the targets does
+ * not matter.
+ * Refusals (HMRM_E_ARG) before the scene is looked at, in this order: hmrm_cell_map's own, in its order, with `out` for its
+ * out; NULL targets; n_targets outside 1 .. 256.  Then: a NULL scene, the rect, stride_bytes below 2 * w or odd, an odd d_out
+ * address (device entry), the 2^24-side rule.
+ * Capped rays are counted per RAY, so a cell can contribute up to K of them: hmrm_cell_map_sum returns HMRM_E_NOTERM with a
+ * valid map, hmrm_cell_map_sum_device reports them through hmrm_scene_take_capped; END rays never count.  Not a frame:
+ * everything hmrm_cell_map says about the probe, the calibration, the camera cache and hmrm_debug_kernel_choice holds.  The host
+ * entry is synchronous on the scene's stream and stages the targets and the map through scene-owned device buffers that grow
+ * on demand; the device entry does no host sync and reads d_targets on hip_stream. */
+int hmrm_cell_map_sum(const hmrm_scene *scene, const hmrm_cell_map_params *p,
+                      const double *targets /* n_targets x 3, host */, int32_t n_targets,
+                      const hmrm_cell_rect *rect /* NULL: the map */,
+                      uint16_t *out, size_t stride_bytes);
+int hmrm_cell_map_sum_device(const hmrm_scene *scene, const hmrm_cell_map_params *p,
+                             const void *d_targets /* n_targets x 24 bytes, DEVICE, 8-byte aligned */, int32_t n_targets,
+                             const hmrm_cell_rect *rect, void *d_out /* 2-byte aligned */, size_t stride_bytes,
+                             void *hip_stream);
+/* Host only, no GPU: rings * per_ring (1 .. 256 in total) directions of the upper hemisphere, cosine-weighted, so that a plain
+ * count over them (status mode) is a sky-view factor.  Ring i, slot j: u = (i + 0.5) / rings, z = sqrt(u), r = sqrt(1.0 - u),
+ * a = 2 pi (j + 0.5 * (i & 1)) / per_ring, out_xyz[3 * (i * per_ring + j) ..] = (r cos a, r sin a, z), libm's functions.
+ * Returns the count, or HMRM_E_ARG (NULL out_xyz, a count below 1 or a product outside 1 .. 256). */
+int hmrm_sky_directions(int32_t rings, int32_t per_ring, double *out_xyz);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -683,7 +718,12 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * -- hmrm_record_orbit_shaded; another value warns "WARNING: Unknown sun_scope: v" and keeps the old one),
  * `sun_map <path.png>` (echoed like `output`; after its frames the CLI writes the whole map's HMRM_MAP_WEIGHT cell map as a
  * one-component PNG: the config's sun, the camera's sampling, HMRM_MAP_DIFFUSE with `shading on`, HMRM_MAP_NO_SHADOWS only for
- * `shading on` without `shadows on`), `sun_map_lift v` (default 0: hmrm_cell_map_params.lift of that map).
+ * `shading on` without `shadows on`), `sun_map_lift v` (default 0: hmrm_cell_map_params.lift of that map),
+ * `sky_map <path.png>` (echoed like `output`; after its frames and an optional sun_map the CLI writes the whole map's sky-view
+ * map as a one-component PNG: hmrm_cell_map_sum in status mode over hmrm_sky_directions(r, n), K = r * n, with
+ * shadow_step_dist, shadow_max_steps, sun_map_lift and the camera's sampling; byte = (c * 255 + K / 2) / K for count c),
+ * `sky_map_rings r n` (default 4 16; a product outside 1 .. 256 warns "WARNING: sky_map_rings must give 1..256 directions" and
+ * keeps the old value).
  * Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
@@ -709,6 +749,8 @@ int32_t      hmrm_config_shading(const hmrm_config *cfg);       /* additive `sha
 int32_t      hmrm_config_sun_scope(const hmrm_config *cfg);     /* additive `sun_scope single|all`: 0|1 */
 const char  *hmrm_config_sun_map_path(const hmrm_config *cfg);  /* additive `sun_map <path.png>`: "" = none */
 double       hmrm_config_sun_map_lift(const hmrm_config *cfg);  /* additive `sun_map_lift v` */
+const char  *hmrm_config_sky_map_path(const hmrm_config *cfg);  /* additive `sky_map <path.png>`: "" = none */
+void         hmrm_config_sky_map_rings(const hmrm_config *cfg, int32_t *rings, int32_t *per_ring); /* additive `sky_map_rings r n` */
 /* The sun of the additive keys: sun_dir, shadow_step_dist (the config's step_dist when the key was absent),
  * shadow_max_steps, shadow_ambient; flags = HMRM_TRACE_INTERIOR when `interior on`. */
 void         hmrm_config_get_sun(const hmrm_config *cfg, hmrm_sun *out);
