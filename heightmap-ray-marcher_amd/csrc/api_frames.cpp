@@ -1,0 +1,702 @@
+// api_frames.cpp -- the C ABI declared in include/hmrm.h, frame entry points: the synchronous frames, the ticketed ones (the
+// asynchronous read-back ring, frames into device memory through the launch lanes), row strips, one frame over several
+// scenes, and the kernel timing of bench.py.
+#include <algorithm>
+#include <cstring>
+#include <new>
+
+#include "api_internal.hpp"
+#include "host_pool.hpp"
+
+namespace {
+
+thread_local double g_last_kernel_ms = -1.0;
+
+// Antialiasing (hmrm_render_aa, HMRM_AA): factor n in {1, 2, 4, 8} -> *shift = log2 n and *super = the camera of the
+// n x n larger "super frame" the kernel marches (everything else unchanged), which must itself pass check_camera.  Needs
+// no scene and no device: the rejections are testable without a GPU.
+int check_antialias(const hmrm_camera *cam, int32_t factor, hmrm_camera *super, int *shift) {
+	const int sh = factor == 1 ? 0 : factor == 2 ? 1 : factor == 4 ? 2 : factor == 8 ? 3 : -1;
+	if (sh < 0) return fail(HMRM_E_ARG, "antialias factor must be 1, 2, 4 or 8 (got " + std::to_string(factor) + ")");
+	if ((int64_t)cam->width * cam->height * ((int64_t)1 << (2 * sh)) > ((int64_t)1 << 31) / 4)
+		return fail(HMRM_E_ARG, "antialias: the " + std::to_string(factor) + "x super frame has more than 2^29 samples (the reference "
+		                        "indexes the framebuffer with int)");
+	*super = *cam;
+	super->width = cam->width << sh;
+	super->height = cam->height << sh;
+	*shift = sh;
+	return HMRM_OK;
+}
+
+// The antialias factor of a ticketed call's flags (HMRM_AA), refusing bits the ABI does not define.
+int antialias_of_flags(uint32_t flags, int32_t *factor) {
+	if (flags & ~(HMRM_NO_PROBE | HMRM_AA_MASK))
+		return fail(HMRM_E_ARG, "flags: unknown bits (defined: HMRM_NO_PROBE and the antialias factor HMRM_AA(n))");
+	const int32_t n = (int32_t)((flags & HMRM_AA_MASK) >> 8);
+	*factor = n == 0 ? 1 : n;
+	return HMRM_OK;
+}
+
+// hmrm_render's frame into d_out.
+FrameRequest plain_request(uint32_t *d_out, int64_t out_stride_px) {
+	return FrameRequest{d_out, out_stride_px, nullptr, nullptr, false, false, Interior::kNot, nullptr};
+}
+
+// The next lane in turn (lanes are created on first use; call with s->mu held).
+int next_lane(hmrm_scene *s, hipStream_t *out) {
+	const uint32_t i = s->lane_next++ % kLanes;
+	if (!s->lanes[i]) HIP_TRY(hipStreamCreateWithFlags(&s->lanes[i], hipStreamNonBlocking));
+	*out = s->lanes[i];
+	return HMRM_OK;
+}
+
+// What every frame entry point sets up before it launches: the launch state of `stream`, the cached record of `cam` -- the
+// camera the kernel marches: the super camera of an antialiased frame, `aa_shift` the log2 of its factor -- and the row map of
+// the whole frame (strips and bands: the caller puts its own in its place).  Call with s->mu held.
+struct FrameSetup {
+	StreamCtx *c = nullptr;
+	FrameSlot *slot = nullptr;
+	hmrm::DevFrame f;
+	hmrm::RowMap rows;
+};
+int setup_frame(hmrm_scene *s, hipStream_t stream, const hmrm_camera *cam, int aa_shift, FrameSetup *fs) {
+	int rc = ctx_for(s, stream, &fs->c);
+	if (rc) return rc;
+	if ((rc = prepare_frame(s, fs->c, cam, &fs->f, &fs->slot))) return rc;
+	fs->f.aa_shift = aa_shift;
+	fs->rows = hmrm::RowMap{0, cam->height, 0, 0, 1, {}, {}, nullptr};
+	return HMRM_OK;
+}
+
+// A frame in the caller's device memory: rows of whole pixels, the stride in pixels an int.
+int check_device_stride(const hmrm_camera *cam, size_t stride_bytes) {
+	if (stride_bytes < (size_t)cam->width * 4 || (stride_bytes & 3) || stride_bytes / 4 > 0x7fffffffu)
+		return fail(HMRM_E_ARG, "stride_bytes must be >= width*4, a multiple of 4 and below 2^33");
+	return HMRM_OK;
+}
+
+int ensure_frame(hmrm_scene *s, size_t px) {
+	if (px <= s->frame_px) return HMRM_OK;
+	if (s->d_frame) (void)hipFree(s->d_frame);
+	s->d_frame = nullptr;
+	s->frame_px = 0;
+	HIP_TRY(hipMalloc((void **)&s->d_frame, px * sizeof(uint32_t)));
+	s->frame_px = px;
+	return HMRM_OK;
+}
+
+} // namespace
+
+namespace hmrm {
+
+int ensure_stats(hmrm_scene *s, size_t px) {
+	if (px <= s->stats_px) return HMRM_OK;
+	if (s->d_steps) (void)hipFree(s->d_steps);
+	if (s->d_entry) (void)hipFree(s->d_entry);
+	s->d_steps = nullptr;
+	s->d_entry = nullptr;
+	s->stats_px = 0;
+	HIP_TRY(hipMalloc((void **)&s->d_steps, px * sizeof(uint32_t)));
+	HIP_TRY(hipMalloc((void **)&s->d_entry, px * sizeof(double)));
+	s->stats_px = px;
+	return HMRM_OK;
+}
+
+} // namespace hmrm
+
+extern "C" {
+
+// What the synchronous frames differ in.  aa_factor > 1 (hmrm_render_aa): the launch marches the super frame and writes the
+// W x H box-filtered frame (no per-pixel arrays then).
+struct SyncFrame {
+	hmrm_stats *stats;  // hmrm_render_stats' outputs, with want_stats
+	uint32_t *steps_pp;
+	double *entry_d;
+	bool want_stats;
+	int32_t aa_factor;
+	bool interior; // hmrm_render_interior
+	const LitFrame *lit;
+};
+constexpr SyncFrame kPlainSync{nullptr, nullptr, nullptr, false, 1, false, nullptr};
+
+static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes, const SyncFrame &how) {
+	// (locals named as in the device calls below: HIP_TRY quotes its expression in the error text)
+	hmrm_stats *const stats = how.stats;
+	uint32_t *const steps_pp = how.steps_pp;
+	double *const entry_d = how.entry_d;
+	const bool want_stats = how.want_stats;
+	int rc = check_camera(cam);
+	if (rc) return rc;
+	hmrm_camera super;
+	int aa_shift = 0;
+	if ((rc = check_antialias(cam, how.aa_factor, &super, &aa_shift))) return rc;
+	if (!s || !rgba) return fail(HMRM_E_ARG, "NULL argument");
+	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+	if (stride_bytes < W * 4) return fail(HMRM_E_ARG, "stride_bytes < width*4");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	if ((rc = ensure_frame(s, W * H))) return rc;
+	if (want_stats && aa_shift == 0 && (rc = ensure_stats(s, W * H))) return rc;
+	FrameSetup fs;
+	if ((rc = setup_frame(s, s->stream, &super, aa_shift, &fs))) return rc;
+	StreamCtx *const c = fs.c;
+	Interior interior = Interior::kNot; // (decided once per frame where every ray starts at the camera: FrameRequest)
+	if (how.interior) {
+		const hmrm::DevFrame &f = fs.f;
+		const double *o = f.cam;
+		const bool cam_inside = f.c0[0] < o[0] && o[0] < f.c1[0] && f.c1[1] < o[1] && o[1] < f.c0[1] && f.c0[2] < o[2] && o[2] < f.c1[2];
+		interior = (cam->projection == HMRM_ORTHOGRAPHIC || cam_inside) ? Interior::kByKernels : Interior::kHostSawNone;
+	}
+	if (want_stats) {
+		HIP_TRY(hipMemsetAsync(c->d_counters, 0, 2 * sizeof(unsigned long long), s->stream));
+		HIP_TRY(hipMemsetAsync(c->d_counters + 4, 0, 4 * sizeof(unsigned long long), s->stream));
+	}
+	HIP_TRY(hipEventRecord(s->ev0, s->stream));
+	const bool per_pixel = want_stats && aa_shift == 0; // (per-pixel arrays are of the plain frame only)
+	const FrameRequest req{s->d_frame, (int64_t)W, per_pixel ? s->d_steps : nullptr, per_pixel ? s->d_entry : nullptr, want_stats, false,
+	                       interior, how.lit};
+	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req))) return rc;
+	HIP_TRY(hipEventRecord(s->ev1, s->stream));
+	HIP_TRY(hipMemcpy2DAsync(rgba, stride_bytes, s->d_frame, W * 4, W * 4, H, hipMemcpyDeviceToHost,
+	                         s->stream));
+	unsigned long long counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	HIP_TRY(hipMemcpyAsync(counters, c->d_counters, sizeof counters, hipMemcpyDeviceToHost, s->stream));
+	if (per_pixel && steps_pp)
+		HIP_TRY(hipMemcpyAsync(steps_pp, s->d_steps, W * H * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+	if (per_pixel && entry_d)
+		HIP_TRY(hipMemcpyAsync(entry_d, s->d_entry, W * H * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	float ms = 0.f;
+	HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+	g_last_kernel_ms = ms;
+	const unsigned long long capped = new_capped(c, counters[2]);
+	if (stats) {
+		stats->rays = (uint64_t)super.width * (uint64_t)super.height;
+		stats->steps = counters[0];
+		stats->hits = counters[1];
+		stats->capped = capped;
+		stats->leap_attempts = counters[4];
+		stats->leaps = counters[5];
+		stats->groups = counters[6];
+		stats->leaped_steps = counters[7];
+	}
+	return noterm(capped);
+}
+
+int hmrm_render(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes) {
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, kPlainSync);
+}
+
+// Progressive refresh of the reference's frame driver (hmap.cpp:976-983): only pixels
+// p = cycle, cycle + cycle_period, ... (p = x + y*width) of the caller's framebuffer are
+// rewritten, the rest keeps what earlier frames left there.  The whole frame is rendered on
+// the device (sub-millisecond) and the selected pixels are merged on the host.
+int hmrm_render_cycle(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes,
+                      int32_t cycle, int32_t cycle_period) {
+	if (cycle_period <= 0 || cycle < 0 || cycle >= cycle_period) return fail(HMRM_E_ARG, "need 0 <= cycle < cycle_period");
+	int rc = check_camera(cam);
+	if (rc) return rc;
+	if (!rgba) return fail(HMRM_E_ARG, "NULL argument");
+	if (stride_bytes < (size_t)cam->width * 4) return fail(HMRM_E_ARG, "stride_bytes < width*4");
+	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+	std::vector<uint8_t> full(W * H * 4);
+	rc = hmrm_render(scene, cam, full.data(), W * 4);
+	if (rc != HMRM_OK && rc != HMRM_E_NOTERM) return rc;
+	for (size_t p = (size_t)cycle; p < W * H; p += (size_t)cycle_period) {
+		const size_t x = p % W, y = p / W; // hmap.cpp:982-983
+		memcpy(rgba + y * stride_bytes + x * 4, &full[p * 4], 4);
+	}
+	return rc;
+}
+
+int hmrm_render_aa(const hmrm_scene *scene, const hmrm_camera *cam, int32_t factor, uint8_t *rgba, size_t stride_bytes,
+                   hmrm_stats *stats) {
+	SyncFrame how = kPlainSync;
+	how.stats = stats;
+	how.want_stats = stats != nullptr;
+	how.aa_factor = factor;
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, how);
+}
+
+int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes) {
+	SyncFrame how = kPlainSync;
+	how.interior = true;
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, how);
+}
+
+// Sun shadows: hmrm_render's frame (hmrm_render_interior's with HMRM_TRACE_INTERIOR), the hit pixels' shadow rays marched
+// by the same launch.  The sun is checked before anything else is looked at (check_sun: hmrm_render_lit's three refusals,
+// hmrm_render_shaded's too).
+static int check_sun(const hmrm_sun *sun) {
+	if (!sun) return fail(HMRM_E_ARG, "NULL sun");
+	if (sun->flags & ~HMRM_TRACE_INTERIOR) return fail(HMRM_E_ARG, "hmrm_sun.flags: undefined bit");
+	for (uint8_t r : sun->reserved)
+		if (r) return fail(HMRM_E_ARG, "hmrm_sun.reserved must be 0");
+	return HMRM_OK;
+}
+static LitFrame make_lit_frame(const hmrm_sun *sun, uint32_t shade_flags) {
+	return LitFrame{hmrm::SunRules{{sun->dir[0], sun->dir[1], sun->dir[2]}, sun->step_dist, sun->max_steps, sun->ambient},
+	                (sun->flags & HMRM_TRACE_INTERIOR) != 0u, shade_flags};
+}
+static int render_lit_common(const hmrm_scene *scene, const hmrm_camera *cam, const LitFrame *lit, int32_t factor, uint8_t *rgba,
+                             size_t stride_bytes) {
+	SyncFrame how = kPlainSync;
+	how.aa_factor = factor;
+	how.lit = lit;
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, how);
+}
+int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint8_t *rgba, size_t stride_bytes) {
+	if (const int rc = check_sun(sun)) return rc;
+	const LitFrame lit = make_lit_frame(sun, 0u);
+	return render_lit_common(scene, cam, &lit, 1, rgba, stride_bytes);
+}
+
+// hmrm_render_lit's three refusals and hmrm_render_shaded's own, in the header's order.
+static int check_shaded(const hmrm_sun *sun, uint32_t shade_flags) {
+	if (const int rc = check_sun(sun)) return rc;
+	if (shade_flags & ~(HMRM_SHADE_DIFFUSE | HMRM_SHADE_NO_SHADOWS)) return fail(HMRM_E_ARG, "shade_flags: undefined bit");
+	return HMRM_OK;
+}
+
+// Diffuse sun shading: the lit frame whose hit pixels are weighted by their diffuse level, with or without the shadow rays.
+// shade_flags = 0 is hmrm_render_lit itself, launch for launch.
+int hmrm_render_shaded(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags, uint8_t *rgba,
+                       size_t stride_bytes) {
+	if (const int rc = check_shaded(sun, shade_flags)) return rc;
+	const LitFrame lit = make_lit_frame(sun, shade_flags);
+	return render_lit_common(scene, cam, &lit, 1, rgba, stride_bytes);
+}
+
+// The antialiased lit frame: hmrm_render_shaded's of the super camera, box-filtered in the launch.  Factor 1 is
+// hmrm_render_shaded, launch for launch.
+int hmrm_render_shaded_aa(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags, int32_t factor,
+                          uint8_t *rgba, size_t stride_bytes) {
+	if (const int rc = check_shaded(sun, shade_flags)) return rc;
+	const LitFrame lit = make_lit_frame(sun, shade_flags);
+	return render_lit_common(scene, cam, &lit, factor, rgba, stride_bytes);
+}
+
+int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
+                      size_t stride_bytes, hmrm_stats *stats, uint32_t *steps_per_pixel, double *entry_d) {
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes,
+	                     SyncFrame{stats, steps_per_pixel, entry_d, true, 1, false, nullptr});
+}
+
+int hmrm_render_rows_device(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba,
+                            size_t stride_bytes, int32_t row_begin, int32_t row_end, int32_t band_rows,
+                            int32_t band_index, int32_t band_count, void *hip_stream) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	int rc = check_camera(cam);
+	if (rc) return rc;
+	if (!s || !d_rgba) return fail(HMRM_E_ARG, "NULL argument");
+	if ((rc = check_device_stride(cam, stride_bytes))) return rc;
+	hmrm::RowMap rows{};
+	if (band_rows > 0) {
+		if (band_count <= 0 || band_index < 0 || band_index >= band_count)
+			return fail(HMRM_E_ARG, "bad band_index/band_count");
+		// bands band_index, band_index+band_count, ... packed back to back; a trailing
+		// partial band still occupies band_rows rows of the strip (its tail is not written)
+		const int64_t local = hmrm_band_local_rows(cam->height, band_rows, band_index, band_count);
+		rows.row_begin = 0;
+		rows.local_rows = (int32_t)local;
+		rows.band_rows = band_rows;
+		rows.band_index = band_index;
+		rows.band_count = band_count;
+	} else {
+		if (row_begin < 0 || row_end > cam->height || row_begin > row_end)
+			return fail(HMRM_E_ARG, "bad row range");
+		rows.row_begin = row_begin;
+		rows.local_rows = row_end - row_begin;
+		rows.band_rows = 0;
+		rows.band_index = 0;
+		rows.band_count = 1;
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	FrameSetup fs;
+	if ((rc = setup_frame(s, (hipStream_t)hip_stream, cam, 0, &fs))) return rc;
+	return launch_frame(s, fs.c, fs.f, fs.slot, rows, plain_request((uint32_t *)d_rgba, (int64_t)(stride_bytes / 4)));
+}
+
+// One frame over several scenes -- one per GPU, same maps (BASELINE config C4's sharding):
+// scene i renders the cyclic 16-row bands i, i+n, ... into a strip on its own device and the strip crosses
+// its own PCIe link; no exchange between devices (a gather to one GPU first would funnel every byte through
+// that GPU's link).  Three passes so that no device ever waits for another one's copy:
+//   1. every scene's kernel is launched (asynchronous);
+//   2. every scene's device-to-host copy is enqueued behind its kernel.  A copy into PAGEABLE host memory is staged
+//      by the runtime and blocks the calling thread until it is done -- device i+1's copy would start after device
+//      i's had finished -- so the copies go to the caller's frame directly only when that memory is pinned (the
+//      caller registered it, hipHostRegister, or got it from hipHostMalloc), else to a pinned staging strip the
+//      scene owns;
+//   3. scenes are waited for in order and staged strips are copied into the caller's rows by the host pool while
+//      the later devices' copies are still in flight.
+int hmrm_render_multi(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *cam, uint8_t *rgba,
+                      size_t stride_bytes) {
+	int rc = check_camera(cam);
+	if (rc) return rc;
+	if (!scenes || n_scenes <= 0 || !rgba) return fail(HMRM_E_ARG, "NULL argument");
+	const size_t W = (size_t)cam->width;
+	const int H = cam->height;
+	if (stride_bytes < W * 4) return fail(HMRM_E_ARG, "stride_bytes < width*4");
+	constexpr int kBand = 16;
+	const int n = std::min<int>(n_scenes, (H + kBand - 1) / kBand);
+	for (int i = 0; i < n; ++i)
+		if (!scenes[i]) return fail(HMRM_E_ARG, "NULL scene");
+	// is the caller's frame pinned?  (an address the runtime does not know is ordinary pageable memory: the query
+	// fails with hipErrorInvalidValue, which is not an error of this call)
+	bool pinned_dst = false;
+	{
+		// (first AND last byte: a frame only partly inside a registered block would send the later bands' copies
+		// through the runtime's staging, which blocks the calling thread per band)
+		hipPointerAttribute_t attr{}, attr_end{};
+		const uint8_t *last = rgba + (size_t)(H - 1) * stride_bytes + W * 4 - 1;
+		if (hipPointerGetAttributes(&attr, rgba) == hipSuccess && hipPointerGetAttributes(&attr_end, last) == hipSuccess)
+			pinned_dst = attr.type == hipMemoryTypeHost && attr_end.type == hipMemoryTypeHost;
+		else (void)hipGetLastError();
+	}
+	int launched = 0; // scenes with work in flight: drained before an error return (the caller may free `rgba` at once)
+	auto drain = [&](int rc_keep) -> int {
+		const std::string keep = g_error;
+		for (int j = 0; j < launched; ++j)
+			if (hipSetDevice(scenes[j]->device) == hipSuccess) (void)hipStreamSynchronize(scenes[j]->stream);
+		g_error = keep;
+		return rc_keep;
+	};
+	auto launch = [&](int i) -> int {
+		hmrm_scene *s = scenes[i];
+		HIP_TRY(hipSetDevice(s->device));
+		std::lock_guard<std::mutex> lk(s->mu);
+		const int32_t local = hmrm_band_local_rows(H, kBand, i, n);
+		int rc2;
+		if ((rc2 = ensure_frame(s, W * (size_t)local))) return rc2;
+		if (!pinned_dst && s->h_stage_bytes < W * 4 * (size_t)local) {
+			if (s->h_stage) (void)hipHostFree(s->h_stage);
+			s->h_stage = nullptr;
+			s->h_stage_bytes = 0;
+			HIP_TRY(hipHostMalloc((void **)&s->h_stage, W * 4 * (size_t)local, hipHostMallocDefault));
+			s->h_stage_bytes = W * 4 * (size_t)local;
+		}
+		FrameSetup fs;
+		if ((rc2 = setup_frame(s, s->stream, cam, 0, &fs))) return rc2;
+		hmrm::RowMap rows{0, local, kBand, i, n, {}, {}, nullptr};
+		return launch_frame(s, fs.c, fs.f, fs.slot, rows, plain_request(s->d_frame, (int64_t)W));
+	};
+	auto enqueue_copy = [&](int i) -> int {
+		hmrm_scene *s = scenes[i];
+		HIP_TRY(hipSetDevice(s->device));
+		const int32_t local = hmrm_band_local_rows(H, kBand, i, n);
+		if (!pinned_dst) { // the whole strip in one transfer
+			HIP_TRY(hipMemcpyAsync(s->h_stage, s->d_frame, W * 4 * (size_t)local, hipMemcpyDeviceToHost, s->stream));
+			return HMRM_OK;
+		}
+		// band b of this scene's strip is frame rows [(i + b*n) * kBand, ...): contiguous in both
+		for (int b = 0; (i + b * n) * kBand < H; ++b) {
+			const int row0 = (i + b * n) * kBand, nrows = std::min(kBand, H - row0);
+			HIP_TRY(hipMemcpy2DAsync(rgba + (size_t)row0 * stride_bytes, stride_bytes,
+			                         s->d_frame + (size_t)b * kBand * W, W * 4, W * 4, (size_t)nrows,
+			                         hipMemcpyDeviceToHost, s->stream));
+		}
+		return HMRM_OK;
+	};
+	for (int i = 0; i < n; ++i) {
+		rc = launch(i);
+		launched = i + 1; // (a failed launch may still have enqueued a table upload)
+		if (rc != HMRM_OK) return drain(rc);
+	}
+	for (int i = 0; i < n; ++i)
+		if ((rc = enqueue_copy(i)) != HMRM_OK) return drain(rc);
+	unsigned long long capped = 0;
+	for (int i = 0; i < n; ++i) {
+		hmrm_scene *s = scenes[i];
+		hipError_t e = hipSetDevice(s->device);
+		if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+		if (e != hipSuccess) return drain(fail(HMRM_E_DEVICE, std::string("hmrm_render_multi: ") + hipGetErrorString(e)));
+		if (!pinned_dst) {
+			const int bands = (H - i * kBand + n * kBand - 1) / (n * kBand); // bands i, i+n, .. below H
+			const uint8_t *src = s->h_stage;
+			hmrm::parallel_ranges(bands, 4, [&](int b0, int b1) {
+				for (int b = b0; b < b1; ++b) {
+					const int row0 = (i + b * n) * kBand, nrows = std::min(kBand, H - row0);
+					for (int r = 0; r < nrows; ++r)
+						memcpy(rgba + (size_t)(row0 + r) * stride_bytes, src + ((size_t)b * kBand + (size_t)r) * W * 4, W * 4);
+				}
+			});
+		}
+		std::lock_guard<std::mutex> lk(s->mu);
+		StreamCtx *c = nullptr;
+		if ((rc = ctx_for(s, s->stream, &c))) return drain(rc);
+		unsigned long long here = 0;
+		if ((rc = take_capped(c, &here))) return drain(rc);
+		capped += here;
+	}
+	return noterm(capped);
+}
+
+int hmrm_scene_take_capped(const hmrm_scene *scene, void *hip_stream, uint64_t *capped) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	if (!s || !capped) return fail(HMRM_E_ARG, "NULL argument");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	*capped = 0;
+	for (StreamCtx *c : s->ctxs)
+		if (c->stream == (hipStream_t)hip_stream) {
+			HIP_TRY(hipStreamSynchronize(c->stream));
+			unsigned long long n = 0;
+			const int rc = take_capped(c, &n);
+			if (rc) return rc;
+			*capped = n;
+			return noterm(n);
+		}
+	return HMRM_OK; // nothing was ever launched on that stream
+}
+
+// ---- asynchronous frames: kernel k+1 runs while frame k crosses PCIe (the reference's counterpart is
+// the blit of the finished framebuffer, SDL_UpdateTexture, hmap.cpp:1082) ----
+int hmrm_render_begin(const hmrm_scene *scene, const hmrm_camera *cam, int32_t *ticket) {
+	return hmrm_render_begin_flags(scene, cam, 0u, ticket);
+}
+
+// What both ticketed begins refuse first, in this order: the camera, the flags and their antialias factor (-> the super camera
+// and the log2 of the factor), NULL arguments (`have_target`: the device begin's d_rgba is there).  *ticket is -1 from then on.
+static int check_begin(const hmrm_scene *s, const hmrm_camera *cam, uint32_t flags, bool have_target, int32_t *ticket, hmrm_camera *super,
+                       int *aa_shift) {
+	int rc = check_camera(cam);
+	if (rc) return rc;
+	int32_t aa_factor = 1;
+	if ((rc = antialias_of_flags(flags, &aa_factor)) || (rc = check_antialias(cam, aa_factor, super, aa_shift))) return rc;
+	if (!s || !have_target || !ticket) return fail(HMRM_E_ARG, "NULL argument");
+	*ticket = -1;
+	return HMRM_OK;
+}
+// The request of a ticketed frame: never instrumented, never interior; HMRM_NO_PROBE from the flags.
+static FrameRequest ticket_request(uint32_t *d_out, int64_t out_stride_px, uint32_t flags, const LitFrame *lit) {
+	return FrameRequest{d_out, out_stride_px, nullptr, nullptr, false, (flags & HMRM_NO_PROBE) != 0, Interior::kNot, lit};
+}
+
+// `lit` (hmrm_render_shaded_begin): the ticket's frame is a lit one -- launched the way a lit frame is (launch_frame), on the lane.
+static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket, const LitFrame *lit) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	hmrm_camera super;
+	int aa_shift = 0;
+	int rc = check_begin(s, cam, flags, true, ticket, &super, &aa_shift);
+	if (rc) return rc;
+	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	int idx = -1;
+	for (size_t i = 0; i < s->ring.size(); ++i)
+		if (!s->ring[i]->busy) {
+			idx = (int)i;
+			break;
+		}
+	if (idx < 0) {
+		if ((int)s->ring.size() >= kMaxRing) return fail(HMRM_E_ARG, "hmrm_render_begin: every frame of the ring is in use (release one)");
+		RingFrame *r = new (std::nothrow) RingFrame();
+		if (!r) return fail(HMRM_E_ARG, "out of memory");
+		// (complete before it joins the ring: a half-made slot would be picked up as free by the next call)
+		hipError_t e = hipEventCreateWithFlags(&r->kernel_done, hipEventDisableTiming);
+		if (e == hipSuccess) e = hipEventCreateWithFlags(&r->copy_done, hipEventDisableTiming);
+		if (e == hipSuccess) e = hipHostMalloc((void **)&r->h_capped, sizeof(unsigned long long), hipHostMallocDefault);
+		if (e != hipSuccess) {
+			if (r->kernel_done) (void)hipEventDestroy(r->kernel_done);
+			if (r->copy_done) (void)hipEventDestroy(r->copy_done);
+			if (r->h_capped) (void)hipHostFree(r->h_capped);
+			delete r;
+			return fail(HMRM_E_DEVICE, std::string("hmrm_render_begin: ") + hipGetErrorString(e));
+		}
+		s->ring.push_back(r);
+		idx = (int)s->ring.size() - 1;
+	}
+	RingFrame *r = s->ring[(size_t)idx];
+	if (W * H > r->px) {
+		// (the slot is free: nothing in flight touches its buffers)
+		if (r->d_frame) (void)hipFree(r->d_frame);
+		if (r->h_frame) (void)hipHostFree(r->h_frame);
+		r->d_frame = nullptr;
+		r->h_frame = nullptr;
+		r->px = 0;
+		HIP_TRY(hipMalloc((void **)&r->d_frame, W * H * sizeof(uint32_t)));
+		HIP_TRY(hipHostMalloc((void **)&r->h_frame, W * H * 4, hipHostMallocDefault));
+		r->px = W * H;
+	}
+	hipStream_t lane = nullptr;
+	FrameSetup fs;
+	if ((rc = next_lane(s, &lane)) || (rc = setup_frame(s, lane, &super, aa_shift, &fs))) return rc;
+	if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, ticket_request(r->d_frame, (int64_t)W, flags, lit)))) return rc;
+	StreamCtx *const c = fs.c;
+	r->ctx = c;
+	HIP_TRY(hipEventRecord(r->kernel_done, c->stream));
+	HIP_TRY(hipStreamWaitEvent(s->copy_stream, r->kernel_done, 0));
+	HIP_TRY(hipMemcpyAsync(r->h_frame, r->d_frame, W * H * 4, hipMemcpyDeviceToHost, s->copy_stream));
+	HIP_TRY(hipMemcpyAsync(r->h_capped, c->d_counters + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+	                       s->copy_stream));
+	HIP_TRY(hipEventRecord(r->copy_done, s->copy_stream));
+	r->width = cam->width;
+	r->height = cam->height;
+	r->busy = true;
+	*ticket = idx;
+	return HMRM_OK;
+}
+
+int hmrm_render_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket) {
+	return begin_common(scene, cam, flags, ticket, nullptr);
+}
+
+// (the sun goes into the launch by value -- SunRules is a kernel argument -- so the caller's hmrm_sun need not outlive the call)
+int hmrm_render_shaded_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags, uint32_t flags,
+                             int32_t *ticket) {
+	if (const int rc = check_shaded(sun, shade_flags)) return rc;
+	const LitFrame lit = make_lit_frame(sun, shade_flags);
+	return begin_common(scene, cam, flags, ticket, &lit);
+}
+
+int hmrm_render_wait(const hmrm_scene *scene, int32_t ticket, const uint8_t **rgba, size_t *stride_bytes) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	if (!s || !rgba) return fail(HMRM_E_ARG, "NULL argument");
+	RingFrame *r = nullptr;
+	{
+		std::lock_guard<std::mutex> lk(s->mu);
+		if (ticket < 0 || ticket >= (int)s->ring.size() || !s->ring[(size_t)ticket]->busy)
+			return fail(HMRM_E_ARG, "hmrm_render_wait: no such frame in flight");
+		r = s->ring[(size_t)ticket];
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(hipEventSynchronize(r->copy_done)); // (outside the lock: other threads may begin frames meanwhile)
+	*rgba = r->h_frame;
+	if (stride_bytes) *stride_bytes = (size_t)r->width * 4;
+	std::lock_guard<std::mutex> lk(s->mu);
+	return noterm(new_capped(r->ctx, *r->h_capped));
+}
+
+void hmrm_render_release(const hmrm_scene *scene, int32_t ticket) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	if (!s) return;
+	std::lock_guard<std::mutex> lk(s->mu);
+	if (ticket < 0 || ticket >= (int)s->ring.size()) return;
+	RingFrame *r = s->ring[(size_t)ticket];
+	if (!r->busy) return;
+	(void)hipSetDevice(s->device);
+	(void)hipEventSynchronize(r->copy_done); // never hand a slot back while the copy engine writes it
+	r->busy = false;
+}
+
+// ---- frames into device memory through the launch lanes ----
+int hmrm_render_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba, size_t stride_bytes, int32_t *ticket) {
+	return hmrm_render_device_begin_flags(scene, cam, d_rgba, stride_bytes, 0u, ticket);
+}
+
+static int device_begin_common(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba, size_t stride_bytes, uint32_t flags,
+                               int32_t *ticket, const LitFrame *lit) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	hmrm_camera super;
+	int aa_shift = 0;
+	int rc = check_begin(s, cam, flags, d_rgba != nullptr, ticket, &super, &aa_shift);
+	if (rc || (rc = check_device_stride(cam, stride_bytes))) return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	int idx = -1;
+	for (size_t i = 0; i < s->dev_tickets.size(); ++i)
+		if (!s->dev_tickets[i]->busy) {
+			idx = (int)i;
+			break;
+		}
+	if (idx < 0) {
+		if ((int)s->dev_tickets.size() >= kMaxRing) return fail(HMRM_E_ARG, "hmrm_render_device_begin: 64 frames in flight (wait for one)");
+		DevTicket *t = new (std::nothrow) DevTicket();
+		if (!t) return fail(HMRM_E_ARG, "out of memory");
+		hipError_t e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
+		if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_capped, sizeof(unsigned long long), hipHostMallocDefault);
+		if (e != hipSuccess) {
+			if (t->done) (void)hipEventDestroy(t->done);
+			delete t;
+			return fail(HMRM_E_DEVICE, std::string("hmrm_render_device_begin: ") + hipGetErrorString(e));
+		}
+		s->dev_tickets.push_back(t);
+		idx = (int)s->dev_tickets.size() - 1;
+	}
+	DevTicket *t = s->dev_tickets[(size_t)idx];
+	hipStream_t lane = nullptr;
+	FrameSetup fs;
+	if ((rc = next_lane(s, &lane)) || (rc = setup_frame(s, lane, &super, aa_shift, &fs))) return rc;
+	if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, ticket_request((uint32_t *)d_rgba, (int64_t)(stride_bytes / 4), flags, lit)))) return rc;
+	StreamCtx *const c = fs.c;
+	HIP_TRY(hipMemcpyAsync(t->h_capped, c->d_counters + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipEventRecord(t->done, c->stream));
+	t->ctx = c;
+	t->busy = true;
+	*ticket = idx;
+	return HMRM_OK;
+}
+
+int hmrm_render_device_begin_flags(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba, size_t stride_bytes, uint32_t flags,
+                                   int32_t *ticket) {
+	return device_begin_common(scene, cam, d_rgba, stride_bytes, flags, ticket, nullptr);
+}
+
+int hmrm_render_shaded_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, uint32_t shade_flags,
+                                    void *d_rgba, size_t stride_bytes, uint32_t flags, int32_t *ticket) {
+	if (const int rc = check_shaded(sun, shade_flags)) return rc;
+	const LitFrame lit = make_lit_frame(sun, shade_flags);
+	return device_begin_common(scene, cam, d_rgba, stride_bytes, flags, ticket, &lit);
+}
+
+int hmrm_render_device_wait(const hmrm_scene *scene, int32_t ticket) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	DevTicket *t = nullptr;
+	{
+		std::lock_guard<std::mutex> lk(s->mu);
+		if (ticket < 0 || ticket >= (int)s->dev_tickets.size() || !s->dev_tickets[(size_t)ticket]->busy)
+			return fail(HMRM_E_ARG, "hmrm_render_device_wait: no such frame in flight");
+		t = s->dev_tickets[(size_t)ticket];
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(hipEventSynchronize(t->done)); // (outside the lock: other threads may begin frames meanwhile)
+	std::lock_guard<std::mutex> lk(s->mu);
+	t->busy = false;
+	return noterm(new_capped(t->ctx, *t->h_capped));
+}
+
+double hmrm_last_kernel_ms(void) { return g_last_kernel_ms; }
+
+double hmrm_bench_kernel_ms(const hmrm_scene *scene, const hmrm_camera *cam, int32_t iters) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
+	if (check_camera(cam) || !s || iters <= 0) {
+		if (g_error.empty()) g_error = "bad argument";
+		return -1.0;
+	}
+	auto body = [&]() -> int {
+		const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+		HIP_TRY(hipSetDevice(s->device));
+		std::lock_guard<std::mutex> lk(s->mu);
+		int rc = ensure_frame(s, W * H);
+		if (rc) return rc;
+		FrameSetup fs;
+		if ((rc = setup_frame(s, s->stream, cam, 0, &fs))) return rc;
+		const FrameRequest req = plain_request(s->d_frame, (int64_t)W);
+		HIP_TRY(hipEventRecord(s->ev0, s->stream));
+		for (int i = 0; i < iters; ++i)
+			if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, req))) return rc;
+		HIP_TRY(hipEventRecord(s->ev1, s->stream));
+		HIP_TRY(hipStreamSynchronize(s->stream));
+		float ms = 0.f;
+		HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+		g_last_kernel_ms = ms / iters;
+		return HMRM_OK;
+	};
+	if (body() != HMRM_OK) return -1.0;
+	return g_last_kernel_ms;
+}
+
+int32_t hmrm_band_local_rows(int32_t height, int32_t band_rows, int32_t band_index, int32_t band_count) {
+	if (height <= 0 || band_rows <= 0 || band_count <= 0 || band_index < 0 || band_index >= band_count) return 0;
+	int64_t local = 0;
+	for (int64_t b = band_index; b * band_rows < height; b += band_count) local += band_rows;
+	return (int32_t)local;
+}
+
+} // extern "C"
+
+namespace hmrm {
+int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags) { return check_shaded(sun, shade_flags); } // (record.cpp)
+} // namespace hmrm

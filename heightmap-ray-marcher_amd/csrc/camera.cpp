@@ -77,7 +77,7 @@ void fill_row_tables(const HostCamera &cam, int32_t begin, int32_t end, double *
 	}
 }
 
-// What a launch needs of the scene and the march, camera or not (a ray batch has none: api.cpp): the map's size, the box
+// What a launch needs of the scene and the march, camera or not (a ray batch has none: api_queries.cpp): the map's size, the box
 // corners, the nudge, the step and the helpers derived from grid_width.
 void fill_scene_fields(int32_t map_w, int32_t map_h, double min_height, double max_height, double grid_width,
                        double step_dist, DevFrame *f) {
@@ -144,7 +144,7 @@ void build_frame(const HostCamera &cam, int32_t map_w, int32_t map_h, double min
 		store(f->plane_down, ll - ul);
 	} else if (cam.projection == 2) {
 		// src/Spherical.cpp:11-14, then the separable halves of :18-25 (callers that fill the tables
-		// in pieces -- api.cpp, on several host threads -- pass null here and call the two fills themselves)
+		// in pieces -- api_launch.cpp, on several host threads -- pass null here and call the two fills themselves)
 		if (col_cos_ha && col_sin_ha) fill_col_tables(cam, 0, cam.width, col_cos_ha, col_sin_ha);
 		if (row_sin_va && row_cos_va) fill_row_tables(cam, 0, cam.height, row_sin_va, row_cos_va);
 	} else {
@@ -185,7 +185,7 @@ void build_frame(const HostCamera &cam, int32_t map_w, int32_t map_h, double min
 	const double cells_per_step = std::fabs(cam.step_dist / grid_width);
 	f->min_window = cells_per_step > 0.35 ? 16 : 4;
 	f->finest_pause = cells_per_step > 0.35 ? 6 : 0;
-	f->min_level = 0; // (api.cpp turns min_window into a level of the pyramid it built)
+	f->min_level = 0; // (api_launch.cpp turns min_window into a level of the pyramid it built)
 }
 
 } // namespace hmrm

@@ -62,11 +62,11 @@ struct DevFrame {
 	int32_t box_side_known[3];
 	int32_t diag_mode;           // tools only: what the instrumented kernel writes per pixel
 	int32_t sampling;            // 0 nearest cell (the reference), 1 bilinear quality mode, 2 nearest cell with float thresholds
-	int32_t min_level;           // finest pyramid level worth an attempt (api.cpp, from min_window)
+	int32_t min_level;           // finest pyramid level worth an attempt (api_launch.cpp, from min_window)
 	int32_t min_window;          // ... as a window size in cells (camera.cpp)
 	int32_t finest_pause;        // extra groups marched after a refused attempt at that level (camera.cpp)
 	int32_t aa_shift;            // antialiasing (hmrm_render_aa): log2 n of the n x n samples box-filtered into one output
-	                             // pixel, 0 = off.  Set per launch by api.cpp, not part of the cached record; the kernels read
+	                             // pixel, 0 = off.  Set per launch by api_frames.cpp, not part of the cached record; the kernels read
 	                             // it only in their antialiased instantiations (device_common.hpp store_box_filtered).
 };
 
@@ -192,13 +192,13 @@ struct RowMap {
 	int32_t local_rows;    // rows held by the output buffer
 	int32_t band_rows;     // 0 = contiguous; else cyclic bands of this many rows
 	int32_t band_index, band_count;
-	// Launch order (api.cpp choose_tile_order): the grid's rows are handed out to tile rows in up to kOrderSegs
+	// Launch order (api_launch.cpp choose_tile_order): the grid's rows are handed out to tile rows in up to kOrderSegs
 	// contiguous pieces.  Grid row j belongs to the last piece k with j >= seg_first[k] (seg_first[0] = 0 is
 	// implicit; unused pieces have seg_first = INT32_MAX) and renders tile row (j + seg_delta[k]) mod tile rows --
 	// the last piece may wrap around the end of the frame.  Together the pieces cover every tile row once.
 	int32_t seg_first[3];  // pieces 1..3
 	int32_t seg_delta[4];  // pieces 0..3
-	// Calibration launch (api.cpp, launch order from measurement): when not null, every wave folds its duration, and
+	// Calibration launch (api_launch.cpp, launch order from measurement): when not null, every wave folds its duration, and
 	// a tile row's first wave its start time (s_memrealtime ticks, 10 ns), into the row's record: kMeasureStride words
 	// per tile row (march_frame.hpp k_render_fast).  Scheduling aid only.
 	unsigned long long *measure;
@@ -211,7 +211,7 @@ constexpr int kOrderSegs = 4;
 static_assert(sizeof(DevFrame) == 352,"DevFrame must not grow");
 
 // ---- ray batches (hmrm_trace_rays, hmrm.h): caller-supplied rays through the same march, PROJ == 4 in the kernels ----
-// Mirrors of hmrm_ray / hmrm_ray_hit (api.cpp asserts the sizes agree), and what a launch is handed beside the
+// Mirrors of hmrm_ray / hmrm_ray_hit (api_queries.cpp asserts the sizes agree), and what a launch is handed beside the
 // DevFrame -- extra arguments of the batch kernels' own __global__ entry points (render_rays.hip, render.hip), so
 // that neither DevFrame nor the frame kernels' argument lists change.  The DevFrame of a batch has no camera:
 // projection = 4, the plane fields zero, and the batch laid out as a "frame" kWaveW (8) pixels wide and
@@ -303,7 +303,7 @@ void build_frame(const HostCamera &cam, int32_t map_w, int32_t map_h,
                  double *row_sin_va, double *row_cos_va);  // height entries each (spherical) or null
 
 // The part of build_frame that needs no camera (camera.cpp): map size, box corners (hmap.cpp:968-974), nudge (:998),
-// step_dist (:68) and the grid_width helpers.  A ray batch's DevFrame is a zeroed one plus these (api.cpp).
+// step_dist (:68) and the grid_width helpers.  A ray batch's DevFrame is a zeroed one plus these (api_queries.cpp).
 void fill_scene_fields(int32_t map_w, int32_t map_h, double min_height, double max_height, double grid_width,
                        double step_dist, DevFrame *out);
 

@@ -1,4 +1,4 @@
-// host_pool.hpp -- a few persistent helper threads for the per-camera host set-up (api.cpp prepare_frame): the
+// host_pool.hpp -- a few persistent helper threads for the per-camera host set-up (api_launch.cpp prepare_frame): the
 // reference evaluates Spherical's sin / cos per pixel inside its OpenMP loop (src/Spherical.cpp:23-25,
 // main/hmap.cpp:978); here they are W + H table entries per camera, glibc calls that must stay on the host, and
 // for a moving camera they are filled by several host threads while the GPU renders the previous frame.

@@ -45,4 +45,42 @@ inline hipError_t select_tables(DevFrame *f, FastKernel kernel, const double *d_
 	return hipSuccess;
 }
 
+// The march units' own frame launchers, one per family and AA variant (launch_frame_march, render_fast.hip, picks): each
+// translation unit instantiates its kernels, so that the units compile side by side.  The plain ones may be instrumented
+// and measured (march_frame.hpp launch_fast); the others refuse a measured launch, and a frame whose f.aa_shift is not their kind.
+hipError_t launch_render_fast(const FrameLaunch &l, FastKernel kernel);          // render_fast.hip
+hipError_t launch_render_fast_aa(const FrameLaunch &l, FastKernel kernel);       // render_fast_aa.hip
+hipError_t launch_render_interior(const FrameLaunch &l, FastKernel kernel);      // render_interior.hip (no AA variant)
+hipError_t launch_render_lit(const FrameLaunch &l, FastKernel kernel);           // render_lit.hip
+hipError_t launch_render_lit_aa(const FrameLaunch &l, FastKernel kernel);        // render_lit_aa.hip
+hipError_t launch_render_shaded(const FrameLaunch &l, FastKernel kernel);        // render_shaded.hip
+hipError_t launch_render_shaded_aa(const FrameLaunch &l, FastKernel kernel);     // render_shaded_aa.hip
+hipError_t launch_render_lit_shaded(const FrameLaunch &l, FastKernel kernel);    // render_lit_shaded.hip
+hipError_t launch_render_lit_shaded_aa(const FrameLaunch &l, FastKernel kernel); // render_lit_shaded_aa.hip
+
+// The segment rules of a frame launch: no limits, the interior rule for the interior family and where the sun's flags ask.
+inline SegRules frame_seg_rules(const FrameLaunch &l) {
+	return SegRules{nullptr, 0u, (l.family == kFrameInterior || l.primary_interior) ? 1u : 0u};
+}
+
+// The launcher body of the interior, lit and shaded units, antialiased (`aa`) or not: k_render_fast's launch shape (one
+// workgroup per tile, grid rows beyond 32768 in blockIdx.z).  `launch(proj, gwm, leap, samp, grid, args...)` launches the
+// unit's kernel with those template arguments on that grid, with `args...` as its leading arguments: frame, row map, table,
+// colours, target, stride, tile rows, counters, segment rules (a unit whose kernel takes the sun adds it).
+template <class Launch>
+hipError_t launch_march_family(const FrameLaunch &l, FastKernel kernel, bool aa, Launch &&launch) {
+	if ((l.f.aa_shift != 0) != aa || l.rows.measure != nullptr) return hipErrorInvalidValue;
+	DevFrame fr = l.f;
+	const double *d_thr = nullptr;
+	if (const hipError_t e = select_tables(&fr, kernel, l.d_thr, l.d_thr32, l.d_records, &d_thr); e != hipSuccess) return e;
+	const LaunchGrid g = tile_grid(l.f, l.rows);
+	if (g.tiles_y == 0) return g.err;
+	const StatsOut st{l.d_counters, nullptr, nullptr};
+	const SegRules seg = frame_seg_rules(l);
+	dispatch_march(l.f.projection, l.f.grid_mode, kernel, l.f.sampling, [&](auto proj, auto gwm, auto leap, auto samp) {
+		launch(proj, gwm, leap, samp, g.grid, fr, l.rows, d_thr, l.d_cmap, l.d_out, l.out_stride_px, g.tiles_y, st, seg);
+	});
+	return hipGetLastError();
+}
+
 } // namespace hmrm

@@ -28,13 +28,13 @@ double measured_makespan(const unsigned long long *rec, int tiles_y);
 int plan_order_from_measurement(const unsigned long long *rec, int tiles_y, int rot, int *pb, int *pc);
 int split_hot_range(const unsigned long long *rec, int tiles_y, int rot, double head_frac, double tail_frac, int *pb, int *pc);
 
-// ---- the calibration as a state machine (host logic only: api.cpp owns the HIP events and the record buffers) -----------
+// ---- the calibration as a state machine (host logic only: api_launch.cpp owns the HIP events and the record buffers) -----------
 // A camera that is rendered again and again is CALIBRATED: a short list of trial orders -- [0] the rotation, then the
 // model's plan and a generic head / tail / middle split made from the rotation's first records -- each timed by
 // kOrderSamples measured full-frame launches, after which the one with the shortest measured makespan stays (another
 // order must beat the rotation by 1 %).  The last candidate of ONE record per scene is not an order but the OTHER KERNEL:
 // the plain speculative groups without pyramid leaps (with leaps over window records where the frame's sampling allows
-// them: api.cpp launch_kernel), under the rotation.  On content that admits no jumps (needles on a plateau,
+// them: api_launch.cpp launch_kernel), under the rotation.  On content that admits no jumps (needles on a plateau,
 // white noise: profiles/r04_content.txt) the leap kernel's attempts are pure overhead; the kernel that measures 3 % faster
 // renders the scene from then on.  Same pixels whatever is chosen.
 constexpr int kOrderSamples = 2; // measured launches per trial (one launch's makespan wobbles by a few per cent)
@@ -47,7 +47,7 @@ struct OrderTrial {
 };
 
 // Which kernel suits a scene's content: probed ONCE per scene and height update, by the first camera that gets calibrated
-// or -- for cameras that never repeat -- by the scene's shadow probe (api.cpp); everybody else renders with the verdict.
+// or -- for cameras that never repeat -- by the scene's shadow probe (api_launch.cpp); everybody else renders with the verdict.
 struct KernelChoice {
 	bool probed = false;           // some record's trials hold (or held) the probe, or the shadow probe has been launched
 	bool use_group = false;        // the verdict: the other kernel -- the plain groups, or for nearest-sampling frames their

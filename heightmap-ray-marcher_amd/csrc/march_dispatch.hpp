@@ -1,15 +1,54 @@
 // march_dispatch.hpp -- from the run-time values that pick a march kernel (projection, grid mode, kernel kind, sampling)
 // to its template arguments <PROJ, GWM, LEAP, SAMP>: the one ladder of every unit that instantiates render_wave_tile
-// (march.hpp).  The callable gets the four values as std::integral_constants and is called exactly once.  Host code
-// only, nothing from HIP: tests/fuzz_host_logic.cpp compiles it with g++.
+// (march.hpp).  The callable gets the four values as std::integral_constants and is called exactly once.  In front of it,
+// route_frame: from what a frame asks for to the family of kernels that renders it.  Host code only, nothing from HIP:
+// tests/fuzz_host_logic.cpp compiles it with g++.
 #pragma once
 #include <type_traits>
 
 namespace hmrm {
 
 // kPlainGroups: speculative step groups; kLeaps: plus exact leaps over empty pyramid windows; kRecords: leaps over windows
-// of the record level that are empty but for a few recorded cells (render.hpp launch_render_fast).
+// of the record level that are empty but for a few recorded cells (render.hpp launch_frame_march).
 enum FastKernel { kPlainGroups = 0, kLeaps = 1, kRecords = 2 };
+
+// Which kernels render a frame (render.hpp FrameLaunch): hmrm_render's, or the ones built with the interior rule, with
+// shadow rays, with diffuse shading without or with shadow rays.
+enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded };
+
+// Which launch a frame gets.  `forced`: HMRM_KERNEL (2: simple); `huge_side`: a map side of 2^24 cells or more -- the production
+// kernel indexes cells and windows with 24-bit multiplies, leap_common.hpp index_2d; `interior`: hmrm_render_interior's frame
+// whose rays may start inside the box; `lit`: the frame has a sun, with hmrm_render_shaded's `shade_flags` (the values of
+// HMRM_SHADE_*; 0: hmrm_render_lit's frame, by its kernels).  A sun takes precedence over `interior`: such a frame carries
+// the rule in FrameLaunch::primary_interior.  `aa` (the frame has an antialias factor) changes no route: the antialiased variant
+// of a family is its launchers' matter (f.aa_shift), and the one family without such kernels, the interior one, has no entry
+// point that takes a factor.
+constexpr unsigned kShadeDiffuse = 1u, kShadeNoShadows = 2u;
+struct FrameRoute {
+	bool refused;     // no kernel renders this frame: a huge side with another sampling than nearest
+	bool literal;     // the literal loop (which only knows the reference's sampling), else a march kernel
+	FrameFamily family;
+	bool shadows;     // the launch marches shadow rays
+	bool ambient_sun; // the sun handed to the launch is the caller's with ambient = 255
+};
+inline FrameRoute route_frame(int forced, bool huge_side, int sampling, bool /*aa*/, bool interior, bool lit, unsigned shade_flags) {
+	FrameRoute r{huge_side && sampling != 0, (forced == 2 || huge_side) && sampling == 0, kFramePlain, false, false};
+	if (lit) {
+		// (HMRM_SHADE_NO_SHADOWS without HMRM_SHADE_DIFFUSE is hmrm_render's frame by definition.  It goes through the shaded kernel
+		// with every weight 255 all the same, not through the interior / plain kernels: the interior launcher always sets the
+		// interior rule, which this frame has only with HMRM_TRACE_INTERIOR, and the plain one belongs to frames that may be
+		// measured or be the probe, which no frame of this entry point is.  The levels it computes for nothing are the price of
+		// one route; the combination is an identity for tests, not something to render with.)
+		r.shadows = !(shade_flags & kShadeNoShadows);
+		r.family = !r.shadows ? kFrameShaded : shade_flags ? kFrameLitShaded : kFrameLit; // (kFrameLitShaded: HMRM_SHADE_DIFFUSE alone)
+		// Without HMRM_SHADE_DIFFUSE a pixel that is not shadowed has the weight 255: the kernels without shadow rays get that
+		// from ambient = 255, whatever the level.
+		r.ambient_sun = !r.shadows && !(shade_flags & kShadeDiffuse);
+	} else if (interior) {
+		r.family = kFrameInterior;
+	}
+	return r;
+}
 
 template <int V>
 using MarchConst = std::integral_constant<int, V>;

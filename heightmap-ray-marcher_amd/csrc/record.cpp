@@ -9,7 +9,7 @@
 // Frames are independent, so the sweep shards over devices the way BASELINE config C5
 // says: frame k is rendered by scene k mod N (one scene per GPU, maps replicated), no
 // exchange between devices.  Per scene one host thread keeps a few frames in flight
-// through the asynchronous ring of api.cpp (kernel k+1 overlaps the PCIe copy of frame
+// through the asynchronous ring of api_frames.cpp (kernel k+1 overlaps the PCIe copy of frame
 // k); finished frames stay in the ring's pinned memory and are lent to a shared pool of
 // PNG encoder threads (the stb-identical encoder needs ~0.3 s per 4K frame on one
 // core, the GPU 0.25 ms), which give the slot back when the file is written.  Memory is
@@ -30,8 +30,8 @@
 #include "image_io.hpp"
 
 namespace hmrm {
-int set_error(int code, const char *msg);
-int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags); // (api.cpp: the refusals of hmrm_render_shaded_begin's sun)
+int set_error(int code, const char *msg); // (api_scene.cpp: hmrm_last_error's text)
+int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags); // (api_frames.cpp: the refusals of hmrm_render_shaded_begin's sun)
 }
 
 extern "C" {

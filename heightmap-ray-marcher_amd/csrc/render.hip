@@ -510,12 +510,18 @@ hipError_t launch_upload_tables(const double *h_pinned, double *d_dst, size_t n,
 }
 
 // ------------------------------------------------------------- launchers ----
-hipError_t launch_probe(const DevFrame &f, int px, int py, double *d_out7, hipStream_t stream) {
-	switch (f.projection) {
-	case 1: hipLaunchKernelGGL(k_probe<1>, dim3(1), dim3(64), 0, stream, f, px, py, d_out7); break;
-	case 2: hipLaunchKernelGGL(k_probe<2>, dim3(1), dim3(64), 0, stream, f, px, py, d_out7); break;
-	default: hipLaunchKernelGGL(k_probe<3>, dim3(1), dim3(64), 0, stream, f, px, py, d_out7); break;
+// fn(proj): the projection as the kernels' template argument.
+template <class Fn>
+static void dispatch_projection(int projection, Fn &&fn) {
+	switch (projection) {
+	case 1: fn(MarchConst<1>{}); break;
+	case 2: fn(MarchConst<2>{}); break;
+	default: fn(MarchConst<3>{}); break;
 	}
+}
+
+hipError_t launch_probe(const DevFrame &f, int px, int py, double *d_out7, hipStream_t stream) {
+	dispatch_projection(f.projection, [&](auto proj) { hipLaunchKernelGGL(k_probe<proj()>, dim3(1), dim3(64), 0, stream, f, px, py, d_out7); });
 	return hipGetLastError();
 }
 
@@ -539,30 +545,6 @@ double max_key_to_double(unsigned long long key) {
 	double v;
 	__builtin_memcpy(&v, &b, sizeof v);
 	return v;
-}
-
-template <bool STATS, bool AA>
-static hipError_t launch_render_t(const DevFrame &f, const RowMap &rows, const double *d_thr,
-                                  const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
-                                  StatsOut st, hipStream_t stream) {
-	const LaunchGrid g = tile_grid(f, rows);
-	if (g.tiles_y == 0) return g.err;
-	const dim3 block(kBlockThreads);
-	switch (f.projection) {
-	case 1:
-		hipLaunchKernelGGL((k_render<1, STATS, AA>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
-		                   out_stride_px, g.tiles_y, st);
-		break;
-	case 2:
-		hipLaunchKernelGGL((k_render<2, STATS, AA>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
-		                   out_stride_px, g.tiles_y, st);
-		break;
-	default:
-		hipLaunchKernelGGL((k_render<3, STATS, AA>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out,
-		                   out_stride_px, g.tiles_y, st);
-		break;
-	}
-	return hipGetLastError();
 }
 
 hipError_t launch_trace_rays_literal(const DevFrame &f, const double *d_thr, const uint32_t *d_cmap, const RayBatch &batch,
@@ -603,112 +585,74 @@ hipError_t launch_cell_map_sum_literal(const DevFrame &f, const double *d_thr, u
 	return hipGetLastError();
 }
 
-hipError_t launch_render_interior_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                          uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                          hipStream_t stream) {
-	const LaunchGrid g = tile_grid(f, rows);
+// One frame by the literal loop.  `launch(proj, grid, args...)` launches the family's kernel for that projection on that grid
+// with `args...` as its leading arguments: frame, row map, table, colours, target, stride, tile rows, counters.
+template <class Launch>
+static hipError_t launch_literal(const FrameLaunch &l, const StatsOut &st, Launch &&launch) {
+	const LaunchGrid g = tile_grid(l.f, l.rows);
 	if (g.tiles_y == 0) return g.err;
-	const dim3 block(kBlockThreads);
-	const StatsOut st{d_counters, nullptr, nullptr};
-	const SegRules seg{nullptr, 0u, 1u};
-	switch (f.projection) {
-	case 1: hipLaunchKernelGGL(k_render_interior_literal<1>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg); break;
-	case 2: hipLaunchKernelGGL(k_render_interior_literal<2>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg); break;
-	default: hipLaunchKernelGGL(k_render_interior_literal<3>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg); break;
-	}
+	dispatch_projection(l.f.projection, [&](auto proj) {
+		launch(proj, g.grid, l.f, l.rows, l.d_thr, l.d_cmap, l.d_out, l.out_stride_px, g.tiles_y, st);
+	});
 	return hipGetLastError();
 }
 
-hipError_t launch_render_lit_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                     uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
-                                     bool primary_interior, hipStream_t stream) {
-	const LaunchGrid g = tile_grid(f, rows);
-	if (g.tiles_y == 0) return g.err;
+static hipError_t launch_plain_literal(const FrameLaunch &l); // (hmrm_render's frame: below)
+
+// The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
+// shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
+// this order, which is the order of the kernels in the code object.)
+hipError_t launch_frame_literal(const FrameLaunch &l) {
+	if (l.family == kFramePlain) return launch_plain_literal(l);
+	const StatsOut st{l.d_counters, nullptr, nullptr};
+	const SegRules seg = frame_seg_rules(l);
 	const dim3 block(kBlockThreads);
-	const StatsOut st{d_counters, nullptr, nullptr};
-	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
-	switch (f.projection) {
-	case 1: hipLaunchKernelGGL(k_render_lit_literal<1>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	case 2: hipLaunchKernelGGL(k_render_lit_literal<2>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	default: hipLaunchKernelGGL(k_render_lit_literal<3>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
+	if (l.family == kFrameInterior)
+		return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
+			hipLaunchKernelGGL(k_render_interior_literal<proj()>, grid, block, 0, l.stream, args..., seg);
+		});
+	if (l.f.aa_shift == 0) switch (l.family) {
+		case kFrameLit:
+			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
+				hipLaunchKernelGGL(k_render_lit_literal<proj()>, grid, block, 0, l.stream, args..., seg, l.sun);
+			});
+		case kFrameLitShaded:
+			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
+				hipLaunchKernelGGL((k_render_shaded_literal<proj(), true>), grid, block, 0, l.stream, args..., seg, l.sun);
+			});
+		default:
+			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
+				hipLaunchKernelGGL((k_render_shaded_literal<proj(), false>), grid, block, 0, l.stream, args..., seg, l.sun);
+			});
+		}
+	// The antialiased ones: f is the super frame, d_out the filtered frame's.  Never a measured launch.
+	if (l.rows.measure != nullptr) return hipErrorInvalidValue;
+	switch (l.family) {
+	case kFrameLit:
+		return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
+			hipLaunchKernelGGL(k_render_lit_literal_aa<proj()>, grid, block, 0, l.stream, args..., seg, l.sun);
+		});
+	case kFrameLitShaded:
+		return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
+			hipLaunchKernelGGL((k_render_shaded_literal_aa<proj(), true>), grid, block, 0, l.stream, args..., seg, l.sun);
+		});
+	default:
+		return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
+			hipLaunchKernelGGL((k_render_shaded_literal_aa<proj(), false>), grid, block, 0, l.stream, args..., seg, l.sun);
+		});
 	}
-	return hipGetLastError();
 }
 
-template <bool SHADOWS>
-static hipError_t launch_render_shaded_literal_t(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                                 uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                                 const SunRules &sun, bool primary_interior, hipStream_t stream) {
-	const LaunchGrid g = tile_grid(f, rows);
-	if (g.tiles_y == 0) return g.err;
-	const dim3 block(kBlockThreads);
-	const StatsOut st{d_counters, nullptr, nullptr};
-	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
-	switch (f.projection) {
-	case 1: hipLaunchKernelGGL((k_render_shaded_literal<1, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	case 2: hipLaunchKernelGGL((k_render_shaded_literal<2, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	default: hipLaunchKernelGGL((k_render_shaded_literal<3, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	}
-	return hipGetLastError();
+// hmrm_render's frame: instrumented or not, antialiased or not.
+template <bool STATS, bool AA>
+static hipError_t launch_render_t(const FrameLaunch &l) {
+	return launch_literal(l, StatsOut{l.d_counters, l.d_steps, l.d_entry}, [&](auto proj, dim3 grid, const auto &...args) {
+		hipLaunchKernelGGL((k_render<proj(), STATS, AA>), grid, dim3(kBlockThreads), 0, l.stream, args...);
+	});
 }
-hipError_t launch_render_shaded_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                        uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
-                                        bool primary_interior, bool shadows, hipStream_t stream) {
-	return shadows ? launch_render_shaded_literal_t<true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream)
-	               : launch_render_shaded_literal_t<false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream);
-}
-
-// The antialiased ones: f is the super frame, d_out the filtered frame's.
-hipError_t launch_render_lit_literal_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                        uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
-                                        bool primary_interior, hipStream_t stream) {
-	if (f.aa_shift == 0 || rows.measure != nullptr) return hipErrorInvalidValue;
-	const LaunchGrid g = tile_grid(f, rows);
-	if (g.tiles_y == 0) return g.err;
-	const dim3 block(kBlockThreads);
-	const StatsOut st{d_counters, nullptr, nullptr};
-	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
-	switch (f.projection) {
-	case 1: hipLaunchKernelGGL(k_render_lit_literal_aa<1>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	case 2: hipLaunchKernelGGL(k_render_lit_literal_aa<2>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	default: hipLaunchKernelGGL(k_render_lit_literal_aa<3>, g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	}
-	return hipGetLastError();
-}
-template <bool SHADOWS>
-static hipError_t launch_render_shaded_literal_aa_t(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                                    uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                                    const SunRules &sun, bool primary_interior, hipStream_t stream) {
-	if (f.aa_shift == 0 || rows.measure != nullptr) return hipErrorInvalidValue;
-	const LaunchGrid g = tile_grid(f, rows);
-	if (g.tiles_y == 0) return g.err;
-	const dim3 block(kBlockThreads);
-	const StatsOut st{d_counters, nullptr, nullptr};
-	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
-	switch (f.projection) {
-	case 1: hipLaunchKernelGGL((k_render_shaded_literal_aa<1, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	case 2: hipLaunchKernelGGL((k_render_shaded_literal_aa<2, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	default: hipLaunchKernelGGL((k_render_shaded_literal_aa<3, SHADOWS>), g.grid, block, 0, stream, f, rows, d_thr, d_cmap, d_out, out_stride_px, g.tiles_y, st, seg, sun); break;
-	}
-	return hipGetLastError();
-}
-hipError_t launch_render_shaded_literal_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                           uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
-                                           bool primary_interior, bool shadows, hipStream_t stream) {
-	return shadows ? launch_render_shaded_literal_aa_t<true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream)
-	               : launch_render_shaded_literal_aa_t<false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, d_counters, sun, primary_interior, stream);
-}
-
-hipError_t launch_render(const DevFrame &f, const RowMap &rows, const double *d_thr,
-                         const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
-                         unsigned long long *d_counters, uint32_t *d_steps, double *d_entry,
-                         bool stats, hipStream_t stream) {
-	StatsOut st{d_counters, d_steps, d_entry};
-	if (f.aa_shift)
-		return stats ? launch_render_t<true, true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream)
-		             : launch_render_t<false, true>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream);
-	return stats ? launch_render_t<true, false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream)
-	             : launch_render_t<false, false>(f, rows, d_thr, d_cmap, d_out, out_stride_px, st, stream);
+static hipError_t launch_plain_literal(const FrameLaunch &l) {
+	if (l.f.aa_shift) return l.stats ? launch_render_t<true, true>(l) : launch_render_t<false, true>(l);
+	return l.stats ? launch_render_t<true, false>(l) : launch_render_t<false, false>(l);
 }
 
 } // namespace hmrm

@@ -1,10 +1,10 @@
-// render.hpp -- launch interface of render.hip (device code) for api.cpp.
+// render.hpp -- launch interface of the device code (render.hip and the march units) for the host side (api_*.cpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #include "frame.hpp"
-#include "march_dispatch.hpp" // (enum FastKernel)
+#include "march_dispatch.hpp" // (enum FastKernel, enum FrameFamily)
 
 namespace hmrm {
 
@@ -16,28 +16,42 @@ hipError_t launch_prepare_heights(const uint8_t *d_rgb, double *d_out, int64_t n
                                   unsigned long long *d_max_key, hipStream_t stream);
 double max_key_to_double(unsigned long long key);
 
-// One pass of the pixel loop over the rows described by `rows`, into d_out
-// (uint32 RGBA per pixel, out_stride_px pixels per local row).
-// d_counters: 3 x uint64 {steps, hits, capped}; steps/hits only filled when stats.
-hipError_t launch_render(const DevFrame &f, const RowMap &rows, const double *d_thr,
-                         const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
-                         unsigned long long *d_counters, uint32_t *d_steps, double *d_entry,
-                         bool stats, hipStream_t stream);
-
-// Production kernel (march.hpp; the frame launchers in render_fast.hip): speculative step groups (kPlainGroups), plus exact leaps over empty pyramid
-// windows (kLeaps), or over windows of the record level that are empty but for a few recorded cells the ray's path
-// misses (kRecords: nearest sampling only, `d_records` from launch_build_records).  Same outputs as launch_render.
-// f.sampling == 2 reads the float copy of the table (d_thr32, launch_thr_to_float) instead of d_thr.
-hipError_t launch_render_fast(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                              const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
-                              unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
-                              FastKernel kernel, const WindowRecord *d_records, hipStream_t stream);
-// The same launch with the antialiased epilogue (f.aa_shift != 0; render_fast_aa.hip, a translation unit of its own so
-// that the two halves of the kernel's instantiations compile in parallel).  launch_render_fast hands such frames to it.
-hipError_t launch_render_fast_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                                 const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
-                                 unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
-                                 FastKernel kernel, const WindowRecord *d_records, hipStream_t stream);
+// One frame launch: a pass of the pixel loop over the rows described by `rows`, into d_out (uint32 RGBA per pixel,
+// out_stride_px pixels per local row).  Everything a frame launcher takes, named: a launcher reads what its family needs.
+// f.aa_shift != 0 selects the family's antialiased kernels: f is then the super frame, every sample is rendered (lit, shaded)
+// on its own and the launch writes the box-filtered frame, (f.screen_w >> f.aa_shift) pixels wide, into d_out.
+struct FrameLaunch {
+	// the tables the scene owns: f.sampling == 2 reads the float copy of the table (d_thr32, launch_thr_to_float) instead of
+	// d_thr; d_records (launch_build_records) is read by kRecords only
+	const double *d_thr;
+	const float *d_thr32;
+	const uint32_t *d_cmap;
+	const WindowRecord *d_records;
+	// the target.  d_counters: 3 x uint64 {steps, hits, capped} (+ diagnostics); steps / hits and the per-pixel d_steps / d_entry
+	// are only filled when stats, and only by the plain family; [2] counts capped primary and capped shadow rays, per sample
+	uint32_t *d_out;
+	int64_t out_stride_px;
+	unsigned long long *d_counters;
+	uint32_t *d_steps;
+	double *d_entry;
+	bool stats;
+	const DevFrame &f;
+	const RowMap &rows;
+	// kFramePlain may be a measured launch (rows.measure); the others refuse one.  kFrameInterior (hmrm_render_interior): every
+	// primary ray under the interior rule.  kFrameLit (hmrm_render_lit): a hit pixel's shadow ray is marched in the same launch.
+	// kFrameShaded (hmrm_render_shaded): no shadow rays, neither sun.step_dist nor sun.max_steps is looked at, every hit pixel
+	// at the weight of its diffuse level.  kFrameLitShaded: kFrameLit whose lit pixels get that weight.
+	FrameFamily family;
+	SunRules sun;          // the lit and shaded families: direction, shadow march and ambient level (frame.hpp)
+	bool primary_interior; // ... and whether their primary rays are under the interior rule too
+	hipStream_t stream;
+};
+// The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups
+// (kPlainGroups), plus exact leaps over empty pyramid windows (kLeaps), or over windows of the record level that are empty but
+// for a few recorded cells the ray's path misses (kRecords: nearest sampling only).
+hipError_t launch_frame_march(const FrameLaunch &l, FastKernel kernel);
+// The literal one-step-at-a-time loop (render.hip), nearest sampling only.  Same outputs.
+hipError_t launch_frame_literal(const FrameLaunch &l);
 // Ray batches (hmrm_trace_rays; render_rays.hip): batch.n caller-supplied rays through the same march, one hmrm_ray_hit
 // record per ray.  `f` is a DevFrame without a camera -- projection 4, kBatchW pixels wide, at least ceil(n / kBatchW) rows
 // (frame.hpp RayBatch); the row map is the identity.  d_counters[2] counts the rays stopped by the step cap, nothing else
@@ -73,61 +87,6 @@ hipError_t launch_cell_map_sum(const DevFrame &f, const double *d_thr, const flo
                                const WindowRecord *d_records, hipStream_t stream);
 hipError_t launch_cell_map_sum_literal(const DevFrame &f, const double *d_thr, uint16_t *d_out, int64_t stride_bytes,
                                        const CellRules &cells, const CellSums &sums, unsigned long long *d_counters, hipStream_t stream);
-// Frames under the interior rule (hmrm_render_interior; render_interior.hip: the production kernels' instantiations with the
-// rule, a translation unit of its own, and the literal loop in render.hip).  Not instrumented, not antialiased, never measured.
-hipError_t launch_render_interior(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                                  const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                  FastKernel kernel, const WindowRecord *d_records, hipStream_t stream);
-hipError_t launch_render_interior_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                          uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                          hipStream_t stream);
-// Frames with sun shadows (hmrm_render_lit; frame.hpp SunRules; render_lit.hip: the production kernels' instantiations that
-// march a hit pixel's shadow ray in the same launch, and the literal loop in render.hip).  `primary_interior`: the primary
-// rays are under the interior rule too.  d_counters[2] counts capped primary and capped shadow rays.  Never measured.
-hipError_t launch_render_lit(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                             const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                             FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
-                             hipStream_t stream);
-hipError_t launch_render_lit_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                     uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
-                                     bool primary_interior, hipStream_t stream);
-// Hill-shaded frames (hmrm_render_shaded; `sun` brings the direction and the ambient level): launch_render_shaded
-// (render_shaded.hip) marches no shadow rays and looks at neither sun.step_dist nor sun.max_steps -- every hit pixel at the
-// weight of its diffuse level; launch_render_lit_shaded (render_lit_shaded.hip) is launch_render_lit whose lit pixels get that
-// weight; the literal loop (render.hip) does either.  Counters and launches as launch_render_lit.
-hipError_t launch_render_shaded(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                                const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
-                                hipStream_t stream);
-hipError_t launch_render_lit_shaded(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                                    const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                    FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
-                                    hipStream_t stream);
-hipError_t launch_render_shaded_literal(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                        uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
-                                        bool primary_interior, bool shadows, hipStream_t stream);
-// The antialiased counterparts (hmrm_render_shaded_aa; march_lit_aa.hpp and the three render_*_aa.hip units; the literal loop in
-// render.hip): f is the super frame with f.aa_shift != 0, every sample is lit and shaded on its own and the launch writes the
-// box-filtered frame, (f.screen_w >> f.aa_shift) pixels wide, into d_out.  They refuse f.aa_shift == 0, as the ones above
-// refuse the opposite.  Counters as above, per sample.
-hipError_t launch_render_lit_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                                const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
-                                hipStream_t stream);
-hipError_t launch_render_shaded_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                                   const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                   FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
-                                   hipStream_t stream);
-hipError_t launch_render_lit_shaded_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const float *d_thr32,
-                                       const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                       FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
-                                       hipStream_t stream);
-hipError_t launch_render_lit_literal_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                        uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
-                                        bool primary_interior, hipStream_t stream);
-hipError_t launch_render_shaded_literal_aa(const DevFrame &f, const RowMap &rows, const double *d_thr, const uint32_t *d_cmap,
-                                           uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, const SunRules &sun,
-                                           bool primary_interior, bool shadows, hipStream_t stream);
 // The record table of the thr table: rec_row(map_w) x ceil(map_h / 4) WindowRecords.
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream);
 // thr32[i] = (float)thr[i], round to nearest (the "float heights" mode).
@@ -143,7 +102,7 @@ hipError_t launch_build_mip_up(const float *d_src, int src_w, int src_h, float *
 // round-up-to-float of a double (the pyramid's rounding), on the host: for the whole-map element
 float round_up_to_float_host(double v);
 
-// Pixel tile (= workgroup) shape of launch_render / launch_render_fast.
+// Pixel tile (= workgroup) shape of the frame launches.
 void render_tile_shape(int *tile_w, int *tile_h);
 
 // GetRay + distance() of pixel (px,py): d_out7 = pos[3], dir[3], d.

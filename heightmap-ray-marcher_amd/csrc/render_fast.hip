@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void k_build_records(const double *__restrict_
 hipError_t launch_build_records(const double *d_thr, int map_w, int map_h, WindowRecord *d_dst, hipStream_t stream) {
 	const int rw = rec_row(map_w), rh = (map_h + 3) >> 2;
 	const dim3 grid((unsigned)((rw + 15) / 16), (unsigned)((rh + 15) / 16));
-	if (grid.y > 65535u) return hipErrorInvalidValue; // (api.cpp does not build records for such maps)
+	if (grid.y > 65535u) return hipErrorInvalidValue; // (api_scene.cpp does not build records for such maps)
 	hipLaunchKernelGGL(k_build_records, grid, dim3(256), 0, stream, d_thr, map_w, map_h, d_dst, rw, rh);
 	return hipGetLastError();
 }
@@ -272,15 +272,21 @@ hipError_t launch_thr_to_float(const double *d_thr, float *d_thr32, int64_t n, h
 	return hipGetLastError();
 }
 
-hipError_t launch_render_fast(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
-                              const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
-                              unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
-                              FastKernel kernel, const WindowRecord *d_records, hipStream_t stream) {
-	if (f.aa_shift)
-		return launch_render_fast_aa(f, rows, d_thr_f64, d_thr32, d_cmap, d_out, out_stride_px, d_counters, d_steps, d_entry,
-		                             stats, kernel, d_records, stream);
-	return launch_fast<false>(f, rows, d_thr_f64, d_thr32, d_cmap, d_out, out_stride_px, d_counters, d_steps, d_entry, stats,
-	                          kernel, d_records, stream);
+hipError_t launch_render_fast(const FrameLaunch &l, FastKernel kernel) {
+	return launch_fast<false>(l.f, l.rows, l.d_thr, l.d_thr32, l.d_cmap, l.d_out, l.out_stride_px, l.d_counters, l.d_steps, l.d_entry,
+	                          l.stats, kernel, l.d_records, l.stream);
+}
+
+// The family's unit, and its antialiased one for a frame with a factor (launch_common.hpp).
+hipError_t launch_frame_march(const FrameLaunch &l, FastKernel kernel) {
+	const bool aa = l.f.aa_shift != 0;
+	switch (l.family) {
+	case kFrameInterior: return launch_render_interior(l, kernel); // (refuses a factor)
+	case kFrameLit: return aa ? launch_render_lit_aa(l, kernel) : launch_render_lit(l, kernel);
+	case kFrameShaded: return aa ? launch_render_shaded_aa(l, kernel) : launch_render_shaded(l, kernel);
+	case kFrameLitShaded: return aa ? launch_render_lit_shaded_aa(l, kernel) : launch_render_lit_shaded(l, kernel);
+	default: return aa ? launch_render_fast_aa(l, kernel) : launch_render_fast(l, kernel);
+	}
 }
 
 void render_tile_shape(int *tile_w, int *tile_h) {

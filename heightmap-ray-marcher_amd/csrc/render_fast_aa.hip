@@ -6,12 +6,9 @@
 
 namespace hmrm {
 
-hipError_t launch_render_fast_aa(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
-                                 const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px,
-                                 unsigned long long *d_counters, uint32_t *d_steps, double *d_entry, bool stats,
-                                 FastKernel kernel, const WindowRecord *d_records, hipStream_t stream) {
-	return launch_fast<true>(f, rows, d_thr_f64, d_thr32, d_cmap, d_out, out_stride_px, d_counters, d_steps, d_entry, stats,
-	                         kernel, d_records, stream);
+hipError_t launch_render_fast_aa(const FrameLaunch &l, FastKernel kernel) {
+	return launch_fast<true>(l.f, l.rows, l.d_thr, l.d_thr32, l.d_cmap, l.d_out, l.out_stride_px, l.d_counters, l.d_steps, l.d_entry,
+	                         l.stats, kernel, l.d_records, l.stream);
 }
 
 } // namespace hmrm

@@ -13,15 +13,10 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
 	lit_aa_wave_tile<true, true, PROJ, GWM, LEAP, SAMP>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, seg, sun);
 }
 
-hipError_t launch_render_lit_shaded_aa(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
-		const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters, FastKernel kernel,
-		const WindowRecord *d_records, const SunRules &sun, bool primary_interior, hipStream_t stream) {
-	return launch_lit_aa(f, rows, d_thr_f64, d_thr32, d_counters, kernel, d_records, primary_interior,
-	                     [&](auto proj, auto gwm, auto leap, auto samp, dim3 grid, const DevFrame &fr, const double *d_thr, int tiles_y,
-	                         const StatsOut &st, const SegRules &seg) {
-		                     hipLaunchKernelGGL((k_render_lit_shaded_aa<proj(), gwm(), leap(), samp()>), grid, dim3(kBlockThreads), 0, stream, fr, rows,
-		                                        d_thr, d_cmap, d_out, out_stride_px, tiles_y, st, seg, sun);
-	                     });
+hipError_t launch_render_lit_shaded_aa(const FrameLaunch &l, FastKernel kernel) {
+	return launch_march_family(l, kernel, true, [&](auto proj, auto gwm, auto leap, auto samp, dim3 grid, const auto &...args) {
+		hipLaunchKernelGGL((k_render_lit_shaded_aa<proj(), gwm(), leap(), samp()>), grid, dim3(kBlockThreads), 0, l.stream, args..., l.sun);
+	});
 }
 
 } // namespace hmrm

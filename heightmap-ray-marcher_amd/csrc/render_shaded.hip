@@ -23,24 +23,10 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
 	                                                                          (int)(threadIdx.x & 63), RayBatch{}, seg, sun);
 }
 
-// `primary_interior`: the rays are under the interior rule (HMRM_TRACE_INTERIOR; the kernel tests each origin).
-hipError_t launch_render_shaded(const DevFrame &f, const RowMap &rows, const double *d_thr_f64, const float *d_thr32,
-                                const uint32_t *d_cmap, uint32_t *d_out, int64_t out_stride_px, unsigned long long *d_counters,
-                                FastKernel kernel, const WindowRecord *d_records, const SunRules &sun, bool primary_interior,
-                                hipStream_t stream) {
-	if (f.aa_shift != 0 || rows.measure != nullptr) return hipErrorInvalidValue;
-	DevFrame fr = f;
-	const double *d_thr = nullptr;
-	if (const hipError_t e = select_tables(&fr, kernel, d_thr_f64, d_thr32, d_records, &d_thr); e != hipSuccess) return e;
-	const LaunchGrid g = tile_grid(f, rows);
-	if (g.tiles_y == 0) return g.err;
-	const StatsOut st{d_counters, nullptr, nullptr};
-	const SegRules seg{nullptr, 0u, primary_interior ? 1u : 0u};
-	dispatch_march(f.projection, f.grid_mode, kernel, f.sampling, [&](auto proj, auto gwm, auto leap, auto samp) {
-		hipLaunchKernelGGL((k_render_shaded<proj(), gwm(), leap(), samp()>), g.grid, dim3(kBlockThreads), 0, stream, fr, rows, d_thr, d_cmap,
-		                   d_out, out_stride_px, g.tiles_y, st, seg, sun);
+hipError_t launch_render_shaded(const FrameLaunch &l, FastKernel kernel) {
+	return launch_march_family(l, kernel, false, [&](auto proj, auto gwm, auto leap, auto samp, dim3 grid, const auto &...args) {
+		hipLaunchKernelGGL((k_render_shaded<proj(), gwm(), leap(), samp()>), grid, dim3(kBlockThreads), 0, l.stream, args..., l.sun);
 	});
-	return hipGetLastError();
 }
 
 } // namespace hmrm

@@ -1,4 +1,4 @@
-// row_cost.cpp -- scheduling aid for the launch order (api.cpp choose_tile_rot): per block of screen rows the
+// row_cost.cpp -- scheduling aid for the launch order (api_launch.cpp choose_tile_rot): per block of screen rows the
 // longest in-box ray, in steps, over a few sample columns.  Approximate arithmetic on purpose -- nothing here
 // reaches a pixel -- so this file is compiled with the compiler's builtins (camera.cpp is not: -fno-builtin keeps
 // its libm calls literal, and made fmin / fmax / sqrt here 150 us of function calls per 4K camera).

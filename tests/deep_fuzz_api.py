@@ -1,4 +1,4 @@
-"""Model-based fuzz of whole API call sequences against the CPU oracle (the host state of csrc/api.cpp: per-stream caches of
+"""Model-based fuzz of whole API call sequences against the CPU oracle (the host state of csrc/api_*.cpp: per-stream caches of
 frame records, the spherical-table arena and donor halves, launch-order calibration and both kernel probes, ticket rings and
 launch lanes, capped counters per stream, hmrm_scene_update with frames in flight, antialiased frames sharing a record with the
 plain frame of the super camera).  Test infrastructure, not collected by pytest:
@@ -52,8 +52,8 @@ MILESTONES = {12: "burst", 40: "update", 70: "orbit", 100: "reopen", 120: "sweep
 ENV_EVERY = 36            # ... and the knobs move on: five kernel settings and the step caps within one period
 SENTINEL = 0xA5
 MAX_IN_FLIGHT = 12
-FRAME_SLOTS = 64          # api.cpp kFrameSlots: cached frame records per stream
-ELIGIBLE_ROWS = 177       # 12 tile rows of 16 pixels: the smallest frame whose launch order is calibrated (api.cpp launch_frame)
+FRAME_SLOTS = 64          # api_internal.hpp kFrameSlots: cached frame records per stream
+ELIGIBLE_ROWS = 177       # 12 tile rows of 16 pixels: the smallest frame whose launch order is calibrated (api_launch.cpp launch_frame)
 MAX_SUPER_PX = 40000      # keeps one oracle frame cheap
 MEMO_FRAMES = 1000        # oracle frames kept (tickets in flight hold their own)
 # (width, height): few distinct sizes so that records collide; some tall enough for calibration by themselves, some under a factor
@@ -138,7 +138,7 @@ def camera_of(spec, seed):
 
 
 class CtxMirror:
-    """What one stream context of api.cpp caches (prepare_frame): 64 records, least recently used first out; the arena of
+    """What one stream context of api_launch.cpp caches (prepare_frame): 64 records, least recently used first out; the arena of
     spherical tables, regrown -- every spherical record dropped -- when a wider camera arrives.  Bookkeeping for the coverage
     report only: expected pixels never depend on it."""
 
@@ -400,7 +400,7 @@ class Plan:
         self.cover["projections"][cam.projection] += 1
         self.cover["samplings"][cam.sampling] += 1
         self.cover["factors"][op["n"]] += 1
-        # what api.cpp launch_frame calls eligible: a full frame of >= 12 tile rows, not instrumented, not the literal loop
+        # what api_launch.cpp launch_frame calls eligible: a full frame of >= 12 tile rows, not instrumented, not the literal loop
         if full and not stats and sup.height >= ELIGIBLE_ROWS and self.kernel != "simple":
             # a record and its calibration live in ONE stream context, and re-reading the knobs resets them
             rec = (ctx, key, self.envs)

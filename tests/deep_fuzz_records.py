@@ -4,7 +4,7 @@ wide (clipped windows), every projection, all three kinds of grid width, cameras
 Test infrastructure, not collected by pytest: python tests/deep_fuzz_records.py <first seed> <scenes> [seconds] [updates].
 
 With `updates` every scene lives through three more hmrm_scene_update calls (other height range, other luminance weights)
-and is compared with the oracle after each: the records are built on demand (api.cpp ensure_records), so a stale table
+and is compared with the oracle after each: the records are built on demand (api_scene.cpp ensure_records), so a stale table
 would show here.  Odd seeds run that mode with HMRM_KERNEL unset and eight moving-camera frames per update, so that the
 scene's own probe (launch_order.cpp) makes the choice between the kernels -- and makes it again after every update."""
 import importlib, os, sys, time
@@ -88,7 +88,7 @@ for k in range(count):
     if updates_mode:
         free_choice = bool(seed & 1)
         camu = cam
-        if free_choice:  # (the probe wants a full frame of at least 12 tile rows: api.cpp launch_frame `eligible`)
+        if free_choice:  # (the probe wants a full frame of at least 12 tile rows: api_launch.cpp launch_frame `eligible`)
             del os.environ["HMRM_KERNEL"]
             camu = hm.Camera.make(width=cam.width, height=208, projection=proj, hfov=cam.hfov, hang=hang, vang=vang, pos=tuple(pos),
                                   ortho_width=cam.ortho_width, step_dist=sd, bg=(cam.bg_r, cam.bg_g, cam.bg_b))

@@ -8,7 +8,8 @@
 //                     every RowMap they lead to must hand every tile row to exactly one grid row, whatever the records
 //                     hold -- and the calibration's state machine under random event sequences;
 //   march_dispatch.hpp  the ladder from (projection, grid mode, kernel kind, sampling) to the march kernels' template
-//                     arguments: every combination reaches its callable exactly once, with exactly those constants.
+//                     arguments: every combination reaches its callable exactly once, with exactly those constants; and
+//                     route_frame, from a frame's request to its family of kernels, against the table written out here.
 //
 // usage: fuzz_host_logic <rounds> ; prints "host logic ok: ..." and returns 0, or aborts under the sanitizers.
 #include <cmath>
@@ -237,7 +238,7 @@ int fuzz_orders(int rounds) {
 			}
 			hmrm::RowMap r;
 			std::memset(&r, 0, sizeof(r));
-			const int safe_rot = rot < 0 || rot >= tiles_y ? 0 : rot; // (api.cpp passes choose_tile_rot's result: inside the frame)
+			const int safe_rot = rot < 0 || rot >= tiles_y ? 0 : rot; // (api_launch.cpp passes choose_tile_rot's result: inside the frame)
 			hmrm::set_tile_order(&r, tiles_y, safe_rot, n, b, c);
 			if (!order_is_a_permutation(r, tiles_y)) {
 				fprintf(stderr, "orders: tiles_y %d rot %d source %d pieces %d [%d+%d %d+%d %d+%d]: not a permutation\n", tiles_y, rot,
@@ -342,6 +343,44 @@ int check_dispatch() {
 	return calls_checked;
 }
 
+// ---- the route from a frame's request to its kernels ------------------------------------------------------------------
+// The table route_frame (march_dispatch.hpp) implements, written out: every value of HMRM_KERNEL (0 leap, 1 group, 2 simple,
+// 3 rec), a map with a side of 2^24 cells or not, the three sampling modes, hmrm_render_interior's flag, and no sun or a sun
+// with each value of hmrm_render_shaded's flags (1 HMRM_SHADE_DIFFUSE, 2 HMRM_SHADE_NO_SHADOWS), each antialiased or not: the
+// factor changes no route (every family's launch picks its AA kernels from the frame's own aa_shift).
+int check_routes() {
+	int routes = 0;
+	for (int forced = 0; forced <= 3; ++forced)
+		for (int huge = 0; huge <= 1; ++huge)
+			for (int sampling = 0; sampling <= 2; ++sampling)
+				for (int aa = 0; aa <= 1; ++aa)
+					for (int interior = 0; interior <= 1; ++interior)
+						for (int sun = -1; sun <= 3; ++sun) { // -1: no sun, else the shade flags
+							const hmrm::FrameRoute r = hmrm::route_frame(forced, huge != 0, sampling, aa != 0, interior != 0, sun >= 0, sun >= 0 ? (unsigned)sun : 0u);
+							// literal only for the reference's sampling, when asked for or when the march kernels cannot index the map;
+							// a huge side with another sampling has no kernel at all
+							const bool want_literal = sampling == 0 && (forced == 2 || huge);
+							const bool want_refused = huge && sampling != 0;
+							hmrm::FrameFamily want_family = hmrm::kFramePlain;
+							bool want_shadows = false, want_ambient = false;
+							switch (sun) {
+							case -1: want_family = interior ? hmrm::kFrameInterior : hmrm::kFramePlain; break; // (the bare flag counts without a sun only)
+							case 0: want_family = hmrm::kFrameLit; want_shadows = true; break;        // hmrm_render_lit's kernels
+							case 1: want_family = hmrm::kFrameLitShaded; want_shadows = true; break;  // DIFFUSE alone: the caller's sun
+							case 2: want_family = hmrm::kFrameShaded; want_ambient = true; break;     // NO_SHADOWS alone: every weight 255
+							default: want_family = hmrm::kFrameShaded; break;                         // both: diffuse levels, the caller's sun
+							}
+							if (r.refused != want_refused || r.literal != want_literal || r.family != want_family || r.shadows != want_shadows ||
+							    r.ambient_sun != want_ambient) {
+								fprintf(stderr, "route: (kernel %d, huge %d, sampling %d, aa %d, interior %d, sun %d) -> refused %d literal %d family %d shadows %d ambient %d\n",
+								        forced, huge, sampling, aa, interior, sun, (int)r.refused, (int)r.literal, (int)r.family, (int)r.shadows, (int)r.ambient_sun);
+								return -1;
+							}
+							++routes;
+						}
+	return routes;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -361,7 +400,9 @@ int main(int argc, char **argv) {
 	const int s = fuzz_calibration(rounds);
 	if (s < 0) return 1;
 	if (check_dispatch() < 0) return 1;
-	printf("host logic ok: %d config streams (%d accepted), %d cameras, %d launch orders, %d calibration runs (%d settled)\n", rounds, a, f,
-	       o, rounds, s);
+	const int r = check_routes();
+	if (r < 0) return 1;
+	printf("host logic ok: %d config streams (%d accepted), %d cameras, %d launch orders, %d calibration runs (%d settled), %d frame routes\n",
+	       rounds, a, f, o, rounds, s, r);
 	return 0;
 }

@@ -209,7 +209,7 @@ def _orbit(gpu, cam, k):
 @pytest.mark.parametrize("kind,proj", [("needles", 2), ("smooth", 1)])
 def test_calibration_and_both_probes_under_antialiasing(gpu, oracle, kind, proj, capfd):
     """An antialiased frame shares the cache record, the launch-order calibration and the kernel probes with the plain frame of
-    its super camera (api.cpp check_antialias -> prepare_frame) but runs another kernel instantiation into a W x H buffer.  A
+    its super camera (api_frames.cpp check_antialias -> api_launch.cpp prepare_frame) but runs another kernel instantiation into a W x H buffer.  A
     camera whose 4x super frame has 15 tile rows: rendered 16 times (first launch, measured trials of either kernel, settled
     launches), then 14 cameras that never repeat through device tickets (the sixth unprobed frame is launched twice), each
     interleaved with the plain frame of the super camera itself; on a map where the groups may win and on a smooth one; with

@@ -258,7 +258,7 @@ def test_hostile_content_full_frames_match_oracle(gpu, oracle, kind):
 
 
 def test_kernel_probe_never_changes_a_pixel(gpu, oracle):
-    """The scene's one-time kernel probe (api.cpp launch_frame: the launch-order calibration of the first repeatedly
+    """The scene's one-time kernel probe (api_launch.cpp launch_frame: the launch-order calibration of the first repeatedly
     rendered camera also times the plain-groups kernel and the scene keeps the faster one): every frame of the sequence
     that carries the probe -- before it, the measured launches of either kernel, after the verdict -- equals the oracle's,
     on a map where the groups win (needles under C5's camera) and on one where the leaps win; HMRM_TRY_GROUP=0 keeps
@@ -754,7 +754,7 @@ def test_window_records_are_the_ninth_highest_and_the_cells_above_it(gpu):
 
 
 def test_window_records_follow_a_height_update(gpu, oracle):
-    """The records are built when the record kernel is first about to run after a height update (api.cpp ensure_records), not
+    """The records are built when the record kernel is first about to run after a height update (api_scene.cpp ensure_records), not
     by the update: frames before and after hmrm_scene_update -- other height range, other luminance weights -- equal the
     oracle's under HMRM_KERNEL=rec, and the table read back afterwards describes the NEW thresholds."""
     rng = np.random.RandomState(11)
@@ -1099,7 +1099,7 @@ def test_strip_pipeline_renders_whole_frames_on_the_gpu(gpu, oracle):
 
 def test_two_streams_two_spherical_cameras(gpu, oracle):
     """hmrm_render_rows_device from two HIP streams with two different spherical cameras, alternating
-    without a host sync in between: each stream has its own tables / counters (api.cpp StreamCtx), so
+    without a host sync in between: each stream has its own tables / counters (api_internal.hpp StreamCtx), so
     neither launch can read the other camera's sin/cos tables."""
     import torch
     rgb, cmap = scenes.small_maps(128, 128, 61)
@@ -1130,7 +1130,7 @@ def test_two_streams_two_spherical_cameras(gpu, oracle):
 def test_moving_spherical_camera_shares_table_halves(gpu, oracle):
     """A moving spherical camera on one stream, no host sync between frames: the library copies the row tables
     (sin / cos of va) or the column tables (of ha) from a cached record when only the other half changed
-    (api.cpp prepare_frame), fills the rest on its host pool and uploads with a kernel of the launch stream.
+    (api_launch.cpp prepare_frame), fills the rest on its host pool and uploads with a kernel of the launch stream.
     Orbit steps (hang and pos change), tilts (vang), both, a translation, a bigger frame in between (the
     per-stream table arena is re-allocated) and more cameras than the cache has slots: every frame equals the
     oracle's (Spherical.cpp:17-31)."""
@@ -1648,7 +1648,7 @@ def test_bilinear_full_size_c3_subsampled(gpu, oracle):
 
 
 def test_launch_order_never_changes_a_pixel(gpu, oracle):
-    """The cost-rotated launch order (api.cpp choose_tile_rot) is scheduling only: HMRM_TILE_ORDER=0
+    """The cost-rotated launch order (api_launch.cpp choose_tile_rot) is scheduling only: HMRM_TILE_ORDER=0
     (row-major) and the default order give identical frames, counters and strips; checked where the
     rotation is non-trivial (horizon in mid-frame) and on a row strip that starts past it."""
     import torch
@@ -1683,7 +1683,7 @@ def test_launch_order_never_changes_a_pixel(gpu, oracle):
 
 
 def test_calibrated_and_pieced_launch_orders_never_change_a_pixel(gpu, oracle, capfd):
-    """The launch order beyond the rotation (api.cpp: up to three tile-row pieces started first, the rest wrapping
+    """The launch order beyond the rotation (api_launch.cpp: up to three tile-row pieces started first, the rest wrapping
     around; calibrated per cached camera from a measured launch, then verified by a second measured launch) is
     scheduling only.  A camera rendered again and again walks through every calibration state -- plain, measured,
     candidate measured, settled -- and every frame, on the scene's stream and on a caller's, equals the oracle's;

@@ -1,4 +1,4 @@
-"""Launch state per stream (csrc/api.cpp StreamCtx) now that nothing is recorded behind a frame on a caller's stream: the
+"""Launch state per stream (csrc/api_internal.hpp StreamCtx) now that nothing is recorded behind a frame on a caller's stream: the
 same pixels whichever stream a frame is launched on, the launch-order calibration of a caller's stream while the scene's
 ticket lanes are busy (others_idle asks those streams directly), and the recycling of a stream's state -- behind a device
 synchronisation -- when a scene is driven from more streams than it keeps state for, with work in flight on a stream whose
@@ -13,7 +13,7 @@ import scenes
 pytestmark = pytest.mark.gpu
 
 MAP = 64
-MAX_STREAM_CTX = 32  # api.cpp kMaxStreamCtx
+MAX_STREAM_CTX = 32  # api_internal.hpp kMaxStreamCtx
 
 
 @pytest.fixture(scope="module")
@@ -32,7 +32,7 @@ def scene(gpu):
 
 
 def spherical(gpu, width=64, height=192):
-    """12 tile rows of 16 pixels: the smallest frame whose launch order is calibrated (api.cpp launch_frame)."""
+    """12 tile rows of 16 pixels: the smallest frame whose launch order is calibrated (api_launch.cpp launch_frame)."""
     return gpu.Camera.make(width=width, height=height, projection=gpu.SPHERICAL, hfov=gpu.degrees_to_rads(160), hang=0.0,
                            vang=gpu.degrees_to_rads(110), pos=(-20.0, 20.0, 30.0), step_dist=0.25, bg=(1, 2, 3))
 
