@@ -109,6 +109,7 @@ int32_t hmrm_config_sun_scope(const hmrm_config *c) { return c->cfg.sun_scope; }
 const char *hmrm_config_sun_map_path(const hmrm_config *c) { return c->cfg.sun_map_path.c_str(); }
 double hmrm_config_sun_map_lift(const hmrm_config *c) { return c->cfg.sun_map_lift; }
 const char *hmrm_config_sky_map_path(const hmrm_config *c) { return c->cfg.sky_map_path.c_str(); }
+const char *hmrm_config_range_map_path(const hmrm_config *c) { return c->cfg.range_map_path.c_str(); }
 void hmrm_config_sky_map_rings(const hmrm_config *c, int32_t *rings, int32_t *per_ring) {
 	if (rings) *rings = c->cfg.sky_map_rings;
 	if (per_ring) *per_ring = c->cfg.sky_map_per_ring;
@@ -213,6 +214,25 @@ int hmrm_write_ppm(const char *path, int32_t w, int32_t h, int32_t comp, const u
 	if (!hmrm::encode_pnm(w, h, comp, data, stride_bytes, &pnm)) return fail(HMRM_E_ARG, "bad image arguments");
 	if (!hmrm::write_file(path, pnm.data(), pnm.size()))
 		return fail(HMRM_E_IO, std::string("Failed to write image to ") + path);
+	return HMRM_OK;
+}
+
+// The portable float map: "Pf" (one component) or "PF" (three), width and height, the scale -1.0 -- negative: little-endian
+// floats -- then the rows BOTTOM TO TOP, each w * comp floats as they are in memory.
+int hmrm_write_pfm(const char *path, int32_t w, int32_t h, int32_t comp, const float *data, size_t stride_bytes) {
+	if (!path || !data) return fail(HMRM_E_ARG, "NULL argument");
+	if (w <= 0 || h <= 0 || (comp != 1 && comp != 3) || stride_bytes < (size_t)w * (size_t)comp * sizeof(float))
+		return fail(HMRM_E_ARG, "bad image arguments");
+	static_assert(sizeof(float) == 4, "PFM holds IEEE binary32");
+	const uint16_t endian_probe = 1;
+	if (*reinterpret_cast<const uint8_t *>(&endian_probe) != 1) return fail(HMRM_E_ARG, "hmrm_write_pfm: little-endian hosts only");
+	const std::string head = std::string(comp == 1 ? "Pf\n" : "PF\n") + std::to_string(w) + " " + std::to_string(h) + "\n-1.0\n";
+	const size_t row = (size_t)w * (size_t)comp * sizeof(float);
+	std::vector<uint8_t> pfm(head.size() + row * (size_t)h);
+	memcpy(pfm.data(), head.data(), head.size());
+	for (int32_t y = 0; y < h; ++y)
+		memcpy(pfm.data() + head.size() + (size_t)y * row, reinterpret_cast<const uint8_t *>(data) + (size_t)(h - 1 - y) * stride_bytes, row);
+	if (!hmrm::write_file(path, pfm.data(), pfm.size())) return fail(HMRM_E_IO, std::string("Failed to write image to ") + path);
 	return HMRM_OK;
 }
 

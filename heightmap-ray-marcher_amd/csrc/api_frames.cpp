@@ -224,6 +224,98 @@ int hmrm_render_interior(const hmrm_scene *scene, const hmrm_camera *cam, uint8_
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, how);
 }
 
+// ---- geometry frames: hmrm_render's frame (hmrm_render_interior's with HMRM_TRACE_INTERIOR) and up to three more planes -- hit
+// cell, range, slope -- from the same launch ----
+// The five refusals of the header, in its order; needs no scene and no device.  A stride is compared with the camera's width
+// only when there is a camera with one: a camera that check_camera refuses is refused right after.
+static int check_geometry_planes(const hmrm_geometry_planes *p, const hmrm_camera *cam, bool device) {
+	if (!p) return fail(HMRM_E_ARG, "geometry frame: NULL planes");
+	if (p->flags & ~HMRM_TRACE_INTERIOR) return fail(HMRM_E_ARG, "hmrm_geometry_planes.flags: undefined bit");
+	if (p->reserved != 0u) return fail(HMRM_E_ARG, "hmrm_geometry_planes.reserved must be 0");
+	if (!p->rgba && !p->cell && !p->range && !p->slope) return fail(HMRM_E_ARG, "geometry frame: every plane is NULL");
+	const size_t width = (cam && cam->width > 0) ? (size_t)cam->width : 0;
+	auto plane = [&](const char *name, const void *ptr, size_t stride, size_t elem) -> int {
+		if (!ptr) return HMRM_OK;
+		if (stride < elem * width || (stride % elem) != 0 || stride / elem > 0x7fffffffu)
+			return fail(HMRM_E_ARG, std::string("geometry frame: ") + name + "_stride must be >= " + std::to_string(elem) +
+			                            " * width, a multiple of " + std::to_string(elem) + " and below 2^31 elements");
+		if (((uintptr_t)ptr % elem) != 0 && (device || elem == 8))
+			return fail(HMRM_E_ARG, std::string("geometry frame: ") + name + " must be " + std::to_string(elem) + "-byte aligned");
+		return HMRM_OK;
+	};
+	int rc;
+	if ((rc = plane("rgba", p->rgba, p->rgba_stride, 4)) || (rc = plane("cell", p->cell, p->cell_stride, 4)) ||
+	    (rc = plane("range", p->range, p->range_stride, 4)) || (rc = plane("slope", p->slope, p->slope_stride, 8)))
+		return rc;
+	return HMRM_OK;
+}
+
+static int ensure_geom(hmrm_scene *s, size_t bytes) {
+	if (bytes <= s->geom_cap) return HMRM_OK;
+	if (s->d_geom) (void)hipFree(s->d_geom);
+	s->d_geom = nullptr;
+	s->geom_cap = 0;
+	HIP_TRY(hipMalloc((void **)&s->d_geom, bytes));
+	s->geom_cap = bytes;
+	return HMRM_OK;
+}
+
+// Launched the way an interior frame is (FrameRequest::own_kernels): never measured, never the probe, with the scene's current
+// kernel.  With the flag every origin is tested by the kernels, whatever the projection.  `device`: p holds device pointers and
+// the launch goes to `stream` without a host sync; else the planes are staged through the scene's buffer, slope first (8-byte
+// elements), rows packed, and copied to the caller's behind the launch.
+static int render_geometry_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm_geometry_planes *p, bool device, hipStream_t stream) {
+	int rc = check_geometry_planes(p, cam, device);
+	if (rc || (rc = check_camera(cam))) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	uint32_t *d_rgba = (uint32_t *)p->rgba;
+	hmrm::GeomPlanes dev{p->cell, p->range, p->slope, (int64_t)(p->cell_stride / 4), (int64_t)(p->range_stride / 4), (int64_t)(p->slope_stride / 8)};
+	int64_t rgba_stride_px = (int64_t)(p->rgba_stride / 4);
+	if (!device) {
+		const size_t px = W * H;
+		if ((rc = ensure_geom(s, px * ((p->slope ? 8 : 0) + (p->rgba ? 4 : 0) + (p->cell ? 4 : 0) + (p->range ? 4 : 0))))) return rc;
+		uint8_t *at = s->d_geom;
+		auto take = [&](const void *wanted, size_t elem) -> void * {
+			if (!wanted) return nullptr;
+			void *here = at;
+			at += px * elem;
+			return here;
+		};
+		dev.slope = (float *)take(p->slope, 8);
+		d_rgba = (uint32_t *)take(p->rgba, 4);
+		dev.cell = (int32_t *)take(p->cell, 4);
+		dev.range = (float *)take(p->range, 4);
+		dev.cell_stride = dev.range_stride = dev.slope_stride = rgba_stride_px = (int64_t)W;
+		stream = s->stream;
+	}
+	FrameSetup fs;
+	if ((rc = setup_frame(s, stream, cam, 0, &fs))) return rc;
+	StreamCtx *const c = fs.c;
+	FrameRequest req = plain_request(d_rgba, rgba_stride_px);
+	req.interior = (p->flags & HMRM_TRACE_INTERIOR) ? Interior::kByKernels : Interior::kNot;
+	req.geom = &dev;
+	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req)) || device) return rc;
+	if (p->slope) HIP_TRY(hipMemcpy2DAsync(p->slope, p->slope_stride, dev.slope, W * 8, W * 8, H, hipMemcpyDeviceToHost, s->stream));
+	if (p->rgba) HIP_TRY(hipMemcpy2DAsync(p->rgba, p->rgba_stride, d_rgba, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
+	if (p->cell) HIP_TRY(hipMemcpy2DAsync(p->cell, p->cell_stride, dev.cell, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
+	if (p->range) HIP_TRY(hipMemcpy2DAsync(p->range, p->range_stride, dev.range, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
+	unsigned long long capped_now = 0;
+	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	return noterm(new_capped(c, capped_now));
+}
+
+int hmrm_render_geometry(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_geometry_planes *host_planes) {
+	return render_geometry_common(const_cast<hmrm_scene *>(scene), cam, host_planes, false, nullptr);
+}
+
+int hmrm_render_geometry_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_geometry_planes *device_planes, void *hip_stream) {
+	return render_geometry_common(const_cast<hmrm_scene *>(scene), cam, device_planes, true, (hipStream_t)hip_stream);
+}
+
 // Sun shadows: hmrm_render's frame (hmrm_render_interior's with HMRM_TRACE_INTERIOR), the hit pixels' shadow rays marched
 // by the same launch.  The sun is checked before anything else is looked at (check_sun: hmrm_render_lit's three refusals,
 // hmrm_render_shaded's too).

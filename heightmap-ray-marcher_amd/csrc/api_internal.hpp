@@ -176,6 +176,8 @@ struct hmrm_scene {
 	size_t cells_cap = 0;
 	double *d_targets = nullptr; // ... and of hmrm_cell_map_sum's targets (its words go through d_cells)
 	size_t targets_cap = 0;
+	uint8_t *d_geom = nullptr; // ... and of hmrm_render_geometry's planes: the wanted ones back to back, rows packed
+	size_t geom_cap = 0;
 	// launch state per stream; `mu` guards the list and the slot choice (launches themselves are
 	// asynchronous), so that threads driving different streams of one scene do not collide
 	std::mutex mu;
@@ -232,9 +234,12 @@ struct FrameRequest {
 	bool no_probe; // the caller cannot have this frame launched twice (HMRM_NO_PROBE)
 	Interior interior;
 	const LitFrame *lit; // null: no sun
-	// Frames under the interior rule or with a sun run kernels of their own, with the scene's current kernel kind (HMRM_KERNEL or
-	// the probe's verdict, read only).
-	bool own_kernels() const { return interior != Interior::kNot || lit != nullptr; }
+	// hmrm_render_geometry's frame: the device planes the launch stores beside the pixel (d_out may be null then); null: none.
+	// Its primary rays are under the interior rule when `interior` is not kNot -- the geometry kernels test each origin.
+	const hmrm::GeomPlanes *geom = nullptr;
+	// Frames under the interior rule, with a sun or with geometry planes run kernels of their own, with the scene's current kernel
+	// kind (HMRM_KERNEL or the probe's verdict, read only).
+	bool own_kernels() const { return interior != Interior::kNot || lit != nullptr || geom != nullptr; }
 	// Special frames -- those and instrumented ones -- are launched in the plain rotation order: never measured, never a probe,
 	// not counted towards the probe.
 	bool special() const { return stats || own_kernels(); }

@@ -85,7 +85,7 @@ void poll_shadow_probe(hmrm_scene *s) {
 // The launch of `req` on the context's stream, for the plain family (launch_kernel sets another).
 hmrm::FrameLaunch frame_launch(const hmrm_scene *s, const StreamCtx *c, const hmrm::DevFrame &f, const hmrm::RowMap &rows, const FrameRequest &req) {
 	return hmrm::FrameLaunch{s->d_thr, s->d_thr32, s->d_cmap, s->d_records, req.d_out, req.out_stride_px, c->d_counters, req.d_steps,
-	                         req.d_entry, req.stats, f, rows, hmrm::kFramePlain, hmrm::SunRules{}, false, c->stream};
+	                         req.d_entry, req.stats, f, rows, hmrm::kFramePlain, hmrm::SunRules{}, false, hmrm::GeomPlanes{}, c->stream};
 }
 
 // The shadow probe: this frame twice into the same buffer -- production kernel, then the other kernel (launch_kernel: the
@@ -141,6 +141,11 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		l.sun = lit->sun;
 		if (route.ambient_sun) l.sun.ambient = 255u;
 		l.primary_interior = lit->primary_interior;
+	}
+	if (req.geom) { // (the literal-or-march decision is the plain frame's: route_frame knows no geometry family)
+		l.family = hmrm::kFrameGeometry;
+		l.geo = *req.geom;
+		l.primary_interior = req.interior != Interior::kNot;
 	}
 	if (route.literal) {
 		HIP_TRY(hmrm::launch_frame_literal(l));

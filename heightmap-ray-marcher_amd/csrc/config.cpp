@@ -17,6 +17,7 @@
 //   shading on|off, sun_scope single|all
 //   sun_map <path.png>, sun_map_lift v                (the whole map's light map, hmrm_cell_map, written by the CLI)
 //   sky_map <path.png>, sky_map_rings r n             (the whole map's sky-view map, hmrm_cell_map_sum, written by the CLI)
+//   range_map <path.pfm>                              (the camera's range plane, hmrm_render_geometry, written by the CLI)
 #include "config.hpp"
 
 #include <cmath>
@@ -311,6 +312,7 @@ const Row kGrammar[] = {
 	{"sun_map_lift", scalar<&Config::sun_map_lift>},
 	{"sky_map", scalar<&Config::sky_map_path>},
 	{"sky_map_rings", sky_map_rings_key},
+	{"range_map", scalar<&Config::range_map_path>},
 };
 
 } // namespace

@@ -64,6 +64,9 @@ struct Config {
 	// over hmrm_sky_directions(r, n), scaled to a byte); `sky_map_rings r n` -- the directions, r * n in 1 .. 256
 	std::string sky_map_path;
 	int sky_map_rings = 4, sky_map_per_ring = 16;
+	// additive: `range_map <path.pfm>` -- the CLI also writes the range plane of the configured camera's geometry frame
+	// (hmrm_render_geometry; under the interior rule with `interior on`) there as a one-component portable float map
+	std::string range_map_path;
 
 	bool heightmap_dirty = false; // should_update_heightmap, sticky until taken
 	std::ostringstream log;       // what the reference prints to stdout

@@ -135,21 +135,34 @@ __device__ __forceinline__ uint32_t diffuse_level(double gx, double gy, const do
 	k = k > 0.0 ? (k < 1.0 ? k : 1.0) : 0.0;
 	return (uint32_t)(k * 255.0 + 0.5);
 }
-// ... of the hit cell `cell` for the nearest-cell modes: central differences of the threshold table the march reads (F32: its
-// float copy, widened), one-sided on the map's border, 0 along a side of one cell.
+// The gradient (gx, gy) of the hit cell `cell` for the nearest-cell modes: central differences of the threshold table the march
+// reads (F32: its float copy, widened), one-sided on the map's border, 0 along a side of one cell.  The one expression behind
+// the diffuse level and the slope plane of a geometry frame -- written as a macro that declares gx and gy in its user's scope,
+// not as a function: a helper between diffuse_level_nearest and these loads, whichever way it handed the two doubles back (by
+// reference, by value, to a callable; inlining forced or not), made the compiler order the existing kernels' instructions
+// differently, and those kernels keep theirs.
+#define HMRM_GRADIENT_NEAREST(F32, f, thr, cell)                                                                    \
+	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);                                         \
+	const int w = f.map_w, h = f.map_h;                                                                             \
+	const int cy = (int)(cell / (unsigned)w), cx = (int)(cell - (unsigned)cy * (unsigned)w);                        \
+	const int xm = max(cx - 1, 0), xp = min(cx + 1, w - 1), ym = max(cy - 1, 0), yp = min(cy + 1, h - 1);           \
+	const size_t row = (size_t)cy * (size_t)w, ixm = row + (size_t)xm, ixp = row + (size_t)xp;                      \
+	const size_t iym = (size_t)ym * (size_t)w + (size_t)cx, iyp = (size_t)yp * (size_t)w + (size_t)cx;              \
+	const double txm = F32 ? (double)thr32[ixm] : thr[ixm], txp = F32 ? (double)thr32[ixp] : thr[ixp];              \
+	const double tym = F32 ? (double)thr32[iym] : thr[iym], typ = F32 ? (double)thr32[iyp] : thr[iyp];              \
+	const double gx = xp > xm ? (txp - txm) / ((double)(xp - xm) * f.grid_width) : 0.0;                             \
+	const double gy = yp > ym ? (typ - tym) / ((double)(yp - ym) * f.grid_width) : 0.0
+struct Gradient { double gx, gy; };
+template <bool F32>
+__device__ __forceinline__ Gradient gradient_nearest(const DevFrame &f, const double *__restrict__ thr, unsigned cell) {
+	HMRM_GRADIENT_NEAREST(F32, f, thr, cell);
+	return Gradient{gx, gy};
+}
+// ... and the diffuse level of that cell.
 template <bool F32>
 __device__ __forceinline__ uint32_t diffuse_level_nearest(const DevFrame &f, const double *__restrict__ thr, unsigned cell,
                                                           const double (&s)[3]) {
-	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
-	const int w = f.map_w, h = f.map_h;
-	const int cy = (int)(cell / (unsigned)w), cx = (int)(cell - (unsigned)cy * (unsigned)w);
-	const int xm = max(cx - 1, 0), xp = min(cx + 1, w - 1), ym = max(cy - 1, 0), yp = min(cy + 1, h - 1);
-	const size_t row = (size_t)cy * (size_t)w, ixm = row + (size_t)xm, ixp = row + (size_t)xp;
-	const size_t iym = (size_t)ym * (size_t)w + (size_t)cx, iyp = (size_t)yp * (size_t)w + (size_t)cx;
-	const double txm = F32 ? (double)thr32[ixm] : thr[ixm], txp = F32 ? (double)thr32[ixp] : thr[ixp];
-	const double tym = F32 ? (double)thr32[iym] : thr[iym], typ = F32 ? (double)thr32[iyp] : thr[iyp];
-	const double gx = xp > xm ? (txp - txm) / ((double)(xp - xm) * f.grid_width) : 0.0;
-	const double gy = yp > ym ? (typ - tym) / ((double)(yp - ym) * f.grid_width) : 0.0;
+	HMRM_GRADIENT_NEAREST(F32, f, thr, cell);
 	return diffuse_level(gx, gy, s);
 }
 // The weight w in 0..255 of a hit pixel that is not shadowed, from its level, and the pixel under a weight:
@@ -481,6 +494,27 @@ __device__ __forceinline__ void store_box_filtered(uint32_t *__restrict__ out, i
 	const int corner = ((1 << shift) - 1) * (kWaveW + 1); // lane bits that must be zero in a block's first lane
 	if (live && (lane & corner) == 0)
 		out[(uint64_t)(uint32_t)(lrow >> shift) * (uint64_t)out_stride_px + (uint32_t)(px >> shift)] = pack_rgba(r, gg, b);
+}
+
+// Epilogue of the geometry frames (hmrm_render_geometry; frame.hpp GeomPlanes): the cell and range planes of a lane whose ray
+// hit in cell `cell` at int_point = (x, y, z), or did not hit.  The pointers are kernel arguments: each test is a scalar branch.
+// The ray's origin is made again here rather than held across the march (it is per pixel only for orthographic frames); the
+// range is hmrm.h's: sqrt((ex * ex + ey * ey) + ez * ez) in doubles, correctly rounded, then rounded to float.
+template <int PROJ>
+__device__ __forceinline__ void store_geometry(const DevFrame &f, const GeomPlanes &geo, const PixelId &pid, bool hit, unsigned cell,
+                                               double x, double y, double z) {
+	if (geo.cell != nullptr) geo.cell[(uint64_t)(uint32_t)pid.lrow * (uint64_t)geo.cell_stride + (uint32_t)pid.px] = hit ? (int32_t)cell : -1;
+	if (geo.range != nullptr) {
+		const DevRay o = make_ray<PROJ>(f, pid.px, pid.py);
+		const double ex = x - o.px, ey = y - o.py, ez = z - o.pz;
+		const double r = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+		geo.range[(uint64_t)(uint32_t)pid.lrow * (uint64_t)geo.range_stride + (uint32_t)pid.px] = hit ? (float)r : __builtin_huge_valf();
+	}
+}
+// ... and the slope plane: one 8-byte store per lane.
+__device__ __forceinline__ void store_slope(const GeomPlanes &geo, const PixelId &pid, bool hit, double gx, double gy) {
+	const float2 v = hit ? make_float2((float)gx, (float)gy) : make_float2(0.0f, 0.0f);
+	reinterpret_cast<float2 *>(geo.slope)[(uint64_t)(uint32_t)pid.lrow * (uint64_t)geo.slope_stride + (uint32_t)pid.px] = v;
 }
 
 } // namespace hmrm

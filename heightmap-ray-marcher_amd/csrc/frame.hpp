@@ -287,6 +287,19 @@ struct CellSums {
 };
 constexpr int kMaxSumTargets = 256;
 
+// ---- geometry frames (hmrm_render_geometry; GEOM in the kernels) ----
+// What the march knows about a pixel besides its colour, stored by the same launch: the hit cell gridx + gridy * W (-1: no
+// hit), the distance from the ray's origin to int_point as a float (+inf: no hit), and the surface gradient (gx, gy) of
+// hmrm_render_shaded's level as two floats (+0, +0: no hit).  Every pointer may be null -- that plane is not written; so may
+// the kernel's colour target, and the colour is not fetched then.  Strides count ELEMENTS per local row: int32s, floats,
+// pairs of floats.  An extra argument of the geometry kernels' own __global__ entry points, like SegRules.
+struct GeomPlanes {
+	int32_t *cell;
+	float *range;
+	float *slope; // pairs, 8-byte aligned
+	int64_t cell_stride, range_stride, slope_stride;
+};
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

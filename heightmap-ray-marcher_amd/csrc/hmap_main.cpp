@@ -20,6 +20,7 @@
 // one byte per cell under the config's sun, the camera's sampling, `sun_map_lift` above the surface; diffuse levels with
 // `shading on`, shadow rays unless `shading on` stands without `shadows on`) is written there as a one-component PNG.
 // `sky_map <path.png>`: after that, the whole map's sky-view map (hmrm_cell_map_sum over `sky_map_rings r n` sky directions).
+// `range_map <path.pfm>`: after the frames and before the sun map, the range plane of the configured camera (hmrm_render_geometry).
 #include <sys/stat.h>
 
 #include <cmath>
@@ -49,6 +50,31 @@ static int wanted_devices(hmrm_config *cfg, int *visible_out) {
 static bool ends_with(const std::string &s, const char *suffix) {
 	const size_t n = strlen(suffix);
 	return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+// `range_map <path.pfm>`: the range plane of the configured camera's geometry frame (hmrm_render_geometry; under the interior rule
+// with `interior on`) as a one-component portable float map.  Returns false when it could not be made or written.
+static bool write_range_map(hmrm_config *cfg, hmrm_scene *scene, const hmrm_camera &cam, bool interior) {
+	const std::string path = hmrm_config_range_map_path(cfg);
+	if (path.empty()) return true;
+	std::vector<float> range((size_t)cam.width * cam.height);
+	hmrm_geometry_planes planes;
+	memset(&planes, 0, sizeof planes);
+	planes.range = range.data();
+	planes.range_stride = (size_t)cam.width * sizeof(float);
+	planes.flags = interior ? HMRM_TRACE_INTERIOR : 0u;
+	const int rc = hmrm_render_geometry(scene, &cam, &planes);
+	if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+		std::cerr << hmrm_last_error() << "\n";
+		return false;
+	}
+	if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+	if (hmrm_write_pfm(path.c_str(), cam.width, cam.height, 1, range.data(), planes.range_stride) != HMRM_OK) {
+		std::cerr << "Failed to write range map to " << path << "\n";
+		return false;
+	}
+	std::cout << "Saved range map at " << path << "\n";
+	return true;
 }
 
 // `sun_map <path>`: the whole map's light map, one byte per cell.  Returns false when it could not be made or written.
@@ -205,6 +231,7 @@ int main(int argc, char *argv[]) {
 			                             aa > 1 ? HMRM_AA(aa) : 0u);
 		if (rc != HMRM_OK) std::cerr << hmrm_last_error() << "\n";
 		for (size_t i = 1; i < scenes.size(); ++i) hmrm_scene_destroy(scenes[i]);
+		if (rc == HMRM_OK && !write_range_map(cfg, scene, cam, interior)) rc = HMRM_E_IO;
 		if (rc == HMRM_OK && !write_sun_map(cfg, scene, cam, shading, shadows)) rc = HMRM_E_IO;
 		if (rc == HMRM_OK && !write_sky_map(cfg, scene, cam)) rc = HMRM_E_IO;
 		hmrm_scene_destroy(scene);
@@ -318,6 +345,7 @@ int main(int argc, char *argv[]) {
 		std::cerr << "Failed to write screenshot to " << path << "\n";
 	else
 		std::cout << "Saved screenshot at " << path << "\n";
+	if (wrc == HMRM_OK && !write_range_map(cfg, scene, cam, interior)) wrc = HMRM_E_IO;
 	if (wrc == HMRM_OK && !write_sun_map(cfg, scene, cam, shading, shadows)) wrc = HMRM_E_IO;
 	if (wrc == HMRM_OK && !write_sky_map(cfg, scene, cam)) wrc = HMRM_E_IO;
 

@@ -96,6 +96,17 @@ constexpr double kUpRatio = HMRM_UP_RATIO; // see the level policy in k_render_f
 #define HMRM_EARLY_LOAD 1
 #endif
 constexpr bool kEarlyLoad = HMRM_EARLY_LOAD != 0;
+// Geometry frames (GEOM below), for A/B builds of render_geometry.hip: HMRM_GEOM_CHAIN 1 keeps the hit point the way the ray
+// batches do (a select chain over the group's positions into three doubles held across the loop) instead of KEEP_P's re-add;
+// HMRM_GEOM_CARRY 0 reads the level state off the level at every attempt instead of carrying it.  The defaults are what the
+// registers decided: DESIGN.md 5.16.
+#ifndef HMRM_GEOM_CHAIN
+#define HMRM_GEOM_CHAIN 0
+#endif
+#ifndef HMRM_GEOM_CARRY
+#define HMRM_GEOM_CARRY 0
+#endif
+constexpr bool kGeomChain = HMRM_GEOM_CHAIN != 0, kGeomCarry = HMRM_GEOM_CARRY != 0;
 
 // ---- bilinear quality mode (HMRM_BILINEAR; a build-side addition, not in the reference) ----
 // Same definition, operation for operation, as oracle/hmrm_oracle.c "bilinear quality mode":
@@ -123,15 +134,23 @@ __device__ __forceinline__ double bil_mix(const Bil &b, double f00, double f10, 
 	const double c = f01 + b.tx * (f11 - f01);
 	return a + b.ty * (c - a);
 }
-// Diffuse level (device_common.hpp diffuse_level) of the interpolated surface at a hit point whose neighbours and weights are
-// `b`: the gradient of bil_mix's surface there, a = f10 - f00, b = f11 - f01 mixed along y, c = f01 - f00, d = f11 - f10 along x.
+// The gradient of the interpolated surface at a hit point whose neighbours and weights are `b`: that of bil_mix's surface there,
+// a = f10 - f00, b = f11 - f01 mixed along y, c = f01 - f00, d = f11 - f10 along x -- and its diffuse level (device_common.hpp
+// diffuse_level).  The slope plane of a geometry frame stores the former.
+// (A macro that declares gx and gy in its user's scope, for the reason device_common.hpp gives at HMRM_GRADIENT_NEAREST.)
+#define HMRM_GRADIENT_BILINEAR(f, thr, b)                                                   \
+	const double t00 = thr[b.c00], t10 = thr[b.c10], t01 = thr[b.c01], t11 = thr[b.c11];    \
+	const double ax = t10 - t00, bx = t11 - t01;                                            \
+	const double gx = (ax + b.ty * (bx - ax)) / f.grid_width;                               \
+	const double cy = t01 - t00, dy = t11 - t10;                                            \
+	const double gy = (cy + b.tx * (dy - cy)) / f.grid_width
+__device__ __forceinline__ Gradient gradient_bilinear(const DevFrame &f, const double *__restrict__ thr, const Bil &b) {
+	HMRM_GRADIENT_BILINEAR(f, thr, b);
+	return Gradient{gx, gy};
+}
 __device__ __forceinline__ uint32_t diffuse_level_bilinear(const DevFrame &f, const double *__restrict__ thr, const Bil &b,
                                                            const double (&s)[3]) {
-	const double t00 = thr[b.c00], t10 = thr[b.c10], t01 = thr[b.c01], t11 = thr[b.c11];
-	const double ax = t10 - t00, bx = t11 - t01;
-	const double gx = (ax + b.ty * (bx - ax)) / f.grid_width;
-	const double cy = t01 - t00, dy = t11 - t10;
-	const double gy = (cy + b.tx * (dy - cy)) / f.grid_width;
+	HMRM_GRADIENT_BILINEAR(f, thr, b);
 	return diffuse_level(gx, gy, s);
 }
 // Colour at a hit: R,G,B interpolated and rounded with floor(f + 0.5); the alpha-0 rule
@@ -214,15 +233,21 @@ __device__ __forceinline__ DevRay cell_ray_of(const CellRules &c, const DevFrame
 // LIT's "entry, then the march loop, once more" generalised: the wave runs it once per target of a wave-uniform list, the lane
 // folds each pass's value -- k_cell_map's byte for that target, or 1 for a ray that did not hit -- into a register, and the
 // epilogue stores ONE 16-bit WORD through `out` (`out_stride_px` counts bytes).  Capped rays are counted per pass.
+// GEOM (instantiated in render_geometry.hip only; hmrm_render_geometry, frame.hpp GeomPlanes; implies SEG): a geometry frame.  An
+// epilogue: beside the pixel the lane stores its hit cell, the distance from its ray's origin to int_point and the surface
+// gradient SHADE takes its level from, each through a pointer of `geo` that may be null -- and so may `out`: the colour is not
+// fetched then.  A lane that hit leaves the loop with int_point in x, y, z (KEEP_P's re-add, with z stepped like x and y) and
+// with hcell; the ray's origin is made again in the epilogue.  Again `if constexpr` statements beside the others' own.
 template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false, bool SHADE = false,
-          bool SUM = false>
+          bool SUM = false, bool GEOM = false>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
                                                 int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{},
                                                 const SunRules &sun = SunRules{}, const CellRules &cells = CellRules{},
-                                                const CellSums &sums = CellSums{}) {
+                                                const CellSums &sums = CellSums{}, const GeomPlanes &geo = GeomPlanes{}) {
 	constexpr bool CELLS = PROJ == 5;
+	static_assert(!GEOM || (SEG && !CELLS && PROJ != 4 && !STATS && !AA && !LIT && !SHADE), "geometry frames: plain frames under the segment rules");
 	static_assert(!SUM || CELLS, "accumulated cell maps: the cell kernels' march, once per target");
 	static_assert(!CELLS || (SEG && !STATS && !AA && !LIT && !SHADE), "cell maps: segment rays, one byte per cell");
 	static_assert(!LIT || (SEG && PROJ != 4), "sun shadows: frames, under the segment rules");
@@ -232,22 +257,27 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	// the point too; without LIT the plain groups take it that way, the leap kernels keep the hit's exact cell coordinates
 	// instead (KEEP_Q) -- each the cheaper of the two in registers for its family, DESIGN.md 5.12 -- and from them they also
 	// mix the pixel behind the loop (DEFER), shaded or not.
-	constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && LEAP != 0;
-	constexpr bool KEEP_P = LIT || (SHADE && BILINEAR && !KEEP_Q);
+	// GEOM wants the whole point, in every sampling mode: KEEP_P with z stepped like x and y (no threshold is kept), which holds
+	// nothing across the loop -- RAYS' select chain keeps three doubles more.
+	constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && LEAP != 0 && !GEOM;
+	constexpr bool KEEP_P = LIT || (SHADE && BILINEAR && !KEEP_Q) || (GEOM && !kGeomChain);
+	constexpr bool CHAIN = PROJ == 4 || (GEOM && kGeomChain); // (the hit point by RAYS' select chain: hx, hy, hz)
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	// DEFER: a hit lane's colour is fetched behind the march loop, from the hit cell it leaves the loop with (hcell below; the
 	// bilinear mode: and from the hit point, KEEP_P / KEEP_Q), not inside it.  Two exceptions keep the in-loop form.  The record
 	// kernels of the interior and the shaded frames without shadow rays: two of them sit on the scalar registers' limit and the
 	// epilogue's load costs them a spill slot (profiles/r09_registers.txt).  And the bilinear mode of the plain groups: leaving
 	// the loop with the hit point made that kernel 20 % SLOWER where it was measured (0.263 -> 0.316 ms, profiles/r09_ab.txt).
-	constexpr bool DEFER = !CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0);
+	// (GEOM: always behind the loop -- a null colour target skips the fetch there, a scalar branch)
+	constexpr bool DEFER = GEOM || (!CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0));
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || !STATS, "segment rules: production kernels only");
 	static_assert(!SEG || !AA || LIT || SHADE, "segment rules: antialiased for the sun-lit frames only");
 	constexpr bool REC = LEAP == 2;                     // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
 	// CARRY: a ray holds its level state in a register (see the leap state below).  The cell maps, the sun shadows, the ray batches
-	// and the shaded record kernels sit on a register granule: a register more would cost them a resident wave per SIMD.
-	constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !RAYS && !(SHADE && REC);
+	// and the shaded record kernels sit on a register granule: a register more would cost them a resident wave per SIMD -- as it
+	// would six of the geometry kernels (general grid widths: 73 against 71 vector registers, 81 against 80 with window records).
+	constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !RAYS && !(SHADE && REC) && !(GEOM && !kGeomCarry);
 	constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
 	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
 	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
@@ -299,7 +329,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 
 		uint32_t rgba = 0;
 		bool real_hit = false;
-		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired)
+		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired; GEOM: hz, beside hqx and hqy)
 		// The cell hmap.cpp:1016 fired in (LIT: for the primary ray).  The one thing a hit lane of the nearest-cell modes carries out
 		// of the march loop: its colour (below the loop: one load for all hit lanes of the wave, where the loop had one, and a wait
 		// for it, in every trip in which any lane hit), SHADE's diffuse level and the ray batches' record are all made from it.
@@ -743,7 +773,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							if constexpr (LIT) hcell = lt.phase ? hcell : hit_cell; // (the primary ray's)
 							else hcell = hit_cell;
 							real_hit = true;
-							if constexpr (RAYS) {
+							if constexpr (CHAIN) {
 								hx = X[0]; hy = Y[0]; hz = Z[0];
 #pragma unroll
 								for (int j = 1; j < U; ++j) {
@@ -757,12 +787,14 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								// below.  The lane leaves the loop with it in x, y, z, which nothing else reads after a hit, so no
 								// register is held across the loop for it; and X[hit_j] is made again from the group's start with
 								// the same sequential adds (the same bits) so that X[1 .. U-2] need not outlive the cell indices.
-								double ox = x, oy = y, ot = T[0];
+								// (GEOM: int_point itself -- z is stepped like x and y, no threshold is kept)
+								double ox = x, oy = y, ot = GEOM ? z : T[0];
 #pragma unroll
 								for (int j = 1; j < U; ++j) {
 									ox = hit_j >= j ? ox + sx : ox;
 									oy = hit_j >= j ? oy + sy : oy;
-									ot = hit_j == j ? T[j] : ot;
+									if constexpr (GEOM) ot = hit_j >= j ? ot + sz : ot;
+									else ot = hit_j == j ? T[j] : ot;
 								}
 								x = ox; y = oy; z = ot;
 							}
@@ -794,8 +826,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								if constexpr (KEEP_Q) { hqx = qx; hqy = qy; }
 								if constexpr (LIT) hcell = lt.phase ? hcell : (unsigned)c; // (as in the group: the colour comes behind the loop)
 								else hcell = (unsigned)c;
-								if constexpr (RAYS) { hx = xs; hy = ys; hz = zs; }
-								if constexpr (KEEP_P) { x = xs; y = ys; z = t; } // (as above)
+								if constexpr (CHAIN) { hx = xs; hy = ys; hz = zs; }
+								if constexpr (KEEP_P) { x = xs; y = ys; z = GEOM ? zs : t; } // (as above)
 								done = true;
 								break;
 							}
@@ -826,6 +858,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					if (lt.phase == 0) { lt.hx = x; lt.hy = y; lt.t = z; }
 				} else
 				if constexpr (LIT) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
+				else if constexpr (GEOM && kGeomChain) { hqx = hx; hqy = hy; }
+				else if constexpr (GEOM) { hqx = x; hqy = y; hz = z; } // (int_point of a lane that hit)
 				else if constexpr (KEEP_P) { hqx = x; hqy = y; } // (SHADE, bilinear: the same two, for the gradient at P)
 			}
 			if constexpr (LIT) {
@@ -908,7 +942,10 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		} while ((LIT || SUM) && again);
 		// The hit lanes' colour: fetched here, once, behind the march (LIT, nearest-cell modes: behind both marches).
 		double qxh = hqx, qyh = hqy; // (bilinear: the hit's cell coordinates, for the colour and SHADE's gradient)
-		if constexpr (BILINEAR && KEEP_P && !LIT) cell_coords_of(hqx, hqy, qxh, qyh);
+		if constexpr (BILINEAR && (KEEP_P || GEOM) && !LIT) cell_coords_of(hqx, hqy, qxh, qyh);
+		if constexpr (GEOM) {
+			if (out != nullptr && real_hit) rgba = BILINEAR ? bilinear_pixel(qxh, qyh) : shade_hit(f, cmap[hcell]);
+		} else
 		if constexpr (DEFER && !LIT) {
 			if (real_hit) rgba = BILINEAR ? bilinear_pixel(qxh, qyh) : shade_hit(f, cmap[hcell]);
 		}
@@ -975,6 +1012,18 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				v = cell_weight(cells, real_hit, q);
 			}
 			reinterpret_cast<uint8_t *>(out)[(uint64_t)(uint32_t)pid.lrow * (uint64_t)out_stride_px + (uint32_t)pid.px] = (uint8_t)v;
+		} else
+		if constexpr (GEOM) { // (a capped ray is no hit in any plane; its pixel is the miss shade, as in every frame)
+			if (out != nullptr) out[(uint64_t)(uint32_t)pid.lrow * (uint32_t)out_stride_px + (uint32_t)pid.px] = rgba;
+			store_geometry<PROJ>(f, geo, pid, real_hit, hcell, hqx, hqy, hz);
+			if (geo.slope != nullptr) {
+				Gradient g{0.0, 0.0};
+				if (real_hit) {
+					if constexpr (BILINEAR) g = gradient_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h));
+					else g = gradient_nearest<F32>(f, thr, hcell);
+				}
+				store_slope(geo, pid, real_hit, g.gx, g.gy);
+			}
 		} else
 		if constexpr (RAYS) {
 			const unsigned cy = hcell / (unsigned)f.map_w; // (gridx, gridy of hmap.cpp:1001-1004 from gridx + gridy * W)

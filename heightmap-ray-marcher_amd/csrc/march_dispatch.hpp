@@ -13,8 +13,10 @@ namespace hmrm {
 enum FastKernel { kPlainGroups = 0, kLeaps = 1, kRecords = 2 };
 
 // Which kernels render a frame (render.hpp FrameLaunch): hmrm_render's, or the ones built with the interior rule, with
-// shadow rays, with diffuse shading without or with shadow rays.
-enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded };
+// shadow rays, with diffuse shading without or with shadow rays, or the ones that store the geometry planes too.
+// (kFrameGeometry is no result of route_frame: a geometry frame takes the literal-or-march decision from it and sets the
+// family itself, api_launch.cpp.)
+enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded, kFrameGeometry };
 
 // Which launch a frame gets.  `forced`: HMRM_KERNEL (2: simple); `huge_side`: a map side of 2^24 cells or more -- the production
 // kernel indexes cells and windows with 24-bit multiplies, leap_common.hpp index_2d; `interior`: hmrm_render_interior's frame

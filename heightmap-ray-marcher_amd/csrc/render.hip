@@ -92,7 +92,8 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
                                                     const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                     int64_t out_stride_px, const StatsOut &st, const RayBatch &batch,
                                                     const SegRules &seg = SegRules{}, const SunRules &sun = SunRules{},
-                                                    LitState<true> *lit = nullptr, unsigned *hit_cell = nullptr) {
+                                                    LitState<true> *lit = nullptr, unsigned *hit_cell = nullptr,
+                                                    double *hit_z = nullptr) { // (hit_z: pass 1, may be null: int_point's z, geometry frames)
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	static_assert(LIT == 0 || (SEG && !RAYS), "sun shadows: frames, under the segment rules");
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
@@ -181,6 +182,7 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 					if constexpr (LIT == 1) {
 						lit->hx = x; lit->hy = y; lit->t = t;
 						if (hit_cell) *hit_cell = (unsigned)cell; // (maps hold at most 2^29 cells)
+						if (hit_z) *hit_z = z;
 					}
 					break;
 				}
@@ -420,6 +422,31 @@ __global__ __launch_bounds__(kBlockThreads) void k_cell_map_sum_literal(const De
 	*reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(out) + (int64_t)pid.lrow * stride_bytes + 2 * (int64_t)pid.px) = (uint16_t)acc;
 }
 
+// A pixel of a geometry frame (hmrm_render_geometry with HMRM_KERNEL=simple, or on a map with a side of 2^24 cells; frame.hpp
+// GeomPlanes): the primary ray of a lit pixel -- its colour, whether it hit, where and in which cell -- then the planes, each
+// through a pointer that may be null.  Nearest sampling only, like every literal kernel.
+template <int PROJ>
+__global__ __launch_bounds__(kBlockThreads) void k_render_geometry_literal(const DevFrame f, const RowMap rows,
+                                                                           const double *__restrict__ thr,
+                                                                           const uint32_t *__restrict__ cmap,
+                                                                           uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                           int tiles_y, StatsOut st, const SegRules seg,
+                                                                           const GeomPlanes geo) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	unsigned cell = 0u;
+	double hz = 0.0;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, SunRules{}, &lt, &cell, &hz);
+	if (!pid.live) return;
+	if (out != nullptr) out[(int64_t)pid.lrow * out_stride_px + pid.px] = lt.rgba;
+	store_geometry<PROJ>(f, geo, pid, lt.primary_hit, cell, lt.hx, lt.hy, hz);
+	if (geo.slope != nullptr) {
+		Gradient g{0.0, 0.0};
+		if (lt.primary_hit) g = gradient_nearest<false>(f, thr, cell);
+		store_slope(geo, pid, lt.primary_hit, g.gx, g.gy);
+	}
+}
+
 // Per-ray parity hook: GetRay + distance() of one pixel -> out[0..2] pos, [3..5] dir, [6] d.
 template <int PROJ>
 __global__ void k_probe(const DevFrame f, int px, int py, double *__restrict__ out) {
@@ -598,6 +625,7 @@ static hipError_t launch_literal(const FrameLaunch &l, const StatsOut &st, Launc
 }
 
 static hipError_t launch_plain_literal(const FrameLaunch &l); // (hmrm_render's frame: below)
+static hipError_t launch_geometry_literal(const FrameLaunch &l); // (hmrm_render_geometry's: the last kernels of the code object)
 
 // The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
 // shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
@@ -611,6 +639,7 @@ hipError_t launch_frame_literal(const FrameLaunch &l) {
 		return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
 			hipLaunchKernelGGL(k_render_interior_literal<proj()>, grid, block, 0, l.stream, args..., seg);
 		});
+	if (l.family == kFrameGeometry) return launch_geometry_literal(l);
 	if (l.f.aa_shift == 0) switch (l.family) {
 		case kFrameLit:
 			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
@@ -653,6 +682,15 @@ static hipError_t launch_render_t(const FrameLaunch &l) {
 static hipError_t launch_plain_literal(const FrameLaunch &l) {
 	if (l.f.aa_shift) return l.stats ? launch_render_t<true, true>(l) : launch_render_t<false, true>(l);
 	return l.stats ? launch_render_t<true, false>(l) : launch_render_t<false, false>(l);
+}
+
+// A geometry frame: the interior family's arguments and the planes.  No antialiased variant, never a measured launch.
+static hipError_t launch_geometry_literal(const FrameLaunch &l) {
+	if (l.f.aa_shift != 0 || l.rows.measure != nullptr) return hipErrorInvalidValue;
+	const SegRules seg = frame_seg_rules(l);
+	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
+		hipLaunchKernelGGL(k_render_geometry_literal<proj()>, grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.geo);
+	});
 }
 
 } // namespace hmrm

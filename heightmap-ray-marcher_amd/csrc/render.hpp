@@ -43,7 +43,10 @@ struct FrameLaunch {
 	// at the weight of its diffuse level.  kFrameLitShaded: kFrameLit whose lit pixels get that weight.
 	FrameFamily family;
 	SunRules sun;          // the lit and shaded families: direction, shadow march and ambient level (frame.hpp)
-	bool primary_interior; // ... and whether their primary rays are under the interior rule too
+	bool primary_interior; // ... and whether their primary rays are under the interior rule too (the geometry family's as well)
+	// kFrameGeometry (hmrm_render_geometry): the frame of the plain or, with primary_interior, the interior family, and the planes
+	// of `geo` the same launch stores beside it (frame.hpp GeomPlanes; d_out may be null then: no colour plane)
+	GeomPlanes geo;
 	hipStream_t stream;
 };
 // The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups

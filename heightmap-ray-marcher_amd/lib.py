@@ -160,6 +160,23 @@ class CellRect(C.Structure):
 
 assert C.sizeof(CellMapParams) == 56 and C.sizeof(CellRect) == 16
 
+
+class GeometryPlanes(C.Structure):
+    """hmrm_geometry_planes (72 bytes): where Scene.render_geometry's planes go -- host or device addresses, each with its row
+    stride in bytes; a null address: that plane is not written"""
+    _fields_ = [("rgba", C.c_void_p), ("rgba_stride", C.c_size_t), ("cell", C.c_void_p), ("cell_stride", C.c_size_t),
+                ("range", C.c_void_p), ("range_stride", C.c_size_t), ("slope", C.c_void_p), ("slope_stride", C.c_size_t),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def make(cls, rgba=(0, 0), cell=(0, 0), range=(0, 0), slope=(0, 0), interior=False):
+        """Each plane: (address, stride_bytes); address 0 = not wanted.  interior: HMRM_TRACE_INTERIOR."""
+        flat = [int(v) or None if i % 2 == 0 else int(v) for i, v in enumerate((*rgba, *cell, *range, *slope))]
+        return cls(*flat, TRACE_INTERIOR if interior else 0, 0)
+
+
+assert C.sizeof(GeometryPlanes) == 72
+
 # the same layouts as numpy structured dtypes (arrays of rays in, arrays of records out)
 RAY_DTYPE = np.dtype([("pos", np.float64, 3), ("dir", np.float64, 3)])
 RAY_HIT_DTYPE = np.dtype([("point", np.float64, 3), ("entry_d", np.float64), ("steps", np.uint32),
@@ -234,6 +251,8 @@ def _load():
         "hmrm_cell_map_sum": (C.c_int, [vp, C.POINTER(CellMapParams), dp, i32, C.POINTER(CellRect), vp, C.c_size_t]),
         "hmrm_cell_map_sum_device": (C.c_int, [vp, C.POINTER(CellMapParams), vp, i32, C.POINTER(CellRect), vp, C.c_size_t, vp]),
         "hmrm_sky_directions": (C.c_int, [i32, i32, dp]),
+        "hmrm_render_geometry": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(GeometryPlanes)]),
+        "hmrm_render_geometry_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(GeometryPlanes), vp]),
         "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
@@ -263,6 +282,7 @@ def _load():
         "hmrm_config_sun_map_lift": (C.c_double, [vp]),
         "hmrm_config_sky_map_path": (C.c_char_p, [vp]),
         "hmrm_config_sky_map_rings": (None, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "hmrm_config_range_map_path": (C.c_char_p, [vp]),
         "hmrm_config_get_sun": (None, [vp, C.POINTER(Sun)]),
         "hmrm_record_orbit_multi": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32]),
@@ -302,6 +322,7 @@ def _load():
         "hmrm_write_png": (C.c_int, [C.c_char_p, i32, i32, i32, vp, C.c_size_t]),
         "hmrm_write_png_memory": (C.c_int, [i32, i32, i32, vp, C.c_size_t, C.POINTER(u8p), C.POINTER(C.c_size_t)]),
         "hmrm_write_ppm": (C.c_int, [C.c_char_p, i32, i32, i32, vp, C.c_size_t]),
+        "hmrm_write_pfm": (C.c_int, [C.c_char_p, i32, i32, i32, vp, C.c_size_t]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the ABI lost a symbol: fail loudly
@@ -696,6 +717,39 @@ class Scene:
                                             C.byref(r) if r is not None else None, C.c_void_p(d_ptr), int(stride_bytes),
                                             C.c_void_p(stream)))
 
+    def render_geometry(self, cam: Camera, rgba=True, cell=True, range=True, slope=True, interior=False, allow_capped=False,
+                        pad_px=0) -> dict:
+        """One geometry frame (hmrm_render_geometry): render()'s frame -- render_interior()'s with interior=True -- and, from
+        the same launch, the planes asked for -> {"rgba": (H, W, 4) uint8, "cell": (H, W) int32 (hit cell y * map_w + x, -1: no
+        hit), "range": (H, W) float32 (origin to hit point, +inf: no hit), "slope": (H, W, 2) float32 (gx, gy of the diffuse
+        level's gradient; the normal is (-gx, gy, 1))}, only the keys that are True.  pad_px > 0: every plane's rows are that
+        many pixels wider (returned whole; the padding keeps its poison bytes 0xA5).  Capped rays: HMRM_E_NOTERM unless
+        allow_capped."""
+        self._sync_env()
+        w, h, wp = cam.width, cam.height, cam.width + int(pad_px)
+        out = {}
+        if rgba:
+            out["rgba"] = np.full((h, wp, 4), 0xA5, dtype=np.uint8)
+        if cell:
+            out["cell"] = np.full((h, wp), 0xA5, dtype=np.uint8).repeat(4, axis=1).view(np.int32)
+        if range:
+            out["range"] = np.full((h, wp), 0xA5, dtype=np.uint8).repeat(4, axis=1).view(np.float32)
+        if slope:
+            out["slope"] = np.full((h, wp, 8), 0xA5, dtype=np.uint8).view(np.float32)
+        at = lambda k, elem: (out[k].ctypes.data, wp * elem) if k in out else (0, 0)
+        p = GeometryPlanes.make(at("rgba", 4), at("cell", 4), at("range", 4), at("slope", 8), interior)
+        _check(lib.hmrm_render_geometry(self._h, C.byref(cam), C.byref(p)), allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return out
+
+    def render_geometry_device(self, cam: Camera, rgba=(0, 0), cell=(0, 0), range=(0, 0), slope=(0, 0), interior=False,
+                               stream: int = 0):
+        """hmrm_render_geometry_device: the same planes into device memory -- each an (address, stride_bytes) pair, address 0 =
+        not wanted; slope 8-byte aligned, the others 4-byte -- enqueued on `stream` without a host sync; take_capped(stream)
+        reports the capped rays."""
+        self._sync_env()
+        p = GeometryPlanes.make(rgba, cell, range, slope, interior)
+        _check(lib.hmrm_render_geometry_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(stream)))
+
     def pick(self, cam: Camera, px: int, py: int, allow_capped=False) -> np.ndarray:
         """hmrm_pick: the record (RAY_HIT_DTYPE scalar) of the ray of pixel (px, py) of `cam`."""
         self._sync_env()
@@ -967,6 +1021,10 @@ class Config:
         """Additive `sky_map <path.png>`: where the CLI writes the whole map's sky-view map (Scene.cell_map_sum over sky_directions)."""
         return lib.hmrm_config_sky_map_path(self._h).decode()
 
+    def range_map_path(self) -> str:
+        """Additive `range_map <path.pfm>`: where the CLI writes the camera's range plane (Scene.render_geometry); "" = none."""
+        return lib.hmrm_config_range_map_path(self._h).decode()
+
     def sky_map_rings(self):
         """Additive `sky_map_rings r n`: (rings, per_ring) of that map's sky_directions."""
         r, n = C.c_int32(0), C.c_int32(0)
@@ -1056,3 +1114,11 @@ def write_ppm(path: str, img: np.ndarray):
     img = np.ascontiguousarray(img, dtype=np.uint8)
     h, w, comp = img.shape
     _check(lib.hmrm_write_ppm(os.fsencode(path), w, h, comp, _ptr(img), w * comp))
+
+
+def write_pfm(path: str, img: np.ndarray):
+    """hmrm_write_pfm: an (h, w) or (h, w, 1) float32 array as "Pf", an (h, w, 3) one as "PF"; rows bottom to top, scale -1.0."""
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    h, w = img.shape[:2]
+    comp = 1 if img.ndim == 2 else img.shape[2]
+    _check(lib.hmrm_write_pfm(os.fsencode(path), w, h, comp, _ptr(img), w * comp * 4))

@@ -550,6 +550,59 @@ int hmrm_cell_map_sum_device(const hmrm_scene *scene, const hmrm_cell_map_params
  * Returns the count, or HMRM_E_ARG (NULL out_xyz, a count below 1 or a product outside 1 .. 256). */
 int hmrm_sky_directions(int32_t rings, int32_t per_ring, double *out_xyz);
 
+/* ---------------------------------------------------------- geometry frames */
+/* The geometry behind the picture (build-side addition), exact: a depth plane to composite a caller's own objects over the
+ * terrain or for distance fog, an ID plane to pick any pixel without a second call, a slope plane to relight a still frame
+ * under a moving sun without marching again (INTEGRATION.md 2a has the three recipes).  It is the screen-space counterpart of
+ * the cell maps: the march already knows all of it for every pixel, and an epilogue of the same launch stores it -- no ray is
+ * read from memory and no record is written.
+ * A GEOMETRY FRAME of a camera is hmrm_render's frame plus up to three more planes; with HMRM_TRACE_INTERIOR in `flags` it is
+ * hmrm_render_interior's frame instead.  Each plane is optional, and all of them come from the SAME launch.
+ * Let R(x, y) be the hmrm_ray_hit record hmrm_trace_rays writes for the ray GetRay makes for pixel (x, y) -- the pos and dir
+ * hmrm_debug_ray returns; with the interior flag the record hmrm_trace_segments writes for it with HMRM_TRACE_INTERIOR and no
+ * limits -- under the camera's step_dist, background and sampling.  O is that ray's pos, W x H the map.
+ *   rgba,  uint32 per pixel: R.rgba -- byte for byte the frame of hmrm_render / hmrm_render_interior.
+ *   cell,  int32 per pixel:  R.cell_y * W + R.cell_x when R.status == HMRM_RAY_HIT (a map has at most 2^29 cells), else -1.
+ *   range, float per pixel:  for a hit ex = P.x - O.x, ey = P.y - O.y, ez = P.z - O.z with P = R.point,
+ *                            r = sqrt((ex * ex + ey * ey) + ez * ez) in plain IEEE doubles in this order, no contraction, the
+ *                            sqrt correctly rounded, and the plane holds (float)r, rounded to nearest even; else +inf (bits
+ *                            0x7f800000).  The Euclidean distance from the ray's origin to int_point: not the entry distance,
+ *                            not a step count; view-space z is range times the pixel's direction along the view axis.
+ *   slope, two floats per pixel: for a hit ((float)gx, (float)gy), gx and gy the doubles of THE LEVEL q above
+ *                            (hmrm_render_shaded) for the camera's sampling mode -- nearest modes: central differences of the
+ *                            threshold table around the hit cell; HMRM_BILINEAR: the gradient of the interpolated surface at P
+ *                            -- the normal is (-gx, gy, 1); else (+0.0f, +0.0f).
+ * Nothing is special-cased: alpha-0 hit cells are hits, as in hmrm_render_lit.  Capped rays are non-hits in all planes and are
+ * counted as in hmrm_render_interior: hmrm_render_geometry returns HMRM_E_NOTERM with valid planes; END cannot occur (no limit).
+ * Like the shading arithmetic, range and slope are tested at unit world scale only.
+ * Every pointer of the struct may be NULL: that plane is not written, and nothing is fetched for it (no colour without rgba).
+ * Rows are `stride` bytes apart; bytes between rows are not touched.
+ * Refusals (HMRM_E_ARG, with a message) before the scene is looked at, in this order: NULL planes; an undefined flag bit;
+ * reserved != 0; all four pointers NULL; a bad stride or alignment of a non-NULL plane (rgba, cell, range: stride >= 4 * width,
+ * a multiple of 4; slope: >= 8 * width, a multiple of 8, the pointer 8-byte aligned; device planes are aligned to their
+ * element).  Then the camera checks of hmrm_render, then a NULL scene, then the 2^24-side rule of frames.
+ * hmrm_render_geometry is synchronous on the scene's stream, one such call at a time per scene; it stages the planes through
+ * scene-owned device buffers that grow on demand.  hmrm_render_geometry_device takes DEVICE pointers, launches on hip_stream,
+ * does no host sync and reports capped rays through hmrm_scene_take_capped for its stream -- hmrm_trace_rays_device's contract.
+ * A geometry frame is launched the way an interior frame is: one launch, never measured, never the scene's probe and not
+ * counted towards it; hmrm_debug_kernel_choice and every later frame are as they would have been.  It runs the scene's current
+ * kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST); every kernel writes the same bytes, the
+ * literal loop too (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest sampling only).  All three projections, grid modes
+ * and sampling modes.
+ * OUT OF SCOPE: antialiasing (a filtered depth is not defined); tickets and lanes; row strips or bands; hmrm_render_multi,
+ * hmrm_render_cycle, recording and statistics; a sun -- the slope plane is what a caller relights from. */
+typedef struct hmrm_geometry_planes {   /* every pointer may be NULL: that plane is not written */
+	void    *rgba;   size_t rgba_stride;    /* bytes per row, >= 4 * width, multiple of 4 */
+	int32_t *cell;   size_t cell_stride;    /* >= 4 * width, multiple of 4 */
+	float   *range;  size_t range_stride;   /* >= 4 * width, multiple of 4 */
+	float   *slope;  size_t slope_stride;   /* >= 8 * width, multiple of 8; pointer 8-byte aligned */
+	uint32_t flags;                          /* HMRM_TRACE_INTERIOR; any other bit: HMRM_E_ARG */
+	uint32_t reserved;                       /* must be 0 */
+} hmrm_geometry_planes;
+int hmrm_render_geometry(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_geometry_planes *host_planes);
+int hmrm_render_geometry_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_geometry_planes *device_planes,
+                                void *hip_stream);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -723,7 +776,10 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * map as a one-component PNG: hmrm_cell_map_sum in status mode over hmrm_sky_directions(r, n), K = r * n, with
  * shadow_step_dist, shadow_max_steps, sun_map_lift and the camera's sampling; byte = (c * 255 + K / 2) / K for count c),
  * `sky_map_rings r n` (default 4 16; a product outside 1 .. 256 warns "WARNING: sky_map_rings must give 1..256 directions" and
- * keeps the old value).
+ * keeps the old value),
+ * `range_map <path.pfm>` (echoed like `output`; after its frames and before an optional sun_map the CLI writes the range plane
+ * of the configured camera -- hmrm_render_geometry with that plane alone, under the interior rule with `interior on` -- as a
+ * one-component portable float map, hmrm_write_pfm).
  * Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
@@ -751,6 +807,7 @@ const char  *hmrm_config_sun_map_path(const hmrm_config *cfg);  /* additive `sun
 double       hmrm_config_sun_map_lift(const hmrm_config *cfg);  /* additive `sun_map_lift v` */
 const char  *hmrm_config_sky_map_path(const hmrm_config *cfg);  /* additive `sky_map <path.png>`: "" = none */
 void         hmrm_config_sky_map_rings(const hmrm_config *cfg, int32_t *rings, int32_t *per_ring); /* additive `sky_map_rings r n` */
+const char  *hmrm_config_range_map_path(const hmrm_config *cfg); /* additive `range_map <path.pfm>`: "" = none */
 /* The sun of the additive keys: sun_dir, shadow_step_dist (the config's step_dist when the key was absent),
  * shadow_max_steps, shadow_ambient; flags = HMRM_TRACE_INTERIOR when `interior on`. */
 void         hmrm_config_get_sun(const hmrm_config *cfg, hmrm_sun *out);
@@ -786,6 +843,11 @@ int  hmrm_write_png_memory(int32_t w, int32_t h, int32_t comp, const uint8_t *da
 /* Binary PPM (P6), alpha dropped -- build-side addition named by north_star. */
 int  hmrm_write_ppm(const char *path, int32_t w, int32_t h, int32_t comp,
                     const uint8_t *data, size_t stride_bytes);
+/* Portable float map (build-side addition, for the float planes of hmrm_render_geometry): header "Pf" (comp 1) or "PF"
+ * (comp 3), "w h", the scale "-1.0" (negative: little-endian), then the rows BOTTOM TO TOP, w * comp IEEE floats each, bit
+ * for bit (+inf included).  HMRM_E_ARG for a NULL argument, a size below 1, another comp or a stride below one row. */
+int  hmrm_write_pfm(const char *path, int32_t w, int32_t h, int32_t comp /* 1 or 3 */,
+                    const float *data, size_t stride_bytes);
 
 #ifdef __cplusplus
 }
