@@ -8,7 +8,7 @@ Host-side mirror of the reference's interface for the hot path only
 """
 from .lib import (  # noqa: F401
     Camera, Config, HmrmError, Scene, SceneParams, Stats,
-    Ray, RayHit, TraceParams, SegmentParams, Sun, CellMapParams, CellRect, GeometryPlanes, MAP_TOWARDS_POINT, MAP_WEIGHT, MAP_DIFFUSE, MAP_NO_SHADOWS, RAY_END, TRACE_INTERIOR, SHADE_DIFFUSE, SHADE_NO_SHADOWS, RAY_DTYPE, RAY_HIT_DTYPE, RAY_MISS, RAY_HIT, RAY_CAPPED, MAX_RAYS, as_rays,
+    Ray, RayHit, TraceParams, SegmentParams, Sun, CellMapParams, CellRect, GeometryPlanes, LightPlanes, MAP_TOWARDS_POINT, MAP_WEIGHT, MAP_DIFFUSE, MAP_NO_SHADOWS, RAY_END, TRACE_INTERIOR, SHADE_DIFFUSE, SHADE_NO_SHADOWS, RAY_DTYPE, RAY_HIT_DTYPE, RAY_MISS, RAY_HIT, RAY_CAPPED, MAX_RAYS, as_rays,
     PERSPECTIVE, SPHERICAL, ORTHOGRAPHIC, NEAREST, BILINEAR, NEAREST_F32,
     HMRM_OK, HMRM_E_ARG, HMRM_E_IO, HMRM_E_IMAGE, HMRM_E_CONFIG, HMRM_E_DEVICE, HMRM_E_NOTERM,
     EXPORTED_SYMBOLS, LIB_PATH, NO_PROBE, AA_FACTORS, aa_flags,

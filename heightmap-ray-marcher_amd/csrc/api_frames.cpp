@@ -368,6 +368,97 @@ int hmrm_render_shaded_aa(const hmrm_scene *scene, const hmrm_camera *cam, const
 	return render_lit_common(scene, cam, &lit, factor, rgba, stride_bytes);
 }
 
+// ---- accumulated lit frames: the lit frame whose shadow march runs once per direction of a list, the weights summed per pixel ----
+// The refusals about the planes, in the header's order; needs no scene and no device.  A stride is compared with the camera's
+// width only when there is a camera with one: a camera that check_camera refuses is refused right after.
+static int check_light_planes(const hmrm_light_planes *p, const hmrm_camera *cam, bool device) {
+	if (!p) return fail(HMRM_E_ARG, "lit sum: NULL planes");
+	if (p->reserved[0] != 0u || p->reserved[1] != 0u) return fail(HMRM_E_ARG, "hmrm_light_planes.reserved must be 0");
+	if (!p->rgba && !p->light) return fail(HMRM_E_ARG, "lit sum: both planes are NULL");
+	const size_t width = (cam && cam->width > 0) ? (size_t)cam->width : 0;
+	auto plane = [&](const char *name, const void *ptr, size_t stride, size_t elem) -> int {
+		if (!ptr) return HMRM_OK;
+		if (stride < elem * width || (stride % elem) != 0 || stride / elem > 0x7fffffffu)
+			return fail(HMRM_E_ARG, std::string("lit sum: ") + name + "_stride must be >= " + std::to_string(elem) + " * width, a multiple of " +
+			                            std::to_string(elem) + " and below 2^31 elements");
+		if (device && ((uintptr_t)ptr % elem) != 0)
+			return fail(HMRM_E_ARG, std::string("lit sum: ") + name + " must be " + std::to_string(elem) + "-byte aligned");
+		return HMRM_OK;
+	};
+	int rc;
+	if ((rc = plane("rgba", p->rgba, p->rgba_stride, 4)) || (rc = plane("light", p->light, p->light_stride, 2))) return rc;
+	return HMRM_OK;
+}
+
+static int ensure_light(hmrm_scene *s, size_t px) {
+	if (px <= s->light_cap) return HMRM_OK;
+	if (s->d_light) (void)hipFree(s->d_light);
+	s->d_light = nullptr;
+	s->light_cap = 0;
+	HIP_TRY(hipMalloc((void **)&s->d_light, px * sizeof(uint16_t)));
+	s->light_cap = px;
+	return HMRM_OK;
+}
+
+// Launched the way a lit frame is (FrameRequest::own_kernels): never measured, never the probe, with the scene's current kernel.
+// `device`: dirs and p hold device pointers and the launch goes to `stream` without a host sync; else the directions are staged
+// through the scene's target list, the pixels through its frame buffer and the light plane through a buffer of its own, rows
+// packed, and copied to the caller's behind the launch.
+static int render_lit_sum_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm_sun *sun, const void *dirs, int32_t n_dirs,
+                                 uint32_t shade_flags, const hmrm_light_planes *p, bool device, hipStream_t stream) {
+	int rc = check_shaded(sun, shade_flags);
+	if (rc) return rc;
+	if (!dirs) return fail(HMRM_E_ARG, "lit sum: NULL dirs");
+	if (n_dirs < 1 || n_dirs > hmrm::kMaxSumDirs) return fail(HMRM_E_ARG, "lit sum: n_dirs must be 1 .. 256 (got " + std::to_string(n_dirs) + ")");
+	if ((rc = check_light_planes(p, cam, device))) return rc;
+	if (device && ((uintptr_t)dirs & 7u)) return fail(HMRM_E_ARG, "lit sum: d_dirs must be 8-byte aligned");
+	if ((rc = check_camera(cam))) return rc;
+	if (!s) return fail(HMRM_E_ARG, "NULL argument");
+	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	uint32_t *d_rgba = (uint32_t *)p->rgba;
+	int64_t rgba_stride_px = (int64_t)(p->rgba_stride / 4);
+	hmrm::LightSum sum{static_cast<const double *>(dirs), p->light, (int64_t)p->light_stride, n_dirs, shade_flags};
+	if (!device) {
+		if (p->rgba && (rc = ensure_frame(s, W * H))) return rc;
+		if (p->light && (rc = ensure_light(s, W * H))) return rc;
+		if ((rc = ensure_targets(s, (size_t)n_dirs))) return rc; // (hmrm_cell_map_sum's staging of its targets)
+		d_rgba = p->rgba ? s->d_frame : nullptr;
+		rgba_stride_px = (int64_t)W;
+		sum.dirs = s->d_targets;
+		sum.light = p->light ? s->d_light : nullptr;
+		sum.light_stride = (int64_t)(2 * W);
+		stream = s->stream;
+		HIP_TRY(hipMemcpyAsync(s->d_targets, dirs, (size_t)n_dirs * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+	}
+	FrameSetup fs;
+	if ((rc = setup_frame(s, stream, cam, 0, &fs))) return rc;
+	StreamCtx *const c = fs.c;
+	LitFrame lit = make_lit_frame(sun, shade_flags);
+	lit.sum = &sum;
+	FrameRequest req = plain_request(d_rgba, rgba_stride_px);
+	req.lit = &lit;
+	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req)) || device) return rc;
+	if (p->rgba) HIP_TRY(hipMemcpy2DAsync(p->rgba, p->rgba_stride, d_rgba, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
+	if (p->light) HIP_TRY(hipMemcpy2DAsync(p->light, p->light_stride, sum.light, W * 2, W * 2, H, hipMemcpyDeviceToHost, s->stream));
+	unsigned long long capped_now = 0;
+	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	return noterm(new_capped(c, capped_now));
+}
+
+int hmrm_render_lit_sum(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, const double *dirs, int32_t n_dirs,
+                        uint32_t shade_flags, const hmrm_light_planes *host_planes) {
+	return render_lit_sum_common(const_cast<hmrm_scene *>(scene), cam, sun, dirs, n_dirs, shade_flags, host_planes, false, nullptr);
+}
+
+int hmrm_render_lit_sum_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, const void *d_dirs, int32_t n_dirs,
+                               uint32_t shade_flags, const hmrm_light_planes *device_planes, void *hip_stream) {
+	return render_lit_sum_common(const_cast<hmrm_scene *>(scene), cam, sun, d_dirs, n_dirs, shade_flags, device_planes, true,
+	                             (hipStream_t)hip_stream);
+}
+
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
                       size_t stride_bytes, hmrm_stats *stats, uint32_t *steps_per_pixel, double *entry_d) {
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes,

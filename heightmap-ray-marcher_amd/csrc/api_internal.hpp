@@ -178,6 +178,8 @@ struct hmrm_scene {
 	size_t targets_cap = 0;
 	uint8_t *d_geom = nullptr; // ... and of hmrm_render_geometry's planes: the wanted ones back to back, rows packed
 	size_t geom_cap = 0;
+	uint16_t *d_light = nullptr; // ... and of hmrm_render_lit_sum's light plane, rows packed (its directions go through d_targets,
+	size_t light_cap = 0;        //     its pixels through d_frame)
 	// launch state per stream; `mu` guards the list and the slot choice (launches themselves are
 	// asynchronous), so that threads driving different streams of one scene do not collide
 	std::mutex mu;
@@ -219,6 +221,9 @@ struct LitFrame {
 	hmrm::SunRules sun;
 	bool primary_interior; // HMRM_TRACE_INTERIOR: the primary rays under the interior rule too
 	uint32_t shade_flags;  // hmrm_render_shaded's HMRM_SHADE_*; 0: hmrm_render_lit's frame, by its kernels
+	// hmrm_render_lit_sum's frame: the list of directions (device memory: pointer and count), the flags once more and the device
+	// light plane (frame.hpp LightSum; the request's d_out may be null then: no colour plane); null: one sun, sun.dir
+	const hmrm::LightSum *sum = nullptr;
 };
 
 // hmrm_render_interior's frame.  Perspective and spherical rays all start at the camera, so the host decides the rule once per
@@ -262,5 +267,7 @@ int take_capped(StreamCtx *c, unsigned long long *out);
 int noterm(unsigned long long capped);
 // api_frames.cpp (s->mu held): the scene's per-pixel scratch, which hmrm_pick and hmrm_debug_ray borrow
 int ensure_stats(hmrm_scene *s, size_t px);
+// api_queries.cpp (s->mu held): the scene's staging of a list of n targets or directions
+int ensure_targets(hmrm_scene *s, size_t n);
 } // namespace hmrm
 #pragma GCC visibility pop

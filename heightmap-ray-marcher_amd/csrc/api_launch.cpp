@@ -133,7 +133,7 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 	const bool huge_side = s->map_w >= (1 << 24) || s->map_h >= (1 << 24);
 	const LitFrame *lit = req.lit;
 	const hmrm::FrameRoute route = hmrm::route_frame(s->knobs.kernel, huge_side, f.sampling, f.aa_shift != 0, req.interior == Interior::kByKernels,
-	                                                 lit != nullptr, lit ? lit->shade_flags : 0u);
+	                                                 lit != nullptr, lit ? lit->shade_flags : 0u, lit && lit->sum);
 	if (route.refused) return fail(HMRM_E_ARG, "maps with a side of 2^24 cells or more support nearest sampling only");
 	hmrm::FrameLaunch l = frame_launch(s, c, f, rows_in_order, req);
 	l.family = route.family;
@@ -141,6 +141,7 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		l.sun = lit->sun;
 		if (route.ambient_sun) l.sun.ambient = 255u;
 		l.primary_interior = lit->primary_interior;
+		if (lit->sum) l.lsum = *lit->sum;
 	}
 	if (req.geom) { // (the literal-or-march decision is the plain frame's: route_frame knows no geometry family)
 		l.family = hmrm::kFrameGeometry;

@@ -209,6 +209,11 @@ int check_cell_sum_rect(const hmrm_scene *s, const hmrm_cell_rect *rect, size_t 
 	return HMRM_OK;
 }
 
+} // namespace
+
+namespace hmrm {
+// The scene's staging of a list of n targets or directions, three doubles each (hmrm_cell_map_sum; api_frames.cpp stages
+// hmrm_render_lit_sum's directions through it too).  (s->mu held.)
 int ensure_targets(hmrm_scene *s, size_t n) {
 	if (n <= s->targets_cap) return HMRM_OK;
 	if (s->d_targets) (void)hipFree(s->d_targets);
@@ -218,6 +223,9 @@ int ensure_targets(hmrm_scene *s, size_t n) {
 	s->targets_cap = n;
 	return HMRM_OK;
 }
+} // namespace hmrm
+
+namespace {
 
 // One accumulated cell map on the context's stream: launch_cells' recipe with the list of targets beside the rules.
 int launch_cell_sums(hmrm_scene *s, StreamCtx *c, const hmrm_cell_map_params *p, const double *d_targets, int32_t n_targets,

@@ -361,6 +361,7 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	if (s->d_limits) (void)hipFree(s->d_limits);
 	if (s->d_cells) (void)hipFree(s->d_cells);
 	if (s->d_targets) (void)hipFree(s->d_targets);
+	if (s->d_light) (void)hipFree(s->d_light);
 	if (s->d_geom) (void)hipFree(s->d_geom);
 	if (s->ev0) (void)hipEventDestroy(s->ev0);
 	if (s->ev1) (void)hipEventDestroy(s->ev1);

@@ -48,6 +48,9 @@ struct Config {
 	// additive: `shading on|off|1|0` -- diffuse sun shading of that frame (hmrm_render_shaded), with the shadow rays when
 	// `shadows on`; the sun is the same
 	int shading = 0;
+	// additive: `sky_light on|off|1|0` -- that frame lit by the sky instead of the sun (hmrm_render_lit_sum over the directions of
+	// `sky_map_rings`), diffuse with `shading on`; the shadow march's keys are the sun's, `sun_dir` is not used
+	int sky_light = 0;
 	// additive: `sun_scope single|all` -- 0: shadows / shading apply to the plain single frame only; 1: also with `antialias n` > 1
 	// (hmrm_render_shaded_aa) and to `record orbit` (hmrm_record_orbit_shaded)
 	int sun_scope = 0;

@@ -242,6 +242,35 @@ __device__ __forceinline__ void sum_target(const CellSums &sums, int k, CellRule
 	rules->target[2] = t[2];
 }
 
+// Accumulated lit frames (hmrm_render_lit_sum; frame.hpp LightSum): what a lane keeps across its shadow passes beside LitState's
+// hit point; empty in every other instantiation, as SegState is.  `k` is the same for a whole wave.
+template <bool LSUM> struct LitSumState {};
+template <> struct LitSumState<true> {
+	int k = 0;        // the shadow pass = the direction's index
+	uint32_t acc = 0; // w_0 + .. + w_{k-1} (at most 256 * 255) + 2^16 * the rays of this lane that the step cap stopped (at most 257)
+};
+// Direction k of the list, for every lane of the wave: the index is made a scalar so that the three doubles are scalar loads.
+__device__ __forceinline__ void sum_direction(const LightSum &ls, int k, double (&s)[3]) {
+	const double *__restrict__ t = ls.dirs + 3 * (size_t)(unsigned)__builtin_amdgcn_readfirstlane(k);
+	s[0] = t[0];
+	s[1] = t[1];
+	s[2] = t[2];
+}
+// The pixel of a hit under the sum S of its n weights: (c * S + (255 n) / 2) / (255 n) per channel in integers, A stays 255.
+// c * S <= 255 * 65280 < 2^24; the divisor is the same for the whole launch.
+// n copies of one weight w give (c * w + 127) / 255, the pixel of that weight alone, for every n.  Proof: let c * w = 255 q + r,
+// 0 <= r <= 254; that pixel is q + [r >= 128].  With S = n w the numerator is 255 n q + (n r + floor(255 n / 2)), so the quotient
+// is q + floor((n r + floor(127.5 n)) / (255 n)).  For r >= 128: n r + floor(127.5 n) >= 128 n + 127 n = 255 n, and with
+// r <= 254 it is below 254 n + 127.5 n + 1 <= 510 n: the floor is 1.  For r <= 127: n r + floor(127.5 n) <= 254.5 n < 255 n:
+// the floor is 0.
+__device__ __forceinline__ uint32_t shade_summed(uint32_t rgba, uint32_t sum, uint32_t n) {
+	const uint32_t den = 255u * n, half = den / 2u;
+	const uint32_t r = ((rgba & 255u) * sum + half) / den;
+	const uint32_t g = (((rgba >> 8) & 255u) * sum + half) / den;
+	const uint32_t b = (((rgba >> 16) & 255u) * sum + half) / den;
+	return r | (g << 8) | (b << 16) | (rgba & 0xff000000u);
+}
+
 // Relative error of the hardware reciprocal.  MEASURED on gfx950 (tools/rcp_accuracy.py over 1.6e11 inputs: the
 // leading 32 mantissa bits exhaustively in six binades, hashed mantissas / signs / exponents 2^-1000..2^1000, and the
 // product n * rcp(d) against n / d; profiles/r03_rcp_accuracy.txt): |rcp(x) * x - 1| <= 2^-24.36 everywhere, the same

@@ -300,6 +300,22 @@ struct GeomPlanes {
 	int64_t cell_stride, range_stride, slope_stride;
 };
 
+// ---- accumulated lit frames (hmrm_render_lit_sum; LSUM in the kernels) ----
+// The lit kernels' shadow march run n times per hit pixel over a list of directions (device memory, n x 3 doubles, the same for
+// every lane: the index is wave-uniform) -- SunRules::dir is not looked at, direction k takes its place for pass k -- with the
+// pixel's weights w_k of hmrm_render_shaded under `flags` (HMRM_SHADE_*) summed in a register: S <= 255 n <= 65280.  One pixel
+// at the weight S / (255 n) is stored at the end, and / or S itself as a 16-bit word at (char *)light + row * light_stride +
+// 2 * column (0xFFFF: no hit).  `light` may be null, and so may the kernel's colour target: the colour is not fetched then.  A
+// sibling of SunRules in the sum kernels' own __global__ entry points: k_render_lit's arguments do not change.
+struct LightSum {
+	const double *dirs;
+	uint16_t *light;
+	int64_t light_stride; // bytes per local row, even
+	int32_t n;            // 1 .. 256
+	uint32_t flags;       // kShadeDiffuse | kShadeNoShadows (march_dispatch.hpp)
+};
+constexpr int kMaxSumDirs = 256;
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

@@ -174,6 +174,7 @@ int main(int argc, char *argv[]) {
 	const bool interior = hmrm_config_interior(cfg) != 0;
 	const bool shadows = hmrm_config_shadows(cfg) != 0;
 	const bool shading = hmrm_config_shading(cfg) != 0;
+	const bool sky_light = hmrm_config_sky_light(cfg) != 0; // (the single frame under the sky's directions: hmrm_render_lit_sum)
 	// `sun_scope all`: shadows / shading also apply to antialiased and recorded frames
 	const bool sun_all = hmrm_config_sun_scope(cfg) != 0 && (shadows || shading);
 	const uint32_t shade_flags = shading ? (HMRM_SHADE_DIFFUSE | (shadows ? 0u : HMRM_SHADE_NO_SHADOWS)) : 0u;
@@ -189,6 +190,7 @@ int main(int argc, char *argv[]) {
 			if (shadows) std::cerr << "WARNING: shadows is ignored with record orbit\n";
 			if (shading) std::cerr << "WARNING: shading is ignored with record orbit\n";
 		}
+		if (sky_light) std::cerr << "WARNING: sky_light is ignored with record orbit\n";
 		// `record orbit`: recording_frame_count frames on a circle around the map centre through
 		// the configured camera position, always looking at the centre;
 		// files screenshots/hmap_<epoch>_<n>.png as hmap.cpp:1131-1144.
@@ -251,7 +253,34 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: shadows is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
 	if (shading && !lit_aa && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: shading is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (lit_aa) {
+	if (sky_light && (want_dev > 1 || aa > 1)) // (whatever sun_scope says: there is no antialiased accumulated frame)
+		std::cerr << "WARNING: sky_light is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
+	if (sky_light && want_dev <= 1 && aa == 1) {
+		// every hit pixel under the K = r * n cosine-weighted sky directions of `sky_map_rings`, shadow rays always on, the diffuse
+		// level per direction with `shading on`; ambient, step and limit are the sun's keys, sun_dir is not used
+		int32_t rings = 0, per_ring = 0;
+		hmrm_config_sky_map_rings(cfg, &rings, &per_ring);
+		std::vector<double> dirs((size_t)3 * rings * per_ring);
+		const int K = hmrm_sky_directions(rings, per_ring, dirs.data());
+		if (K < 1) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		hmrm_sun sun;
+		hmrm_config_get_sun(cfg, &sun);
+		hmrm_light_planes planes;
+		memset(&planes, 0, sizeof planes);
+		planes.rgba = framebuf.data();
+		planes.rgba_stride = (size_t)cam.width * 4;
+		rc = hmrm_render_lit_sum(scene, &cam, &sun, dirs.data(), K, shading ? HMRM_SHADE_DIFFUSE : 0u, &planes);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height << " rays with sky light from " << K << " directions"
+		          << (shading ? " and sun shading" : "") << (interior ? " under the interior rule" : "") << "\n";
+	} else if (lit_aa) {
 		hmrm_sun sun;
 		hmrm_config_get_sun(cfg, &sun);
 		rc = hmrm_render_shaded_aa(scene, &cam, &sun, shade_flags, aa, framebuf.data(), (size_t)cam.width * 4);

@@ -1,7 +1,8 @@
 // march.hpp -- the production march for gfx950: render_wave_tile, one wave's 8 x 8 pixels (or 64 batch rays), and its
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
 // render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
-// counterparts (march_lit_aa.hpp), render_cells.hip and render_cell_sums.hip, each with a __global__ kernel of its own.
+// counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip and render_lit_sum.hip, each with
+// a __global__ kernel of its own.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
 // the reference loop main/hmap.cpp:978-1058; two bit-preserving restructurings:
@@ -238,15 +239,26 @@ __device__ __forceinline__ DevRay cell_ray_of(const CellRules &c, const DevFrame
 // gradient SHADE takes its level from, each through a pointer of `geo` that may be null -- and so may `out`: the colour is not
 // fetched then.  A lane that hit leaves the loop with int_point in x, y, z (KEEP_P's re-add, with z stepped like x and y) and
 // with hcell; the ray's origin is made again in the epilogue.  Again `if constexpr` statements beside the others' own.
+// LSUM (instantiated in render_lit_sum.hip only; hmrm_render_lit_sum, frame.hpp LightSum; needs LIT, without SHADE -- whether the
+// weights are diffuse is a run-time flag): an accumulated lit frame, LIT and SUM joined.  The primary march runs once; then the
+// wave runs "entry, then the march loop" once per direction of a wave-uniform list for the lanes whose primary ray hit, each of
+// which folds the pass's weight -- hmrm_render_shaded's for that direction -- into a register; the epilogue stores ONE pixel at
+// the weight sum / (255 n) through `out` and / or the sum as ONE 16-bit word through `lsum.light`, either of which may be null.
+// Across the passes a lane keeps LitState's hit point, hcell, the sum and (wave-uniform) the pass; the gradient and the lane's
+// pixel are made again.  With HMRM_SHADE_NO_SHADOWS no shadow pass runs: the n levels are computed behind the primary march.
+// Termination: every pass is the march loop with a budget of its own, min(step cap, the shadow rays' limit) <= the step cap, and
+// the outer loop runs at most 1 + n times -- the primary pass and one per direction, the pass number only ever grows.
 template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false, bool SHADE = false,
-          bool SUM = false, bool GEOM = false>
+          bool SUM = false, bool GEOM = false, bool LSUM = false>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
                                                 int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{},
                                                 const SunRules &sun = SunRules{}, const CellRules &cells = CellRules{},
-                                                const CellSums &sums = CellSums{}, const GeomPlanes &geo = GeomPlanes{}) {
+                                                const CellSums &sums = CellSums{}, const GeomPlanes &geo = GeomPlanes{},
+                                                const LightSum &lsum = LightSum{}) {
 	constexpr bool CELLS = PROJ == 5;
+	static_assert(!LSUM || (LIT && !SHADE && !AA), "accumulated lit frames: the lit kernels' marches, the weights by a run-time flag");
 	static_assert(!GEOM || (SEG && !CELLS && PROJ != 4 && !STATS && !AA && !LIT && !SHADE), "geometry frames: plain frames under the segment rules");
 	static_assert(!SUM || CELLS, "accumulated cell maps: the cell kernels' march, once per target");
 	static_assert(!CELLS || (SEG && !STATS && !AA && !LIT && !SHADE), "cell maps: segment rays, one byte per cell");
@@ -269,7 +281,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	// epilogue's load costs them a spill slot (profiles/r09_registers.txt).  And the bilinear mode of the plain groups: leaving
 	// the loop with the hit point made that kernel 20 % SLOWER where it was measured (0.263 -> 0.316 ms, profiles/r09_ab.txt).
 	// (GEOM: always behind the loop -- a null colour target skips the fetch there, a scalar branch)
-	constexpr bool DEFER = GEOM || (!CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0));
+	// (LSUM: always behind the loop, like GEOM -- and behind every march: the hit point outlives them)
+	constexpr bool DEFER = GEOM || LSUM || (!CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0));
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || !STATS, "segment rules: production kernels only");
 	static_assert(!SEG || !AA || LIT || SHADE, "segment rules: antialiased for the sun-lit frames only");
@@ -296,6 +309,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	uint32_t my_hit = 0, my_cap = 0;
 	uint32_t aa_rgba = 0; // (AA: this lane's sample, filtered by the whole wave below)
 	SumState<SUM> sm; // (empty unless SUM: device_common.hpp)
+	LitSumState<LSUM> lm; // (empty unless LSUM)
 
 	if (pid.live) {
 		DevRay ray = make_ray<PROJ>(f, pid.px, pid.py);
@@ -348,7 +362,32 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			return shade_hit_bilinear(f, cmap, (int)hcell, bil_setup(qx, qy, f.map_w, f.map_h));
 		};
 
-		do { // (once; LIT: once more with the shadow rays; SUM: once per target)
+		// LSUM: the weight of a lane that hit under direction `s` -- hmrm_render_shaded's: the ambient level for a shadowed pixel, else
+		// 255 or, HMRM_SHADE_DIFFUSE, that of the level of the primary hit.  (The hit cell, or the hit point, goes through an empty
+		// statement: the gradient made from it does not depend on the direction, and the compiler would otherwise make it once,
+		// before the first pass, and hold it in vector registers across every march -- the lesson of SUM's cell.)
+		[[maybe_unused]] auto sum_weight = [&](bool shadowed, const double (&s)[3]) -> uint32_t {
+			uint32_t w = shadowed ? sun.ambient : 255u;
+			if constexpr (LSUM) {
+				if ((lsum.flags & kShadeDiffuse) != 0u && !shadowed) {
+					uint32_t q;
+					if constexpr (BILINEAR) {
+						double px = lt.hx, py = lt.hy, qxs, qys;
+						asm volatile("" : "+v"(px), "+v"(py));
+						cell_coords_of(px, py, qxs, qys);
+						q = diffuse_level_bilinear(f, thr, bil_setup(qxs, qys, f.map_w, f.map_h), s);
+					} else {
+						unsigned hc = hcell;
+						asm volatile("" : "+v"(hc));
+						q = diffuse_level_nearest<F32>(f, thr, hc, s);
+					}
+					w = shade_weight(sun.ambient, q);
+				}
+			}
+			return w;
+		};
+
+		do { // (once; LIT: once more with the shadow rays; SUM: once per target; LSUM: once more per direction)
 			if (!(d == __builtin_huge_val()) && !(d < 0.0)) { // intersection(), AABB.cpp:33-44
 				double x = ray.px + d * ray.dx;
 				double y = ray.py + d * ray.dy;
@@ -854,7 +893,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				}
 				if (COUNT) my_steps = (unsigned long long)(unsigned)(budget0 - budget);
 				if constexpr (SEG && COUNT) my_steps = (unsigned long long)(unsigned)(sg.budget - budget);
-				if constexpr (LIT && SHADE && BILINEAR) { // (the primary hit's point outlives the shadow march: the gradient is taken there)
+				if constexpr ((LIT && SHADE && BILINEAR) || LSUM) { // (the primary hit's point outlives the shadow march: the gradient is taken there; LSUM: every pass's ray starts there)
 					if (lt.phase == 0) { lt.hx = x; lt.hy = y; lt.t = z; }
 				} else
 				if constexpr (LIT) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
@@ -862,6 +901,49 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				else if constexpr (GEOM) { hqx = x; hqy = y; hz = z; } // (int_point of a lane that hit)
 				else if constexpr (KEEP_P) { hqx = x; hqy = y; } // (SHADE, bilinear: the same two, for the gradient at P)
 			}
+			if constexpr (LSUM) {
+				// After the primary rays: as LIT below, except that no pixel is kept -- the hit point and hcell are, for every pass -- and
+				// that the wave takes direction 0 of the list.  After a shadow pass: a lane that hit folds the weight of this direction
+				// into its sum and counts the ray if the step cap stopped it (an END ray is not a capped one; the primary ray counts
+				// the same way, once); while directions are left the wave takes the next one, and the ray, its d, its budget, real_hit
+				// and the cap state start over -- everything derived from them is computed again by the next pass.
+				again = false;
+				double sdir[3];
+				lm.acc += (my_cap != 0u && !sg.ends) ? 0x10000u : 0u; // (the lanes that sat the pass out have my_cap = 0)
+				my_cap = 0u;
+				if (lt.phase == 0) {
+					lt.primary_hit = real_hit;
+					if (__builtin_amdgcn_ballot_w64(real_hit) != 0ull) {
+						lt.phase = 1;
+						lt.dz = ray.dz;
+						if ((lsum.flags & kShadeNoShadows) != 0u) { // (no march: the n weights of the lanes that hit, here)
+#pragma unroll 1
+							for (int k = 0; k < lsum.n; ++k) {
+								sum_direction(lsum, k, sdir);
+								if (lt.primary_hit) lm.acc += sum_weight(false, sdir);
+							}
+						} else {
+							again = true;
+						}
+					}
+				} else {
+					sum_direction(lsum, lm.k, sdir); // (loaded again behind the march rather than held across it)
+					if (lt.primary_hit) lm.acc += sum_weight(real_hit, sdir);
+					++lm.k;
+					again = lm.k < lsum.n;
+				}
+				if (again) {
+					sum_direction(lsum, lm.k, sdir);
+					ray.px = lt.hx; ray.py = lt.hy; ray.pz = lt.t; // (shadow_ray's, towards direction k)
+					ray.dx = sdir[0]; ray.dy = sdir[1]; ray.dz = sdir[2];
+					d = __builtin_huge_val();
+					if (lt.primary_hit) {
+						d = shadow_entry(ray, f);
+						sg.budget = segment_budget(SegRules{nullptr, sun.max_steps, 1u}, 0, f.step_cap, &sg.ends);
+					}
+					real_hit = false;
+				}
+			} else
 			if constexpr (LIT) {
 				// After the primary rays: the lanes that hit keep their pixel and become their shadow rays -- the ray, its d, its step
 				// (above) and its budget min(step cap, L) are replaced, everything derived from them is computed again by the second
@@ -939,7 +1021,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					real_hit = false;
 				}
 			}
-		} while ((LIT || SUM) && again);
+		} while ((LIT || SUM) && again); // (LSUM implies LIT)
 		// The hit lanes' colour: fetched here, once, behind the march (LIT, nearest-cell modes: behind both marches).
 		double qxh = hqx, qyh = hqy; // (bilinear: the hit's cell coordinates, for the colour and SHADE's gradient)
 		if constexpr (BILINEAR && (KEEP_P || GEOM) && !LIT) cell_coords_of(hqx, hqy, qxh, qyh);
@@ -949,6 +1031,18 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		if constexpr (DEFER && !LIT) {
 			if (real_hit) rgba = BILINEAR ? bilinear_pixel(qxh, qyh) : shade_hit(f, cmap[hcell]);
 		}
+		if constexpr (LSUM) { // (the colour once, behind every march, and only for a colour target; then the pixel under its sum)
+			real_hit = lt.primary_hit;
+			if (out != nullptr && real_hit) {
+				uint32_t lit_rgba;
+				if constexpr (BILINEAR) {
+					cell_coords_of(lt.hx, lt.hy, qxh, qyh);
+					lit_rgba = bilinear_pixel(qxh, qyh);
+				} else lit_rgba = shade_hit(f, cmap[hcell]);
+				rgba = shade_summed(lit_rgba, lm.acc & 0xffffu, (uint32_t)lsum.n);
+			}
+			ray.dz = lt.phase ? lt.dz : ray.dz; // (the primary ray's, for the miss shade)
+		} else
 		if constexpr (LIT) {
 			if (lt.primary_hit) { // MISS, END and CAPPED shadow rays leave the pixel lit
 				uint32_t lit_rgba = lt.rgba;
@@ -988,6 +1082,15 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			my_cap = sg.ended ? 0u : my_cap;
 		}
 		// (row and pitch are below 2^31, api.cpp: one 32 x 32 -> 64-bit multiply-add)
+		if constexpr (LSUM) { // (the lane's pixel is made again from its number in the wave; each pointer test is a scalar branch)
+			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave,
+			                                      (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+			if (out != nullptr) out[(uint64_t)(uint32_t)me.lrow * (uint32_t)out_stride_px + (uint32_t)me.px] = rgba;
+			if (lsum.light != nullptr) {
+				uint8_t *row = reinterpret_cast<uint8_t *>(lsum.light) + (uint64_t)(uint32_t)me.lrow * (uint64_t)lsum.light_stride;
+				reinterpret_cast<uint16_t *>(row)[(uint32_t)me.px] = real_hit ? (uint16_t)lm.acc : (uint16_t)0xffffu;
+			}
+		} else
 		if constexpr (SUM) { // (one 16-bit store per lane: hmrm.h fixes the alignment at 2 bytes, so a wave's row is not widened further)
 			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave,
 			                                      (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
@@ -1044,6 +1147,9 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		                   pid.lrow, pid.live, aa_rgba);
 	else if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, lane, pid.px, pid.lrow, pid.live, aa_rgba);
 	// (SUM: capped rays are counted per ray, up to n per lane -- publish_counters' production path adds one per lane)
+	if constexpr (LSUM) { // (likewise: the primary ray once and every shadow ray, up to 1 + n per lane)
+		if ((lm.acc >> 16) != 0u) atomicAdd(&st.counters[2], (unsigned long long)(lm.acc >> 16));
+	} else
 	if constexpr (SUM) {
 		if ((sm.acc >> 16) != 0u) atomicAdd(&st.counters[2], (unsigned long long)(sm.acc >> 16));
 	} else

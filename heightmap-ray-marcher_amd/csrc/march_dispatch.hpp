@@ -15,8 +15,9 @@ enum FastKernel { kPlainGroups = 0, kLeaps = 1, kRecords = 2 };
 // Which kernels render a frame (render.hpp FrameLaunch): hmrm_render's, or the ones built with the interior rule, with
 // shadow rays, with diffuse shading without or with shadow rays, or the ones that store the geometry planes too.
 // (kFrameGeometry is no result of route_frame: a geometry frame takes the literal-or-march decision from it and sets the
-// family itself, api_launch.cpp.)
-enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded, kFrameGeometry };
+// family itself, api_launch.cpp.)  kFrameLitSum: the accumulated lit frame's (hmrm_render_lit_sum), one family for its four
+// `shade_flags`, which its kernels read at run time.
+enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded, kFrameGeometry, kFrameLitSum };
 
 // Which launch a frame gets.  `forced`: HMRM_KERNEL (2: simple); `huge_side`: a map side of 2^24 cells or more -- the production
 // kernel indexes cells and windows with 24-bit multiplies, leap_common.hpp index_2d; `interior`: hmrm_render_interior's frame
@@ -24,7 +25,7 @@ enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFr
 // HMRM_SHADE_*; 0: hmrm_render_lit's frame, by its kernels).  A sun takes precedence over `interior`: such a frame carries
 // the rule in FrameLaunch::primary_interior.  `aa` (the frame has an antialias factor) changes no route: the antialiased variant
 // of a family is its launchers' matter (f.aa_shift), and the one family without such kernels, the interior one, has no entry
-// point that takes a factor.
+// point that takes a factor.  `sum` (with `lit`): hmrm_render_lit_sum's frame -- one family whatever the flags, the caller's sun.
 constexpr unsigned kShadeDiffuse = 1u, kShadeNoShadows = 2u;
 struct FrameRoute {
 	bool refused;     // no kernel renders this frame: a huge side with another sampling than nearest
@@ -33,9 +34,13 @@ struct FrameRoute {
 	bool shadows;     // the launch marches shadow rays
 	bool ambient_sun; // the sun handed to the launch is the caller's with ambient = 255
 };
-inline FrameRoute route_frame(int forced, bool huge_side, int sampling, bool /*aa*/, bool interior, bool lit, unsigned shade_flags) {
+inline FrameRoute route_frame(int forced, bool huge_side, int sampling, bool /*aa*/, bool interior, bool lit, unsigned shade_flags,
+                              bool sum = false) {
 	FrameRoute r{huge_side && sampling != 0, (forced == 2 || huge_side) && sampling == 0, kFramePlain, false, false};
-	if (lit) {
+	if (lit && sum) {
+		r.family = kFrameLitSum;
+		r.shadows = !(shade_flags & kShadeNoShadows);
+	} else if (lit) {
 		// (HMRM_SHADE_NO_SHADOWS without HMRM_SHADE_DIFFUSE is hmrm_render's frame by definition.  It goes through the shaded kernel
 		// with every weight 255 all the same, not through the interior / plain kernels: the interior launcher always sets the
 		// interior rule, which this frame has only with HMRM_TRACE_INTERIOR, and the plain one belongs to frames that may be

@@ -447,6 +447,44 @@ __global__ __launch_bounds__(kBlockThreads) void k_render_geometry_literal(const
 	}
 }
 
+// A pixel of an accumulated lit frame (hmrm_render_lit_sum with HMRM_KERNEL=simple, or on a map with a side of 2^24 cells;
+// frame.hpp LightSum): the primary ray of a lit pixel, then the loop over the directions around pass 3 -- the shadow ray towards
+// direction k through the literal loop (unless HMRM_SHADE_NO_SHADOWS), hmrm_render_shaded's weight for it added up -- then the
+// pixel under its sum and / or the sum itself, each through a pointer that may be null.  Every pass publishes its own capped ray.
+template <int PROJ>
+__global__ __launch_bounds__(kBlockThreads) void k_render_lit_sum_literal(const DevFrame f, const RowMap rows,
+                                                                          const double *__restrict__ thr,
+                                                                          const uint32_t *__restrict__ cmap,
+                                                                          uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                          int tiles_y, StatsOut st, const SegRules seg, const SunRules sun,
+                                                                          const LightSum lsum) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	unsigned cell = 0u;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, sun, &lt, &cell);
+	uint32_t acc = 0u;
+	for (int k = 0; k < lsum.n; ++k) {
+		SunRules sk = sun;
+		sk.dir[0] = lsum.dirs[3 * k];
+		sk.dir[1] = lsum.dirs[3 * k + 1];
+		sk.dir[2] = lsum.dirs[3 * k + 2];
+		lt.phase = 0;
+		if ((lsum.flags & kShadeNoShadows) == 0u)
+			render_lane_literal<PROJ, false, false, true, 3>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
+			                                                 SegRules{nullptr, sun.max_steps, 1u}, sk, &lt);
+		if (pid.live && lt.primary_hit) {
+			uint32_t w = lt.phase != 0 ? sun.ambient : 255u;
+			if ((lsum.flags & kShadeDiffuse) != 0u && lt.phase == 0) w = shade_weight(sun.ambient, diffuse_level_nearest<false>(f, thr, cell, sk.dir));
+			acc += w;
+		}
+	}
+	if (!pid.live) return;
+	if (out != nullptr) out[(int64_t)pid.lrow * out_stride_px + pid.px] = lt.primary_hit ? shade_summed(lt.rgba, acc, (uint32_t)lsum.n) : lt.rgba;
+	if (lsum.light != nullptr)
+		*reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(lsum.light) + (int64_t)pid.lrow * lsum.light_stride + 2 * (int64_t)pid.px) =
+		    lt.primary_hit ? (uint16_t)acc : (uint16_t)0xffffu;
+}
+
 // Per-ray parity hook: GetRay + distance() of one pixel -> out[0..2] pos, [3..5] dir, [6] d.
 template <int PROJ>
 __global__ void k_probe(const DevFrame f, int px, int py, double *__restrict__ out) {
@@ -625,7 +663,8 @@ static hipError_t launch_literal(const FrameLaunch &l, const StatsOut &st, Launc
 }
 
 static hipError_t launch_plain_literal(const FrameLaunch &l); // (hmrm_render's frame: below)
-static hipError_t launch_geometry_literal(const FrameLaunch &l); // (hmrm_render_geometry's: the last kernels of the code object)
+static hipError_t launch_geometry_literal(const FrameLaunch &l); // (hmrm_render_geometry's, and behind them hmrm_render_lit_sum's:
+static hipError_t launch_lit_sum_literal(const FrameLaunch &l);  //  the last kernels of the code object)
 
 // The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
 // shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
@@ -640,6 +679,7 @@ hipError_t launch_frame_literal(const FrameLaunch &l) {
 			hipLaunchKernelGGL(k_render_interior_literal<proj()>, grid, block, 0, l.stream, args..., seg);
 		});
 	if (l.family == kFrameGeometry) return launch_geometry_literal(l);
+	if (l.family == kFrameLitSum) return launch_lit_sum_literal(l);
 	if (l.f.aa_shift == 0) switch (l.family) {
 		case kFrameLit:
 			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
@@ -690,6 +730,16 @@ static hipError_t launch_geometry_literal(const FrameLaunch &l) {
 	const SegRules seg = frame_seg_rules(l);
 	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
 		hipLaunchKernelGGL(k_render_geometry_literal<proj()>, grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.geo);
+	});
+}
+
+// An accumulated lit frame: the lit family's arguments and the list.  No antialiased variant, never a measured launch.
+static hipError_t launch_lit_sum_literal(const FrameLaunch &l) {
+	if (l.f.aa_shift != 0 || l.rows.measure != nullptr) return hipErrorInvalidValue;
+	if (l.lsum.n < 1 || l.lsum.n > kMaxSumDirs || !l.lsum.dirs || (!l.d_out && !l.lsum.light)) return hipErrorInvalidValue;
+	const SegRules seg = frame_seg_rules(l);
+	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
+		hipLaunchKernelGGL(k_render_lit_sum_literal<proj()>, grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.sun, l.lsum);
 	});
 }
 

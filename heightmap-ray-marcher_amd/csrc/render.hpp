@@ -48,6 +48,9 @@ struct FrameLaunch {
 	// of `geo` the same launch stores beside it (frame.hpp GeomPlanes; d_out may be null then: no colour plane)
 	GeomPlanes geo;
 	hipStream_t stream;
+	// kFrameLitSum (hmrm_render_lit_sum): kFrameLit whose shadow march runs once per direction of the list, the weights summed;
+	// sun.dir is not looked at, d_out may be null (no colour plane) and so may lsum.light (frame.hpp LightSum)
+	LightSum lsum = LightSum{nullptr, nullptr, 0, 0, 0u};
 };
 // The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups
 // (kPlainGroups), plus exact leaps over empty pyramid windows (kLeaps), or over windows of the record level that are empty but

@@ -286,6 +286,7 @@ hipError_t launch_frame_march(const FrameLaunch &l, FastKernel kernel) {
 	case kFrameShaded: return aa ? launch_render_shaded_aa(l, kernel) : launch_render_shaded(l, kernel);
 	case kFrameLitShaded: return aa ? launch_render_lit_shaded_aa(l, kernel) : launch_render_lit_shaded(l, kernel);
 	case kFrameGeometry: return launch_render_geometry(l, kernel); // (refuses a factor)
+	case kFrameLitSum: return launch_render_lit_sum(l, kernel); // (refuses a factor)
 	default: return aa ? launch_render_fast_aa(l, kernel) : launch_render_fast(l, kernel);
 	}
 }

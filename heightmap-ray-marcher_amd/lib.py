@@ -177,6 +177,21 @@ class GeometryPlanes(C.Structure):
 
 assert C.sizeof(GeometryPlanes) == 72
 
+
+class LightPlanes(C.Structure):
+    """hmrm_light_planes (40 bytes): where Scene.render_lit_sum's planes go -- host or device addresses, each with its row stride
+    in bytes; a null address: that plane is not written"""
+    _fields_ = [("rgba", C.c_void_p), ("rgba_stride", C.c_size_t), ("light", C.c_void_p), ("light_stride", C.c_size_t),
+                ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def make(cls, rgba=(0, 0), light=(0, 0)):
+        """Each plane: (address, stride_bytes); address 0 = not wanted."""
+        return cls(int(rgba[0]) or None, int(rgba[1]), int(light[0]) or None, int(light[1]), (C.c_uint32 * 2)())
+
+
+assert C.sizeof(LightPlanes) == 40
+
 # the same layouts as numpy structured dtypes (arrays of rays in, arrays of records out)
 RAY_DTYPE = np.dtype([("pos", np.float64, 3), ("dir", np.float64, 3)])
 RAY_HIT_DTYPE = np.dtype([("point", np.float64, 3), ("entry_d", np.float64), ("steps", np.uint32),
@@ -253,6 +268,8 @@ def _load():
         "hmrm_sky_directions": (C.c_int, [i32, i32, dp]),
         "hmrm_render_geometry": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(GeometryPlanes)]),
         "hmrm_render_geometry_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(GeometryPlanes), vp]),
+        "hmrm_render_lit_sum": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), dp, i32, C.c_uint32, C.POINTER(LightPlanes)]),
+        "hmrm_render_lit_sum_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, i32, C.c_uint32, C.POINTER(LightPlanes), vp]),
         "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
@@ -277,6 +294,7 @@ def _load():
         "hmrm_config_interior": (i32, [vp]),
         "hmrm_config_shadows": (i32, [vp]),
         "hmrm_config_shading": (i32, [vp]),
+        "hmrm_config_sky_light": (i32, [vp]),
         "hmrm_config_sun_scope": (i32, [vp]),
         "hmrm_config_sun_map_path": (C.c_char_p, [vp]),
         "hmrm_config_sun_map_lift": (C.c_double, [vp]),
@@ -750,6 +768,36 @@ class Scene:
         p = GeometryPlanes.make(rgba, cell, range, slope, interior)
         _check(lib.hmrm_render_geometry_device(self._h, C.byref(cam), C.byref(p), C.c_void_p(stream)))
 
+    def render_lit_sum(self, cam: Camera, sun: Sun, dirs, diffuse=False, shadows=True, light=False, allow_capped=False, rgba=True,
+                       pad_px=0):
+        """One accumulated lit frame (hmrm_render_lit_sum): render()'s frame -- render_interior()'s for a sun made with
+        interior=True -- in which every hit pixel is weighted by the SUM of render_shaded()'s weights under each of the
+        K = 1 .. 256 directions `dirs` ((K, 3): towards a sun or a patch of sky, used as given; sun.dir is not looked at), the
+        primary rays marched once -> the (H, W, 4) uint8 frame; with light=True (frame, light), light the (H, W) uint16 sums
+        (0xFFFF: no hit); with rgba=False the light plane alone.  pad_px > 0: every plane's rows are that many pixels wider
+        (returned whole; the padding keeps its poison bytes 0xA5).  Capped rays: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        if not rgba and not light:
+            raise ValueError("render_lit_sum: no plane asked for")
+        h, wp = cam.height, cam.width + int(pad_px)
+        fb = np.full((h, wp, 4), 0xA5, dtype=np.uint8) if rgba else None
+        lp = np.full((h, wp, 2), 0xA5, dtype=np.uint8).view(np.uint16).reshape(h, wp) if light else None
+        p = LightPlanes.make((fb.ctypes.data, wp * 4) if rgba else (0, 0), (lp.ctypes.data, wp * 2) if light else (0, 0))
+        _check(lib.hmrm_render_lit_sum(self._h, C.byref(cam), C.byref(sun), d.ctypes.data_as(C.POINTER(C.c_double)), len(d),
+                                       shade_flags(diffuse, shadows), C.byref(p)), allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return (fb, lp) if rgba and light else (fb if rgba else lp)
+
+    def render_lit_sum_device(self, cam: Camera, sun: Sun, d_dirs: int, n_dirs: int, rgba=(0, 0), light=(0, 0), diffuse=False,
+                              shadows=True, stream: int = 0):
+        """hmrm_render_lit_sum_device: the same planes into device memory -- each an (address, stride_bytes) pair, address 0 =
+        not wanted; rgba 4-byte aligned, light 2-byte -- the directions read from device memory (n_dirs x 3 float64, 8-byte
+        aligned), enqueued on `stream` without a host sync; take_capped(stream) reports the capped rays."""
+        self._sync_env()
+        p = LightPlanes.make(rgba, light)
+        _check(lib.hmrm_render_lit_sum_device(self._h, C.byref(cam), C.byref(sun), C.c_void_p(d_dirs), int(n_dirs),
+                                              shade_flags(diffuse, shadows), C.byref(p), C.c_void_p(stream)))
+
     def pick(self, cam: Camera, px: int, py: int, allow_capped=False) -> np.ndarray:
         """hmrm_pick: the record (RAY_HIT_DTYPE scalar) of the ray of pixel (px, py) of `cam`."""
         self._sync_env()
@@ -1008,6 +1056,11 @@ class Config:
     def shading(self) -> bool:
         """Additive `shading on|off`: the CLI renders its single frame with hmrm_render_shaded."""
         return bool(lib.hmrm_config_shading(self._h))
+
+    def sky_light(self) -> bool:
+        """Additive `sky_light on|off`: the CLI renders its single frame with hmrm_render_lit_sum over the sky directions of
+        `sky_map_rings`."""
+        return bool(lib.hmrm_config_sky_light(self._h))
 
     def sun_scope(self) -> int:
         """Additive `sun_scope single|all`: 0 | 1 -- whether shadows / shading also apply to antialiased and recorded frames."""

@@ -603,6 +603,60 @@ int hmrm_render_geometry(const hmrm_scene *scene, const hmrm_camera *cam, const 
 int hmrm_render_geometry_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_geometry_planes *device_planes,
                                 void *hip_stream);
 
+/* ------------------------------------------------------ accumulated lit frames */
+/* Many suns or sky directions per pixel in one launch (build-side addition), exact: a soft shadow from K samples on the sun's
+ * disc, an ambient-occlusion (sky-view) term, or sun plus sky composited from two light planes (INTEGRATION.md 2a has the three
+ * recipes).  It is the screen-space counterpart of hmrm_cell_map_sum: the primary rays are marched ONCE, then every pixel whose
+ * primary ray hit casts one shadow ray per direction, and the weights are summed per pixel before anything is quantised.
+ * THE PRIMARY RAY.  Every pixel first gets hmrm_render's value; with HMRM_TRACE_INTERIOR in sun->flags hmrm_render_interior's.
+ * K = n_dirs, in 1 .. 256.
+ * THE VALUE PER DIRECTION.  For a pixel whose primary ray HIT (alpha-0 hit cells count, as in hmrm_render_lit) and direction k
+ * let w_k be exactly the weight hmrm_render_shaded defines for that pixel when sun->dir is replaced by dirs[3k .. 3k+2] and
+ * shade_flags is the one given: without HMRM_SHADE_NO_SHADOWS the pixel casts hmrm_render_lit's shadow ray towards direction k
+ * -- origin (P.x, P.y, t), dir as given and NOT normalised, sun->step_dist, sun->max_steps, the camera's sampling, the interior
+ * rule always on -- and a shadow ray whose status is HIT gives w_k = ambient; a pixel that is not shadowed gets 255 or,
+ * HMRM_SHADE_DIFFUSE, the weight of THE LEVEL q under direction k.  Nothing is special-cased: NaN, infinite, zero and
+ * below-horizon directions go through the same arithmetic.  sun->dir itself is not looked at.
+ * THE SUM AND THE PLANES.  S = w_0 + .. + w_{K-1}, at most 65280.
+ *   rgba,  uint32 per pixel: for a hit R, G and B become (c * S + (255 * K) / 2) / (255 * K) in integers, A stays 255; the other
+ *          pixels -- misses, sky, capped primary rays -- keep the primary ray's value.
+ *   light, native uint16 per pixel: S for a hit, 0xFFFF otherwise.
+ * Either pointer may be NULL: that plane is not written, and no colour is fetched without rgba.  Rows are `stride` bytes apart;
+ * bytes between rows are not touched.
+ * Consequences, byte for byte: K = 1 is hmrm_render_shaded with sun->dir = dirs[0], under all four shade_flags; K copies of one
+ * direction give that direction's K = 1 frame with light = K * w (the rounding term (255 * K) / 2 was chosen for that); the order
+ * of the directions does not matter; HMRM_SHADE_NO_SHADOWS alone, or ambient = 255 without HMRM_SHADE_DIFFUSE, is hmrm_render /
+ * hmrm_render_interior.
+ * CAPPED RAYS.  A capped primary ray counts once; shadow rays count per RAY, up to K per pixel, as in hmrm_cell_map_sum; a capped
+ * shadow ray leaves its direction lit, as in hmrm_render_lit.  hmrm_render_lit_sum returns HMRM_E_NOTERM with valid planes; the
+ * device entry reports through hmrm_scene_take_capped for its stream, with no host sync -- hmrm_render_geometry_device's
+ * contract.  END rays never count.
+ * Refusals (HMRM_E_ARG, with a message) before the scene is looked at, in this order: hmrm_render_shaded's four; NULL dirs;
+ * n_dirs outside 1 .. 256; NULL planes; reserved not 0; both pointers NULL; a bad stride or alignment of a non-NULL plane (rgba:
+ * stride >= 4 * width, a multiple of 4; light: >= 2 * width, even; device pointers are aligned to their element, d_dirs to 8).
+ * Then the camera checks of hmrm_render, then a NULL scene, then the 2^24-side rule of frames.
+ * hmrm_render_lit_sum is synchronous on the scene's stream, one such call at a time per scene; it stages the directions, the
+ * pixels and the light plane through scene-owned device buffers that grow on demand.  hmrm_render_lit_sum_device takes DEVICE
+ * pointers (d_dirs: n_dirs x 3 doubles, read when the launch runs) and launches on hip_stream.
+ * Launched the way a lit frame is: one launch, never measured, never the scene's probe and not counted towards it;
+ * hmrm_debug_kernel_choice and every later frame are as they would have been.  It runs the scene's current kernel (HMRM_KERNEL or
+ * the probe's verdict; the window records apply to HMRM_NEAREST); every kernel writes the same bytes, the literal loop too
+ * (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest sampling only).  All three projections, grid modes and sampling modes.
+ * The work is bounded: every ray has its own budget of at most the step cap, and a pixel marches at most 1 + K rays.
+ * OUT OF SCOPE: antialiasing; tickets and lanes; row strips or bands; hmrm_render_multi, hmrm_render_cycle, recording and
+ * statistics; per-direction weights or colours; a baked per-cell light map read by the frame kernels. */
+typedef struct hmrm_light_planes {      /* either pointer may be NULL: that plane is not written */
+	void     *rgba;  size_t rgba_stride;   /* bytes per row, >= 4 * width, multiple of 4 */
+	uint16_t *light; size_t light_stride;  /* bytes per row, >= 2 * width, even */
+	uint32_t  reserved[2];                 /* must be 0 */
+} hmrm_light_planes;
+int hmrm_render_lit_sum(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun,
+                        const double *dirs /* n_dirs x 3, host */, int32_t n_dirs, uint32_t shade_flags,
+                        const hmrm_light_planes *host_planes);
+int hmrm_render_lit_sum_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun,
+                               const void *d_dirs /* n_dirs x 24 bytes, DEVICE, 8-byte aligned */, int32_t n_dirs,
+                               uint32_t shade_flags, const hmrm_light_planes *device_planes, void *hip_stream);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -777,6 +831,10 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * shadow_step_dist, shadow_max_steps, sun_map_lift and the camera's sampling; byte = (c * 255 + K / 2) / K for count c),
  * `sky_map_rings r n` (default 4 16; a product outside 1 .. 256 warns "WARNING: sky_map_rings must give 1..256 directions" and
  * keeps the old value),
+ * `sky_light on|off|1|0` (default off; the CLI renders its single frame with hmrm_render_lit_sum over those same directions --
+ * shadow rays always on, HMRM_SHADE_DIFFUSE with `shading on`, shadow_ambient, shadow_step_dist, shadow_max_steps and interior
+ * as for `shadows`, sun_dir not used; ignored, with a warning, with `antialias n` > 1, `devices n` > 1 or `record orbit`,
+ * whatever sun_scope says; another value warns "WARNING: Unknown sky_light: v" and keeps the old one),
  * `range_map <path.pfm>` (echoed like `output`; after its frames and before an optional sun_map the CLI writes the range plane
  * of the configured camera -- hmrm_render_geometry with that plane alone, under the interior rule with `interior on` -- as a
  * one-component portable float map, hmrm_write_pfm).
@@ -802,6 +860,7 @@ int32_t      hmrm_config_antialias(const hmrm_config *cfg);     /* additive `ant
 int32_t      hmrm_config_interior(const hmrm_config *cfg);      /* additive `interior on|off`: 1|0 */
 int32_t      hmrm_config_shadows(const hmrm_config *cfg);       /* additive `shadows on|off`: 1|0 */
 int32_t      hmrm_config_shading(const hmrm_config *cfg);       /* additive `shading on|off`: 1|0 */
+int32_t      hmrm_config_sky_light(const hmrm_config *cfg);     /* additive `sky_light on|off`: 1|0 */
 int32_t      hmrm_config_sun_scope(const hmrm_config *cfg);     /* additive `sun_scope single|all`: 0|1 */
 const char  *hmrm_config_sun_map_path(const hmrm_config *cfg);  /* additive `sun_map <path.png>`: "" = none */
 double       hmrm_config_sun_map_lift(const hmrm_config *cfg);  /* additive `sun_map_lift v` */
