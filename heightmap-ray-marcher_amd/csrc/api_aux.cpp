@@ -247,14 +247,14 @@ int hmrm_debug_ray(const hmrm_scene *scene, const hmrm_camera *cam, int32_t px, 
 	if (px < 0 || py < 0 || px >= cam->width || py >= cam->height) return fail(HMRM_E_ARG, "pixel out of range");
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
-	if ((rc = ensure_stats(s, 8))) return rc;
+	if ((rc = s->d_entry.reserve(8 * sizeof(double)))) return rc; // (borrowed: the probe's seven doubles)
 	StreamCtx *c = nullptr;
 	if ((rc = ctx_for(s, s->stream, &c))) return rc;
 	hmrm::DevFrame f;
 	if ((rc = prepare_frame(s, c, cam, &f, nullptr))) return rc;
-	HIP_TRY(hmrm::launch_probe(f, px, py, s->d_entry, s->stream));
+	HIP_TRY(hmrm::launch_probe(f, px, py, s->d_entry.as<double>(), s->stream));
 	double host[7];
-	HIP_TRY(hipMemcpyAsync(host, s->d_entry, sizeof host, hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipMemcpyAsync(host, s->d_entry.ptr, sizeof host, hipMemcpyDeviceToHost, s->stream));
 	HIP_TRY(hipStreamSynchronize(s->stream));
 	for (int i = 0; i < 3; ++i) { pos[i] = host[i]; dir[i] = host[3 + i]; }
 	*entry_d = host[6];

@@ -75,34 +75,44 @@ int check_device_stride(const hmrm_camera *cam, size_t stride_bytes) {
 	return HMRM_OK;
 }
 
-int ensure_frame(hmrm_scene *s, size_t px) {
-	if (px <= s->frame_px) return HMRM_OK;
-	if (s->d_frame) (void)hipFree(s->d_frame);
-	s->d_frame = nullptr;
-	s->frame_px = 0;
-	HIP_TRY(hipMalloc((void **)&s->d_frame, px * sizeof(uint32_t)));
-	s->frame_px = px;
+// One plane of a frame with several (geometry frames, lit sums; `prefix` names the family): a stride of whole elements that covers
+// the camera's width -- compared only when there is a camera with one: `width` is 0 else, and check_camera refuses right after --
+// and, with check_align, a pointer aligned to its elements.  A NULL plane is not wanted and passes.
+int check_plane(const char *prefix, const char *name, const void *ptr, size_t stride, size_t elem, size_t width, bool check_align) {
+	if (!ptr) return HMRM_OK;
+	if (stride < elem * width || (stride % elem) != 0 || stride / elem > 0x7fffffffu)
+		return fail(HMRM_E_ARG, std::string(prefix) + name + "_stride must be >= " + std::to_string(elem) + " * width, a multiple of " +
+		                            std::to_string(elem) + " and below 2^31 elements");
+	if (check_align && ((uintptr_t)ptr % elem) != 0)
+		return fail(HMRM_E_ARG, std::string(prefix) + name + " must be " + std::to_string(elem) + "-byte aligned");
+	return HMRM_OK;
+}
+size_t width_or_0(const hmrm_camera *cam) { return (cam && cam->width > 0) ? (size_t)cam->width : 0; }
+
+// A ticket pool (the read-back ring, the device tickets): *idx = the first free slot, else a new one while the pool has fewer
+// than kMaxRing, else the refusal `full`.  A new slot joins the pool only once complete() has made it whole -- a half-made slot
+// would be picked up as free by the next call -- and is torn down by the function hmrm_scene_destroy uses.  (s->mu held.)
+template <class Ticket> int acquire_ticket(std::vector<Ticket *> &pool, const char *who, const char *full, int *idx) {
+	for (size_t i = 0; i < pool.size(); ++i)
+		if (!pool[i]->busy) {
+			*idx = (int)i;
+			return HMRM_OK;
+		}
+	if ((int)pool.size() >= kMaxRing) return fail(HMRM_E_ARG, std::string(who) + ": " + full);
+	Ticket *t = new (std::nothrow) Ticket();
+	if (!t) return fail(HMRM_E_ARG, "out of memory");
+	const hipError_t e = t->complete();
+	if (e != hipSuccess) {
+		t->teardown();
+		delete t;
+		return fail(HMRM_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+	}
+	pool.push_back(t);
+	*idx = (int)pool.size() - 1;
 	return HMRM_OK;
 }
 
 } // namespace
-
-namespace hmrm {
-
-int ensure_stats(hmrm_scene *s, size_t px) {
-	if (px <= s->stats_px) return HMRM_OK;
-	if (s->d_steps) (void)hipFree(s->d_steps);
-	if (s->d_entry) (void)hipFree(s->d_entry);
-	s->d_steps = nullptr;
-	s->d_entry = nullptr;
-	s->stats_px = 0;
-	HIP_TRY(hipMalloc((void **)&s->d_steps, px * sizeof(uint32_t)));
-	HIP_TRY(hipMalloc((void **)&s->d_entry, px * sizeof(double)));
-	s->stats_px = px;
-	return HMRM_OK;
-}
-
-} // namespace hmrm
 
 extern "C" {
 
@@ -120,10 +130,6 @@ struct SyncFrame {
 constexpr SyncFrame kPlainSync{nullptr, nullptr, nullptr, false, 1, false, nullptr};
 
 static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes, const SyncFrame &how) {
-	// (locals named as in the device calls below: HIP_TRY quotes its expression in the error text)
-	hmrm_stats *const stats = how.stats;
-	uint32_t *const steps_pp = how.steps_pp;
-	double *const entry_d = how.entry_d;
 	const bool want_stats = how.want_stats;
 	int rc = check_camera(cam);
 	if (rc) return rc;
@@ -135,8 +141,9 @@ static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, s
 	if (stride_bytes < W * 4) return fail(HMRM_E_ARG, "stride_bytes < width*4");
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
-	if ((rc = ensure_frame(s, W * H))) return rc;
-	if (want_stats && aa_shift == 0 && (rc = ensure_stats(s, W * H))) return rc;
+	const bool per_pixel = want_stats && aa_shift == 0; // (per-pixel arrays are of the plain frame only)
+	if ((rc = s->d_frame.reserve(W * H * sizeof(uint32_t)))) return rc;
+	if (per_pixel && ((rc = s->d_steps.reserve(W * H * sizeof(uint32_t))) || (rc = s->d_entry.reserve(W * H * sizeof(double))))) return rc;
 	FrameSetup fs;
 	if ((rc = setup_frame(s, s->stream, &super, aa_shift, &fs))) return rc;
 	StreamCtx *const c = fs.c;
@@ -152,25 +159,23 @@ static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, s
 		HIP_TRY(hipMemsetAsync(c->d_counters + 4, 0, 4 * sizeof(unsigned long long), s->stream));
 	}
 	HIP_TRY(hipEventRecord(s->ev0, s->stream));
-	const bool per_pixel = want_stats && aa_shift == 0; // (per-pixel arrays are of the plain frame only)
-	const FrameRequest req{s->d_frame, (int64_t)W, per_pixel ? s->d_steps : nullptr, per_pixel ? s->d_entry : nullptr, want_stats, false,
-	                       interior, how.lit};
+	const FrameRequest req{s->d_frame.as<uint32_t>(), (int64_t)W, per_pixel ? s->d_steps.as<uint32_t>() : nullptr,
+	                       per_pixel ? s->d_entry.as<double>() : nullptr, want_stats, false, interior, how.lit};
 	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req))) return rc;
 	HIP_TRY(hipEventRecord(s->ev1, s->stream));
-	HIP_TRY(hipMemcpy2DAsync(rgba, stride_bytes, s->d_frame, W * 4, W * 4, H, hipMemcpyDeviceToHost,
-	                         s->stream));
+	HIP_TRY(hipMemcpy2DAsync(rgba, stride_bytes, s->d_frame.ptr, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
 	unsigned long long counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	HIP_TRY(hipMemcpyAsync(counters, c->d_counters, sizeof counters, hipMemcpyDeviceToHost, s->stream));
-	if (per_pixel && steps_pp)
-		HIP_TRY(hipMemcpyAsync(steps_pp, s->d_steps, W * H * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-	if (per_pixel && entry_d)
-		HIP_TRY(hipMemcpyAsync(entry_d, s->d_entry, W * H * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+	if (per_pixel && how.steps_pp)
+		HIP_TRY(hipMemcpyAsync(how.steps_pp, s->d_steps.ptr, W * H * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+	if (per_pixel && how.entry_d)
+		HIP_TRY(hipMemcpyAsync(how.entry_d, s->d_entry.ptr, W * H * sizeof(double), hipMemcpyDeviceToHost, s->stream));
 	HIP_TRY(hipStreamSynchronize(s->stream));
 	float ms = 0.f;
 	HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
 	g_last_kernel_ms = ms;
 	const unsigned long long capped = new_capped(c, counters[2]);
-	if (stats) {
+	if (hmrm_stats *const stats = how.stats) {
 		stats->rays = (uint64_t)super.width * (uint64_t)super.height;
 		stats->steps = counters[0];
 		stats->hits = counters[1];
@@ -233,30 +238,15 @@ static int check_geometry_planes(const hmrm_geometry_planes *p, const hmrm_camer
 	if (p->flags & ~HMRM_TRACE_INTERIOR) return fail(HMRM_E_ARG, "hmrm_geometry_planes.flags: undefined bit");
 	if (p->reserved != 0u) return fail(HMRM_E_ARG, "hmrm_geometry_planes.reserved must be 0");
 	if (!p->rgba && !p->cell && !p->range && !p->slope) return fail(HMRM_E_ARG, "geometry frame: every plane is NULL");
-	const size_t width = (cam && cam->width > 0) ? (size_t)cam->width : 0;
-	auto plane = [&](const char *name, const void *ptr, size_t stride, size_t elem) -> int {
-		if (!ptr) return HMRM_OK;
-		if (stride < elem * width || (stride % elem) != 0 || stride / elem > 0x7fffffffu)
-			return fail(HMRM_E_ARG, std::string("geometry frame: ") + name + "_stride must be >= " + std::to_string(elem) +
-			                            " * width, a multiple of " + std::to_string(elem) + " and below 2^31 elements");
-		if (((uintptr_t)ptr % elem) != 0 && (device || elem == 8))
-			return fail(HMRM_E_ARG, std::string("geometry frame: ") + name + " must be " + std::to_string(elem) + "-byte aligned");
-		return HMRM_OK;
-	};
+	// (a host plane of 4-byte elements may sit anywhere; the slope's 8-byte pairs are refused misaligned in host memory too)
+	const size_t width = width_or_0(cam);
+	const char *const pre = "geometry frame: ";
 	int rc;
-	if ((rc = plane("rgba", p->rgba, p->rgba_stride, 4)) || (rc = plane("cell", p->cell, p->cell_stride, 4)) ||
-	    (rc = plane("range", p->range, p->range_stride, 4)) || (rc = plane("slope", p->slope, p->slope_stride, 8)))
+	if ((rc = check_plane(pre, "rgba", p->rgba, p->rgba_stride, 4, width, device)) ||
+	    (rc = check_plane(pre, "cell", p->cell, p->cell_stride, 4, width, device)) ||
+	    (rc = check_plane(pre, "range", p->range, p->range_stride, 4, width, device)) ||
+	    (rc = check_plane(pre, "slope", p->slope, p->slope_stride, 8, width, true)))
 		return rc;
-	return HMRM_OK;
-}
-
-static int ensure_geom(hmrm_scene *s, size_t bytes) {
-	if (bytes <= s->geom_cap) return HMRM_OK;
-	if (s->d_geom) (void)hipFree(s->d_geom);
-	s->d_geom = nullptr;
-	s->geom_cap = 0;
-	HIP_TRY(hipMalloc((void **)&s->d_geom, bytes));
-	s->geom_cap = bytes;
 	return HMRM_OK;
 }
 
@@ -276,8 +266,8 @@ static int render_geometry_common(hmrm_scene *s, const hmrm_camera *cam, const h
 	int64_t rgba_stride_px = (int64_t)(p->rgba_stride / 4);
 	if (!device) {
 		const size_t px = W * H;
-		if ((rc = ensure_geom(s, px * ((p->slope ? 8 : 0) + (p->rgba ? 4 : 0) + (p->cell ? 4 : 0) + (p->range ? 4 : 0))))) return rc;
-		uint8_t *at = s->d_geom;
+		if ((rc = s->d_geom.reserve(px * ((p->slope ? 8 : 0) + (p->rgba ? 4 : 0) + (p->cell ? 4 : 0) + (p->range ? 4 : 0))))) return rc;
+		uint8_t *at = s->d_geom.as<uint8_t>();
 		auto take = [&](const void *wanted, size_t elem) -> void * {
 			if (!wanted) return nullptr;
 			void *here = at;
@@ -302,10 +292,7 @@ static int render_geometry_common(hmrm_scene *s, const hmrm_camera *cam, const h
 	if (p->rgba) HIP_TRY(hipMemcpy2DAsync(p->rgba, p->rgba_stride, d_rgba, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
 	if (p->cell) HIP_TRY(hipMemcpy2DAsync(p->cell, p->cell_stride, dev.cell, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
 	if (p->range) HIP_TRY(hipMemcpy2DAsync(p->range, p->range_stride, dev.range, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
-	unsigned long long capped_now = 0;
-	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return noterm(new_capped(c, capped_now));
+	return finish_host_call(s, c);
 }
 
 int hmrm_render_geometry(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_geometry_planes *host_planes) {
@@ -375,28 +362,12 @@ static int check_light_planes(const hmrm_light_planes *p, const hmrm_camera *cam
 	if (!p) return fail(HMRM_E_ARG, "lit sum: NULL planes");
 	if (p->reserved[0] != 0u || p->reserved[1] != 0u) return fail(HMRM_E_ARG, "hmrm_light_planes.reserved must be 0");
 	if (!p->rgba && !p->light) return fail(HMRM_E_ARG, "lit sum: both planes are NULL");
-	const size_t width = (cam && cam->width > 0) ? (size_t)cam->width : 0;
-	auto plane = [&](const char *name, const void *ptr, size_t stride, size_t elem) -> int {
-		if (!ptr) return HMRM_OK;
-		if (stride < elem * width || (stride % elem) != 0 || stride / elem > 0x7fffffffu)
-			return fail(HMRM_E_ARG, std::string("lit sum: ") + name + "_stride must be >= " + std::to_string(elem) + " * width, a multiple of " +
-			                            std::to_string(elem) + " and below 2^31 elements");
-		if (device && ((uintptr_t)ptr % elem) != 0)
-			return fail(HMRM_E_ARG, std::string("lit sum: ") + name + " must be " + std::to_string(elem) + "-byte aligned");
-		return HMRM_OK;
-	};
+	// (alignment is the device form's refusal only: host planes are reached by copies)
+	const size_t width = width_or_0(cam);
 	int rc;
-	if ((rc = plane("rgba", p->rgba, p->rgba_stride, 4)) || (rc = plane("light", p->light, p->light_stride, 2))) return rc;
-	return HMRM_OK;
-}
-
-static int ensure_light(hmrm_scene *s, size_t px) {
-	if (px <= s->light_cap) return HMRM_OK;
-	if (s->d_light) (void)hipFree(s->d_light);
-	s->d_light = nullptr;
-	s->light_cap = 0;
-	HIP_TRY(hipMalloc((void **)&s->d_light, px * sizeof(uint16_t)));
-	s->light_cap = px;
+	if ((rc = check_plane("lit sum: ", "rgba", p->rgba, p->rgba_stride, 4, width, device)) ||
+	    (rc = check_plane("lit sum: ", "light", p->light, p->light_stride, 2, width, device)))
+		return rc;
 	return HMRM_OK;
 }
 
@@ -421,16 +392,17 @@ static int render_lit_sum_common(hmrm_scene *s, const hmrm_camera *cam, const hm
 	int64_t rgba_stride_px = (int64_t)(p->rgba_stride / 4);
 	hmrm::LightSum sum{static_cast<const double *>(dirs), p->light, (int64_t)p->light_stride, n_dirs, shade_flags};
 	if (!device) {
-		if (p->rgba && (rc = ensure_frame(s, W * H))) return rc;
-		if (p->light && (rc = ensure_light(s, W * H))) return rc;
-		if ((rc = ensure_targets(s, (size_t)n_dirs))) return rc; // (hmrm_cell_map_sum's staging of its targets)
-		d_rgba = p->rgba ? s->d_frame : nullptr;
+		const size_t dirs_bytes = (size_t)n_dirs * 3 * sizeof(double);
+		if (p->rgba && (rc = s->d_frame.reserve(W * H * sizeof(uint32_t)))) return rc;
+		if (p->light && (rc = s->d_light.reserve(W * H * sizeof(uint16_t)))) return rc;
+		if ((rc = s->d_targets.reserve(dirs_bytes))) return rc; // (hmrm_cell_map_sum's staging of its targets)
+		d_rgba = p->rgba ? s->d_frame.as<uint32_t>() : nullptr;
 		rgba_stride_px = (int64_t)W;
-		sum.dirs = s->d_targets;
-		sum.light = p->light ? s->d_light : nullptr;
+		sum.dirs = s->d_targets.as<double>();
+		sum.light = p->light ? s->d_light.as<uint16_t>() : nullptr;
 		sum.light_stride = (int64_t)(2 * W);
 		stream = s->stream;
-		HIP_TRY(hipMemcpyAsync(s->d_targets, dirs, (size_t)n_dirs * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+		HIP_TRY(hipMemcpyAsync(s->d_targets.ptr, dirs, dirs_bytes, hipMemcpyHostToDevice, s->stream));
 	}
 	FrameSetup fs;
 	if ((rc = setup_frame(s, stream, cam, 0, &fs))) return rc;
@@ -442,10 +414,7 @@ static int render_lit_sum_common(hmrm_scene *s, const hmrm_camera *cam, const hm
 	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req)) || device) return rc;
 	if (p->rgba) HIP_TRY(hipMemcpy2DAsync(p->rgba, p->rgba_stride, d_rgba, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
 	if (p->light) HIP_TRY(hipMemcpy2DAsync(p->light, p->light_stride, sum.light, W * 2, W * 2, H, hipMemcpyDeviceToHost, s->stream));
-	unsigned long long capped_now = 0;
-	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return noterm(new_capped(c, capped_now));
+	return finish_host_call(s, c);
 }
 
 int hmrm_render_lit_sum(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun, const double *dirs, int32_t n_dirs,
@@ -551,32 +520,26 @@ int hmrm_render_multi(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_ca
 		std::lock_guard<std::mutex> lk(s->mu);
 		const int32_t local = hmrm_band_local_rows(H, kBand, i, n);
 		int rc2;
-		if ((rc2 = ensure_frame(s, W * (size_t)local))) return rc2;
-		if (!pinned_dst && s->h_stage_bytes < W * 4 * (size_t)local) {
-			if (s->h_stage) (void)hipHostFree(s->h_stage);
-			s->h_stage = nullptr;
-			s->h_stage_bytes = 0;
-			HIP_TRY(hipHostMalloc((void **)&s->h_stage, W * 4 * (size_t)local, hipHostMallocDefault));
-			s->h_stage_bytes = W * 4 * (size_t)local;
-		}
+		if ((rc2 = s->d_frame.reserve(W * 4 * (size_t)local))) return rc2;
+		if (!pinned_dst && (rc2 = s->h_stage.reserve(W * 4 * (size_t)local))) return rc2;
 		FrameSetup fs;
 		if ((rc2 = setup_frame(s, s->stream, cam, 0, &fs))) return rc2;
 		hmrm::RowMap rows{0, local, kBand, i, n, {}, {}, nullptr};
-		return launch_frame(s, fs.c, fs.f, fs.slot, rows, plain_request(s->d_frame, (int64_t)W));
+		return launch_frame(s, fs.c, fs.f, fs.slot, rows, plain_request(s->d_frame.as<uint32_t>(), (int64_t)W));
 	};
 	auto enqueue_copy = [&](int i) -> int {
 		hmrm_scene *s = scenes[i];
 		HIP_TRY(hipSetDevice(s->device));
 		const int32_t local = hmrm_band_local_rows(H, kBand, i, n);
 		if (!pinned_dst) { // the whole strip in one transfer
-			HIP_TRY(hipMemcpyAsync(s->h_stage, s->d_frame, W * 4 * (size_t)local, hipMemcpyDeviceToHost, s->stream));
+			HIP_TRY(hipMemcpyAsync(s->h_stage.ptr, s->d_frame.ptr, W * 4 * (size_t)local, hipMemcpyDeviceToHost, s->stream));
 			return HMRM_OK;
 		}
 		// band b of this scene's strip is frame rows [(i + b*n) * kBand, ...): contiguous in both
 		for (int b = 0; (i + b * n) * kBand < H; ++b) {
 			const int row0 = (i + b * n) * kBand, nrows = std::min(kBand, H - row0);
 			HIP_TRY(hipMemcpy2DAsync(rgba + (size_t)row0 * stride_bytes, stride_bytes,
-			                         s->d_frame + (size_t)b * kBand * W, W * 4, W * 4, (size_t)nrows,
+			                         s->d_frame.as<uint32_t>() + (size_t)b * kBand * W, W * 4, W * 4, (size_t)nrows,
 			                         hipMemcpyDeviceToHost, s->stream));
 		}
 		return HMRM_OK;
@@ -596,7 +559,7 @@ int hmrm_render_multi(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_ca
 		if (e != hipSuccess) return drain(fail(HMRM_E_DEVICE, std::string("hmrm_render_multi: ") + hipGetErrorString(e)));
 		if (!pinned_dst) {
 			const int bands = (H - i * kBand + n * kBand - 1) / (n * kBand); // bands i, i+n, .. below H
-			const uint8_t *src = s->h_stage;
+			const uint8_t *src = s->h_stage.as<uint8_t>();
 			hmrm::parallel_ranges(bands, 4, [&](int b0, int b1) {
 				for (int b = b0; b < b1; ++b) {
 					const int row0 = (i + b * n) * kBand, nrows = std::min(kBand, H - row0);
@@ -667,50 +630,19 @@ static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
 	int idx = -1;
-	for (size_t i = 0; i < s->ring.size(); ++i)
-		if (!s->ring[i]->busy) {
-			idx = (int)i;
-			break;
-		}
-	if (idx < 0) {
-		if ((int)s->ring.size() >= kMaxRing) return fail(HMRM_E_ARG, "hmrm_render_begin: every frame of the ring is in use (release one)");
-		RingFrame *r = new (std::nothrow) RingFrame();
-		if (!r) return fail(HMRM_E_ARG, "out of memory");
-		// (complete before it joins the ring: a half-made slot would be picked up as free by the next call)
-		hipError_t e = hipEventCreateWithFlags(&r->kernel_done, hipEventDisableTiming);
-		if (e == hipSuccess) e = hipEventCreateWithFlags(&r->copy_done, hipEventDisableTiming);
-		if (e == hipSuccess) e = hipHostMalloc((void **)&r->h_capped, sizeof(unsigned long long), hipHostMallocDefault);
-		if (e != hipSuccess) {
-			if (r->kernel_done) (void)hipEventDestroy(r->kernel_done);
-			if (r->copy_done) (void)hipEventDestroy(r->copy_done);
-			if (r->h_capped) (void)hipHostFree(r->h_capped);
-			delete r;
-			return fail(HMRM_E_DEVICE, std::string("hmrm_render_begin: ") + hipGetErrorString(e));
-		}
-		s->ring.push_back(r);
-		idx = (int)s->ring.size() - 1;
-	}
+	if ((rc = acquire_ticket(s->ring, "hmrm_render_begin", "every frame of the ring is in use (release one)", &idx))) return rc;
 	RingFrame *r = s->ring[(size_t)idx];
-	if (W * H > r->px) {
-		// (the slot is free: nothing in flight touches its buffers)
-		if (r->d_frame) (void)hipFree(r->d_frame);
-		if (r->h_frame) (void)hipHostFree(r->h_frame);
-		r->d_frame = nullptr;
-		r->h_frame = nullptr;
-		r->px = 0;
-		HIP_TRY(hipMalloc((void **)&r->d_frame, W * H * sizeof(uint32_t)));
-		HIP_TRY(hipHostMalloc((void **)&r->h_frame, W * H * 4, hipHostMallocDefault));
-		r->px = W * H;
-	}
+	// (the slot is free: nothing in flight touches its buffers)
+	if ((rc = r->d_frame.reserve(W * H * 4)) || (rc = r->h_frame.reserve(W * H * 4))) return rc;
 	hipStream_t lane = nullptr;
 	FrameSetup fs;
 	if ((rc = next_lane(s, &lane)) || (rc = setup_frame(s, lane, &super, aa_shift, &fs))) return rc;
-	if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, ticket_request(r->d_frame, (int64_t)W, flags, lit)))) return rc;
+	if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, ticket_request(r->d_frame.as<uint32_t>(), (int64_t)W, flags, lit)))) return rc;
 	StreamCtx *const c = fs.c;
 	r->ctx = c;
 	HIP_TRY(hipEventRecord(r->kernel_done, c->stream));
 	HIP_TRY(hipStreamWaitEvent(s->copy_stream, r->kernel_done, 0));
-	HIP_TRY(hipMemcpyAsync(r->h_frame, r->d_frame, W * H * 4, hipMemcpyDeviceToHost, s->copy_stream));
+	HIP_TRY(hipMemcpyAsync(r->h_frame.ptr, r->d_frame.ptr, W * H * 4, hipMemcpyDeviceToHost, s->copy_stream));
 	HIP_TRY(hipMemcpyAsync(r->h_capped, c->d_counters + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost,
 	                       s->copy_stream));
 	HIP_TRY(hipEventRecord(r->copy_done, s->copy_stream));
@@ -745,7 +677,7 @@ int hmrm_render_wait(const hmrm_scene *scene, int32_t ticket, const uint8_t **rg
 	}
 	HIP_TRY(hipSetDevice(s->device));
 	HIP_TRY(hipEventSynchronize(r->copy_done)); // (outside the lock: other threads may begin frames meanwhile)
-	*rgba = r->h_frame;
+	*rgba = r->h_frame.as<uint8_t>();
 	if (stride_bytes) *stride_bytes = (size_t)r->width * 4;
 	std::lock_guard<std::mutex> lk(s->mu);
 	return noterm(new_capped(r->ctx, *r->h_capped));
@@ -778,25 +710,7 @@ static int device_begin_common(const hmrm_scene *scene, const hmrm_camera *cam, 
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
 	int idx = -1;
-	for (size_t i = 0; i < s->dev_tickets.size(); ++i)
-		if (!s->dev_tickets[i]->busy) {
-			idx = (int)i;
-			break;
-		}
-	if (idx < 0) {
-		if ((int)s->dev_tickets.size() >= kMaxRing) return fail(HMRM_E_ARG, "hmrm_render_device_begin: 64 frames in flight (wait for one)");
-		DevTicket *t = new (std::nothrow) DevTicket();
-		if (!t) return fail(HMRM_E_ARG, "out of memory");
-		hipError_t e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
-		if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_capped, sizeof(unsigned long long), hipHostMallocDefault);
-		if (e != hipSuccess) {
-			if (t->done) (void)hipEventDestroy(t->done);
-			delete t;
-			return fail(HMRM_E_DEVICE, std::string("hmrm_render_device_begin: ") + hipGetErrorString(e));
-		}
-		s->dev_tickets.push_back(t);
-		idx = (int)s->dev_tickets.size() - 1;
-	}
+	if ((rc = acquire_ticket(s->dev_tickets, "hmrm_render_device_begin", "64 frames in flight (wait for one)", &idx))) return rc;
 	DevTicket *t = s->dev_tickets[(size_t)idx];
 	hipStream_t lane = nullptr;
 	FrameSetup fs;
@@ -852,11 +766,11 @@ double hmrm_bench_kernel_ms(const hmrm_scene *scene, const hmrm_camera *cam, int
 		const size_t W = (size_t)cam->width, H = (size_t)cam->height;
 		HIP_TRY(hipSetDevice(s->device));
 		std::lock_guard<std::mutex> lk(s->mu);
-		int rc = ensure_frame(s, W * H);
+		int rc = s->d_frame.reserve(W * H * sizeof(uint32_t));
 		if (rc) return rc;
 		FrameSetup fs;
 		if ((rc = setup_frame(s, s->stream, cam, 0, &fs))) return rc;
-		const FrameRequest req = plain_request(s->d_frame, (int64_t)W);
+		const FrameRequest req = plain_request(s->d_frame.as<uint32_t>(), (int64_t)W);
 		HIP_TRY(hipEventRecord(s->ev0, s->stream));
 		for (int i = 0; i < iters; ++i)
 			if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, req))) return rc;

@@ -1,10 +1,11 @@
-// api_internal.hpp -- what the translation units behind the C ABI (api_*.cpp) share: the scene and the launch state it keeps
-// per stream, the request a frame entry point hands to the launch path, and the functions that cross those files.  Not
-// installed and not included by include/hmrm.h.
+// api_internal.hpp -- what the translation units behind the C ABI (api_*.cpp) share: the grow-only scratch buffer, the scene and
+// the launch state it keeps per stream, the ticket kinds, the request a frame entry point hands to the launch path, and the
+// functions that cross those files.  Not installed and not included by include/hmrm.h.
 //   api_scene.cpp    scene lifetime: create, update, destroy; knobs, stream contexts, pyramids, records, read-backs; the
 //                    per-thread error text
-//   api_launch.cpp   the frame launch path: the cached per-camera record, calibration and probe, launch_frame
-//   api_frames.cpp   the frame entry points: synchronous, tickets, rows, multi, bench
+//   api_launch.cpp   the frame launch path: the cached per-camera record, calibration and probe, launch_frame; the capped-ray
+//                    count and the tail of a host-memory call
+//   api_frames.cpp   the frame entry points: synchronous, tickets (and their pool), rows, multi, bench; the plane checker
 //   api_queries.cpp  ray batches, segments, cell maps and their sums, pick
 //   api_aux.cpp      config, image IO and the debug hooks
 #pragma once
@@ -53,6 +54,31 @@ struct Knobs {
 	int seg_n = 0;                       // HMRM_TILE_SEGMENTS=b0:c0,b1:c1,.. (tools): tile-row pieces to start first, in this order
 	int seg_b[3] = {0, 0, 0}, seg_c[3] = {0, 0, 0};
 };
+
+// A grow-only allocation, capacity in BYTES: the staging of the host-memory entry points (device memory) and of the frames that
+// cross PCIe behind the caller's back (pinned host memory).  reserve() keeps what is there when it is large enough; else it frees
+// first -- nothing in flight may use the buffer: s->mu held, the stream drained by the previous host call or the slot free --
+// and an allocation that fails leaves an empty buffer.  A plain member: hmrm_scene_destroy releases by hand, after hipSetDevice.
+template <bool kPinned> struct Scratch {
+	void *ptr = nullptr;
+	size_t cap = 0;
+	int reserve(size_t bytes) {
+		if (bytes <= cap) return HMRM_OK;
+		release();
+		if (kPinned) HIP_TRY(hipHostMalloc(&ptr, bytes, hipHostMallocDefault));
+		else HIP_TRY(hipMalloc(&ptr, bytes));
+		cap = bytes;
+		return HMRM_OK;
+	}
+	template <class T> T *as() const { return static_cast<T *>(ptr); }
+	void release() {
+		if (ptr) (void)(kPinned ? hipHostFree(ptr) : hipFree(ptr));
+		ptr = nullptr;
+		cap = 0;
+	}
+};
+using DeviceScratch = Scratch<false>;
+using PinnedScratch = Scratch<true>;
 
 constexpr int kFrameSlots = 64;  // cached per-frame records (and spherical tables) per stream: a 64-frame orbit fits
 constexpr int kMaxMeasRows = 512;  // tile rows (8192 frame rows) a launch order is calibrated for; taller frames keep the rotation
@@ -107,15 +133,29 @@ struct StreamCtx {
 // events that order the two streams.
 struct RingFrame {
 	StreamCtx *ctx = nullptr;   // launch state of the lane the frame's kernel ran on (its capped-ray counter)
-	uint32_t *d_frame = nullptr;
-	uint8_t *h_frame = nullptr; // pinned
+	DeviceScratch d_frame;      // width x height uint32 RGBA, rows packed
+	PinnedScratch h_frame;      // the same bytes
 	unsigned long long *h_capped = nullptr; // pinned: the stream's cumulative capped-ray counter after this frame
-	size_t px = 0;
 	int32_t width = 0, height = 0;
 	hipEvent_t kernel_done = nullptr, copy_done = nullptr;
 	bool busy = false;
+	// What acquire_ticket (api_frames.cpp) asks of a ticket kind: complete() makes a fresh slot usable -- its events and its pinned
+	// counter word; the frame buffers grow with the first frame -- and teardown() frees whatever a slot holds, half-made or used.
+	hipError_t complete() {
+		hipError_t e = hipEventCreateWithFlags(&kernel_done, hipEventDisableTiming);
+		if (e == hipSuccess) e = hipEventCreateWithFlags(&copy_done, hipEventDisableTiming);
+		if (e == hipSuccess) e = hipHostMalloc((void **)&h_capped, sizeof(unsigned long long), hipHostMallocDefault);
+		return e;
+	}
+	void teardown() {
+		d_frame.release();
+		h_frame.release();
+		if (h_capped) (void)hipHostFree(h_capped);
+		if (kernel_done) (void)hipEventDestroy(kernel_done);
+		if (copy_done) (void)hipEventDestroy(copy_done);
+	}
 };
-constexpr int kMaxRing = 64;
+constexpr int kMaxRing = 64; // slots of either ticket pool
 // Launch lanes: the ticketed entry points (hmrm_render_begin, hmrm_render_device_begin) send consecutive frames to
 // kLanes scene-owned streams in turn, so that one launch's tail (a few long waves) overlaps the next launch's start
 // without the caller managing streams -- what bench.py's `frames_in_flight` block does by hand (C2: 0.064 -> 0.045 ms per
@@ -127,6 +167,15 @@ struct DevTicket {
 	hipEvent_t done = nullptr;
 	unsigned long long *h_capped = nullptr; // pinned: the lane's cumulative capped-ray counter after this frame
 	bool busy = false;
+	hipError_t complete() { // (as RingFrame's)
+		hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+		if (e == hipSuccess) e = hipHostMalloc((void **)&h_capped, sizeof(unsigned long long), hipHostMallocDefault);
+		return e;
+	}
+	void teardown() {
+		if (done) (void)hipEventDestroy(done);
+		if (h_capped) (void)hipHostFree(h_capped);
+	}
 };
 
 struct hmrm_scene {
@@ -158,28 +207,20 @@ struct hmrm_scene {
 	std::vector<DevTicket *> dev_tickets;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	unsigned long long *d_maxkey = nullptr; // UpdateHeightmap's max(thr) reduction
-	// scratch of the host-memory entry points (hmrm_render*, one caller at a time)
-	uint32_t *d_frame = nullptr;
-	size_t frame_px = 0;
-	uint8_t *h_stage = nullptr; // pinned staging strip of hmrm_render_multi (pageable destination frames)
-	size_t h_stage_bytes = 0;
-	uint32_t *d_steps = nullptr;
-	double *d_entry = nullptr;
-	size_t stats_px = 0;
-	// staging of hmrm_trace_rays / hmrm_pick (host rays in, host records out): grown on demand, freed with the scene
-	hmrm::BatchRay *d_rays = nullptr;
-	hmrm::BatchHit *d_hits = nullptr;
-	size_t batch_cap = 0;
-	uint32_t *d_limits = nullptr; // ... and of hmrm_trace_segments' per-ray limits
-	size_t limits_cap = 0;
-	uint8_t *d_cells = nullptr; // ... and of hmrm_cell_map: the rect's bytes, rows packed
-	size_t cells_cap = 0;
-	double *d_targets = nullptr; // ... and of hmrm_cell_map_sum's targets (its words go through d_cells)
-	size_t targets_cap = 0;
-	uint8_t *d_geom = nullptr; // ... and of hmrm_render_geometry's planes: the wanted ones back to back, rows packed
-	size_t geom_cap = 0;
-	uint16_t *d_light = nullptr; // ... and of hmrm_render_lit_sum's light plane, rows packed (its directions go through d_targets,
-	size_t light_cap = 0;        //     its pixels through d_frame)
+	// scratch of the host-memory entry points (one caller at a time, s->mu held): each grown on demand by the entry point that knows
+	// the size, all released by hmrm_scene_destroy
+	DeviceScratch d_frame;   // hmrm_render*'s pixels (uint32 RGBA, rows packed); hmrm_render_multi's strip; hmrm_render_lit_sum's pixels
+	PinnedScratch h_stage;   // pinned staging strip of hmrm_render_multi (pageable destination frames)
+	DeviceScratch d_steps;   // hmrm_render_stats' per-pixel steps (uint32) ...
+	DeviceScratch d_entry;   // ... and entry distances (double).  hmrm_pick and hmrm_debug_ray borrow it for their probe's seven or
+	                         // eight doubles, hmrm_pick also for a spherical camera's tables at + 8: 8 + 2W + 2H doubles
+	DeviceScratch d_rays;    // hmrm_trace_rays / hmrm_trace_segments: host rays in (hmrm::BatchRay) ...
+	DeviceScratch d_hits;    // ... and host records out (hmrm::BatchHit); hmrm_pick's one record
+	DeviceScratch d_limits;  // hmrm_trace_segments' per-ray limits (uint32)
+	DeviceScratch d_cells;   // hmrm_cell_map's rect of bytes, hmrm_cell_map_sum's rect of 16-bit words: rows packed
+	DeviceScratch d_targets; // hmrm_cell_map_sum's targets and hmrm_render_lit_sum's directions: three doubles each
+	DeviceScratch d_geom;    // hmrm_render_geometry's planes: the wanted ones back to back, slope first, rows packed
+	DeviceScratch d_light;   // hmrm_render_lit_sum's light plane (uint16), rows packed
 	// launch state per stream; `mu` guards the list and the slot choice (launches themselves are
 	// asynchronous), so that threads driving different streams of one scene do not collide
 	std::mutex mu;
@@ -256,7 +297,7 @@ namespace hmrm {
 int ctx_for(hmrm_scene *s, hipStream_t stream, StreamCtx **out);
 int ensure_records(hmrm_scene *s);
 int ensure_bilinear_pyramid(hmrm_scene *s);
-// api_launch.cpp.  prepare_frame, wait_for_measure_fence, launch_frame, new_capped, take_capped: s->mu held.
+// api_launch.cpp.  prepare_frame, wait_for_measure_fence, launch_frame, new_capped, take_capped, finish_host_call: s->mu held.
 int check_camera(const hmrm_camera *cam);
 void to_host_camera(const hmrm_camera *cam, hmrm::HostCamera *hc);
 int prepare_frame(hmrm_scene *s, StreamCtx *c, const hmrm_camera *cam, hmrm::DevFrame *f, FrameSlot **slot_out);
@@ -264,10 +305,7 @@ int wait_for_measure_fence(hmrm_scene *s, StreamCtx *c);
 int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot *slot, const hmrm::RowMap &rows, const FrameRequest &req);
 unsigned long long new_capped(StreamCtx *c, unsigned long long now);
 int take_capped(StreamCtx *c, unsigned long long *out);
+int finish_host_call(hmrm_scene *s, StreamCtx *c, unsigned long long *capped_out = nullptr);
 int noterm(unsigned long long capped);
-// api_frames.cpp (s->mu held): the scene's per-pixel scratch, which hmrm_pick and hmrm_debug_ray borrow
-int ensure_stats(hmrm_scene *s, size_t px);
-// api_queries.cpp (s->mu held): the scene's staging of a list of n targets or directions
-int ensure_targets(hmrm_scene *s, size_t n);
 } // namespace hmrm
 #pragma GCC visibility pop

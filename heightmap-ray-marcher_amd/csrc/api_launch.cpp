@@ -425,6 +425,19 @@ int take_capped(StreamCtx *c, unsigned long long *out) {
 	return HMRM_OK;
 }
 
+// The tail of a host-memory entry point that launched on the scene's own stream (c: its context) and has enqueued its copies
+// to the caller's memory there: the stream's capped-ray count comes back behind them, the stream is drained -- the caller's
+// memory is filled then, and the scene's scratch is free for the next call -- and the call's result is noterm() of the new
+// capped rays (*capped_out: how many, for a caller that reports them in its stats).  (s->mu held.)
+int finish_host_call(hmrm_scene *s, StreamCtx *c, unsigned long long *capped_out) {
+	unsigned long long capped_now = 0;
+	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	const unsigned long long capped = new_capped(c, capped_now);
+	if (capped_out) *capped_out = capped;
+	return noterm(capped);
+}
+
 // What a call returns for `capped` rays at the step cap: HMRM_OK for none.
 int noterm(unsigned long long capped) {
 	if (!capped) return HMRM_OK;

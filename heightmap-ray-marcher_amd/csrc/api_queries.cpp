@@ -43,29 +43,6 @@ int check_segments(const hmrm_segment_params *p, const void *rays, int64_t n, co
 	return HMRM_OK;
 }
 
-int ensure_limits(hmrm_scene *s, size_t n) {
-	if (n <= s->limits_cap) return HMRM_OK;
-	if (s->d_limits) (void)hipFree(s->d_limits);
-	s->d_limits = nullptr;
-	s->limits_cap = 0;
-	HIP_TRY(hipMalloc((void **)&s->d_limits, n * sizeof(uint32_t)));
-	s->limits_cap = n;
-	return HMRM_OK;
-}
-
-int ensure_batch(hmrm_scene *s, size_t n) {
-	if (n <= s->batch_cap) return HMRM_OK;
-	if (s->d_rays) (void)hipFree(s->d_rays);
-	if (s->d_hits) (void)hipFree(s->d_hits);
-	s->d_rays = nullptr;
-	s->d_hits = nullptr;
-	s->batch_cap = 0;
-	HIP_TRY(hipMalloc((void **)&s->d_rays, n * sizeof(hmrm::BatchRay)));
-	HIP_TRY(hipMalloc((void **)&s->d_hits, n * sizeof(hmrm::BatchHit)));
-	s->batch_cap = n;
-	return HMRM_OK;
-}
-
 // The DevFrame of a launch without a camera (ray batches, cell maps): a zeroed record plus the scene's box, grid and pyramid.
 // The leap policy's hints come from a camera's step length in cells for frames (camera.cpp); such a launch's directions have
 // any length, so it gets the fine-step defaults: windows from 4 cells on, no pause (HMRM_MIN_LEVEL / HMRM_FINEST_PAUSE apply).
@@ -105,33 +82,43 @@ int cameraless_kernel(hmrm_scene *s, int sampling, bool *literal, hmrm::FastKern
 	return *k == hmrm::kRecords ? ensure_records(s) : HMRM_OK;
 }
 
-// One batch on the context's stream.  The DevFrame has no camera: a zeroed record plus the scene's box, grid and pyramid,
-// laid out as a frame kBatchW pixels wide (frame.hpp RayBatch).  A batch is not a frame: it takes no cached record, is
-// never measured, never probes and does not count towards the scene's probe; it only READS the scene's kernel choice
-// (HMRM_KERNEL or the probe's verdict), and waits -- in stream order -- for a measured launch in flight like any launch.
+// What every launch without a camera does before its kernel goes out, in this order: the DevFrame (cameraless_frame) laid out as a
+// w x h "frame" of the given projection code, the wait -- in stream order -- for a measured launch in flight, and only then the
+// kernel (cameraless_kernel: a probe's verdict may have arrived meanwhile).  Such a launch is not a frame: it takes no cached
+// record, is never measured, never probes and does not count towards the scene's probe.
+struct Cameraless {
+	hmrm::DevFrame f;
+	bool literal = false;
+	hmrm::FastKernel k = hmrm::kLeaps;
+};
+int cameraless_prologue(hmrm_scene *s, StreamCtx *c, double step_dist, int sampling, int32_t w, int32_t h, int32_t projection, Cameraless *out) {
+	int rc = cameraless_frame(s, step_dist, sampling, &out->f);
+	if (rc) return rc;
+	out->f.screen_w = w;
+	out->f.screen_h = h;
+	out->f.projection = projection;
+	if ((rc = wait_for_measure_fence(s, c))) return rc;
+	return cameraless_kernel(s, sampling, &out->literal, &out->k);
+}
+
+// One batch on the context's stream, laid out as a frame kBatchW pixels wide (frame.hpp RayBatch).
 // `seg` (hmrm_trace_segments; null: hmrm_trace_rays): the segment rules, run by the segment kernels (render_segments.hip).
 int launch_batch(hmrm_scene *s, StreamCtx *c, double step_dist, const uint8_t bg[3], int sampling, const hmrm::BatchRay *d_rays,
                  int64_t n, hmrm::BatchHit *d_hits, const hmrm::SegRules *seg = nullptr) {
-	hmrm::DevFrame f;
-	int rc = cameraless_frame(s, step_dist, sampling, &f);
+	Cameraless cl;
+	const int rc = cameraless_prologue(s, c, step_dist, sampling, hmrm::kBatchW, (int32_t)((n + hmrm::kBatchW - 1) / hmrm::kBatchW), 4, &cl);
 	if (rc) return rc;
-	f.screen_w = hmrm::kBatchW;
-	f.screen_h = (int32_t)((n + hmrm::kBatchW - 1) / hmrm::kBatchW);
-	f.projection = 4;
+	hmrm::DevFrame &f = cl.f;
 	f.bg[0] = bg[0];
 	f.bg[1] = bg[1];
 	f.bg[2] = bg[2];
 	const hmrm::RayBatch batch{d_rays, d_hits, n};
-	if ((rc = wait_for_measure_fence(s, c))) return rc;
-	bool literal = false;
-	hmrm::FastKernel k;
-	if ((rc = cameraless_kernel(s, sampling, &literal, &k))) return rc;
-	if (literal) {
+	if (cl.literal) {
 		if (seg) HIP_TRY(hmrm::launch_trace_segments_literal(f, s->d_thr, s->d_cmap, batch, *seg, c->d_counters, c->stream));
 		else HIP_TRY(hmrm::launch_trace_rays_literal(f, s->d_thr, s->d_cmap, batch, c->d_counters, c->stream));
 	} else {
-		if (seg) HIP_TRY(hmrm::launch_trace_segments(f, s->d_thr, s->d_thr32, s->d_cmap, batch, *seg, c->d_counters, k, s->d_records, c->stream));
-		else HIP_TRY(hmrm::launch_trace_rays(f, s->d_thr, s->d_thr32, s->d_cmap, batch, c->d_counters, k, s->d_records, c->stream));
+		if (seg) HIP_TRY(hmrm::launch_trace_segments(f, s->d_thr, s->d_thr32, s->d_cmap, batch, *seg, c->d_counters, cl.k, s->d_records, c->stream));
+		else HIP_TRY(hmrm::launch_trace_rays(f, s->d_thr, s->d_thr32, s->d_cmap, batch, c->d_counters, cl.k, s->d_records, c->stream));
 	}
 	return HMRM_OK;
 }
@@ -162,33 +149,14 @@ int check_cell_rect(const hmrm_scene *s, const hmrm_cell_rect *rect, size_t stri
 	return HMRM_OK;
 }
 
-int ensure_cells(hmrm_scene *s, size_t n) {
-	if (n <= s->cells_cap) return HMRM_OK;
-	if (s->d_cells) (void)hipFree(s->d_cells);
-	s->d_cells = nullptr;
-	s->cells_cap = 0;
-	HIP_TRY(hipMalloc((void **)&s->d_cells, n));
-	s->cells_cap = n;
-	return HMRM_OK;
-}
-
-// One cell map on the context's stream: launch_batch's recipe -- a DevFrame without a camera whose "frame" is the rect, the
-// fine-step leap hints, no cached record, never measured, never a probe and not counted towards it; it only READS the scene's
-// kernel choice and waits, in stream order, for a measured launch in flight.
+// One cell map on the context's stream: a launch without a camera whose "frame" is the rect.
 int launch_cells(hmrm_scene *s, StreamCtx *c, const hmrm_cell_map_params *p, const hmrm_cell_rect &r, uint8_t *d_out, size_t stride_bytes) {
-	hmrm::DevFrame f;
-	int rc = cameraless_frame(s, p->step_dist, p->sampling, &f);
+	Cameraless cl;
+	const int rc = cameraless_prologue(s, c, p->step_dist, p->sampling, r.w, r.h, 5, &cl);
 	if (rc) return rc;
-	f.screen_w = r.w;
-	f.screen_h = r.h;
-	f.projection = 5;
 	const hmrm::CellRules cells{{p->target[0], p->target[1], p->target[2]}, p->lift, r.x0, r.y0, p->max_steps, p->flags, p->ambient};
-	if ((rc = wait_for_measure_fence(s, c))) return rc;
-	bool literal = false;
-	hmrm::FastKernel k;
-	if ((rc = cameraless_kernel(s, p->sampling, &literal, &k))) return rc;
-	if (literal) HIP_TRY(hmrm::launch_cell_map_literal(f, s->d_thr, d_out, (int64_t)stride_bytes, cells, c->d_counters, c->stream));
-	else HIP_TRY(hmrm::launch_cell_map(f, s->d_thr, s->d_thr32, d_out, (int64_t)stride_bytes, cells, c->d_counters, k, s->d_records, c->stream));
+	if (cl.literal) HIP_TRY(hmrm::launch_cell_map_literal(cl.f, s->d_thr, d_out, (int64_t)stride_bytes, cells, c->d_counters, c->stream));
+	else HIP_TRY(hmrm::launch_cell_map(cl.f, s->d_thr, s->d_thr32, d_out, (int64_t)stride_bytes, cells, c->d_counters, cl.k, s->d_records, c->stream));
 	return HMRM_OK;
 }
 
@@ -209,52 +177,26 @@ int check_cell_sum_rect(const hmrm_scene *s, const hmrm_cell_rect *rect, size_t 
 	return HMRM_OK;
 }
 
-} // namespace
-
-namespace hmrm {
-// The scene's staging of a list of n targets or directions, three doubles each (hmrm_cell_map_sum; api_frames.cpp stages
-// hmrm_render_lit_sum's directions through it too).  (s->mu held.)
-int ensure_targets(hmrm_scene *s, size_t n) {
-	if (n <= s->targets_cap) return HMRM_OK;
-	if (s->d_targets) (void)hipFree(s->d_targets);
-	s->d_targets = nullptr;
-	s->targets_cap = 0;
-	HIP_TRY(hipMalloc((void **)&s->d_targets, n * 3 * sizeof(double)));
-	s->targets_cap = n;
-	return HMRM_OK;
-}
-} // namespace hmrm
-
-namespace {
-
 // One accumulated cell map on the context's stream: launch_cells' recipe with the list of targets beside the rules.
 int launch_cell_sums(hmrm_scene *s, StreamCtx *c, const hmrm_cell_map_params *p, const double *d_targets, int32_t n_targets,
                      const hmrm_cell_rect &r, uint16_t *d_out, size_t stride_bytes) {
-	hmrm::DevFrame f;
-	int rc = cameraless_frame(s, p->step_dist, p->sampling, &f);
+	Cameraless cl;
+	const int rc = cameraless_prologue(s, c, p->step_dist, p->sampling, r.w, r.h, 5, &cl);
 	if (rc) return rc;
-	f.screen_w = r.w;
-	f.screen_h = r.h;
-	f.projection = 5;
 	const hmrm::CellRules cells{{0.0, 0.0, 0.0}, p->lift, r.x0, r.y0, p->max_steps, p->flags, p->ambient}; // (p->target is not looked at)
 	const hmrm::CellSums sums{d_targets, n_targets};
-	if ((rc = wait_for_measure_fence(s, c))) return rc;
-	bool literal = false;
-	hmrm::FastKernel k;
-	if ((rc = cameraless_kernel(s, p->sampling, &literal, &k))) return rc;
-	if (literal) HIP_TRY(hmrm::launch_cell_map_sum_literal(f, s->d_thr, d_out, (int64_t)stride_bytes, cells, sums, c->d_counters, c->stream));
-	else HIP_TRY(hmrm::launch_cell_map_sum(f, s->d_thr, s->d_thr32, d_out, (int64_t)stride_bytes, cells, sums, c->d_counters, k, s->d_records, c->stream));
+	if (cl.literal) HIP_TRY(hmrm::launch_cell_map_sum_literal(cl.f, s->d_thr, d_out, (int64_t)stride_bytes, cells, sums, c->d_counters, c->stream));
+	else HIP_TRY(hmrm::launch_cell_map_sum(cl.f, s->d_thr, s->d_thr32, d_out, (int64_t)stride_bytes, cells, sums, c->d_counters, cl.k, s->d_records, c->stream));
 	return HMRM_OK;
 }
 
 // The host-memory half of hmrm_trace_rays / hmrm_pick: the records of the scene's staging buffer and the stream's capped-ray
 // count come back, the stream is drained.  (s->mu held.)
 int finish_batch(hmrm_scene *s, StreamCtx *c, hmrm_ray_hit *hits, int64_t n, hmrm_stats *stats) {
-	HIP_TRY(hipMemcpyAsync(hits, s->d_hits, (size_t)n * sizeof(hmrm_ray_hit), hipMemcpyDeviceToHost, s->stream));
-	unsigned long long capped_now = 0;
-	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	const unsigned long long capped = new_capped(c, capped_now);
+	HIP_TRY(hipMemcpyAsync(hits, s->d_hits.ptr, (size_t)n * sizeof(hmrm_ray_hit), hipMemcpyDeviceToHost, s->stream));
+	unsigned long long capped = 0;
+	const int rc = finish_host_call(s, c, &capped);
+	if (rc == HMRM_E_DEVICE) return rc;
 	if (stats) {
 		*stats = hmrm_stats{};
 		stats->rays = (uint64_t)n;
@@ -264,97 +206,51 @@ int finish_batch(hmrm_scene *s, StreamCtx *c, hmrm_ray_hit *hits, int64_t n, hmr
 		}
 		stats->capped = capped;
 	}
-	return noterm(capped);
+	return rc;
 }
 
-} // namespace
-
-extern "C" {
-
-int hmrm_trace_rays(const hmrm_scene *scene, const hmrm_trace_params *p, const hmrm_ray *rays, int64_t n, hmrm_ray_hit *hits,
-                    hmrm_stats *stats) {
-	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
-	int rc = check_trace(p, rays, n, hits);
-	if (rc) return rc;
+// hmrm_trace_rays, hmrm_trace_segments and their device forms behind their own argument checks (check_trace, check_segments).
+// `sp`: the segment rules (null: plain rays -- or a segment call without params, which check_segments lets through for n == 0
+// only); `max_steps`: the segments' per-ray limits or null.  `device`: rays, max_steps and hits are device pointers and the
+// launch goes to `stream` without a host sync; else they are staged through the scene's buffers, on its own stream.
+int trace_common(hmrm_scene *s, const hmrm_trace_params *p, const hmrm_segment_params *sp, const void *rays, const void *max_steps,
+                 int64_t n, void *hits, hmrm_stats *stats, bool device, hipStream_t stream) {
 	if (!s) return fail(HMRM_E_ARG, "NULL argument");
 	if (n == 0) {
-		if (stats) *stats = hmrm_stats{};
+		if (!device && stats) *stats = hmrm_stats{};
 		return HMRM_OK;
 	}
+	if (device && (((uintptr_t)rays | (uintptr_t)hits) & 7u)) return fail(HMRM_E_ARG, "trace: d_rays and d_hits must be 8-byte aligned");
+	if (device && ((uintptr_t)max_steps & 3u)) return fail(HMRM_E_ARG, "trace: d_max_steps must be 4-byte aligned");
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
-	if ((rc = ensure_batch(s, (size_t)n))) return rc;
-	StreamCtx *c = nullptr;
-	if ((rc = ctx_for(s, s->stream, &c))) return rc;
-	HIP_TRY(hipMemcpyAsync(s->d_rays, rays, (size_t)n * sizeof(hmrm_ray), hipMemcpyHostToDevice, s->stream));
-	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
-	if ((rc = launch_batch(s, c, p->step_dist, bg, p->sampling, s->d_rays, n, s->d_hits))) return rc;
-	return finish_batch(s, c, hits, n, stats);
-}
-
-int hmrm_trace_rays_device(const hmrm_scene *scene, const hmrm_trace_params *p, const void *d_rays, int64_t n, void *d_hits,
-                           void *hip_stream) {
-	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
-	int rc = check_trace(p, d_rays, n, d_hits);
-	if (rc) return rc;
-	if (!s) return fail(HMRM_E_ARG, "NULL argument");
-	if (n == 0) return HMRM_OK;
-	if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 7u) return fail(HMRM_E_ARG, "trace: d_rays and d_hits must be 8-byte aligned");
-	HIP_TRY(hipSetDevice(s->device));
-	std::lock_guard<std::mutex> lk(s->mu);
-	StreamCtx *c = nullptr;
-	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
-	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
-	return launch_batch(s, c, p->step_dist, bg, p->sampling, static_cast<const hmrm::BatchRay *>(d_rays), n,
-	                    static_cast<hmrm::BatchHit *>(d_hits));
-}
-
-int hmrm_trace_segments(const hmrm_scene *scene, const hmrm_segment_params *p, const hmrm_ray *rays, const uint32_t *max_steps,
-                        int64_t n, hmrm_ray_hit *hits, hmrm_stats *stats) {
-	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
-	hmrm_trace_params plain{};
-	int rc = check_segments(p, rays, n, hits, &plain);
-	if (rc) return rc;
-	if (!s) return fail(HMRM_E_ARG, "NULL argument");
-	if (n == 0) {
-		if (stats) *stats = hmrm_stats{};
-		return HMRM_OK;
+	int rc;
+	if (!device) {
+		if ((rc = s->d_rays.reserve((size_t)n * sizeof(hmrm::BatchRay))) || (rc = s->d_hits.reserve((size_t)n * sizeof(hmrm::BatchHit)))) return rc;
+		if (max_steps && (rc = s->d_limits.reserve((size_t)n * sizeof(uint32_t)))) return rc;
+		stream = s->stream;
 	}
-	HIP_TRY(hipSetDevice(s->device));
-	std::lock_guard<std::mutex> lk(s->mu);
-	if ((rc = ensure_batch(s, (size_t)n))) return rc;
-	if (max_steps && (rc = ensure_limits(s, (size_t)n))) return rc;
 	StreamCtx *c = nullptr;
-	if ((rc = ctx_for(s, s->stream, &c))) return rc;
-	HIP_TRY(hipMemcpyAsync(s->d_rays, rays, (size_t)n * sizeof(hmrm_ray), hipMemcpyHostToDevice, s->stream));
-	if (max_steps) HIP_TRY(hipMemcpyAsync(s->d_limits, max_steps, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+	if ((rc = ctx_for(s, stream, &c))) return rc;
+	if (!device) {
+		HIP_TRY(hipMemcpyAsync(s->d_rays.ptr, rays, (size_t)n * sizeof(hmrm_ray), hipMemcpyHostToDevice, s->stream));
+		if (max_steps) HIP_TRY(hipMemcpyAsync(s->d_limits.ptr, max_steps, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+		rays = s->d_rays.ptr;
+		if (max_steps) max_steps = s->d_limits.ptr;
+	}
+	hmrm::BatchHit *const d_hits = device ? static_cast<hmrm::BatchHit *>(hits) : s->d_hits.as<hmrm::BatchHit>();
 	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
-	const hmrm::SegRules seg{max_steps ? s->d_limits : nullptr, p->max_steps, p->flags & HMRM_TRACE_INTERIOR};
-	if ((rc = launch_batch(s, c, p->step_dist, bg, p->sampling, s->d_rays, n, s->d_hits, &seg))) return rc;
-	return finish_batch(s, c, hits, n, stats);
+	hmrm::SegRules seg{};
+	if (sp) seg = hmrm::SegRules{static_cast<const uint32_t *>(max_steps), sp->max_steps, sp->flags & HMRM_TRACE_INTERIOR};
+	rc = launch_batch(s, c, p->step_dist, bg, p->sampling, static_cast<const hmrm::BatchRay *>(rays), n, d_hits, sp ? &seg : nullptr);
+	if (rc || device) return rc;
+	return finish_batch(s, c, static_cast<hmrm_ray_hit *>(hits), n, stats);
 }
 
-int hmrm_trace_segments_device(const hmrm_scene *scene, const hmrm_segment_params *p, const void *d_rays, const void *d_max_steps,
-                               int64_t n, void *d_hits, void *hip_stream) {
-	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
-	hmrm_trace_params plain{};
-	int rc = check_segments(p, d_rays, n, d_hits, &plain);
-	if (rc) return rc;
-	if (!s) return fail(HMRM_E_ARG, "NULL argument");
-	if (n == 0) return HMRM_OK;
-	if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 7u) return fail(HMRM_E_ARG, "trace: d_rays and d_hits must be 8-byte aligned");
-	if ((uintptr_t)d_max_steps & 3u) return fail(HMRM_E_ARG, "trace: d_max_steps must be 4-byte aligned");
-	HIP_TRY(hipSetDevice(s->device));
-	std::lock_guard<std::mutex> lk(s->mu);
-	StreamCtx *c = nullptr;
-	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
-	const uint8_t bg[3] = {p->bg_r, p->bg_g, p->bg_b};
-	const hmrm::SegRules seg{static_cast<const uint32_t *>(d_max_steps), p->max_steps, p->flags & HMRM_TRACE_INTERIOR};
-	return launch_batch(s, c, p->step_dist, bg, p->sampling, static_cast<const hmrm::BatchRay *>(d_rays), n,
-	                    static_cast<hmrm::BatchHit *>(d_hits), &seg);
-}
-
-int hmrm_cell_map(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect, uint8_t *out, size_t stride_bytes) {
+// hmrm_cell_map and its device form.  `device`: out is a device pointer and the launch goes to `stream` without a host sync; else
+// the rect is staged through the scene's buffer, rows packed, and copied to the caller's behind the launch.
+int cell_map_common(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect, void *out, size_t stride_bytes,
+                    bool device, hipStream_t stream) {
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	int rc = check_cell_map(p, out);
 	if (rc) return rc;
@@ -363,71 +259,94 @@ int hmrm_cell_map(const hmrm_scene *scene, const hmrm_cell_map_params *p, const 
 	if ((rc = check_cell_rect(s, rect, stride_bytes, &r))) return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
-	if ((rc = ensure_cells(s, (size_t)r.w * (size_t)r.h))) return rc;
+	const size_t row_bytes = (size_t)r.w;
+	if (!device) {
+		if ((rc = s->d_cells.reserve(row_bytes * (size_t)r.h))) return rc;
+		stream = s->stream;
+	}
 	StreamCtx *c = nullptr;
-	if ((rc = ctx_for(s, s->stream, &c))) return rc;
-	if ((rc = launch_cells(s, c, p, r, s->d_cells, (size_t)r.w))) return rc;
-	HIP_TRY(hipMemcpy2DAsync(out, stride_bytes, s->d_cells, (size_t)r.w, (size_t)r.w, (size_t)r.h, hipMemcpyDeviceToHost, s->stream));
-	unsigned long long capped_now = 0;
-	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return noterm(new_capped(c, capped_now));
+	if ((rc = ctx_for(s, stream, &c))) return rc;
+	if (device) return launch_cells(s, c, p, r, static_cast<uint8_t *>(out), stride_bytes);
+	if ((rc = launch_cells(s, c, p, r, s->d_cells.as<uint8_t>(), row_bytes))) return rc;
+	HIP_TRY(hipMemcpy2DAsync(out, stride_bytes, s->d_cells.ptr, row_bytes, row_bytes, (size_t)r.h, hipMemcpyDeviceToHost, s->stream));
+	return finish_host_call(s, c);
 }
 
-int hmrm_cell_map_device(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect, void *d_out,
-                         size_t stride_bytes, void *hip_stream) {
-	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
-	int rc = check_cell_map(p, d_out);
-	if (rc) return rc;
-	if (!s) return fail(HMRM_E_ARG, "NULL argument");
-	hmrm_cell_rect r;
-	if ((rc = check_cell_rect(s, rect, stride_bytes, &r))) return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	std::lock_guard<std::mutex> lk(s->mu);
-	StreamCtx *c = nullptr;
-	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
-	return launch_cells(s, c, p, r, static_cast<uint8_t *>(d_out), stride_bytes);
-}
-
-int hmrm_cell_map_sum(const hmrm_scene *scene, const hmrm_cell_map_params *p, const double *targets, int32_t n_targets,
-                      const hmrm_cell_rect *rect, uint16_t *out, size_t stride_bytes) {
+// hmrm_cell_map_sum and its device form, likewise: the host form's targets go through the scene's target list, its words through
+// the buffer hmrm_cell_map's bytes use.
+int cell_map_sum_common(const hmrm_scene *scene, const hmrm_cell_map_params *p, const void *targets, int32_t n_targets,
+                        const hmrm_cell_rect *rect, void *out, size_t stride_bytes, bool device, hipStream_t stream) {
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	int rc = check_cell_map_sum(p, targets, n_targets, out);
 	if (rc) return rc;
 	if (!s) return fail(HMRM_E_ARG, "NULL argument");
 	hmrm_cell_rect r;
 	if ((rc = check_cell_sum_rect(s, rect, stride_bytes, &r))) return rc;
+	if (device && ((uintptr_t)out & 1u)) return fail(HMRM_E_ARG, "cell map sum: d_out must be 2-byte aligned");
+	if (device && ((uintptr_t)targets & 7u)) return fail(HMRM_E_ARG, "cell map sum: d_targets must be 8-byte aligned");
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
-	const size_t row_bytes = 2 * (size_t)r.w;
-	if ((rc = ensure_cells(s, row_bytes * (size_t)r.h))) return rc;
-	if ((rc = ensure_targets(s, (size_t)n_targets))) return rc;
+	const size_t row_bytes = 2 * (size_t)r.w, targets_bytes = (size_t)n_targets * 3 * sizeof(double);
+	if (!device) {
+		if ((rc = s->d_cells.reserve(row_bytes * (size_t)r.h)) || (rc = s->d_targets.reserve(targets_bytes))) return rc;
+		stream = s->stream;
+	}
 	StreamCtx *c = nullptr;
-	if ((rc = ctx_for(s, s->stream, &c))) return rc;
-	HIP_TRY(hipMemcpyAsync(s->d_targets, targets, (size_t)n_targets * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream));
-	if ((rc = launch_cell_sums(s, c, p, s->d_targets, n_targets, r, reinterpret_cast<uint16_t *>(s->d_cells), row_bytes))) return rc;
-	HIP_TRY(hipMemcpy2DAsync(out, stride_bytes, s->d_cells, row_bytes, row_bytes, (size_t)r.h, hipMemcpyDeviceToHost, s->stream));
-	unsigned long long capped_now = 0;
-	HIP_TRY(hipMemcpyAsync(&capped_now, c->d_counters + 2, sizeof capped_now, hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return noterm(new_capped(c, capped_now));
+	if ((rc = ctx_for(s, stream, &c))) return rc;
+	if (device) return launch_cell_sums(s, c, p, static_cast<const double *>(targets), n_targets, r, static_cast<uint16_t *>(out), stride_bytes);
+	HIP_TRY(hipMemcpyAsync(s->d_targets.ptr, targets, targets_bytes, hipMemcpyHostToDevice, s->stream));
+	if ((rc = launch_cell_sums(s, c, p, s->d_targets.as<double>(), n_targets, r, s->d_cells.as<uint16_t>(), row_bytes))) return rc;
+	HIP_TRY(hipMemcpy2DAsync(out, stride_bytes, s->d_cells.ptr, row_bytes, row_bytes, (size_t)r.h, hipMemcpyDeviceToHost, s->stream));
+	return finish_host_call(s, c);
+}
+
+} // namespace
+
+extern "C" {
+
+int hmrm_trace_rays(const hmrm_scene *scene, const hmrm_trace_params *p, const hmrm_ray *rays, int64_t n, hmrm_ray_hit *hits,
+                    hmrm_stats *stats) {
+	if (const int rc = check_trace(p, rays, n, hits)) return rc;
+	return trace_common(const_cast<hmrm_scene *>(scene), p, nullptr, rays, nullptr, n, hits, stats, false, nullptr);
+}
+
+int hmrm_trace_rays_device(const hmrm_scene *scene, const hmrm_trace_params *p, const void *d_rays, int64_t n, void *d_hits,
+                           void *hip_stream) {
+	if (const int rc = check_trace(p, d_rays, n, d_hits)) return rc;
+	return trace_common(const_cast<hmrm_scene *>(scene), p, nullptr, d_rays, nullptr, n, d_hits, nullptr, true, (hipStream_t)hip_stream);
+}
+
+int hmrm_trace_segments(const hmrm_scene *scene, const hmrm_segment_params *p, const hmrm_ray *rays, const uint32_t *max_steps,
+                        int64_t n, hmrm_ray_hit *hits, hmrm_stats *stats) {
+	hmrm_trace_params plain{};
+	if (const int rc = check_segments(p, rays, n, hits, &plain)) return rc;
+	return trace_common(const_cast<hmrm_scene *>(scene), &plain, p, rays, max_steps, n, hits, stats, false, nullptr);
+}
+
+int hmrm_trace_segments_device(const hmrm_scene *scene, const hmrm_segment_params *p, const void *d_rays, const void *d_max_steps,
+                               int64_t n, void *d_hits, void *hip_stream) {
+	hmrm_trace_params plain{};
+	if (const int rc = check_segments(p, d_rays, n, d_hits, &plain)) return rc;
+	return trace_common(const_cast<hmrm_scene *>(scene), &plain, p, d_rays, d_max_steps, n, d_hits, nullptr, true, (hipStream_t)hip_stream);
+}
+
+int hmrm_cell_map(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect, uint8_t *out, size_t stride_bytes) {
+	return cell_map_common(scene, p, rect, out, stride_bytes, false, nullptr);
+}
+
+int hmrm_cell_map_device(const hmrm_scene *scene, const hmrm_cell_map_params *p, const hmrm_cell_rect *rect, void *d_out,
+                         size_t stride_bytes, void *hip_stream) {
+	return cell_map_common(scene, p, rect, d_out, stride_bytes, true, (hipStream_t)hip_stream);
+}
+
+int hmrm_cell_map_sum(const hmrm_scene *scene, const hmrm_cell_map_params *p, const double *targets, int32_t n_targets,
+                      const hmrm_cell_rect *rect, uint16_t *out, size_t stride_bytes) {
+	return cell_map_sum_common(scene, p, targets, n_targets, rect, out, stride_bytes, false, nullptr);
 }
 
 int hmrm_cell_map_sum_device(const hmrm_scene *scene, const hmrm_cell_map_params *p, const void *d_targets, int32_t n_targets,
                              const hmrm_cell_rect *rect, void *d_out, size_t stride_bytes, void *hip_stream) {
-	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
-	int rc = check_cell_map_sum(p, d_targets, n_targets, d_out);
-	if (rc) return rc;
-	if (!s) return fail(HMRM_E_ARG, "NULL argument");
-	hmrm_cell_rect r;
-	if ((rc = check_cell_sum_rect(s, rect, stride_bytes, &r))) return rc;
-	if ((uintptr_t)d_out & 1u) return fail(HMRM_E_ARG, "cell map sum: d_out must be 2-byte aligned");
-	if ((uintptr_t)d_targets & 7u) return fail(HMRM_E_ARG, "cell map sum: d_targets must be 8-byte aligned");
-	HIP_TRY(hipSetDevice(s->device));
-	std::lock_guard<std::mutex> lk(s->mu);
-	StreamCtx *c = nullptr;
-	if ((rc = ctx_for(s, (hipStream_t)hip_stream, &c))) return rc;
-	return launch_cell_sums(s, c, p, static_cast<const double *>(d_targets), n_targets, r, static_cast<uint16_t *>(d_out), stride_bytes);
+	return cell_map_sum_common(scene, p, d_targets, n_targets, rect, d_out, stride_bytes, true, (hipStream_t)hip_stream);
 }
 
 int hmrm_sky_directions(int32_t rings, int32_t per_ring, double *out_xyz) {
@@ -462,8 +381,9 @@ int hmrm_pick(const hmrm_scene *scene, const hmrm_camera *cam, int32_t px, int32
 	std::lock_guard<std::mutex> lk(s->mu);
 	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
 	const bool spherical = cam->projection == HMRM_SPHERICAL;
-	if ((rc = ensure_stats(s, 8 + (spherical ? 2 * W + 2 * H : 0)))) return rc;
-	if ((rc = ensure_batch(s, 1))) return rc;
+	// (borrowed: the scene's entry-distance scratch holds the probe's doubles and the tables, its hit records the one record)
+	if ((rc = s->d_entry.reserve((8 + (spherical ? 2 * W + 2 * H : 0)) * sizeof(double)))) return rc;
+	if ((rc = s->d_hits.reserve(sizeof(hmrm::BatchHit)))) return rc;
 	StreamCtx *c = nullptr;
 	if ((rc = ctx_for(s, s->stream, &c))) return rc;
 	hmrm::HostCamera hc;
@@ -475,7 +395,7 @@ int hmrm_pick(const hmrm_scene *scene, const hmrm_camera *cam, int32_t px, int32
 	                  spherical ? t : nullptr, spherical ? t + W : nullptr, spherical ? t + 2 * W : nullptr,
 	                  spherical ? t + 2 * W + H : nullptr);
 	if (spherical) {
-		double *d_t = s->d_entry + 8;
+		double *d_t = s->d_entry.as<double>() + 8;
 		// (pageable source: the copy is staged before the call returns)
 		HIP_TRY(hipMemcpyAsync(d_t, t, tables.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
 		f.col_cos_ha = d_t;
@@ -484,9 +404,9 @@ int hmrm_pick(const hmrm_scene *scene, const hmrm_camera *cam, int32_t px, int32
 		f.row_cos_va = d_t + 2 * W + H;
 	}
 	// the probe's first six doubles -- pos, dir -- are an hmrm_ray
-	HIP_TRY(hmrm::launch_probe(f, px, py, s->d_entry, s->stream));
+	HIP_TRY(hmrm::launch_probe(f, px, py, s->d_entry.as<double>(), s->stream));
 	const uint8_t bg[3] = {cam->bg_r, cam->bg_g, cam->bg_b};
-	if ((rc = launch_batch(s, c, cam->step_dist, bg, cam->sampling, reinterpret_cast<const hmrm::BatchRay *>(s->d_entry), 1, s->d_hits)))
+	if ((rc = launch_batch(s, c, cam->step_dist, bg, cam->sampling, s->d_entry.as<const hmrm::BatchRay>(), 1, s->d_hits.as<hmrm::BatchHit>())))
 		return rc;
 	return finish_batch(s, c, hit, 1, nullptr);
 }

@@ -322,17 +322,12 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	s->ctxs.clear();
 	if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
 	for (RingFrame *r : s->ring) {
-		if (r->d_frame) (void)hipFree(r->d_frame);
-		if (r->h_frame) (void)hipHostFree(r->h_frame);
-		if (r->h_capped) (void)hipHostFree(r->h_capped);
-		if (r->kernel_done) (void)hipEventDestroy(r->kernel_done);
-		if (r->copy_done) (void)hipEventDestroy(r->copy_done);
+		r->teardown();
 		delete r;
 	}
 	s->ring.clear();
 	for (DevTicket *t : s->dev_tickets) {
-		if (t->done) (void)hipEventDestroy(t->done);
-		if (t->h_capped) (void)hipHostFree(t->h_capped);
+		t->teardown();
 		delete t;
 	}
 	s->dev_tickets.clear();
@@ -349,20 +344,13 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	if (s->d_records) (void)hipFree(s->d_records);
 	if (s->d_mipbuf_bil) (void)hipFree(s->d_mipbuf_bil);
 	if (s->d_maxkey) (void)hipFree(s->d_maxkey);
-	if (s->d_frame) (void)hipFree(s->d_frame);
-	if (s->h_stage) (void)hipHostFree(s->h_stage);
+	for (DeviceScratch *b : {&s->d_frame, &s->d_steps, &s->d_entry, &s->d_rays, &s->d_hits, &s->d_limits, &s->d_cells, &s->d_targets,
+	                         &s->d_geom, &s->d_light})
+		b->release();
+	s->h_stage.release();
 	if (s->h_probe) (void)hipHostFree(s->h_probe);
 	if (s->probe_done) (void)hipEventDestroy(s->probe_done);
 	if (s->measure_fence) (void)hipEventDestroy(s->measure_fence);
-	if (s->d_steps) (void)hipFree(s->d_steps);
-	if (s->d_entry) (void)hipFree(s->d_entry);
-	if (s->d_rays) (void)hipFree(s->d_rays);
-	if (s->d_hits) (void)hipFree(s->d_hits);
-	if (s->d_limits) (void)hipFree(s->d_limits);
-	if (s->d_cells) (void)hipFree(s->d_cells);
-	if (s->d_targets) (void)hipFree(s->d_targets);
-	if (s->d_light) (void)hipFree(s->d_light);
-	if (s->d_geom) (void)hipFree(s->d_geom);
 	if (s->ev0) (void)hipEventDestroy(s->ev0);
 	if (s->ev1) (void)hipEventDestroy(s->ev1);
 	if (s->stream) (void)hipStreamDestroy(s->stream);
