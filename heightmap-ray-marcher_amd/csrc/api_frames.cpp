@@ -126,8 +126,21 @@ struct SyncFrame {
 	int32_t aa_factor;
 	bool interior; // hmrm_render_interior
 	const LitFrame *lit;
+	bool baked = false;          // hmrm_render_baked: the hit pixels under the scene's light plane ...
+	bool baked_interior = false; // ... and, HMRM_TRACE_INTERIOR, every origin tested by the kernels
 };
 constexpr SyncFrame kPlainSync{nullptr, nullptr, nullptr, false, 1, false, nullptr};
+
+// The scene's light plane as a baked frame's launch takes it, or the refusal of a scene without one.  (s->mu held.)
+static int baked_light_of(const hmrm_scene *s, hmrm::BakedLight *out) {
+	if (!s->d_baked || s->baked_scale == 0u) return fail(HMRM_E_ARG, "the scene has no light plane");
+	*out = hmrm::BakedLight{s->d_baked, s->baked_scale};
+	return HMRM_OK;
+}
+static int check_baked_flags(uint32_t baked_flags) {
+	if (baked_flags & ~HMRM_TRACE_INTERIOR) return fail(HMRM_E_ARG, "baked_flags: undefined bit");
+	return HMRM_OK;
+}
 
 static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, size_t stride_bytes, const SyncFrame &how) {
 	const bool want_stats = how.want_stats;
@@ -142,6 +155,8 @@ static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, s
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
 	const bool per_pixel = want_stats && aa_shift == 0; // (per-pixel arrays are of the plain frame only)
+	hmrm::BakedLight baked{nullptr, 0u};
+	if (how.baked && (rc = baked_light_of(s, &baked))) return rc;
 	if ((rc = s->d_frame.reserve(W * H * sizeof(uint32_t)))) return rc;
 	if (per_pixel && ((rc = s->d_steps.reserve(W * H * sizeof(uint32_t))) || (rc = s->d_entry.reserve(W * H * sizeof(double))))) return rc;
 	FrameSetup fs;
@@ -159,8 +174,12 @@ static int render_common(hmrm_scene *s, const hmrm_camera *cam, uint8_t *rgba, s
 		HIP_TRY(hipMemsetAsync(c->d_counters + 4, 0, 4 * sizeof(unsigned long long), s->stream));
 	}
 	HIP_TRY(hipEventRecord(s->ev0, s->stream));
-	const FrameRequest req{s->d_frame.as<uint32_t>(), (int64_t)W, per_pixel ? s->d_steps.as<uint32_t>() : nullptr,
-	                       per_pixel ? s->d_entry.as<double>() : nullptr, want_stats, false, interior, how.lit};
+	FrameRequest req{s->d_frame.as<uint32_t>(), (int64_t)W, per_pixel ? s->d_steps.as<uint32_t>() : nullptr,
+	                 per_pixel ? s->d_entry.as<double>() : nullptr, want_stats, false, interior, how.lit};
+	if (how.baked) { // (with the flag every origin is tested by the kernels, whatever the projection: a geometry frame's rule)
+		req.baked = &baked;
+		req.interior = how.baked_interior ? Interior::kByKernels : Interior::kNot;
+	}
 	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req))) return rc;
 	HIP_TRY(hipEventRecord(s->ev1, s->stream));
 	HIP_TRY(hipMemcpy2DAsync(rgba, stride_bytes, s->d_frame.ptr, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
@@ -428,6 +447,18 @@ int hmrm_render_lit_sum_device(const hmrm_scene *scene, const hmrm_camera *cam, 
 	                             (hipStream_t)hip_stream);
 }
 
+// ---- baked-light frames: hmrm_render's frame (hmrm_render_interior's with HMRM_TRACE_INTERIOR) whose hit pixels take the weight of
+// the scene's light plane, antialiased or not ----
+int hmrm_render_baked(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t baked_flags, int32_t factor, uint8_t *rgba,
+                      size_t stride_bytes) {
+	if (const int rc = check_baked_flags(baked_flags)) return rc;
+	SyncFrame how = kPlainSync;
+	how.aa_factor = factor;
+	how.baked = true;
+	how.baked_interior = (baked_flags & HMRM_TRACE_INTERIOR) != 0u;
+	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, how);
+}
+
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
                       size_t stride_bytes, hmrm_stats *stats, uint32_t *steps_per_pixel, double *entry_d) {
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes,
@@ -619,8 +650,23 @@ static FrameRequest ticket_request(uint32_t *d_out, int64_t out_stride_px, uint3
 	return FrameRequest{d_out, out_stride_px, nullptr, nullptr, false, (flags & HMRM_NO_PROBE) != 0, Interior::kNot, lit};
 }
 
+// A baked ticket (hmrm_render_baked_begin, hmrm_render_baked_device_begin).  The plane is looked up under the lock
+// and goes into the launch by value: a later hmrm_scene_set_light drains the lane before it touches the plane.
+struct BakedTicket {
+	bool on = false;
+	bool interior = false;
+};
+static int apply_baked(const hmrm_scene *s, const BakedTicket &bt, hmrm::BakedLight *light, FrameRequest *req) {
+	if (!bt.on) return HMRM_OK;
+	if (const int rc = baked_light_of(s, light)) return rc;
+	req->baked = light;
+	req->interior = bt.interior ? Interior::kByKernels : Interior::kNot;
+	return HMRM_OK;
+}
+
 // `lit` (hmrm_render_shaded_begin): the ticket's frame is a lit one -- launched the way a lit frame is (launch_frame), on the lane.
-static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket, const LitFrame *lit) {
+static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket, const LitFrame *lit,
+                        const BakedTicket &bt = BakedTicket{}) {
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	hmrm_camera super;
 	int aa_shift = 0;
@@ -629,6 +675,9 @@ static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_
 	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
+	hmrm::BakedLight light{nullptr, 0u};
+	FrameRequest req = ticket_request(nullptr, (int64_t)W, flags, lit);
+	if ((rc = apply_baked(s, bt, &light, &req))) return rc;
 	int idx = -1;
 	if ((rc = acquire_ticket(s->ring, "hmrm_render_begin", "every frame of the ring is in use (release one)", &idx))) return rc;
 	RingFrame *r = s->ring[(size_t)idx];
@@ -637,7 +686,8 @@ static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_
 	hipStream_t lane = nullptr;
 	FrameSetup fs;
 	if ((rc = next_lane(s, &lane)) || (rc = setup_frame(s, lane, &super, aa_shift, &fs))) return rc;
-	if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, ticket_request(r->d_frame.as<uint32_t>(), (int64_t)W, flags, lit)))) return rc;
+	req.d_out = r->d_frame.as<uint32_t>();
+	if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, req))) return rc;
 	StreamCtx *const c = fs.c;
 	r->ctx = c;
 	HIP_TRY(hipEventRecord(r->kernel_done, c->stream));
@@ -701,7 +751,7 @@ int hmrm_render_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, vo
 }
 
 static int device_begin_common(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba, size_t stride_bytes, uint32_t flags,
-                               int32_t *ticket, const LitFrame *lit) {
+                               int32_t *ticket, const LitFrame *lit, const BakedTicket &bt = BakedTicket{}) {
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	hmrm_camera super;
 	int aa_shift = 0;
@@ -709,13 +759,16 @@ static int device_begin_common(const hmrm_scene *scene, const hmrm_camera *cam, 
 	if (rc || (rc = check_device_stride(cam, stride_bytes))) return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	std::lock_guard<std::mutex> lk(s->mu);
+	hmrm::BakedLight light{nullptr, 0u};
+	FrameRequest req = ticket_request((uint32_t *)d_rgba, (int64_t)(stride_bytes / 4), flags, lit);
+	if ((rc = apply_baked(s, bt, &light, &req))) return rc;
 	int idx = -1;
 	if ((rc = acquire_ticket(s->dev_tickets, "hmrm_render_device_begin", "64 frames in flight (wait for one)", &idx))) return rc;
 	DevTicket *t = s->dev_tickets[(size_t)idx];
 	hipStream_t lane = nullptr;
 	FrameSetup fs;
 	if ((rc = next_lane(s, &lane)) || (rc = setup_frame(s, lane, &super, aa_shift, &fs))) return rc;
-	if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, ticket_request((uint32_t *)d_rgba, (int64_t)(stride_bytes / 4), flags, lit)))) return rc;
+	if ((rc = launch_frame(s, fs.c, fs.f, fs.slot, fs.rows, req))) return rc;
 	StreamCtx *const c = fs.c;
 	HIP_TRY(hipMemcpyAsync(t->h_capped, c->d_counters + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipEventRecord(t->done, c->stream));
@@ -735,6 +788,18 @@ int hmrm_render_shaded_device_begin(const hmrm_scene *scene, const hmrm_camera *
 	if (const int rc = check_shaded(sun, shade_flags)) return rc;
 	const LitFrame lit = make_lit_frame(sun, shade_flags);
 	return device_begin_common(scene, cam, d_rgba, stride_bytes, flags, ticket, &lit);
+}
+
+// Baked tickets: from the same ring, the same lanes and the same device-ticket pool as the plain and the lit ones.
+int hmrm_render_baked_begin(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t baked_flags, uint32_t flags, int32_t *ticket) {
+	if (const int rc = check_baked_flags(baked_flags)) return rc;
+	return begin_common(scene, cam, flags, ticket, nullptr, BakedTicket{true, (baked_flags & HMRM_TRACE_INTERIOR) != 0u});
+}
+
+int hmrm_render_baked_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t baked_flags, void *d_rgba,
+                                   size_t stride_bytes, uint32_t flags, int32_t *ticket) {
+	if (const int rc = check_baked_flags(baked_flags)) return rc;
+	return device_begin_common(scene, cam, d_rgba, stride_bytes, flags, ticket, nullptr, BakedTicket{true, (baked_flags & HMRM_TRACE_INTERIOR) != 0u});
 }
 
 int hmrm_render_device_wait(const hmrm_scene *scene, int32_t ticket) {
@@ -796,4 +861,5 @@ int32_t hmrm_band_local_rows(int32_t height, int32_t band_rows, int32_t band_ind
 
 namespace hmrm {
 int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags) { return check_shaded(sun, shade_flags); } // (record.cpp)
+int check_baked_args(uint32_t baked_flags) { return check_baked_flags(baked_flags); }                         // (likewise)
 } // namespace hmrm

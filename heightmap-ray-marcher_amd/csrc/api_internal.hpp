@@ -1,7 +1,7 @@
 // api_internal.hpp -- what the translation units behind the C ABI (api_*.cpp) share: the grow-only scratch buffer, the scene and
 // the launch state it keeps per stream, the ticket kinds, the request a frame entry point hands to the launch path, and the
 // functions that cross those files.  Not installed and not included by include/hmrm.h.
-//   api_scene.cpp    scene lifetime: create, update, destroy; knobs, stream contexts, pyramids, records, read-backs; the
+//   api_scene.cpp    scene lifetime: create, update, destroy; knobs, stream contexts, pyramids, records, the light plane, read-backs; the
 //                    per-thread error text
 //   api_launch.cpp   the frame launch path: the cached per-camera record, calibration and probe, launch_frame; the capped-ray
 //                    count and the tail of a host-memory call
@@ -221,6 +221,10 @@ struct hmrm_scene {
 	DeviceScratch d_targets; // hmrm_cell_map_sum's targets and hmrm_render_lit_sum's directions: three doubles each
 	DeviceScratch d_geom;    // hmrm_render_geometry's planes: the wanted ones back to back, slope first, rows packed
 	DeviceScratch d_light;   // hmrm_render_lit_sum's light plane (uint16), rows packed
+	// The scene's baked light plane (hmrm_scene_set_light, hmrm_scene_bake_light): map_w x map_h uint16, rows packed, read by the
+	// baked frames' kernels; null / 0: none.  Changed only with s->mu held and every stream of the scene drained.
+	uint16_t *d_baked = nullptr;
+	uint32_t baked_scale = 0; // the plane's full scale D, 1 .. 65535
 	// launch state per stream; `mu` guards the list and the slot choice (launches themselves are
 	// asynchronous), so that threads driving different streams of one scene do not collide
 	std::mutex mu;
@@ -283,9 +287,12 @@ struct FrameRequest {
 	// hmrm_render_geometry's frame: the device planes the launch stores beside the pixel (d_out may be null then); null: none.
 	// Its primary rays are under the interior rule when `interior` is not kNot -- the geometry kernels test each origin.
 	const hmrm::GeomPlanes *geom = nullptr;
-	// Frames under the interior rule, with a sun or with geometry planes run kernels of their own, with the scene's current kernel
-	// kind (HMRM_KERNEL or the probe's verdict, read only).
-	bool own_kernels() const { return interior != Interior::kNot || lit != nullptr || geom != nullptr; }
+	// hmrm_render_baked's frame: the scene's light plane, whose weight the launch applies to the hit pixels; null: none.  Its
+	// primary rays are under the interior rule when `interior` is not kNot, as a geometry frame's are.
+	const hmrm::BakedLight *baked = nullptr;
+	// Frames under the interior rule, with a sun, with geometry planes or with baked light run kernels of their own, with the
+	// scene's current kernel kind (HMRM_KERNEL or the probe's verdict, read only).
+	bool own_kernels() const { return interior != Interior::kNot || lit != nullptr || geom != nullptr || baked != nullptr; }
 	// Special frames -- those and instrumented ones -- are launched in the plain rotation order: never measured, never a probe,
 	// not counted towards the probe.
 	bool special() const { return stats || own_kernels(); }
@@ -293,10 +300,13 @@ struct FrameRequest {
 
 // ---- the functions that cross files (comments at their definitions) ----
 namespace hmrm {
-// api_scene.cpp.  ctx_for, ensure_*: s->mu held.
+// api_scene.cpp.  ctx_for, ensure_*, drain_scene_streams, drop_light_plane: s->mu held.
 int ctx_for(hmrm_scene *s, hipStream_t stream, StreamCtx **out);
 int ensure_records(hmrm_scene *s);
 int ensure_bilinear_pyramid(hmrm_scene *s);
+int drain_scene_streams(hmrm_scene *s, bool own_too);
+int ensure_light_plane(hmrm_scene *s);
+void drop_light_plane(hmrm_scene *s);
 // api_launch.cpp.  prepare_frame, wait_for_measure_fence, launch_frame, new_capped, take_capped, finish_host_call: s->mu held.
 int check_camera(const hmrm_camera *cam);
 void to_host_camera(const hmrm_camera *cam, hmrm::HostCamera *hc);

@@ -148,6 +148,11 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		l.geo = *req.geom;
 		l.primary_interior = req.interior != Interior::kNot;
 	}
+	if (req.baked) { // (likewise)
+		l.family = hmrm::kFrameBaked;
+		l.baked = *req.baked;
+		l.primary_interior = req.interior != Interior::kNot;
+	}
 	if (route.literal) {
 		HIP_TRY(hmrm::launch_frame_literal(l));
 		return HMRM_OK;

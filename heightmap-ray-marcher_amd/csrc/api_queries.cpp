@@ -349,6 +349,35 @@ int hmrm_cell_map_sum_device(const hmrm_scene *scene, const hmrm_cell_map_params
 	return cell_map_sum_common(scene, p, d_targets, n_targets, rect, d_out, stride_bytes, true, (hipStream_t)hip_stream);
 }
 
+// hmrm_cell_map_sum's launch over the whole map, its words written straight into the scene's light plane (hmrm_render_baked
+// reads it): the same checks without an `out`, the targets through the scene's target list, on the scene's own stream behind
+// a drain of its other streams.  A HIP failure from the drain on leaves the scene without a plane; capped rays leave a valid one.
+int hmrm_scene_bake_light(hmrm_scene *s, const hmrm_cell_map_params *p, const double *targets, int32_t n_targets) {
+	int rc = check_cell_map_sum(p, targets, n_targets, /* out: the scene's own */ p);
+	if (rc) return rc;
+	if (!s) return fail(HMRM_E_ARG, "light plane: NULL scene");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	if ((rc = drain_scene_streams(s, true))) return rc;
+	const hmrm_cell_rect whole{0, 0, s->map_w, s->map_h};
+	const size_t targets_bytes = (size_t)n_targets * 3 * sizeof(double);
+	StreamCtx *c = nullptr;
+	auto body = [&]() -> int {
+		int rc2;
+		if ((rc2 = ensure_light_plane(s)) || (rc2 = s->d_targets.reserve(targets_bytes)) || (rc2 = ctx_for(s, s->stream, &c))) return rc2;
+		HIP_TRY(hipMemcpyAsync(s->d_targets.ptr, targets, targets_bytes, hipMemcpyHostToDevice, s->stream));
+		return launch_cell_sums(s, c, p, s->d_targets.as<double>(), n_targets, whole, s->d_baked, 2 * (size_t)s->map_w);
+	};
+	if ((rc = body()) == HMRM_OK) rc = finish_host_call(s, c);
+	if (rc == HMRM_E_ARG) return rc; // (a refusal of the launch path, before anything was written: the old plane stays)
+	if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+		drop_light_plane(s);
+		return rc;
+	}
+	s->baked_scale = (p->flags & HMRM_MAP_WEIGHT) ? 255u * (uint32_t)n_targets : (uint32_t)n_targets;
+	return rc;
+}
+
 int hmrm_sky_directions(int32_t rings, int32_t per_ring, double *out_xyz) {
 	if (!out_xyz) return fail(HMRM_E_ARG, "sky directions: NULL out_xyz");
 	if (rings < 1 || per_ring < 1 || (int64_t)rings * per_ring > hmrm::kMaxSumTargets)

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "api_internal.hpp"
 
@@ -103,9 +104,7 @@ int run_update_heights(hmrm_scene *s) {
 	// The ticketed entry points launch on the scene's lanes, not on s->stream: frames still in flight there (and ring
 	// frames the copy stream has not delivered yet) read the tables about to be rewritten.  Drain every stream the
 	// scene owns first; s->stream itself is ordered by the stream.  (Callers' own streams: their business, hmrm.h.)
-	for (StreamCtx *c : s->ctxs)
-		if (c->scene_owned && c->stream != s->stream) HIP_TRY(hipStreamSynchronize(c->stream));
-	if (s->copy_stream) HIP_TRY(hipStreamSynchronize(s->copy_stream));
+	if (const int rc = hmrm::drain_scene_streams(s, false)) return rc;
 	HIP_TRY(hipMemsetAsync(s->d_maxkey, 0, sizeof(unsigned long long), s->stream));
 	HIP_TRY(hmrm::launch_prepare_heights(s->d_rgb, s->d_thr, n, s->params.lum_r, s->params.lum_g,
 	                                     s->params.lum_b, s->params.min_height, s->params.max_height,
@@ -138,6 +137,28 @@ int run_update_heights(hmrm_scene *s) {
 } // namespace
 
 namespace hmrm {
+
+// Every stream the scene owns but its own -- the launch lanes of the ticketed entry points -- and the copy stream of the ring are
+// drained: what is in flight there has finished with the tables (run_update_heights) or the light plane (hmrm_scene_set_light and
+// its siblings) about to change.  `own_too`: s->stream as well, for a change that is not ordered by it.
+int drain_scene_streams(hmrm_scene *s, bool own_too) {
+	for (StreamCtx *c : s->ctxs)
+		if (c->scene_owned && (own_too || c->stream != s->stream)) HIP_TRY(hipStreamSynchronize(c->stream));
+	if (s->copy_stream) HIP_TRY(hipStreamSynchronize(s->copy_stream));
+	return HMRM_OK;
+}
+
+// The scene's light plane: allocated once, map_w x map_h words; dropped by hmrm_scene_clear_light, a HIP failure half-way through
+// a change, and hmrm_scene_destroy.
+int ensure_light_plane(hmrm_scene *s) {
+	if (!s->d_baked) HIP_TRY(hipMalloc((void **)&s->d_baked, (size_t)s->map_w * (size_t)s->map_h * sizeof(uint16_t)));
+	return HMRM_OK;
+}
+void drop_light_plane(hmrm_scene *s) {
+	if (s->d_baked) (void)hipFree(s->d_baked);
+	s->d_baked = nullptr;
+	s->baked_scale = 0;
+}
 
 // The launch state of `stream` (created on first use; the least recently used one is dropped, after
 // the device has drained, when a scene is driven from more than kMaxStreamCtx streams).
@@ -344,6 +365,7 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	if (s->d_records) (void)hipFree(s->d_records);
 	if (s->d_mipbuf_bil) (void)hipFree(s->d_mipbuf_bil);
 	if (s->d_maxkey) (void)hipFree(s->d_maxkey);
+	hmrm::drop_light_plane(s);
 	for (DeviceScratch *b : {&s->d_frame, &s->d_steps, &s->d_entry, &s->d_rays, &s->d_hits, &s->d_limits, &s->d_cells, &s->d_targets,
 	                         &s->d_geom, &s->d_light})
 		b->release();
@@ -355,6 +377,84 @@ void hmrm_scene_destroy(hmrm_scene *s) {
 	if (s->ev1) (void)hipEventDestroy(s->ev1);
 	if (s->stream) (void)hipStreamDestroy(s->stream);
 	delete s;
+}
+
+// ---- the scene's light plane (hmrm_render_baked reads it) ----
+// hmrm_scene_set_light and its device form.  The refusals in the header's order; then the scene's streams are drained -- tickets in
+// flight finish with the old plane -- and the plane is filled: 16-bit words by a strided copy, bytes widened on the host (host
+// form) or by a small kernel on the caller's stream (device form).  A HIP failure from there on leaves the scene without a plane.
+static int set_light_common(hmrm_scene *s, const void *plane, size_t stride_bytes, int32_t format, uint32_t full_scale, bool device,
+                            hipStream_t stream) {
+	if (!s) return fail(HMRM_E_ARG, "light plane: NULL scene");
+	if (!plane) return fail(HMRM_E_ARG, "light plane: NULL plane");
+	if (format != HMRM_LIGHT_U8 && format != HMRM_LIGHT_U16) return fail(HMRM_E_ARG, "light plane: format must be HMRM_LIGHT_U8 or HMRM_LIGHT_U16");
+	if (full_scale < 1u || full_scale > 65535u) return fail(HMRM_E_ARG, "light plane: full_scale must be 1 .. 65535");
+	const size_t W = (size_t)s->map_w, H = (size_t)s->map_h, elem = format == HMRM_LIGHT_U16 ? 2 : 1;
+	if (stride_bytes < elem * W) return fail(HMRM_E_ARG, "light plane: stride_bytes is below a row of the map");
+	if (elem == 2 && (stride_bytes & 1u)) return fail(HMRM_E_ARG, "light plane: stride_bytes must be even for HMRM_LIGHT_U16");
+	if (device && elem == 2 && ((uintptr_t)plane & 1u)) return fail(HMRM_E_ARG, "light plane: d_plane must be 2-byte aligned for HMRM_LIGHT_U16");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	int rc = drain_scene_streams(s, true);
+	if (rc) return rc;
+	auto body = [&]() -> int {
+		if (const int rc_p = ensure_light_plane(s)) return rc_p;
+		if (!device) stream = s->stream;
+		std::vector<uint16_t> wide; // (host bytes: widened here, one packed copy)
+		if (elem == 2) {
+			HIP_TRY(hipMemcpy2DAsync(s->d_baked, W * 2, plane, stride_bytes, W * 2, H, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+		} else if (device) {
+			HIP_TRY(hmrm::launch_widen_light(static_cast<const uint8_t *>(plane), stride_bytes, s->map_w, s->map_h, s->d_baked, stream));
+		} else {
+			wide.resize(W * H);
+			for (size_t y = 0; y < H; ++y) {
+				const uint8_t *row = static_cast<const uint8_t *>(plane) + y * stride_bytes;
+				for (size_t x = 0; x < W; ++x) wide[y * W + x] = row[x];
+			}
+			HIP_TRY(hipMemcpyAsync(s->d_baked, wide.data(), W * H * 2, hipMemcpyHostToDevice, stream));
+		}
+		HIP_TRY(hipStreamSynchronize(stream));
+		return HMRM_OK;
+	};
+	if ((rc = body())) {
+		drop_light_plane(s);
+		return rc;
+	}
+	s->baked_scale = full_scale;
+	return HMRM_OK;
+}
+
+int hmrm_scene_set_light(hmrm_scene *scene, const void *plane, size_t stride_bytes, int32_t format, uint32_t full_scale) {
+	return set_light_common(scene, plane, stride_bytes, format, full_scale, false, nullptr);
+}
+
+int hmrm_scene_set_light_device(hmrm_scene *scene, const void *d_plane, size_t stride_bytes, int32_t format, uint32_t full_scale,
+                                void *hip_stream) {
+	return set_light_common(scene, d_plane, stride_bytes, format, full_scale, true, (hipStream_t)hip_stream);
+}
+
+int hmrm_scene_clear_light(hmrm_scene *s) {
+	if (!s) return fail(HMRM_E_ARG, "light plane: NULL scene");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	if (const int rc = drain_scene_streams(s, true)) return rc;
+	drop_light_plane(s);
+	return HMRM_OK;
+}
+
+int hmrm_scene_light(const hmrm_scene *cs, uint16_t *out, size_t stride_bytes, uint32_t *full_scale) {
+	hmrm_scene *s = const_cast<hmrm_scene *>(cs);
+	if (!s) return fail(HMRM_E_ARG, "light plane: NULL scene");
+	if (!full_scale) return fail(HMRM_E_ARG, "light plane: NULL full_scale");
+	const size_t W = (size_t)s->map_w, H = (size_t)s->map_h;
+	if (out && (stride_bytes < 2 * W || (stride_bytes & 1u))) return fail(HMRM_E_ARG, "light plane: stride_bytes must be >= 2 * map_w and even");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	*full_scale = s->d_baked ? s->baked_scale : 0u;
+	if (!out || *full_scale == 0u) return HMRM_OK;
+	HIP_TRY(hipMemcpy2DAsync(out, stride_bytes, s->d_baked, W * 2, W * 2, H, hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	return HMRM_OK;
 }
 
 int hmrm_debug_reload_env(hmrm_scene *s) {

@@ -14,7 +14,7 @@
 //   output <path>                                   (.png or .ppm)
 //   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8, interior on|off,
 //   shadows on|off, sun_dir x y z, shadow_ambient n, shadow_step_dist v, shadow_max_steps n
-//   shading on|off, sun_scope single|all, sky_light on|off
+//   shading on|off, sun_scope single|all, sky_light on|off, baked_light off|sun|sky
 //   sun_map <path.png>, sun_map_lift v                (the whole map's light map, hmrm_cell_map, written by the CLI)
 //   sky_map <path.png>, sky_map_rings r n             (the whole map's sky-view map, hmrm_cell_map_sum, written by the CLI)
 //   range_map <path.pfm>                              (the camera's range plane, hmrm_render_geometry, written by the CLI)
@@ -224,6 +224,14 @@ void sky_light_key(Config &c, std::istream &in, const char *key, std::string *) 
 	c.log << key << " " << (c.sky_light ? "on" : "off") << "\n";
 }
 
+// the frames under a light plane baked once (hmrm_scene_bake_light, hmrm_render_baked)
+void baked_light_key(Config &c, std::istream &in, const char *key, std::string *) {
+	static const Word words[] = {{"off", 0}, {"sun", 1}, {"sky", 2}};
+	std::string seen;
+	if (!pick(in, words, &c.baked_light, &seen)) c.warn << "WARNING: Unknown baked_light: " << seen << "\n";
+	c.log << key << " " << (c.baked_light == 1 ? "sun" : c.baked_light == 2 ? "sky" : "off") << "\n";
+}
+
 // which frames shadows / shading apply to: the plain single frame, or antialiased and recorded ones too
 void sun_scope_key(Config &c, std::istream &in, const char *key, std::string *) {
 	static const Word words[] = {{"single", 0}, {"all", 1}};
@@ -312,6 +320,7 @@ const Row kGrammar[] = {
 	{"shadows", shadows_key},
 	{"shading", shading_key},
 	{"sky_light", sky_light_key},
+	{"baked_light", baked_light_key},
 	{"sun_scope", sun_scope_key},
 	{"sun_dir", sun_dir_key},
 	{"shadow_ambient", shadow_ambient_key},

@@ -51,6 +51,9 @@ struct Config {
 	// additive: `sky_light on|off|1|0` -- that frame lit by the sky instead of the sun (hmrm_render_lit_sum over the directions of
 	// `sky_map_rings`), diffuse with `shading on`; the shadow march's keys are the sun's, `sun_dir` is not used
 	int sky_light = 0;
+	// additive: `baked_light off|sun|sky` -- 0, 1, 2: the CLI bakes the scene's light plane once before its frames (hmrm_scene_bake_light:
+	// the sun_map's light under `sun_dir`, or the sky_map's count over `sky_map_rings`) and renders them as baked frames (hmrm_render_baked)
+	int baked_light = 0;
 	// additive: `sun_scope single|all` -- 0: shadows / shading apply to the plain single frame only; 1: also with `antialias n` > 1
 	// (hmrm_render_shaded_aa) and to `record orbit` (hmrm_record_orbit_shaded)
 	int sun_scope = 0;

@@ -270,6 +270,16 @@ __device__ __forceinline__ uint32_t shade_summed(uint32_t rgba, uint32_t sum, ui
 	const uint32_t b = (((rgba >> 16) & 255u) * sum + half) / den;
 	return r | (g << 8) | (b << 16) | (rgba & 0xff000000u);
 }
+// The pixel of a hit under the baked light L of full scale D (hmrm_render_baked): min(255, (c * L + D / 2) / D) per channel in
+// unsigned 32-bit integers, A stays 255.  c * L + D / 2 <= 255 * 65535 + 32767 < 2^24; the divisor is the same for the whole
+// launch.  L = D gives c back: (c D + floor(D / 2)) / D = c, the remainder being below D.
+__device__ __forceinline__ uint32_t shade_baked(uint32_t rgba, uint32_t light, uint32_t full_scale) {
+	const uint32_t half = full_scale / 2u;
+	const uint32_t r = min(255u, ((rgba & 255u) * light + half) / full_scale);
+	const uint32_t g = min(255u, (((rgba >> 8) & 255u) * light + half) / full_scale);
+	const uint32_t b = min(255u, (((rgba >> 16) & 255u) * light + half) / full_scale);
+	return r | (g << 8) | (b << 16) | (rgba & 0xff000000u);
+}
 
 // Relative error of the hardware reciprocal.  MEASURED on gfx950 (tools/rcp_accuracy.py over 1.6e11 inputs: the
 // leading 32 mantissa bits exhaustively in six binades, hashed mantissas / signs / exponents 2^-1000..2^1000, and the

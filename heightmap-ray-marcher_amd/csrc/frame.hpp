@@ -316,6 +316,16 @@ struct LightSum {
 };
 constexpr int kMaxSumDirs = 256;
 
+// ---- baked-light frames (hmrm_render_baked; BAKED in the kernels) ----
+// The scene's light plane (hmrm_scene_set_light, hmrm_scene_bake_light): map_w x map_h native uint16, rows packed like the
+// threshold table, and its full scale D in 1 .. 65535.  A pixel whose primary ray hit keeps (c * L + D / 2) / D of its R, G and
+// B, at most 255: L the plane's word of the hit cell, or -- bilinear sampling -- the four neighbours' words mixed like the colour.
+// An extra argument of the baked kernels' own __global__ entry points, like SegRules.
+struct BakedLight {
+	const uint16_t *plane;
+	uint32_t full_scale;
+};
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

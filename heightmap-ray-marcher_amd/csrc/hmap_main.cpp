@@ -149,6 +149,44 @@ static bool write_sky_map(hmrm_config *cfg, hmrm_scene *scene, const hmrm_camera
 	return true;
 }
 
+// `baked_light sun|sky` (mode 1|2): the scene's light plane baked once, before the frames -- the light `sun_map` would write, under
+// `sun_dir`, or the count `sky_map` would scale, over `sky_map_rings`.  Returns false when it could not be baked.
+static bool bake_light(hmrm_config *cfg, hmrm_scene *scene, const hmrm_camera &cam, int mode, bool shading, bool shadows) {
+	hmrm_sun sun;
+	hmrm_config_get_sun(cfg, &sun);
+	hmrm_cell_map_params p;
+	memset(&p, 0, sizeof p);
+	p.step_dist = sun.step_dist;
+	p.lift = hmrm_config_sun_map_lift(cfg);
+	p.max_steps = sun.max_steps;
+	p.sampling = cam.sampling;
+	p.ambient = sun.ambient;
+	std::vector<double> dirs(sun.dir, sun.dir + 3);
+	int K = 1;
+	if (mode == 1) {
+		p.flags = HMRM_MAP_WEIGHT | (shading ? HMRM_MAP_DIFFUSE : 0u) | (shading && !shadows ? HMRM_MAP_NO_SHADOWS : 0u);
+	} else {
+		int32_t rings = 0, per_ring = 0;
+		hmrm_config_sky_map_rings(cfg, &rings, &per_ring);
+		dirs.assign((size_t)3 * rings * per_ring, 0.0);
+		K = hmrm_sky_directions(rings, per_ring, dirs.data());
+		if (K < 1) {
+			std::cerr << hmrm_last_error() << "\n";
+			return false;
+		}
+	}
+	const int rc = hmrm_scene_bake_light(scene, &p, dirs.data(), K);
+	if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+		std::cerr << hmrm_last_error() << "\n";
+		return false;
+	}
+	if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+	uint32_t full_scale = 0;
+	(void)hmrm_scene_light(scene, NULL, 0, &full_scale);
+	std::cout << "baked light: " << K << " direction(s), full scale " << full_scale << "\n";
+	return true;
+}
+
 int main(int argc, char *argv[]) {
 	if (argc != 2) {
 		std::cerr << "USAGE: hmap.exe path/to/config.txt\n";
@@ -174,7 +212,8 @@ int main(int argc, char *argv[]) {
 	const bool interior = hmrm_config_interior(cfg) != 0;
 	const bool shadows = hmrm_config_shadows(cfg) != 0;
 	const bool shading = hmrm_config_shading(cfg) != 0;
-	const bool sky_light = hmrm_config_sky_light(cfg) != 0; // (the single frame under the sky's directions: hmrm_render_lit_sum)
+	bool sky_light = hmrm_config_sky_light(cfg) != 0; // (the single frame under the sky's directions: hmrm_render_lit_sum)
+	const int baked_mode = hmrm_config_baked_light(cfg); // (1 sun, 2 sky: the frames under a light plane baked once)
 	// `sun_scope all`: shadows / shading also apply to antialiased and recorded frames
 	const bool sun_all = hmrm_config_sun_scope(cfg) != 0 && (shadows || shading);
 	const uint32_t shade_flags = shading ? (HMRM_SHADE_DIFFUSE | (shadows ? 0u : HMRM_SHADE_NO_SHADOWS)) : 0u;
@@ -185,7 +224,17 @@ int main(int argc, char *argv[]) {
 	}
 
 	if (hmrm_config_record_mode(cfg) == 1) {
-		if (!sun_all) {
+		int visible_rec = 1;
+		bool baked = baked_mode != 0;
+		if (baked && wanted_devices(cfg, &visible_rec) > 1) {
+			std::cerr << "WARNING: baked_light is ignored with devices > 1\n";
+			baked = false;
+		}
+		if (baked && sky_light) {
+			std::cerr << "WARNING: sky_light is ignored with baked_light\n";
+			sky_light = false;
+		}
+		if (!sun_all && !baked) {
 			if (interior) std::cerr << "WARNING: interior is ignored with record orbit\n";
 			if (shadows) std::cerr << "WARNING: shadows is ignored with record orbit\n";
 			if (shading) std::cerr << "WARNING: shading is ignored with record orbit\n";
@@ -221,7 +270,13 @@ int main(int argc, char *argv[]) {
 			if (rc == HMRM_OK) rc = hmrm_config_create_scene(cfg, &extra);
 			if (rc == HMRM_OK) scenes.push_back(extra);
 		}
-		if (rc == HMRM_OK && sun_all) {
+		if (rc == HMRM_OK && baked) {
+			if (!bake_light(cfg, scene, cam, baked_mode, shading, shadows)) rc = HMRM_E_DEVICE;
+			else
+				rc = hmrm_record_orbit_baked(scenes.data(), (int32_t)scenes.size(), &cam, cx, cy, radius, hang0,
+				                             hmrm_config_recording_frame_count(cfg), dir.c_str(), (long long)id, 0, 1,
+				                             aa > 1 ? HMRM_AA(aa) : 0u, interior ? HMRM_TRACE_INTERIOR : 0u);
+		} else if (rc == HMRM_OK && sun_all) {
 			hmrm_sun sun;
 			hmrm_config_get_sun(cfg, &sun);
 			rc = hmrm_record_orbit_shaded(scenes.data(), (int32_t)scenes.size(), &cam, cx, cy, radius, hang0,
@@ -246,16 +301,33 @@ int main(int argc, char *argv[]) {
 	const int want_dev = wanted_devices(cfg, &visible_dev);
 	if (want_dev > 1 && aa > 1)
 		std::cerr << "WARNING: antialias " << aa << " renders the single frame on one device (devices " << want_dev << " ignored)\n";
-	const bool lit_aa = sun_all && want_dev <= 1 && aa > 1; // (the antialiased lit single frame)
-	if (interior && !lit_aa && (want_dev > 1 || aa > 1))
+	const bool baked = baked_mode != 0 && want_dev <= 1;
+	if (baked_mode != 0 && !baked) std::cerr << "WARNING: baked_light is ignored with devices > 1\n";
+	if (baked && sky_light) {
+		std::cerr << "WARNING: sky_light is ignored with baked_light\n";
+		sky_light = false;
+	}
+	const bool lit_aa = sun_all && want_dev <= 1 && aa > 1 && !baked; // (the antialiased lit single frame)
+	if (interior && !lit_aa && !baked && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: interior is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (shadows && !lit_aa && (want_dev > 1 || aa > 1))
+	if (shadows && !lit_aa && !baked && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: shadows is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (shading && !lit_aa && (want_dev > 1 || aa > 1))
+	if (shading && !lit_aa && !baked && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: shading is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
 	if (sky_light && (want_dev > 1 || aa > 1)) // (whatever sun_scope says: there is no antialiased accumulated frame)
 		std::cerr << "WARNING: sky_light is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (sky_light && want_dev <= 1 && aa == 1) {
+	if (baked) {
+		// the single frame, antialiased or not, under the light plane baked here: `shadows` and `shading` only chose what was baked
+		if (!bake_light(cfg, scene, cam, baked_mode, shading, shadows)) return 1;
+		rc = hmrm_render_baked(scene, &cam, interior ? HMRM_TRACE_INTERIOR : 0u, aa, framebuf.data(), (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height * aa * aa << " rays under baked light"
+		          << (interior ? " under the interior rule" : "") << " in " << hmrm_last_kernel_ms() << " ms (kernel)\n";
+	} else if (sky_light && want_dev <= 1 && aa == 1) {
 		// every hit pixel under the K = r * n cosine-weighted sky directions of `sky_map_rings`, shadow rays always on, the diffuse
 		// level per direction with `shading on`; ambient, step and limit are the sun's keys, sun_dir is not used
 		int32_t rings = 0, per_ring = 0;

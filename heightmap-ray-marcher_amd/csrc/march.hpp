@@ -1,8 +1,8 @@
 // march.hpp -- the production march for gfx950: render_wave_tile, one wave's 8 x 8 pixels (or 64 batch rays), and its
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
 // render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
-// counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip and render_lit_sum.hip, each with
-// a __global__ kernel of its own.
+// counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip, render_lit_sum.hip, render_baked.hip
+// and render_baked_aa.hip, each with a __global__ kernel of its own.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
 // the reference loop main/hmap.cpp:978-1058; two bit-preserving restructurings:
@@ -173,6 +173,14 @@ __device__ __forceinline__ uint32_t shade_hit_bilinear(const DevFrame &f, const 
 	}
 	return pack_rgba(ch[0], ch[1], ch[2]);
 }
+// Baked light at a hit (hmrm_render_baked): the four neighbours' words of the plane mixed like a colour channel and rounded
+// with floor(m + 0.5), clamped to the word's range.
+__device__ __forceinline__ uint32_t baked_light_bilinear(const uint16_t *__restrict__ plane, const Bil &b) {
+	double v = bil_mix(b, (double)plane[b.c00], (double)plane[b.c10], (double)plane[b.c01], (double)plane[b.c11]) + 0.5;
+	if (v < 0.0) v = 0.0;
+	else if (v > 65535.0) v = 65535.0;
+	return (uint32_t)(int)__builtin_floor(v);
+}
 
 // Cell maps: the ray of cell (x0 + px, y0 + py) of the rect, made from the cell's entry of the table the sampling mode's
 // march reads (`thr`: the float copy for SAMP 2, else the doubles -- the bilinear mode's origin sits on the cell's own value).
@@ -248,16 +256,22 @@ __device__ __forceinline__ DevRay cell_ray_of(const CellRules &c, const DevFrame
 // pixel are made again.  With HMRM_SHADE_NO_SHADOWS no shadow pass runs: the n levels are computed behind the primary march.
 // Termination: every pass is the march loop with a budget of its own, min(step cap, the shadow rays' limit) <= the step cap, and
 // the outer loop runs at most 1 + n times -- the primary pass and one per direction, the pass number only ever grows.
+// BAKED (instantiated in render_baked.hip and render_baked_aa.hip only; hmrm_render_baked, frame.hpp BakedLight; implies SEG): a
+// baked-light frame.  An epilogue: a lane whose primary ray hit fetches its colour behind the loop, as GEOM and LSUM do, loads
+// its light from the scene's plane -- one 16-bit load at hcell, or four at the bilinear mode's neighbours of the kept hit point,
+// mixed like the colour -- and keeps the pixel at that weight (device_common.hpp shade_baked).  With AA the weighted sample goes
+// to the box filter.  Again `if constexpr` statements beside the others' own.
 template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false, bool SHADE = false,
-          bool SUM = false, bool GEOM = false, bool LSUM = false>
+          bool SUM = false, bool GEOM = false, bool LSUM = false, bool BAKED = false>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
                                                 int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{},
                                                 const SunRules &sun = SunRules{}, const CellRules &cells = CellRules{},
                                                 const CellSums &sums = CellSums{}, const GeomPlanes &geo = GeomPlanes{},
-                                                const LightSum &lsum = LightSum{}) {
+                                                const LightSum &lsum = LightSum{}, const BakedLight &baked = BakedLight{}) {
 	constexpr bool CELLS = PROJ == 5;
+	static_assert(!BAKED || (SEG && !CELLS && PROJ != 4 && !STATS && !LIT && !SHADE && !GEOM), "baked-light frames: plain frames under the segment rules");
 	static_assert(!LSUM || (LIT && !SHADE && !AA), "accumulated lit frames: the lit kernels' marches, the weights by a run-time flag");
 	static_assert(!GEOM || (SEG && !CELLS && PROJ != 4 && !STATS && !AA && !LIT && !SHADE), "geometry frames: plain frames under the segment rules");
 	static_assert(!SUM || CELLS, "accumulated cell maps: the cell kernels' march, once per target");
@@ -272,7 +286,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	// GEOM wants the whole point, in every sampling mode: KEEP_P with z stepped like x and y (no threshold is kept), which holds
 	// nothing across the loop -- RAYS' select chain keeps three doubles more.
 	constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && LEAP != 0 && !GEOM;
-	constexpr bool KEEP_P = LIT || (SHADE && BILINEAR && !KEEP_Q) || (GEOM && !kGeomChain);
+	// BAKED with bilinear sampling wants the point like SHADE: KEEP_Q in the leap kernels, KEEP_P in the plain groups.
+	constexpr bool KEEP_P = LIT || ((SHADE || BAKED) && BILINEAR && !KEEP_Q) || (GEOM && !kGeomChain);
 	constexpr bool CHAIN = PROJ == 4 || (GEOM && kGeomChain); // (the hit point by RAYS' select chain: hx, hy, hz)
 	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	// DEFER: a hit lane's colour is fetched behind the march loop, from the hit cell it leaves the loop with (hcell below; the
@@ -282,15 +297,18 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	// the loop with the hit point made that kernel 20 % SLOWER where it was measured (0.263 -> 0.316 ms, profiles/r09_ab.txt).
 	// (GEOM: always behind the loop -- a null colour target skips the fetch there, a scalar branch)
 	// (LSUM: always behind the loop, like GEOM -- and behind every march: the hit point outlives them)
-	constexpr bool DEFER = GEOM || LSUM || (!CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0));
+	// (BAKED: behind the loop too -- the light is loaded beside the colour, from the same cell or point -- except in its record
+	// kernels, which keep the interior family's in-loop fetch: deferred, the orthographic one with power-of-two grid widths took
+	// 36 bytes of scratch)
+	constexpr bool DEFER = GEOM || LSUM || (BAKED && LEAP != 2) || (!CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0));
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || !STATS, "segment rules: production kernels only");
-	static_assert(!SEG || !AA || LIT || SHADE, "segment rules: antialiased for the sun-lit frames only");
+	static_assert(!SEG || !AA || LIT || SHADE || BAKED, "segment rules: antialiased for the sun-lit and baked-light frames only");
 	constexpr bool REC = LEAP == 2;                     // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
 	// CARRY: a ray holds its level state in a register (see the leap state below).  The cell maps, the sun shadows, the ray batches
 	// and the shaded record kernels sit on a register granule: a register more would cost them a resident wave per SIMD -- as it
 	// would six of the geometry kernels (general grid widths: 73 against 71 vector registers, 81 against 80 with window records).
-	constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !RAYS && !(SHADE && REC) && !(GEOM && !kGeomCarry);
+	constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !RAYS && !((SHADE || BAKED) && REC) && !(GEOM && !kGeomCarry);
 	constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
 	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
 	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
@@ -1070,6 +1088,14 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					q = diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), sun.dir);
 				} else q = diffuse_level_nearest<F32>(f, thr, hcell, sun.dir);
 				rgba = shade_weighted(rgba, shade_weight(sun.ambient, q));
+			}
+		}
+		if constexpr (BAKED) { // (every hit pixel at the weight of its baked light; an alpha-0 hit cell's background too)
+			if (real_hit) {
+				uint32_t light;
+				if constexpr (BILINEAR) light = baked_light_bilinear(baked.plane, bil_setup(qxh, qyh, f.map_w, f.map_h));
+				else light = baked.plane[hcell];
+				rgba = shade_baked(rgba, light, baked.full_scale);
 			}
 		}
 

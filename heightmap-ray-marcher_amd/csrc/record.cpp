@@ -32,7 +32,19 @@
 namespace hmrm {
 int set_error(int code, const char *msg); // (api_scene.cpp: hmrm_last_error's text)
 int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags); // (api_frames.cpp: the refusals of hmrm_render_shaded_begin's sun)
+int check_baked_args(uint32_t baked_flags);                       // (likewise: hmrm_render_baked_begin's baked_flags)
 }
+
+// What the frames of a sweep are: plain tickets, lit ones (sun, shade_flags) or baked ones (baked_flags).
+struct OrbitFrames {
+	const hmrm_sun *sun = nullptr;
+	uint32_t shade_flags = 0u;
+	bool baked = false;
+	uint32_t baked_flags = 0u;
+};
+static int record_orbit_common(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x, double centre_y,
+                               double radius, double hang0, int32_t frames, const char *dir, long long id, int32_t encoder_threads,
+                               int32_t verbose, uint32_t flags, const OrbitFrames &what);
 
 extern "C" {
 
@@ -62,6 +74,34 @@ int hmrm_record_orbit_shaded(hmrm_scene *const *scenes, int32_t n_scenes, const 
                              double centre_y, double radius, double hang0, int32_t frames, const char *dir,
                              long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags, const hmrm_sun *sun,
                              uint32_t shade_flags) {
+	OrbitFrames what;
+	what.sun = sun;
+	what.shade_flags = shade_flags;
+	return record_orbit_common(scenes, n_scenes, base, centre_x, centre_y, radius, hang0, frames, dir, id, encoder_threads, verbose, flags,
+	                           what);
+}
+
+// hmrm_record_orbit_flags whose frames are baked tickets (hmrm_render_baked_begin with `baked_flags` and `flags`).  Every scene
+// must have a light plane: refused before any frame.
+int hmrm_record_orbit_baked(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
+                            double centre_y, double radius, double hang0, int32_t frames, const char *dir,
+                            long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags, uint32_t baked_flags) {
+	OrbitFrames what;
+	what.baked = true;
+	what.baked_flags = baked_flags;
+	return record_orbit_common(scenes, n_scenes, base, centre_x, centre_y, radius, hang0, frames, dir, id, encoder_threads, verbose, flags,
+	                           what);
+}
+
+} // extern "C"
+
+static int record_orbit_common(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x, double centre_y,
+                               double radius, double hang0, int32_t frames, const char *dir, long long id, int32_t encoder_threads,
+                               int32_t verbose, uint32_t flags, const OrbitFrames &what) {
+	const hmrm_sun *const sun = what.sun;
+	const uint32_t shade_flags = what.shade_flags;
+	if (what.baked)
+		if (const int rc_b = hmrm::check_baked_args(what.baked_flags)) return rc_b;
 	if (!sun && shade_flags != 0u) return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit_shaded: shade_flags without a sun");
 	if (sun)
 		if (const int rc_sun = hmrm::check_shaded_args(sun, shade_flags)) return rc_sun;
@@ -72,6 +112,12 @@ int hmrm_record_orbit_shaded(hmrm_scene *const *scenes, int32_t n_scenes, const 
 	for (int i = 0; i < n_scenes; ++i)
 		if (!scenes[i]) return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit: NULL scene");
 	if (base->width <= 0 || base->height <= 0) return hmrm::set_error(HMRM_E_ARG, "resolution must be positive");
+	if (what.baked)
+		for (int i = 0; i < n_scenes; ++i) {
+			uint32_t full_scale = 0u;
+			if (const int rc_l = hmrm_scene_light(scenes[i], nullptr, 0, &full_scale)) return rc_l;
+			if (full_scale == 0u) return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit_baked: the scene has no light plane");
+		}
 	const size_t W = (size_t)base->width, H = (size_t)base->height;
 	const size_t frame_bytes = W * H * 4;
 	const int n = std::min(n_scenes, frames);
@@ -184,8 +230,9 @@ int hmrm_record_orbit_shaded(hmrm_scene *const *scenes, int32_t n_scenes, const 
 					hmrm_camera cam;
 					hmrm_orbit_camera(base, centre_x, centre_y, radius, hang0, next, frames, &cam);
 					int32_t ticket = -1;
-					const int rc = lit ? hmrm_render_shaded_begin(scenes[i], &cam, &the_sun, shade_flags, flags, &ticket)
-					                   : hmrm_render_begin_flags(scenes[i], &cam, flags, &ticket);
+					const int rc = what.baked ? hmrm_render_baked_begin(scenes[i], &cam, what.baked_flags, flags, &ticket)
+					               : lit      ? hmrm_render_shaded_begin(scenes[i], &cam, &the_sun, shade_flags, flags, &ticket)
+					                          : hmrm_render_begin_flags(scenes[i], &cam, flags, &ticket);
 					if (rc != HMRM_OK) {
 						note_error(rc);
 						break;
@@ -226,6 +273,8 @@ int hmrm_record_orbit_shaded(hmrm_scene *const *scenes, int32_t n_scenes, const 
 	if (verbose) std::printf("Done recording.\n"); // hmap.cpp:1142
 	return HMRM_OK;
 }
+
+extern "C" {
 
 int hmrm_record_orbit_flags(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
                             double centre_y, double radius, double hang0, int32_t frames, const char *dir,

@@ -485,6 +485,30 @@ __global__ __launch_bounds__(kBlockThreads) void k_render_lit_sum_literal(const 
 		    lt.primary_hit ? (uint16_t)acc : (uint16_t)0xffffu;
 }
 
+// A pixel of a baked-light frame (hmrm_render_baked with HMRM_KERNEL=simple, or on a map with a side of 2^24 cells; frame.hpp
+// BakedLight): the primary ray of a lit pixel -- its colour, whether it hit and in which cell -- then the pixel under the plane's
+// word of that cell.  AA: the lane's sample goes to the wave's box filter (every lane of the wave calls it, so no lane returns
+// before) and not to memory.  Nearest sampling only, like every literal kernel.
+template <int PROJ, bool AA>
+__global__ __launch_bounds__(kBlockThreads) void k_render_baked_literal(const DevFrame f, const RowMap rows,
+                                                                        const double *__restrict__ thr,
+                                                                        const uint32_t *__restrict__ cmap,
+                                                                        uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                        int tiles_y, StatsOut st, const SegRules seg,
+                                                                        const BakedLight baked) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	unsigned cell = 0u;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, SunRules{}, &lt, &cell);
+	uint32_t rgba = 0u;
+	if (pid.live) {
+		rgba = lt.rgba;
+		if (lt.primary_hit) rgba = shade_baked(rgba, baked.plane[cell], baked.full_scale);
+	}
+	if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, (int)(threadIdx.x & 63), pid.px, pid.lrow, pid.live, rgba);
+	else if (pid.live) out[(int64_t)pid.lrow * out_stride_px + pid.px] = rgba;
+}
+
 // Per-ray parity hook: GetRay + distance() of one pixel -> out[0..2] pos, [3..5] dir, [6] d.
 template <int PROJ>
 __global__ void k_probe(const DevFrame f, int px, int py, double *__restrict__ out) {
@@ -665,6 +689,7 @@ static hipError_t launch_literal(const FrameLaunch &l, const StatsOut &st, Launc
 static hipError_t launch_plain_literal(const FrameLaunch &l); // (hmrm_render's frame: below)
 static hipError_t launch_geometry_literal(const FrameLaunch &l); // (hmrm_render_geometry's, and behind them hmrm_render_lit_sum's:
 static hipError_t launch_lit_sum_literal(const FrameLaunch &l);  //  the last kernels of the code object)
+static hipError_t launch_baked_literal(const FrameLaunch &l);    // (hmrm_render_baked's, behind those)
 
 // The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
 // shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
@@ -680,6 +705,7 @@ hipError_t launch_frame_literal(const FrameLaunch &l) {
 		});
 	if (l.family == kFrameGeometry) return launch_geometry_literal(l);
 	if (l.family == kFrameLitSum) return launch_lit_sum_literal(l);
+	if (l.family == kFrameBaked) return launch_baked_literal(l);
 	if (l.f.aa_shift == 0) switch (l.family) {
 		case kFrameLit:
 			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
@@ -740,6 +766,32 @@ static hipError_t launch_lit_sum_literal(const FrameLaunch &l) {
 	const SegRules seg = frame_seg_rules(l);
 	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
 		hipLaunchKernelGGL(k_render_lit_sum_literal<proj()>, grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.sun, l.lsum);
+	});
+}
+
+// dst[y * w + x] = src[y * src_stride + x]: one thread per cell, rows in blockIdx.y.
+__global__ __launch_bounds__(256) void k_widen_light(const uint8_t *__restrict__ src, size_t src_stride, int w, int h,
+                                                     uint16_t *__restrict__ dst) {
+	const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	for (int y = (int)blockIdx.y; y < h; y += (int)gridDim.y)
+		if (x < w) dst[(size_t)y * (size_t)w + (size_t)x] = (uint16_t)src[(size_t)y * src_stride + (size_t)x];
+}
+hipError_t launch_widen_light(const uint8_t *d_src, size_t src_stride, int w, int h, uint16_t *d_dst, hipStream_t stream) {
+	if (w <= 0 || h <= 0) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)((w + 255) / 256), (unsigned)(h < 65535 ? h : 65535));
+	hipLaunchKernelGGL(k_widen_light, grid, dim3(256), 0, stream, d_src, src_stride, w, h, d_dst);
+	return hipGetLastError();
+}
+
+// A baked-light frame: the interior family's arguments and the plane, antialiased or not.  Never a measured launch.
+static hipError_t launch_baked_literal(const FrameLaunch &l) {
+	if (l.rows.measure != nullptr || !l.d_out) return hipErrorInvalidValue;
+	if (!l.baked.plane || l.baked.full_scale < 1u || l.baked.full_scale > 65535u) return hipErrorInvalidValue;
+	const SegRules seg = frame_seg_rules(l);
+	const bool aa = l.f.aa_shift != 0;
+	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
+		if (aa) hipLaunchKernelGGL((k_render_baked_literal<proj(), true>), grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.baked);
+		else hipLaunchKernelGGL((k_render_baked_literal<proj(), false>), grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.baked);
 	});
 }
 

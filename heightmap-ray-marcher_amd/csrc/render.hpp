@@ -51,6 +51,9 @@ struct FrameLaunch {
 	// kFrameLitSum (hmrm_render_lit_sum): kFrameLit whose shadow march runs once per direction of the list, the weights summed;
 	// sun.dir is not looked at, d_out may be null (no colour plane) and so may lsum.light (frame.hpp LightSum)
 	LightSum lsum = LightSum{nullptr, nullptr, 0, 0, 0u};
+	// kFrameBaked (hmrm_render_baked): the frame of the plain or, with primary_interior, the interior family, whose hit pixels
+	// take the weight of the scene's light plane (frame.hpp BakedLight); antialiased with f.aa_shift
+	BakedLight baked = BakedLight{nullptr, 0u};
 };
 // The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups
 // (kPlainGroups), plus exact leaps over empty pyramid windows (kLeaps), or over windows of the record level that are empty but
@@ -105,6 +108,9 @@ hipError_t launch_build_mip0(const double *d_thr, int map_w, int map_h, float *d
                              int pitch, hipStream_t stream);
 hipError_t launch_build_mip_up(const float *d_src, int src_w, int src_h, float *d_dst, int dst_w, int dst_h,
                                int pitch, int src_level, hipStream_t stream);
+// A light plane of bytes widened to 16-bit words (hmrm_scene_set_light_device, HMRM_LIGHT_U8; render.hip): w x h bytes, rows
+// src_stride bytes apart, into w x h packed uint16.
+hipError_t launch_widen_light(const uint8_t *d_src, size_t src_stride, int w, int h, uint16_t *d_dst, hipStream_t stream);
 // round-up-to-float of a double (the pyramid's rounding), on the host: for the whole-map element
 float round_up_to_float_host(double v);
 

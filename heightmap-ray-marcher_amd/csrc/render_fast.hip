@@ -287,6 +287,7 @@ hipError_t launch_frame_march(const FrameLaunch &l, FastKernel kernel) {
 	case kFrameLitShaded: return aa ? launch_render_lit_shaded_aa(l, kernel) : launch_render_lit_shaded(l, kernel);
 	case kFrameGeometry: return launch_render_geometry(l, kernel); // (refuses a factor)
 	case kFrameLitSum: return launch_render_lit_sum(l, kernel); // (refuses a factor)
+	case kFrameBaked: return aa ? launch_render_baked_aa(l, kernel) : launch_render_baked(l, kernel);
 	default: return aa ? launch_render_fast_aa(l, kernel) : launch_render_fast(l, kernel);
 	}
 }

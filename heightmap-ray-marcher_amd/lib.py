@@ -81,6 +81,7 @@ RAY_MISS, RAY_HIT, RAY_CAPPED = 0, 1, 2  # hmrm_ray_hit.status (HMRM_RAY_*)
 RAY_END = 3  # ... of hmrm_trace_segments: ended by the ray's own step limit, inside the grid
 TRACE_INTERIOR = 1  # hmrm_segment_params.flags (HMRM_TRACE_INTERIOR)
 SHADE_DIFFUSE, SHADE_NO_SHADOWS = 1, 2  # hmrm_render_shaded's shade_flags (HMRM_SHADE_*)
+LIGHT_U8, LIGHT_U16 = 0, 1  # hmrm_scene_set_light's format (HMRM_LIGHT_*)
 MAX_RAYS = 1 << 29  # rays per batch
 
 
@@ -277,6 +278,17 @@ def _load():
         "hmrm_render_shaded_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, C.c_uint32, C.POINTER(i32)]),
         "hmrm_render_shaded_device_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t, C.c_uint32,
                                                       C.POINTER(i32)]),
+        "hmrm_scene_set_light": (C.c_int, [vp, vp, C.c_size_t, i32, C.c_uint32]),
+        "hmrm_scene_set_light_device": (C.c_int, [vp, vp, C.c_size_t, i32, C.c_uint32, vp]),
+        "hmrm_scene_bake_light": (C.c_int, [vp, C.POINTER(CellMapParams), dp, i32]),
+        "hmrm_scene_clear_light": (C.c_int, [vp]),
+        "hmrm_scene_light": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "hmrm_render_baked": (C.c_int, [vp, C.POINTER(Camera), C.c_uint32, i32, vp, C.c_size_t]),
+        "hmrm_render_baked_begin": (C.c_int, [vp, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(i32)]),
+        "hmrm_render_baked_device_begin": (C.c_int, [vp, C.POINTER(Camera), C.c_uint32, vp, C.c_size_t, C.c_uint32, C.POINTER(i32)]),
+        "hmrm_record_orbit_baked": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
+                                              C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32, C.c_uint32, C.c_uint32]),
+        "hmrm_config_baked_light": (i32, [vp]),
         "hmrm_pick": (C.c_int, [vp, C.POINTER(Camera), i32, i32, C.POINTER(RayHit)]),
         "hmrm_debug_ray": (C.c_int, [vp, C.POINTER(Camera), i32, i32, dp, dp, dp]),
         "hmrm_debug_frame": (C.c_int, [C.POINTER(Camera), C.POINTER(SceneParams), i32, i32, vp, vp]),
@@ -357,7 +369,7 @@ lib, EXPORTED_SYMBOLS = _load()
 # collected on, so it carries this hash and bench.py refuses one that does not match the tree.
 KERNEL_SOURCES = ("render_fast.hip", "render_rays.hip", "leap_common.hpp", "leap_diag.hpp", "render.hip", "device_common.hpp", "frame.hpp",
                   "render.hpp", "api_internal.hpp", "api_launch.cpp", "api_frames.cpp", "launch_order.cpp", "launch_order.hpp", "camera.cpp", "Makefile",
-                  "march.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp")
+                  "march.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip")
 
 
 def kernel_src_sha() -> str:
@@ -798,6 +810,77 @@ class Scene:
         _check(lib.hmrm_render_lit_sum_device(self._h, C.byref(cam), C.byref(sun), C.c_void_p(d_dirs), int(n_dirs),
                                               shade_flags(diffuse, shadows), C.byref(p), C.c_void_p(stream)))
 
+    def set_light(self, plane, full_scale: int, stride_bytes=None):
+        """The scene's light plane from host memory (hmrm_scene_set_light): `plane` is (map_h, >= map_w) uint8 (HMRM_LIGHT_U8,
+        widened) or uint16 (HMRM_LIGHT_U16), its row pitch the stride unless stride_bytes says otherwise; a cell whose light
+        equals full_scale (1 .. 65535) gives the texel back.  Tickets in flight finish with the old plane."""
+        a = np.asarray(plane)
+        if a.dtype not in (np.uint8, np.uint16):
+            raise TypeError("light plane: uint8 or uint16")
+        a = np.ascontiguousarray(a)
+        stride = a.strides[0] if stride_bytes is None else int(stride_bytes)
+        _check(lib.hmrm_scene_set_light(self._h, _ptr(a), stride, LIGHT_U16 if a.dtype == np.uint16 else LIGHT_U8, int(full_scale)))
+
+    def set_light_device(self, d_ptr: int, stride_bytes: int, full_scale: int, u16=True, stream: int = 0):
+        """hmrm_scene_set_light_device: the plane from device memory, read on `stream` behind what the caller enqueued there
+        (cell_map_sum_device's output goes in without a trip over the host); returns after the copy."""
+        _check(lib.hmrm_scene_set_light_device(self._h, C.c_void_p(d_ptr), int(stride_bytes), LIGHT_U16 if u16 else LIGHT_U8,
+                                               int(full_scale), C.c_void_p(stream)))
+
+    def bake_light(self, targets, step_dist, lift=0.0, max_steps=0, point=False, weight=False, diffuse=False, shadows=True,
+                   sampling=NEAREST, ambient=128, allow_capped=False):
+        """cell_map_sum over the whole map written straight into the scene's light plane (hmrm_scene_bake_light): full scale
+        255 * K with weight=True, else K (a count).  Capped rays: HMRM_E_NOTERM, with a valid plane, unless allow_capped."""
+        self._sync_env()
+        t = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1, 3)
+        p = CellMapParams.make((0.0, 0.0, 0.0), step_dist, lift, max_steps, map_flags(point, weight, diffuse, shadows), sampling, ambient)
+        _check(lib.hmrm_scene_bake_light(self._h, C.byref(p), t.ctypes.data_as(C.POINTER(C.c_double)), len(t)),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+
+    def clear_light(self):
+        """Drops the scene's light plane (hmrm_scene_clear_light)."""
+        _check(lib.hmrm_scene_clear_light(self._h))
+
+    def light(self):
+        """The scene's light plane read back (hmrm_scene_light) -> ((map_h, map_w) uint16, full_scale), or (None, 0) for a
+        scene without one."""
+        fs = C.c_uint32()
+        _check(lib.hmrm_scene_light(self._h, None, 0, C.byref(fs)))
+        if fs.value == 0:
+            return None, 0
+        out = np.empty((self.map_h, self.map_w), dtype=np.uint16)
+        _check(lib.hmrm_scene_light(self._h, _ptr(out), 2 * self.map_w, C.byref(fs)))
+        return out, int(fs.value)
+
+    def render_baked(self, cam: Camera, interior=False, factor=1, pad_px=0, allow_capped=False) -> np.ndarray:
+        """One full frame under the scene's baked light (hmrm_render_baked): render()'s frame -- render_interior()'s with
+        interior=True -- whose hit pixels are weighted by the light plane; factor 2, 4 or 8: antialiased like render_aa, every
+        sample weighted on its own -> HxWx4 uint8.  pad_px: the rows are written pad_px pixels apart wider (returned whole,
+        untouched bytes are 0xA5).  Capped primary rays: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        fb = np.full((cam.height, cam.width + int(pad_px), 4), 0xA5, dtype=np.uint8)
+        _check(lib.hmrm_render_baked(self._h, C.byref(cam), TRACE_INTERIOR if interior else 0, int(factor), _ptr(fb),
+                                     (cam.width + int(pad_px)) * 4),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
+    def render_baked_begin(self, cam: Camera, interior=False, aa=1, no_probe=False) -> int:
+        """render_begin for a baked-light frame (hmrm_render_baked_begin) -> ticket of the same ring: render_wait /
+        render_release.  no_probe is accepted and has no effect."""
+        self._sync_env()
+        t = C.c_int32()
+        _check(lib.hmrm_render_baked_begin(self._h, C.byref(cam), TRACE_INTERIOR if interior else 0,
+                                           (NO_PROBE if no_probe else 0) | aa_flags(aa), C.byref(t)))
+        return int(t.value)
+
+    def render_baked_device_begin(self, cam: Camera, d_ptr: int, stride_bytes: int, interior=False, aa=1, no_probe=False) -> int:
+        """render_device_begin for a baked-light frame (hmrm_render_baked_device_begin) -> ticket for render_device_wait."""
+        self._sync_env()
+        t = C.c_int32()
+        _check(lib.hmrm_render_baked_device_begin(self._h, C.byref(cam), TRACE_INTERIOR if interior else 0, C.c_void_p(d_ptr),
+                                                  stride_bytes, (NO_PROBE if no_probe else 0) | aa_flags(aa), C.byref(t)))
+        return int(t.value)
+
     def pick(self, cam: Camera, px: int, py: int, allow_capped=False) -> np.ndarray:
         """hmrm_pick: the record (RAY_HIT_DTYPE scalar) of the ray of pixel (px, py) of `cam`."""
         self._sync_env()
@@ -959,6 +1042,18 @@ def record_orbit_shaded(scenes, base: Camera, centre_x, centre_y, radius, hang0,
            allow=(HMRM_E_NOTERM,))
 
 
+def record_orbit_baked(scenes, base: Camera, centre_x, centre_y, radius, hang0, frames, directory, rec_id, interior=False, aa=1,
+                       encoder_threads=0, verbose=False):
+    """record_orbit_multi whose frames are baked-light ones (hmrm_record_orbit_baked): every scene needs a light plane."""
+    for s in scenes:
+        s._sync_env()
+    arr = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    _check(lib.hmrm_record_orbit_baked(arr, len(scenes), C.byref(base), centre_x, centre_y, radius, hang0, frames,
+                                       os.fsencode(directory), rec_id, encoder_threads, int(verbose), aa_flags(aa),
+                                       TRACE_INTERIOR if interior else 0),
+           allow=(HMRM_E_NOTERM,))
+
+
 def render_multi(scenes, cam: Camera, allow_capped=False) -> np.ndarray:
     """One frame over several scenes (one per GPU): scene i renders the cyclic 16-row bands i, i+n, ..."""
     for s in scenes:
@@ -1056,6 +1151,10 @@ class Config:
     def shading(self) -> bool:
         """Additive `shading on|off`: the CLI renders its single frame with hmrm_render_shaded."""
         return bool(lib.hmrm_config_shading(self._h))
+
+    def baked_light(self) -> int:
+        """`baked_light off|sun|sky`: 0, 1 or 2."""
+        return int(lib.hmrm_config_baked_light(self._h))
 
     def sky_light(self) -> bool:
         """Additive `sky_light on|off`: the CLI renders its single frame with hmrm_render_lit_sum over the sky directions of

@@ -644,7 +644,8 @@ int hmrm_render_geometry_device(const hmrm_scene *scene, const hmrm_camera *cam,
  * (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest sampling only).  All three projections, grid modes and sampling modes.
  * The work is bounded: every ray has its own budget of at most the step cap, and a pixel marches at most 1 + K rays.
  * OUT OF SCOPE: antialiasing; tickets and lanes; row strips or bands; hmrm_render_multi, hmrm_render_cycle, recording and
- * statistics; per-direction weights or colours; a baked per-cell light map read by the frame kernels. */
+ * statistics; per-direction weights or colours; a baked per-cell light map read by the frame kernels (since built:
+ * hmrm_render_baked below). */
 typedef struct hmrm_light_planes {      /* either pointer may be NULL: that plane is not written */
 	void     *rgba;  size_t rgba_stride;   /* bytes per row, >= 4 * width, multiple of 4 */
 	uint16_t *light; size_t light_stride;  /* bytes per row, >= 2 * width, even */
@@ -656,6 +657,74 @@ int hmrm_render_lit_sum(const hmrm_scene *scene, const hmrm_camera *cam, const h
 int hmrm_render_lit_sum_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun,
                                const void *d_dirs /* n_dirs x 24 bytes, DEVICE, 8-byte aligned */, int32_t n_dirs,
                                uint32_t shade_flags, const hmrm_light_planes *device_planes, void *hip_stream);
+
+/* ------------------------------------------------------ baked-light frames */
+/* A per-cell light plane the frame kernels read (build-side addition): the light of a static terrain under a fixed sun or sky
+ * does not depend on the camera, so it is baked once -- hmrm_scene_bake_light, or any plane of the caller's: a painted light
+ * map, a cumulative viewshed, a radiosity solution -- and every later frame costs a plain frame plus a small epilogue
+ * (INTEGRATION.md 2a has three recipes).
+ * THE SCENE'S LIGHT PLANE.  A scene owns at most one: map_w x map_h native uint16 in device memory, rows packed like the threshold
+ * table, and its full scale D in 1 .. 65535: a cell whose light equals D gives the texel back.
+ *   hmrm_scene_set_light         copies a HOST plane of map_w x map_h values, rows stride_bytes apart; format HMRM_LIGHT_U8 (bytes,
+ *                                widened to 16 bits) or HMRM_LIGHT_U16 (native uint16).
+ *   hmrm_scene_set_light_device  the same from DEVICE memory: d_plane is read on hip_stream, behind whatever the caller enqueued
+ *                                there -- the output of hmrm_cell_map_sum_device goes in without a trip over the host -- and the
+ *                                call returns only after the copy has finished.
+ *   hmrm_scene_bake_light        the launch of hmrm_cell_map_sum over the whole map with `p` and the K = n_targets targets (host
+ *                                memory), written straight into the scene's plane: byte for byte the words hmrm_cell_map_sum
+ *                                writes.  D = 255 * K with HMRM_MAP_WEIGHT, else D = K (status mode: a count);
+ *                                HMRM_MAP_TOWARDS_POINT is allowed.  Capped rays: HMRM_E_NOTERM with a valid plane, as there.
+ *   hmrm_scene_clear_light       drops the plane.
+ *   hmrm_scene_light             reads the plane back: *full_scale = D, or 0 when the scene has no plane; `out` may be NULL, else
+ *                                it takes map_w x map_h native uint16, rows stride_bytes (>= 2 * map_w, even) apart.
+ * Every call that changes the plane first drains the scene's own streams and its copy stream, as hmrm_scene_update does: a ticket
+ * begun before the call finishes with the old plane.  Callers' own streams are the caller's business, as there.
+ * hmrm_scene_update leaves the plane as it is: the light is the caller's data, and stale light is the caller's to bake again.
+ * hmrm_scene_destroy frees it.
+ * Refusals of hmrm_scene_set_light and hmrm_scene_set_light_device (HMRM_E_ARG, with a message), in this order: a NULL scene; a
+ * NULL plane; a format outside the enum; full_scale outside 1 .. 65535; a stride below a row, or an odd stride for
+ * HMRM_LIGHT_U16; for the device entry a HMRM_LIGHT_U16 pointer that is not 2-byte aligned.  Of hmrm_scene_bake_light: those of
+ * hmrm_cell_map_sum, in its order and without its `out`, then a NULL scene.  After a refusal the old plane stays; if a HIP call
+ * fails half-way the scene has no plane.
+ * THE BAKED FRAME.  Every pixel first gets hmrm_render's value; with HMRM_TRACE_INTERIOR in baked_flags hmrm_render_interior's.
+ * The primary march is unchanged.  Every pixel whose primary ray HIT (alpha-0 hit cells count, as in hmrm_render_lit) is then
+ * reweighted: for each of R, G and B, c' = min(255, (c * L + D / 2) / D) in unsigned 32-bit integers; A stays 255.  Misses, sky
+ * and capped primary rays are untouched.
+ *   L, HMRM_NEAREST and HMRM_NEAREST_F32: plane[cell_y * map_w + cell_x] of the hit cell (hmrm_ray_hit's).
+ *   L, HMRM_BILINEAR: interpolated like the colour -- the four cells c00, c10, c01, c11 and the weights tx, ty of the bilinear
+ *      mode at P (the ones THE LEVEL q names), the four words read as doubles f00 .. f11, a = f00 + tx * (f10 - f00),
+ *      c = f01 + tx * (f11 - f01), m = a + ty * (c - a) as plain IEEE operations in this order, no contraction; v = m + 0.5
+ *      clamped to [0, 65535], L = (uint32_t)floor(v).
+ * Nothing else is special-cased: L > D over-brightens and saturates at 255; L = D everywhere is hmrm_render /
+ * hmrm_render_interior, byte for byte.
+ * ANTIALIASING.  factor is 1, 2, 4 or 8: the baked frame of hmrm_render_aa's super camera, box-filtered with its formula inside
+ * the launch; every sample is weighted on its own.  Factor 1 is the plain baked frame.
+ * CAPPED RAYS are counted and reported as in hmrm_render_interior: HMRM_E_NOTERM with a valid frame.
+ * TICKETS.  hmrm_render_baked_begin and hmrm_render_baked_device_begin issue tickets from the same rings and lanes as the plain
+ * and lit tickets, waited for and released with the existing calls; `flags` takes HMRM_AA(n) and HMRM_NO_PROBE, which is accepted
+ * and has no effect.  hmrm_record_orbit_baked (below, with the recorders) is hmrm_record_orbit_flags whose frames are baked
+ * tickets.
+ * Refusals (HMRM_E_ARG, with a message), in this order: an undefined bit in baked_flags; those of hmrm_render_aa (tickets: those
+ * of hmrm_render_begin_flags) in their order; a NULL scene; "the scene has no light plane"; the 2^24-side rule of frames.
+ * Launched the way a lit frame is: one launch, never measured, never the scene's probe and not counted towards it;
+ * hmrm_debug_kernel_choice and every later frame are as they would have been.  It runs the scene's current kernel (HMRM_KERNEL or
+ * the probe's verdict; the window records apply to HMRM_NEAREST); every kernel writes the same bytes, the literal loop too
+ * (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest sampling only).  All three projections, grid modes and sampling modes.
+ * OUT OF SCOPE: row strips and bands; hmrm_render_multi, hmrm_render_cycle and statistics; several planes or coloured light; light
+ * for geometry frames; a plane smaller than the map. */
+enum { HMRM_LIGHT_U8 = 0, HMRM_LIGHT_U16 = 1 };
+int hmrm_scene_set_light(hmrm_scene *scene, const void *plane, size_t stride_bytes, int32_t format, uint32_t full_scale);
+int hmrm_scene_set_light_device(hmrm_scene *scene, const void *d_plane, size_t stride_bytes, int32_t format, uint32_t full_scale,
+                                void *hip_stream);
+int hmrm_scene_bake_light(hmrm_scene *scene, const hmrm_cell_map_params *p, const double *targets /* n_targets x 3, host */,
+                          int32_t n_targets);
+int hmrm_scene_clear_light(hmrm_scene *scene);
+int hmrm_scene_light(const hmrm_scene *scene, uint16_t *out /* may be NULL */, size_t stride_bytes, uint32_t *full_scale);
+int hmrm_render_baked(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t baked_flags, int32_t factor, uint8_t *rgba,
+                      size_t stride_bytes);
+int hmrm_render_baked_begin(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t baked_flags, uint32_t flags, int32_t *ticket);
+int hmrm_render_baked_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t baked_flags, void *d_rgba,
+                                   size_t stride_bytes, uint32_t flags, int32_t *ticket);
 
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
@@ -802,6 +871,13 @@ int hmrm_record_orbit_shaded(hmrm_scene *const *scenes, int32_t n_scenes, const 
                              double centre_x, double centre_y, double radius, double hang0, int32_t frames,
                              const char *dir, long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags,
                              const hmrm_sun *sun, uint32_t shade_flags);
+/* hmrm_record_orbit_flags whose frames are baked tickets (hmrm_render_baked_begin with `baked_flags` and `flags`): a flight
+ * through baked light as PNGs.  Every scene must have a light plane, else HMRM_E_ARG before any frame; an undefined bit in
+ * baked_flags is refused before anything else. */
+int hmrm_record_orbit_baked(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base,
+                            double centre_x, double centre_y, double radius, double hang0, int32_t frames,
+                            const char *dir, long long id, int32_t encoder_threads, int32_t verbose, uint32_t flags,
+                            uint32_t baked_flags);
 int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
 
 /* ------------------------------------------------------------------- config */
@@ -835,6 +911,14 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * shadow rays always on, HMRM_SHADE_DIFFUSE with `shading on`, shadow_ambient, shadow_step_dist, shadow_max_steps and interior
  * as for `shadows`, sun_dir not used; ignored, with a warning, with `antialias n` > 1, `devices n` > 1 or `record orbit`,
  * whatever sun_scope says; another value warns "WARNING: Unknown sky_light: v" and keeps the old one),
+ * `baked_light off|sun|sky` (default off; before its frames the CLI bakes the scene's light plane once with
+ * hmrm_scene_bake_light -- sun: one target, sun_dir, with exactly the flags, sun_map_lift, shadow_ambient, shadow_step_dist,
+ * shadow_max_steps and sampling of `sun_map`; sky: status mode over hmrm_sky_directions(sky_map_rings), as `sky_map` -- prints
+ * "baked light: K direction(s), full scale D", and renders the single frame, the `antialias n` frame and `record orbit` as
+ * baked frames, hmrm_render_baked / hmrm_record_orbit_baked, with HMRM_TRACE_INTERIOR for `interior on`; `shadows` and
+ * `shading` then only choose what is baked; `sky_light on` is ignored with "WARNING: sky_light is ignored with baked_light";
+ * `devices n` > 1 ignores the key with "WARNING: baked_light is ignored with devices > 1"; another value warns "WARNING:
+ * Unknown baked_light: v" and keeps the old one),
  * `range_map <path.pfm>` (echoed like `output`; after its frames and before an optional sun_map the CLI writes the range plane
  * of the configured camera -- hmrm_render_geometry with that plane alone, under the interior rule with `interior on` -- as a
  * one-component portable float map, hmrm_write_pfm).
@@ -861,6 +945,7 @@ int32_t      hmrm_config_interior(const hmrm_config *cfg);      /* additive `int
 int32_t      hmrm_config_shadows(const hmrm_config *cfg);       /* additive `shadows on|off`: 1|0 */
 int32_t      hmrm_config_shading(const hmrm_config *cfg);       /* additive `shading on|off`: 1|0 */
 int32_t      hmrm_config_sky_light(const hmrm_config *cfg);     /* additive `sky_light on|off`: 1|0 */
+int32_t      hmrm_config_baked_light(const hmrm_config *cfg);   /* additive `baked_light off|sun|sky`: 0|1|2 */
 int32_t      hmrm_config_sun_scope(const hmrm_config *cfg);     /* additive `sun_scope single|all`: 0|1 */
 const char  *hmrm_config_sun_map_path(const hmrm_config *cfg);  /* additive `sun_map <path.png>`: "" = none */
 double       hmrm_config_sun_map_lift(const hmrm_config *cfg);  /* additive `sun_map_lift v` */
