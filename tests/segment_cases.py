@@ -1,6 +1,7 @@
-"""What tests/test_segments_cpu.py and tests/test_segments_gpu.py share: the 64 x 48 map of tests/test_trace_rays_gpu.py, its
-grid widths and cameras (the inside camera's orthographic plane is 3 cells wide, so that one frame mixes interior origins
-with exterior rays that enter), and the rays no camera makes."""
+"""What the ray-query, segment and sun-lit test modules share: the 64 x 48 map (not square, not a multiple of 16, alpha-0
+texels, zero-height cells), its grid widths and cameras (the inside camera's orthographic plane is 3 cells wide, so that one
+frame mixes interior origins with exterior rays that enter; tests/test_trace_rays_gpu.py has its own, 0.02 cells wide), and
+the rays no camera makes."""
 import numpy as np
 
 import ray_replay
@@ -18,16 +19,27 @@ def maps():
     return rgb, cmap
 
 
+HANG_DEG, VANG_DEG = -50, 112
+MAX_HEIGHT_GW, STEP_DIST_GW = 8.0, 0.2  # in grid widths
+
+
+def hfov_deg(proj):
+    return 150 if proj == 2 else 80
+
+
+def camera_pos(gw, inside):
+    return (20.0 * gw, -20.0 * gw, 7.5 * gw) if inside else (-6.0 * gw, 8.0 * gw, 14.0 * gw)
+
+
 def scene_params(hmrm, gw):
-    return hmrm.SceneParams.make(0.0, 8.0 * gw, grid_width=gw)
+    return hmrm.SceneParams.make(0.0, MAX_HEIGHT_GW * gw, grid_width=gw)
 
 
 def camera(hmrm, gw, proj, inside, sampling=0, width=40, height=30):
     deg = hmrm.degrees_to_rads
-    pos = (20.0 * gw, -20.0 * gw, 7.5 * gw) if inside else (-6.0 * gw, 8.0 * gw, 14.0 * gw)
-    return hmrm.Camera.make(width=width, height=height, projection=proj, hfov=deg(150 if proj == 2 else 80), hang=deg(-50),
-                            vang=deg(112), pos=pos, ortho_width=(3.0 if inside else 1.3) * gw, step_dist=0.2 * gw, bg=BG,
-                            sampling=sampling)
+    return hmrm.Camera.make(width=width, height=height, projection=proj, hfov=deg(hfov_deg(proj)), hang=deg(HANG_DEG),
+                            vang=deg(VANG_DEG), pos=camera_pos(gw, inside), ortho_width=(3.0 if inside else 1.3) * gw,
+                            step_dist=STEP_DIST_GW * gw, bg=BG, sampling=sampling)
 
 
 _rays = {}

@@ -1,41 +1,18 @@
 """Antialiased rendering on the GPU (hmrm_render_aa, HMRM_AA): every frame is compared bit for bit with the CPU oracle's
 frame at n times the resolution, box-filtered in numpy (tests/aa_box.py) -- the definition in include/hmrm.h."""
-import contextlib
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import scenes
 from aa_box import box_filter, super_camera
+from gpu_support import env, gpu
 
 pytestmark = pytest.mark.gpu
 
 CASES = {c[0]: c for c in scenes.cases()}
 FEW = ("persp_outside_pow2", "sph_min_height", "ortho_default_grid")
 EIGHT = ("persp_outside_pow2", "sph_grazing", "ortho_lowside_exit", "persp_width1", "sph_height1")
-
-
-@contextlib.contextmanager
-def env(**kw):
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
 
 
 def _expected(gpu, oracle, heights, cmap, params, cam, n, step_cap=None):
@@ -192,9 +169,7 @@ def test_cli_antialias_key(gpu, oracle, tmp_path):
     outp = str(tmp_path / "frame.png")
     cfgp = tmp_path / "c.txt"
     cfgp.write_text(gpu.synth.config_text(wl, hp, cp, outp) + "antialias 2\n")
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "antialias 2\n" in r.stdout
     assert f"rendered {4 * cam.width * cam.height} rays, {total} ray-steps" in r.stdout
     assert open(outp, "rb").read() == gpu.png_encode(want)

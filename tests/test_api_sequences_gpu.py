@@ -8,18 +8,12 @@ import sys
 
 import pytest
 
+from gpu_support import gpu
 from test_api_sequences_cpu import F, SLICE_SEED
 
 pytestmark = pytest.mark.gpu
 
 SLICE_S = 40   # this slice's own time box (not part of the shares of test_parity_gpu._FUZZ_SHARES)
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
 
 
 def _run(args, timeout):

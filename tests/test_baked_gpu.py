@@ -4,10 +4,8 @@ and the plane, which tests/test_baked_cpu.py pins -- or, without the replay, wit
 hmrm_render_shaded and hmrm_render_lit_sum from the same GPU.  Map, grid widths and cameras are those of tests/segment_cases.py
 at 40 x 30 unless said otherwise (a partial tile row and sky-only waves in every frame); the plane is the formula plane of
 tests/baked_cases.py (full scale 1000) or its byte twin (full scale 255)."""
-import contextlib
+import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,55 +13,23 @@ import pytest
 import aa_box
 import baked_cases as bc
 import cell_map_replay as cmr
+import gpu_support as gs
 import lit_replay as lr
 import ray_replay
 import segment_cases as sc
 import segment_replay as sr
 from baked_cases import BASE_CAP, FULL_SCALE
+from gpu_support import KERNEL_VARIANTS, PROJ_IDS, SAMPLINGS, env, gpu, kernel_variant, same_frame
 from lit_cases import SUNS
 from segment_cases import BG, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W
 from shade_cases import AMBIENT
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
-SAMPLINGS = (0, 1, 2)
-PROJ_IDS = ["persp", "sph", "ortho"]
+samplings_of = functools.partial(gs.samplings_of, nearest_only=("rec", "simple"))  # (the literal loop too: nearest sampling only)
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def samplings_of(variant):
-    return (0,) if variant in ("rec", "simple") else SAMPLINGS  # (window records and the literal loop: nearest sampling only)
-
-
-class World(bc.Replays):
-    def __init__(self, gpu, oracle):
-        super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
-
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
-
+class World(gs.Scenes, bc.Replays):
     def filtered(self, gw, proj, sampling, n, plane=None, full_scale=FULL_SCALE, inside=False, width=20, height=15):
         """The replayed antialiased frame: the baked frame of the n x n larger camera, box-filtered."""
         want = self.baked(gw, proj, sampling, plane, full_scale, inside, width * n, height * n)
@@ -84,26 +50,7 @@ class World(bc.Replays):
         return aa_box.box_filter(frame, n)
 
 
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_frame(got, want_rgba, what):
-    want = np.asarray(want_rgba).reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere((got != want).any(axis=2))
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.shape[0] * got.shape[1]} pixels differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
+world = gs.world_fixture(World)
 
 
 def planes_of(world):
@@ -477,27 +424,19 @@ def test_not_a_frame_for_the_probe(world):
 # ---- 7. CLI ----
 def test_cli_baked_light_key(world, tmp_path):
     gpu, gw = world.gpu, 0.5
-    hp, cp, outp = str(tmp_path / "h.ppm"), str(tmp_path / "c.png"), str(tmp_path / "frame.png")
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
+    cfgp, _, outp = gs.cli_config(gpu, world, tmp_path, gw, output=False)
 
     def text(width, height):
-        return (f"resolution {width} {height}\nhfov 80\nhang -50\nvang 112\npos {-6.0 * gw:.17g} {8.0 * gw:.17g} {14.0 * gw:.17g}\n"
-                f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-                f"projection perspective\nheightmap {hp}\ncolormap {cp}\n")
+        return gs.cli_preamble(gw, tmp_path / "h.ppm", tmp_path / "c.png", width=width, height=height)
 
     sun = SUNS[0]
     keys = (f"sun_dir {sun[0]:.17g} {sun[1]:.17g} {sun[2]:.17g}\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\n"
             f"shadow_max_steps 40\n")
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    cfgp = tmp_path / "c.txt"
 
     def run(body, **kw):
         cfgp.write_text(body)
         with env(**kw):
-            r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr
-        return r
+            return gs.run_hmap(gpu, cfgp)
 
     hillshade = one_sun_plane(world, gw, 0, sun)
     # baked_light sun with shading on: the hillshade of sun_dir, baked once, under the plain frame

@@ -2,80 +2,39 @@
 definition in numpy, whose content tests/test_cell_map_cpu.py pins; one test pins the kernels to hmrm_trace_segments on the same
 GPU without the replay's march.  Maps, grid widths, suns and observer points are those of tests/cell_map_cases.py: step_dist
 0.3 grid widths in direction mode, 1/64 with max_steps 64 in point mode, ambient 128."""
-import contextlib
+import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cell_map_cases as cc
 import cell_map_replay as cmr
+import gpu_support as gs
 import segment_cases as sc
-from cell_map_cases import AMBIENT, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W, MODES, SAMPLINGS, SETTINGS, SUNS
+from cell_map_cases import AMBIENT, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W, MODES, SETTINGS, SUNS
+from gpu_support import KERNEL_VARIANTS, SAMPLINGS, env, gpu, kernel_variant
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "rec", "simple")  # (leap: the production kernel)
 RECTS = ((3, 5, 29, 13), (63, 47, 1, 1), (0, 0, 64, 1), (56, 40, 8, 8))
 SMALL_CAP = 300
+samplings_of = functools.partial(gs.samplings_of, nearest_only=("rec", "simple"))  # (the literal loop too: nearest sampling only)
+same_map = functools.partial(gs.same_cells, dtype=np.uint8)
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them: hmrm_debug_reload_env)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def samplings_of(variant):
-    return (0,) if variant in ("rec", "simple") else SAMPLINGS  # (records and the literal loop: nearest sampling only)
-
-
-class World(cc.Replays):
+class World(gs.Scenes, cc.Replays):
     def __init__(self, gpu, oracle):
         super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
         self.scenes_b = {gw: gpu.Scene(self.rgb_b, self.cmap_b, self.params[gw]) for gw in (0.5, 0.05)}
 
     def close(self):
-        for s in list(self.scenes.values()) + list(self.scenes_b.values()):
+        super().close()
+        for s in self.scenes_b.values():
             s.close()
 
 
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_map(got, want, what):
-    assert got.shape == want.shape and got.dtype == np.uint8, (what, got.shape, want.shape)
-    if got.tobytes() != np.ascontiguousarray(want).tobytes():
-        bad = np.argwhere(got != want)
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.size} cells differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
+world = gs.world_fixture(World)
 
 
 # ---- 1. the base sweep on map A ----
@@ -266,23 +225,16 @@ def test_not_a_frame(world, oracle):
 # ---- 8. CLI ----
 def test_cli_sun_map_key(world, tmp_path):
     gpu, gw = world.gpu, 0.5
-    hp, cp, outp, mapp = (str(tmp_path / n) for n in ("h.ppm", "c.png", "frame.png", "light.png"))
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
-    text = (f"resolution 40 30\nhfov 80\nhang -50\nvang 112\npos {-6.0 * gw:.17g} {8.0 * gw:.17g} {14.0 * gw:.17g}\n"
-            f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-            f"projection perspective\nheightmap {hp}\ncolormap {cp}\noutput {outp}\n"
-            f"sun_dir 0.6 0.5 0.35\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\nsun_map {mapp}\n")
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    cfgp = tmp_path / "c.txt"
+    mapp = str(tmp_path / "light.png")
+    cfgp, text, _ = gs.cli_config(gpu, world, tmp_path, gw)
+    text += f"sun_dir 0.6 0.5 0.35\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\nsun_map {mapp}\n"
     runs = (("", cmr.WEIGHT, 0.0), ("shading on\n", cmr.WEIGHT | cmr.DIFFUSE | cmr.NO_SHADOWS, 0.0),
             (f"shading on\nshadows on\nsampling bilinear\nsun_map_lift {0.25 * gw:.17g}\n", cmr.WEIGHT | cmr.DIFFUSE, 0.25 * gw))
     for keys, flags, lift in runs:
         cfgp.write_text(text + keys)
         sampling = 1 if "bilinear" in keys else 0
         want = world.bytes(gw, sampling, SUNS[0], 0.3 * gw, flags, lift)
-        r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr
+        r = gs.run_hmap(gpu, cfgp)
         assert f"sun_map {mapp}\n" in r.stdout and f"Saved sun map at {mapp}" in r.stdout and "Saved screenshot at" in r.stdout
         assert open(mapp, "rb").read() == gpu.png_encode(want), keys
         os.remove(mapp)

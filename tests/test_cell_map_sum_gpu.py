@@ -2,9 +2,8 @@
 tests/cell_map_replay.py's maps over the targets (tests/cell_sum_cases.py), whose content tests/test_cell_map_sum_cpu.py pins;
 two tests pin the kernels to Scene.cell_map on the same GPU without the replay.  Maps, grid widths, suns and observer points are
 those of tests/cell_map_cases.py: step_dist 0.3 grid widths in direction mode, 1/64 with max_steps 64 in point mode, ambient 128."""
-import contextlib
+import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,71 +11,31 @@ import pytest
 import cell_map_cases as cc
 import cell_map_replay as cmr
 import cell_sum_cases as cs
+import gpu_support as gs
 import segment_cases as sc
-from cell_map_cases import AMBIENT, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W, MODES, SAMPLINGS, SETTINGS, SUNS
+from cell_map_cases import AMBIENT, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W, MODES, SETTINGS, SUNS
+from gpu_support import KERNEL_VARIANTS, SAMPLINGS, env, gpu, kernel_variant
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "rec", "simple")  # (leap: the production kernel)
 RECTS = ((3, 5, 29, 13), (63, 47, 1, 1), (0, 0, 64, 1), (56, 40, 8, 8))
 SMALL_CAP = cs.SMALL_CAP
+samplings_of = functools.partial(gs.samplings_of, nearest_only=("rec", "simple"))  # (the literal loop too: nearest sampling only)
+same_map = functools.partial(gs.same_cells, dtype=np.uint16)
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them: hmrm_debug_reload_env)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def samplings_of(variant):
-    return (0,) if variant in ("rec", "simple") else SAMPLINGS  # (records and the literal loop: nearest sampling only)
-
-
-class World(cc.Replays):
+class World(gs.Scenes, cc.Replays):
     def __init__(self, gpu, oracle):
         super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
         self.scenes_b = {gw: gpu.Scene(self.rgb_b, self.cmap_b, self.params[gw]) for gw in (0.5, 0.05)}
 
     def close(self):
-        for s in list(self.scenes.values()) + list(self.scenes_b.values()):
+        super().close()
+        for s in self.scenes_b.values():
             s.close()
 
 
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_map(got, want, what):
-    assert got.shape == want.shape and got.dtype == np.uint16, (what, got.shape, want.shape, got.dtype)
-    if np.ascontiguousarray(got).tobytes() != np.ascontiguousarray(want).astype(np.uint16).tobytes():
-        bad = np.argwhere(got != want)
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.size} cells differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
+world = gs.world_fixture(World)
 
 
 # ---- 1. the replay sweep on map A: the three suns in one launch ----
@@ -315,15 +274,9 @@ def test_not_a_frame(world, oracle):
 # ---- 11. CLI ----
 def test_cli_sky_map_key(world, tmp_path):
     gpu, gw = world.gpu, 0.5
-    hp, cp, outp, sunp, skyp = (str(tmp_path / n) for n in ("h.ppm", "c.png", "frame.png", "light.png", "sky.png"))
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
-    text = (f"resolution 40 30\nhfov 80\nhang -50\nvang 112\npos {-6.0 * gw:.17g} {8.0 * gw:.17g} {14.0 * gw:.17g}\n"
-            f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-            f"projection perspective\nheightmap {hp}\ncolormap {cp}\noutput {outp}\n"
-            f"sun_dir 0.6 0.5 0.35\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\nsky_map {skyp}\n")
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    cfgp = tmp_path / "c.txt"
+    sunp, skyp = str(tmp_path / "light.png"), str(tmp_path / "sky.png")
+    cfgp, text, _ = gs.cli_config(gpu, world, tmp_path, gw)
+    text += f"sun_dir 0.6 0.5 0.35\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\nsky_map {skyp}\n"
     runs = (("", (4, 16), 0, 0.0, 0, False),
             (f"sampling bilinear\nsky_map_rings 3 7\nshadow_max_steps 40\nsun_map_lift {0.25 * gw:.17g}\nsun_map {sunp}\n", (3, 7), 1, 0.25 * gw, 40, True),
             ("sky_map_rings 16 17\n", (4, 16), 0, 0.0, 0, False))
@@ -333,8 +286,7 @@ def test_cli_sky_map_key(world, tmp_path):
         counts = world.scenes[gw].cell_map_sum(gpu.sky_directions(r, n), 0.3 * gw, lift=lift, max_steps=limit, sampling=sampling)
         assert counts.max() <= K and len(np.unique(counts)) >= 8
         want = ((counts.astype(np.int64) * 255 + K // 2) // K).astype(np.uint8)
-        res = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-        assert res.returncode == 0, res.stderr
+        res = gs.run_hmap(gpu, cfgp)
         assert f"sky_map {skyp}\n" in res.stdout and f"Saved sky map at {skyp}" in res.stdout and "Saved screenshot at" in res.stdout
         assert ("Saved sun map at" in res.stdout) == sun_too and os.path.exists(sunp) == sun_too
         assert ("sky_map_rings must give" in res.stderr) == (keys == "sky_map_rings 16 17\n")

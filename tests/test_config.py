@@ -1,10 +1,11 @@
 """Config grammar = ConsumeConfigStream (main/hmap.cpp:309-520), CPU only."""
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
+
+from gpu_support import hmap_exe
 
 
 @pytest.fixture()
@@ -151,7 +152,7 @@ def test_later_keys_win_and_streams_accumulate(hmrm, maps):
 
 
 def test_cli_usage_and_errors(hmrm, tmp_path):
-    exe = os.path.join(os.path.dirname(hmrm.LIB_PATH), "hmap")
+    exe = hmap_exe(hmrm)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 1 and r.stderr == "USAGE: hmap.exe path/to/config.txt\n"  # hmap.cpp:527-530
     r = subprocess.run([exe, str(tmp_path / "missing.txt")], capture_output=True, text=True)

@@ -9,16 +9,10 @@ import sys
 
 import pytest
 
+from gpu_support import gpu
 from test_family_sequences_cpu import F, SUITE_SEED
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
 
 
 def test_family_sequence_slice(gpu):

@@ -3,72 +3,30 @@ BYTEWISE with tests/geometry_replay.py, the definition in numpy, which tests/tes
 ramp's analytic gradient; one test pins the kernels to hmrm_trace_rays / hmrm_trace_segments records and the device's own
 threshold table without the replay's march.  Map, grid widths and cameras are those of tests/segment_cases.py at 40 x 30 unless
 said otherwise."""
-import contextlib
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
 import geometry_cases as gc
 import geometry_replay as gr
+import gpu_support as gs
 import segment_cases as sc
+from gpu_support import KERNEL_VARIANTS, PROJ_IDS, env, gpu, kernel_variant
 from segment_cases import BG, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
-PROJ_IDS = ["persp", "sph", "ortho"]
 PLANES = ("rgba", "cell", "range", "slope")
 ELEM = dict(rgba=4, cell=4, range=4, slope=8)
+samplings_of = functools.partial(gs.samplings_of, nearest_only=("rec", "simple"))  # (the literal loop too: nearest sampling only)
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
+class World(gs.Scenes, gc.Replays):
+    pass
 
 
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def samplings_of(variant):
-    return (0,) if variant in ("rec", "simple") else (0, 1, 2)  # (window records and the literal loop: nearest sampling only)
-
-
-class World(gc.Replays):
-    def __init__(self, gpu, oracle):
-        super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
-
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
+world = gs.world_fixture(World)
 
 
 def same_planes(got, want, width, what, names=PLANES):
@@ -250,18 +208,10 @@ def test_device_entry_on_a_stream(world):
 def test_cli_range_map_key(world, tmp_path):
     """`range_map out.pfm`: a file that a PFM reader opens as the replay's range plane, outside and, with `interior on`, inside."""
     gpu, gw = world.gpu, 0.5
-    hp, cp, outp, rangep = str(tmp_path / "h.ppm"), str(tmp_path / "c.png"), str(tmp_path / "frame.png"), str(tmp_path / "range.pfm")
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    for inside, pos in ((False, (-6.0 * gw, 8.0 * gw, 14.0 * gw)), (True, (20.0 * gw, -20.0 * gw, 7.5 * gw))):
-        text = (f"resolution 40 30\nhfov 80\nhang -50\nvang 112\npos {pos[0]:.17g} {pos[1]:.17g} {pos[2]:.17g}\n"
-                f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-                f"projection perspective\nheightmap {hp}\ncolormap {cp}\noutput {outp}\nrange_map {rangep}\n" + ("interior on\n" if inside else ""))
-        cfgp = tmp_path / "c.txt"
-        cfgp.write_text(text)
-        r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr
+    rangep = str(tmp_path / "range.pfm")
+    for inside in (False, True):
+        cfgp, _, _ = gs.cli_config(gpu, world, tmp_path, gw, inside, f"range_map {rangep}\n" + ("interior on\n" if inside else ""))
+        r = gs.run_hmap(gpu, cfgp)
         assert f"range_map {rangep}\n" in r.stdout and f"Saved range map at {rangep}\n" in r.stdout
         want, _prim = world.planes(gw, 1, 0, inside)
         back = gr.read_pfm(rangep)

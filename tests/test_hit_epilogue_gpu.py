@@ -11,16 +11,15 @@ What the cases are chosen for, each asserted from the oracle / the replays so th
     are stopped exactly where they would have hit, leave the grid inside that path, and enter a group with budget 0;
   * the three sampling modes, grid widths 1, 0.5 and 0.05 (grid modes 0, 1, 2), the four kernels (default, group, rec, simple),
     and every family once: plain, antialiased, lit, shaded, lit + shaded (also antialiased), ray batches, segments, interior."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import segment_cases as sc
 import segment_replay as sr
 import shade_cases as shc
 from aa_box import box_filter, super_camera
+from gpu_support import env, gpu, same_frame, same_records, samplings_of
 from segment_cases import BG, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W
 
 pytestmark = pytest.mark.gpu
@@ -35,35 +34,11 @@ CAPS = ((12, False), (15, False), (53, False), (54, False), (23, True), (24, Tru
 CAP_IDS = [f"cap{c}{'in' if i else 'out'}" for c, i in CAPS]
 
 
-def samplings_of(kernel):
-    return (0,) if kernel == "rec" else (0, 1, 2)  # (records bound the nearest cell's double thresholds only)
-
-
-@contextlib.contextmanager
-def env(**kv):
-    old = {k: os.environ.get(k) for k in kv}
-    for k, v in kv.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-class World(shc.Replays):
+class World(gs.Scenes, shc.Replays):
     """Scenes per grid width, the oracle's frames, and the replays' caches (computed once, read-only)."""
 
     def __init__(self, gpu, oracle):
         super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
         self._oracle, self._seg = {}, {}
 
     def cam(self, gw, sampling=0, inside=False, proj=1):
@@ -92,43 +67,8 @@ class World(shc.Replays):
             self._seg[key] = r
         return self._seg[key]
 
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
 
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_frame(got, want_rgba, what):
-    want = want_rgba.reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere((got != want).any(axis=2))
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.shape[0] * got.shape[1]} pixels differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
-
-
-def same_records(got, want, what):
-    if got.tobytes() == want.tobytes():
-        return
-    for name in want.dtype.names:
-        a, b = got[name], want[name]
-        bad = np.nonzero((a.reshape(a.shape[0], -1).view(np.uint8) != b.reshape(b.shape[0], -1).view(np.uint8)).any(axis=1))[0]
-        if bad.size:
-            i = int(bad[0])
-            raise AssertionError(f"{what}: field {name!r} differs for {bad.size} of {want.shape[0]} rays; first {i}: got {got[i]}, want {want[i]}")
-    raise AssertionError(f"{what}: records differ in padding")
+world = gs.world_fixture(World)
 
 
 def sun_of(gpu, gw, **kw):

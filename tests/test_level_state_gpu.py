@@ -13,13 +13,14 @@ tests/golden/level_state_counts.json, recorded with the build of commit e2d4f14,
 window geometry from the level number on every attempt: the state is a restatement, no counter may move.
 
 Re-record (only for a change that is meant to change the traversal): python tests/test_level_state_gpu.py --record"""
-import contextlib
 import json
 import os
 import sys
 
 import numpy as np
 import pytest
+
+from gpu_support import env, gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -128,24 +129,6 @@ def camera(hmrm, map_shape, gw, pose, proj, frame, step_cells, sampling):
     return hmrm.Camera.make(pos=tuple(v * gw for v in pos), hang=deg(hang), vang=deg(vang), **kw)
 
 
-@contextlib.contextmanager
-def env(**kv):
-    old = {k: os.environ.get(k) for k in kv}
-    for k, v in kv.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 class World:
     """Maps, oracle heights and expected frames, made once and shared."""
 
@@ -195,13 +178,6 @@ def count(hmrm, world, name, with_levels=False):
                     scene.close()
             out.update(dict(zip(keys, (int(s2.leap_attempts), int(s2.leaps), int(s2.groups), int(s2.leaped_steps)))))
     return fb, fb_stats, out, steps
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
 
 
 @pytest.fixture(scope="module")

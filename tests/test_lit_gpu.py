@@ -2,82 +2,27 @@
 definition in numpy, which tests/test_lit_cpu.py pins to the C oracle and to a scalar loop; one test pins the lit kernels to
 hmrm_trace_rays + hmrm_trace_segments without the replay.  Map, grid widths and cameras are those of tests/segment_cases.py
 at 40 x 30 (the smallest at which every instantiation family runs), shadow step_dist 0.3 * grid width."""
-import contextlib
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import lit_cases as lc
 import lit_replay as lr
 import ray_replay
 import segment_cases as sc
 import segment_replay as sr
+from gpu_support import KERNEL_VARIANTS, PROJ_IDS, env, gpu, kernel_variant, same_frame, samplings_of
 from lit_cases import AMBIENT, SUNS
 from segment_cases import BG, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
-SAMPLINGS = (0, 1, 2)
-PROJ_IDS = ["persp", "sph", "ortho"]
+
+class World(gs.Scenes, lc.Replays):
+    pass
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def samplings_of(variant):
-    return (0,) if variant == "rec" else SAMPLINGS  # (the record kernel applies to nearest sampling only)
-
-
-class World(lc.Replays):
-    def __init__(self, gpu, oracle):
-        super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
-
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_frame(got, want_rgba, what):
-    want = want_rgba.reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere((got != want).any(axis=2))
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.shape[0] * got.shape[1]} pixels differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
+world = gs.world_fixture(World)
 
 
 def sun_of(gpu, gw, direction, **kw):
@@ -333,16 +278,8 @@ def test_update_between_lit_frames(world, oracle):
 # ---- 10. CLI ----
 def test_cli_shadow_keys(world, tmp_path):
     gpu, gw = world.gpu, 0.5
-    hp, cp, outp = str(tmp_path / "h.ppm"), str(tmp_path / "c.png"), str(tmp_path / "frame.png")
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
-    text = (f"resolution 40 30\nhfov 80\nhang -50\nvang 112\npos {-6.0 * gw:.17g} {8.0 * gw:.17g} {14.0 * gw:.17g}\n"
-            f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-            f"projection perspective\nheightmap {hp}\ncolormap {cp}\noutput {outp}\n")
     keys = f"shadows on\nsun_dir 0.6 0.5 0.35\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\n"
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    cfgp = tmp_path / "c.txt"
-    cfgp.write_text(text + keys)
+    cfgp, text, outp = gs.cli_config(gpu, world, tmp_path, gw, extra=keys)
     cfg = gpu.Config().consume_file(str(cfgp))
     assert cfg.shadows() is True and cfg.sun().step_dist == 0.3 * gw
     scene = cfg.create_scene()
@@ -351,17 +288,15 @@ def test_cli_shadow_keys(world, tmp_path):
     scene.close()
     cfg.close()
     same_frame(want, world.lit(gw, 1, 0, SUNS[0])["rgba"], "the config's camera and sun are the tests'")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "shadows on\n" in r.stdout and "sun_dir 0.6 0.5 0.35\n" in r.stdout and "with sun shadows" in r.stdout
     assert open(outp, "rb").read() == gpu.png_encode(want) != gpu.png_encode(plain)
     # shadow_step_dist absent: the camera's step_dist
     cfgp.write_text(text + "shadows on\nsun_dir 0.6 0.5 0.35\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     want02 = world.lit(gw, 1, 0, SUNS[0], sun_step=0.2 * gw)
     assert open(outp, "rb").read() == gpu.png_encode(np.ascontiguousarray(want02["rgba"].reshape(30, 40, 4)))
     # ... ignored, with a warning, together with antialias > 1
     cfgp.write_text(text + keys + "antialias 2\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "WARNING: shadows is ignored with antialias > 1" in r.stderr
+    r = gs.run_hmap(gpu, cfgp)
+    assert "WARNING: shadows is ignored with antialias > 1" in r.stderr

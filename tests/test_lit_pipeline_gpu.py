@@ -4,86 +4,33 @@ definition: aa_box.box_filter of tests/shade_replay.py's frame of the super came
 tests/test_lit_pipeline_cpu.py pins to the C oracle; one test compares the GPU with itself instead (the antialiased frame
 against the filtered hmrm_render_shaded frame of the super camera).  Map, grid widths, cameras and suns are those of
 tests/segment_cases.py / tests/shade_cases.py, shadow step_dist 0.3 * grid width, ambient 96."""
-import contextlib
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import lit_pipeline_cases as lp
 import lit_replay as lr
 import segment_cases as sc
 import shade_cases as shc
 import shade_replay as shr
 from aa_box import box_filter, super_camera
+from gpu_support import KERNEL_VARIANTS, PROJ_IDS, SAMPLINGS, env, gpu, kernel_variant, same_frame, samplings_of
 from segment_cases import BG, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W
 from shade_cases import AMBIENT, SUNS
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
-SAMPLINGS = (0, 1, 2)
-PROJ_IDS = ["persp", "sph", "ortho"]
 UP = (0.0, 0.0, 1.0)
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
+class World(gs.Scenes, shc.Replays):
+    pass
 
 
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def samplings_of(variant):
-    return (0,) if variant == "rec" else SAMPLINGS  # (the record kernel applies to nearest sampling only)
-
-
-class World(shc.Replays):
-    def __init__(self, gpu, oracle):
-        super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
-
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_frame(got, want, what):
-    want = want.reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere((got != want).any(axis=2))
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.shape[0] * got.shape[1]} pixels differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
+world = gs.world_fixture(World)
 
 
 def sun_of(gpu, gw, direction, **kw):
@@ -388,25 +335,16 @@ def test_record_orbit_shaded(world, tmp_path):
 def test_cli_sun_scope_all(world, tmp_path):
     gpu, gw = world.gpu, 0.5
     scene = world.scenes[gw]
-    hp, cp, outp = str(tmp_path / "h.ppm"), str(tmp_path / "c.png"), str(tmp_path / "frame.png")
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
-    text = (f"resolution 20 15\nhfov 80\nhang -50\nvang 112\npos {-6.0 * gw:.17g} {8.0 * gw:.17g} {14.0 * gw:.17g}\n"
-            f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-            f"projection perspective\nheightmap {hp}\ncolormap {cp}\n")
+    cfgp, text, outp = gs.cli_config(gpu, world, tmp_path, gw, output=False, width=20, height=15)
     keys = f"sun_dir 0.6 0.5 0.35\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\nsun_scope all\nantialias 2\nshading on\n"
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    cfgp = tmp_path / "c.txt"
     bare, _ = lp.expected(world, gw, 1, 0, SUNS[0], True, False, lp.BASE)
     full, _ = lp.expected(world, gw, 1, 0, SUNS[0], True, True, lp.BASE)
     cfgp.write_text(text + f"output {outp}\n" + keys)
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "sun_scope all\n" in r.stdout and "rendered 1200 rays at antialias 2 with sun shading in" in r.stdout and "ignored" not in r.stderr
     assert open(outp, "rb").read() == gpu.png_encode(bare)
     cfgp.write_text(text + f"output {outp}\n" + keys + "shadows on\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "at antialias 2 with sun shading and sun shadows in" in r.stdout and "ignored" not in r.stderr
     assert open(outp, "rb").read() == gpu.png_encode(full) != gpu.png_encode(bare)
     # record orbit: the reference's lines, the synchronous frames of the same orbit
@@ -416,8 +354,7 @@ def test_cli_sun_scope_all(world, tmp_path):
     base, sun = cfg.camera(), cfg.sun()
     assert cfg.sun_scope() == 1 and (base.width, base.height) == (20, 15)
     cfg.close()
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert r.stdout.rstrip().endswith("Done recording.") and r.stdout.count("Saved screenshot at ") == 3 and "ignored" not in r.stderr
     files = sorted(rec.iterdir(), key=lambda p: int(p.stem.rsplit("_", 1)[1]))
     assert len(files) == 3

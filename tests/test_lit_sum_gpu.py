@@ -3,82 +3,31 @@ tests/lit_sum_cases.py's replay -- a composition of tests/shade_replay.py's weig
 without the replay, with frames of hmrm_render_shaded and hmrm_render_geometry from the same GPU.  Map, grid widths and cameras
 are those of tests/segment_cases.py at 40 x 30 unless said otherwise (a partial tile row and sky-only waves in every frame),
 shadow step_dist 0.3 * grid width, ambient 96."""
-import contextlib
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import lit_sum_cases as lsc
 import segment_cases as sc
+from gpu_support import KERNEL_VARIANTS, PROJ_IDS, env, gpu, kernel_variant, same_frame
 from lit_sum_cases import AMBIENT, NO_HIT, SUNS
 from segment_cases import GRID_WIDTHS, GW_IDS
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
-SAMPLINGS = (0, 1, 2)
-PROJ_IDS = ["persp", "sph", "ortho"]
 MODES = ((False, True), (True, True), (True, False))  # (diffuse, shadows): shade_flags 0, DIFFUSE, DIFFUSE | NO_SHADOWS
 ALL_MODES = MODES + ((False, False),)
 UP = (0.0, 0.0, 1.0)
+samplings_of = functools.partial(gs.samplings_of, nearest_only=("rec", "simple"))  # (the literal loop too: nearest sampling only)
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
+class World(gs.Scenes, lsc.Replays):
+    pass
 
 
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def samplings_of(variant):
-    return (0,) if variant in ("rec", "simple") else SAMPLINGS  # (window records and the literal loop: nearest sampling only)
-
-
-class World(lsc.Replays):
-    def __init__(self, gpu, oracle):
-        super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
-
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_frame(got, want_rgba, what):
-    want = want_rgba.reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere((got != want).any(axis=2))
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.shape[0] * got.shape[1]} pixels differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
+world = gs.world_fixture(World)
 
 
 def same_light(got, want_light, what):
@@ -401,26 +350,17 @@ def test_not_a_frame_for_the_probe(world, oracle):
 # ---- 8. CLI ----
 def test_cli_sky_light_key(world, tmp_path):
     gpu, gw = world.gpu, 0.5
-    hp, cp, outp = str(tmp_path / "h.ppm"), str(tmp_path / "c.png"), str(tmp_path / "frame.png")
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
-    text = (f"resolution 40 30\nhfov 80\nhang -50\nvang 112\npos {-6.0 * gw:.17g} {8.0 * gw:.17g} {14.0 * gw:.17g}\n"
-            f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-            f"projection perspective\nheightmap {hp}\ncolormap {cp}\n")
+    cfgp, text, outp = gs.cli_config(gpu, world, tmp_path, gw, output=False)
     keys = f"sun_dir 0 0 -1\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\nsky_light on\n"
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    cfgp = tmp_path / "c.txt"
     # the default rings: 4 x 16 directions, no diffuse levels
     cfgp.write_text(text + f"output {outp}\n" + keys)
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "sky_light on\n" in r.stdout and "rendered 1200 rays with sky light from 64 directions" in r.stdout and "ignored" not in r.stderr
     want = world.lit_sum(gw, 1, 0, gpu.sky_directions(4, 16), False, True)
     assert open(outp, "rb").read() == gpu.png_encode(np.ascontiguousarray(want["rgba"].reshape(30, 40, 4)))
     # sky_map_rings 3 7 with shading on, bilinear sampling and a limit
     cfgp.write_text(text + f"output {outp}\n" + keys + "sky_map_rings 3 7\nshading on\nsampling bilinear\nshadow_max_steps 40\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "rendered 1200 rays with sky light from 21 directions" in r.stdout and "ignored" not in r.stderr
     want = world.lit_sum(gw, 1, 1, gpu.sky_directions(3, 7), True, True, max_steps=40)
     assert open(outp, "rb").read() == gpu.png_encode(np.ascontiguousarray(want["rgba"].reshape(30, 40, 4)))
@@ -428,16 +368,13 @@ def test_cli_sky_light_key(world, tmp_path):
     plain = gpu.png_encode(np.ascontiguousarray(world.primary(gw, 1, 0)["rgba"].reshape(30, 40, 4)))
     cfgp.write_text(text + f"output {outp}\n" + keys + "sun_scope all\ndevices 2\n")
     with env(HMRM_OVERSUBSCRIBE_DEVICES=1):  # (a one-GPU box keeps `devices 2`: two scenes on the one device)
-        r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+        r = gs.run_hmap(gpu, cfgp)
     assert "WARNING: sky_light is ignored with devices > 1" in r.stderr and "sky light from" not in r.stdout
     assert open(outp, "rb").read() == plain
     cfgp.write_text(text + f"output {outp}\n" + keys + "sun_scope all\nantialias 2\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "WARNING: sky_light is ignored with antialias > 1" in r.stderr and "sky light from" not in r.stdout
     rec = tmp_path / "rec"
     cfgp.write_text(text + f"output {rec}\n" + keys + "sun_scope all\nrecord orbit\nrecording_frame_count 1\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "WARNING: sky_light is ignored with record orbit" in r.stderr and "sky light from" not in r.stdout

@@ -6,7 +6,6 @@ Sizes the oracle finishes in seconds are compared directly; BASELINE.json's
 full sizes are covered by row-subsampled oracle comparison and by
 size-independent properties (determinism, strips == full frame, counters add up).
 """
-import contextlib
 import importlib
 import os
 import subprocess
@@ -14,7 +13,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import scenes
+from gpu_support import KERNEL_VARIANTS, env, gpu, kernel_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -28,43 +29,7 @@ def _bits(a):
 # HMRM_KERNEL: "leap" = production kernel (speculative groups + exact leaps), "group" = groups
 # only, "simple" = the literal one-step loop, "rec" = groups + leaps over window records (nearest sampling; the plain
 # groups otherwise).  All must agree with the oracle bit for bit.
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
 KERNEL_NAMES = ("the production kernel", "the plain groups", "the literal loop", "the groups with window records")  # Scene.kernel_choice()
-
-
-@contextlib.contextmanager
-def kernel_variant(name):
-    old = os.environ.get("HMRM_KERNEL")
-    os.environ["HMRM_KERNEL"] = name
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ["HMRM_KERNEL"]
-        else:
-            os.environ["HMRM_KERNEL"] = old
-
-
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
 
 
 @pytest.mark.parametrize("case", scenes.cases(), ids=scenes.case_ids())
@@ -403,13 +368,11 @@ def test_cli_end_to_end(gpu, oracle, tmp_path):
     params, cam = wl.scene_params(), wl.camera()
     heights = oracle.update_heightmap(rgb, params)
     ofb, *_ = oracle.render(oracle.make_cfg(cam, params, wl.map_size, wl.map_size), heights, cmap)
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
     for ext in ("png", "ppm"):
         outp = str(tmp_path / f"frame.{ext}")
         cfgp = tmp_path / f"c_{ext}.txt"
         cfgp.write_text(gpu.synth.config_text(wl, hp, cp, outp))
-        r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr
+        r = gs.run_hmap(gpu, cfgp)
         assert f"Saved screenshot at {outp}" in r.stdout and r.stdout.startswith("resolution 320 240\n")
         img, n = gpu.image_load(outp, 4)
         assert np.array_equal(img, ofb)
@@ -428,19 +391,19 @@ def test_cli_devices_key(gpu, oracle, tmp_path):
     params, cam = wl.scene_params(), wl.camera()
     heights = oracle.update_heightmap(rgb, params)
     ofb, *_ = oracle.render(oracle.make_cfg(cam, params, wl.map_size, wl.map_size), heights, cmap)
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    envp = dict(os.environ, HMRM_OVERSUBSCRIBE_DEVICES="1")
     outp = str(tmp_path / "frame.png")
     cfgp = tmp_path / "one.txt"
     cfgp.write_text(gpu.synth.config_text(wl, hp, cp, outp) + "devices 3\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300, env=envp)
-    assert r.returncode == 0 and "on 3 devices" in r.stdout and "devices 3" in r.stdout, r.stdout + r.stderr
+    with env(HMRM_OVERSUBSCRIBE_DEVICES=1):
+        r = gs.run_hmap(gpu, cfgp)
+    assert "on 3 devices" in r.stdout and "devices 3" in r.stdout, r.stdout + r.stderr
     assert open(outp, "rb").read() == gpu.png_encode(ofb)
     rec = tmp_path / "rec"
     cfg2 = tmp_path / "rec.txt"
     cfg2.write_text(gpu.synth.config_text(wl, hp, cp, str(rec)) + "devices 3 record orbit recording_frame_count 7\n")
-    r = subprocess.run([exe, str(cfg2)], capture_output=True, text=True, timeout=300, env=envp)
-    assert r.returncode == 0 and r.stdout.count("Saved screenshot at ") == 7, r.stdout + r.stderr
+    with env(HMRM_OVERSUBSCRIBE_DEVICES=1):
+        r = gs.run_hmap(gpu, cfg2)
+    assert r.stdout.count("Saved screenshot at ") == 7, r.stdout + r.stderr
     files = sorted(rec.iterdir())
     assert len(files) == 7
     # frame 0 of the orbit through the configured pose is that pose
@@ -474,11 +437,9 @@ def test_recording_orbit_writes_reference_named_pngs(gpu, oracle, tmp_path):
     gpu.write_ppm(hp, rgb)
     gpu.write_png(cp, cmap)
     cfgp = tmp_path / "rec.txt"
-    cfgp.write_text(f"resolution 40 30 pos -20 20 30 vang 112 max_height 8 grid_width 1 step_dist 0.5 cycle 1\n"
+    cfgp.write_text("resolution 40 30 pos -20 20 30 vang 112 max_height 8 grid_width 1 step_dist 0.5 cycle 1\n"
                     f"heightmap {hp}\ncolormap {cp}\nrecord orbit recording_frame_count 3 output {tmp_path / 'cli'}\n")
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert r.stdout.rstrip().endswith("Done recording.") and r.stdout.count("Saved screenshot at ") == 3
     assert len(list((tmp_path / "cli").iterdir())) == 3
 

@@ -10,6 +10,7 @@ import pytest
 
 import scenes
 import segment_cases as sc
+from gpu_support import gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -22,13 +23,6 @@ N_DIRS = (3, 40, 3)
 MAX_TICKETS = 64  # kMaxRing
 AMBIENT = 96
 NO_HIT = 0xFFFF  # a light sum where the primary ray hit nothing
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
 
 
 @pytest.fixture(scope="module")

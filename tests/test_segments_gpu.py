@@ -3,54 +3,27 @@ include/hmrm.h).  Every record array and every frame is compared BYTEWISE with t
 tests/test_segments_cpu.py pins to ray_replay.replay (rules off), to the C oracle (interior rule) and to a scalar loop.
 The map, grid widths and cameras are those of tests/test_trace_rays_gpu.py (tests/segment_cases.py): the smallest at
 which every instantiation family runs."""
-import contextlib
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import ray_replay
 import segment_cases as sc
 import segment_replay as sr
+from gpu_support import KERNEL_VARIANTS, SAMPLINGS, env, gpu, kernel_variant, same_frame, same_records
 from segment_cases import BG, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
-SAMPLINGS = (0, 1, 2)
 MIXED_N = 3637  # not a multiple of 64
 ODD_CAP = 4096
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-class World:
+class World(gs.Scenes, gs.Maps):
     """Scenes per grid width; rays and replayed records per case, computed once and never modified."""
 
     def __init__(self, gpu, oracle):
-        self.gpu, self.oracle = gpu, oracle
-        self.rgb, self.cmap = sc.maps()
-        self.params = {gw: sc.scene_params(gpu, gw) for gw in GRID_WIDTHS}
-        self.heights = {gw: oracle.update_heightmap(self.rgb, p) for gw, p in self.params.items()}
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
+        super().__init__(gpu, oracle)
         self._cache = {}
 
     def rays(self, gw, proj, inside, width=40, height=30):
@@ -86,43 +59,8 @@ class World:
             self._cache[key] = rays
         return self._cache[key]
 
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
 
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_records(got, want, what):
-    if got.tobytes() == want.tobytes():
-        return
-    for name in want.dtype.names:
-        a, b = got[name], want[name]
-        bad = np.nonzero((a.reshape(a.shape[0], -1).view(np.uint8) != b.reshape(b.shape[0], -1).view(np.uint8)).any(axis=1))[0]
-        if bad.size:
-            i = int(bad[0])
-            raise AssertionError(f"{what}: field {name!r} differs for {bad.size} of {want.shape[0]} rays; first {i}: got {got[i]}, want {want[i]}")
-    raise AssertionError(f"{what}: records differ in padding")
-
-
-def same_frame(got, want_rgba, what):
-    want = want_rgba.reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere((got != want).any(axis=2))
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.shape[0] * got.shape[1]} pixels differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
+world = gs.world_fixture(World)
 
 
 # ---- 1. rules off ----
@@ -428,15 +366,7 @@ def test_update_changes_the_thresholds(world, oracle):
 def test_cli_interior_key(world, tmp_path):
     gpu = world.gpu
     gw = 0.5
-    hp, cp, outp = str(tmp_path / "h.ppm"), str(tmp_path / "c.png"), str(tmp_path / "frame.png")
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
-    text = (f"resolution 40 30\nhfov 150\nhang -50\nvang 112\npos {20.0 * gw:.17g} {-20.0 * gw:.17g} {7.5 * gw:.17g}\n"
-            f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-            f"projection spherical\nheightmap {hp}\ncolormap {cp}\noutput {outp}\n")
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    cfgp = tmp_path / "c.txt"
-    cfgp.write_text(text + "interior on\n")
+    cfgp, text, outp = gs.cli_config(gpu, world, tmp_path, gw, True, "interior on\n", proj=2)
     cfg = gpu.Config().consume_file(str(cfgp))
     assert cfg.interior() is True
     scene = cfg.create_scene()
@@ -446,11 +376,10 @@ def test_cli_interior_key(world, tmp_path):
     cfg.close()
     _rays, replayed = world.interior_case(gw, 2, 0)
     same_frame(want, replayed["rgba"], "the config's camera is the tests' spherical inside camera")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "interior on\n" in r.stdout and "under the interior rule" in r.stdout
     assert open(outp, "rb").read() == gpu.png_encode(want) != gpu.png_encode(plain)
     # ... ignored, with a warning, together with antialias > 1
     cfgp.write_text(text + "interior on\nantialias 2\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "WARNING: interior is ignored with antialias > 1" in r.stderr
+    r = gs.run_hmap(gpu, cfgp)
+    assert "WARNING: interior is ignored with antialias > 1" in r.stderr

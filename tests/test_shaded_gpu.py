@@ -3,84 +3,30 @@ tests/shade_replay.py, the definition in numpy, which tests/test_shaded_cpu.py p
 scalar loop and to a ramp's analytic normal; one test pins the kernels to hmrm_trace_rays records and the device's own
 threshold table without the replay's march.  Map, grid widths and cameras are those of tests/segment_cases.py at 40 x 30
 unless said otherwise, shadow step_dist 0.3 * grid width, ambient 96."""
-import contextlib
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import lit_replay as lr
 import ray_replay
 import segment_cases as sc
 import segment_replay as sr
 import shade_cases as shc
 import shade_replay as shr
+from gpu_support import KERNEL_VARIANTS, PROJ_IDS, SAMPLINGS, env, gpu, kernel_variant, same_frame, samplings_of
 from segment_cases import BG, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W
 from shade_cases import AMBIENT, SUNS
 
 pytestmark = pytest.mark.gpu
 
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
-SAMPLINGS = (0, 1, 2)
-PROJ_IDS = ["persp", "sph", "ortho"]
 MODES = ((True, True), (True, False))  # (diffuse, shadows): HMRM_SHADE_DIFFUSE, HMRM_SHADE_DIFFUSE | HMRM_SHADE_NO_SHADOWS
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
+class World(gs.Scenes, shc.Replays):
+    pass
 
 
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def samplings_of(variant):
-    return (0,) if variant == "rec" else SAMPLINGS  # (the record kernel applies to nearest sampling only)
-
-
-class World(shc.Replays):
-    def __init__(self, gpu, oracle):
-        super().__init__(gpu, oracle)
-        self.gpu = gpu
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
-
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_frame(got, want_rgba, what):
-    want = want_rgba.reshape(got.shape)
-    if got.tobytes() != want.tobytes():
-        bad = np.argwhere((got != want).any(axis=2))
-        y, x = bad[0]
-        raise AssertionError(f"{what}: {bad.shape[0]} of {got.shape[0] * got.shape[1]} pixels differ; first ({x}, {y}): got {got[y, x]}, want {want[y, x]}")
+world = gs.world_fixture(World)
 
 
 def sun_of(gpu, gw, direction, **kw):
@@ -381,31 +327,21 @@ def test_shaded_frame_is_trace_rays_plus_numpy_weights(world, proj, variant):
 # ---- 11. CLI ----
 def test_cli_shading_key(world, tmp_path):
     gpu, gw = world.gpu, 0.5
-    hp, cp, outp = str(tmp_path / "h.ppm"), str(tmp_path / "c.png"), str(tmp_path / "frame.png")
-    gpu.write_ppm(hp, world.rgb)
-    gpu.write_png(cp, world.cmap)
-    text = (f"resolution 40 30\nhfov 80\nhang -50\nvang 112\npos {-6.0 * gw:.17g} {8.0 * gw:.17g} {14.0 * gw:.17g}\n"
-            f"min_height 0.0\nmax_height {8.0 * gw:.17g}\ngrid_width {gw:.17g}\nstep_dist {0.2 * gw:.17g}\nbg_color 12 34 56\ncycle 1\n"
-            f"projection perspective\nheightmap {hp}\ncolormap {cp}\noutput {outp}\n")
     keys = f"sun_dir 0.6 0.5 0.35\nshadow_ambient {AMBIENT}\nshadow_step_dist {0.3 * gw:.17g}\nshading on\n"
-    exe = os.path.join(os.path.dirname(gpu.LIB_PATH), "hmap")
-    cfgp = tmp_path / "c.txt"
-    cfgp.write_text(text + keys)
+    cfgp, text, outp = gs.cli_config(gpu, world, tmp_path, gw, extra=keys)
     cfg = gpu.Config().consume_file(str(cfgp))
     assert cfg.shading() is True and cfg.shadows() is False
     cfg.close()
     bare = world.shaded(gw, 1, 0, SUNS[0], True, False)["rgba"].reshape(30, 40, 4)
     full = world.shaded(gw, 1, 0, SUNS[0], True, True)["rgba"].reshape(30, 40, 4)
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "shading on\n" in r.stdout and "with sun shading in" in r.stdout
     assert open(outp, "rb").read() == gpu.png_encode(np.ascontiguousarray(bare))
     cfgp.write_text(text + keys + "shadows on\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    r = gs.run_hmap(gpu, cfgp)
     assert "with sun shading and sun shadows" in r.stdout
     assert open(outp, "rb").read() == gpu.png_encode(np.ascontiguousarray(full)) != gpu.png_encode(np.ascontiguousarray(bare))
     # ... ignored, with a warning, together with antialias > 1
     cfgp.write_text(text + keys + "antialias 2\n")
-    r = subprocess.run([exe, str(cfgp)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "WARNING: shading is ignored with antialias > 1" in r.stderr and "shadows is ignored" not in r.stderr
+    r = gs.run_hmap(gpu, cfgp)
+    assert "WARNING: shading is ignored with antialias > 1" in r.stderr and "shadows is ignored" not in r.stderr

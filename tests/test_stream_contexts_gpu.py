@@ -9,18 +9,12 @@ import numpy as np
 import pytest
 
 import scenes
+from gpu_support import gpu
 
 pytestmark = pytest.mark.gpu
 
 MAP = 64
 MAX_STREAM_CTX = 32  # api_internal.hpp kMaxStreamCtx
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
 
 
 @pytest.fixture()

@@ -3,67 +3,34 @@ through the march kernels, every record compared BYTEWISE -- against the C oracl
 from oracle.render(per_pixel=True), point and cell from steps - 1 sequential adds), against tests/ray_replay.py (pinned
 to the oracle by tests/test_trace_rays_cpu.py) for rays no camera makes.  One 64 x 48 map (not square, not a multiple of
 16, alpha-0 texels, zero-height cells) at grid widths 1.0, 0.5 and 0.05: one kernel instantiation family each."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import ray_replay
-import scenes
+import segment_cases as sc
+from gpu_support import KERNEL_VARIANTS, PROJ_IDS, SAMPLINGS, env, gpu, kernel_variant, same_records
+from segment_cases import BG, GRID_WIDTHS, GW_IDS, MAP_H, MAP_W
 
 pytestmark = pytest.mark.gpu
 
-MAP_W, MAP_H = 64, 48
-GRID_WIDTHS = (1.0, 0.5, 0.05)  # GWM 0, 1, 2
-KERNEL_VARIANTS = ("leap", "group", "simple", "rec")
-SAMPLINGS = (0, 1, 2)
-BG = (12, 34, 56)
 MIXED_N = 3637  # not a multiple of 64
 
 
-@contextlib.contextmanager
-def env(**kw):
-    """Temporarily set environment knobs (the Python wrappers make a live scene re-read them)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-def kernel_variant(name):
-    return env(HMRM_KERNEL=name)
-
-
-def maps():
-    rgb, cmap = scenes.small_maps(MAP_W, MAP_H, 31)
-    rgb[5:9, 40:47] = 0  # zero-height cells
-    return rgb, cmap
-
-
-class World:
+class World(gs.Scenes, gs.Maps):
     """The scenes (one per grid width), and the oracle's rays and expected records per (grid width, projection, camera,
     sampling), computed once and never modified."""
 
     def __init__(self, gpu, oracle):
-        self.gpu, self.oracle = gpu, oracle
-        self.rgb, self.cmap = maps()
-        self.params = {gw: gpu.SceneParams.make(0.0, 8.0 * gw, grid_width=gw) for gw in GRID_WIDTHS}
-        self.heights = {gw: oracle.update_heightmap(self.rgb, p) for gw, p in self.params.items()}
-        self.scenes = {gw: gpu.Scene(self.rgb, self.cmap, p) for gw, p in self.params.items()}
+        super().__init__(gpu, oracle)
         self._cache = {}
 
     def camera(self, gw, proj, inside, sampling=0, width=40, height=30):
-        deg = self.gpu.degrees_to_rads
-        pos = (20.0 * gw, -20.0 * gw, 7.5 * gw) if inside else (-6.0 * gw, 8.0 * gw, 14.0 * gw)
-        return self.gpu.Camera.make(width=width, height=height, projection=proj, hfov=deg(150 if proj == 2 else 80), hang=deg(-50),
-                                    vang=deg(112), pos=pos, ortho_width=(0.02 if inside else 1.3) * gw, step_dist=0.2 * gw, bg=BG, sampling=sampling)
+        """segment_cases' camera, but the inside orthographic plane is 0.02 cells wide, not 3."""
+        cam = sc.camera(self.gpu, gw, proj, inside, sampling, width, height)
+        if inside:
+            cam.ortho_width = 0.02 * gw
+        return cam
 
     def camera_case(self, gw, proj, inside, sampling):
         """-> (rays n x 6, expected records, camera)"""
@@ -93,41 +60,14 @@ class World:
             self._cache[key] = (rays, want)
         return self._cache[key]
 
-    def close(self):
-        for s in self.scenes.values():
-            s.close()
 
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
-
-
-@pytest.fixture(scope="module")
-def world(gpu, oracle):
-    w = World(gpu, oracle)
-    yield w
-    w.close()
-
-
-def same_records(got, want, what):
-    if got.tobytes() == want.tobytes():
-        return
-    for name in want.dtype.names:
-        a, b = got[name], want[name]
-        bad = np.nonzero((a.reshape(a.shape[0], -1).view(np.uint8) != b.reshape(b.shape[0], -1).view(np.uint8)).any(axis=1))[0]
-        if bad.size:
-            i = int(bad[0])
-            raise AssertionError(f"{what}: field {name!r} differs for {bad.size} of {want.shape[0]} rays; first {i}: got {got[i]}, want {want[i]}")
-    raise AssertionError(f"{what}: records differ in padding")
+world = gs.world_fixture(World)
 
 
 # ---- 1. camera-ray parity with the oracle ----
-@pytest.mark.parametrize("gw", GRID_WIDTHS, ids=["gw1", "gw0.5", "gw0.05"])
+@pytest.mark.parametrize("gw", GRID_WIDTHS, ids=GW_IDS)
 @pytest.mark.parametrize("variant", KERNEL_VARIANTS)
-@pytest.mark.parametrize("proj", [1, 2, 3], ids=["persp", "sph", "ortho"])
+@pytest.mark.parametrize("proj", [1, 2, 3], ids=PROJ_IDS)
 def test_camera_rays_equal_the_oracle(world, proj, variant, gw):
     scene = world.scenes[gw]
     with kernel_variant(variant):
@@ -229,7 +169,7 @@ def odd(world, oracle):
     return out
 
 
-@pytest.mark.parametrize("gw", GRID_WIDTHS, ids=["gw1", "gw0.5", "gw0.05"])
+@pytest.mark.parametrize("gw", GRID_WIDTHS, ids=GW_IDS)
 @pytest.mark.parametrize("variant", KERNEL_VARIANTS)
 def test_rays_no_camera_makes(world, odd, variant, gw):
     rays, want = odd[gw]
@@ -394,7 +334,7 @@ def test_update_changes_the_thresholds(world, oracle):
 
 
 # ---- 9. pick ----
-@pytest.mark.parametrize("proj", [1, 2, 3], ids=["persp", "sph", "ortho"])
+@pytest.mark.parametrize("proj", [1, 2, 3], ids=PROJ_IDS)
 def test_pick(world, oracle, proj):
     gw = 0.5
     scene = world.scenes[gw]

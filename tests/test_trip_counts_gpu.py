@@ -12,6 +12,8 @@ import sys
 
 import pytest
 
+from gpu_support import gpu
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trip_counts.json")
@@ -71,13 +73,6 @@ def count(hmrm, name):
         finally:
             scene.close()
     return {k: int(getattr(st, k)) for k in FIELDS}
-
-
-@pytest.fixture(scope="module")
-def gpu(hmrm):
-    assert hmrm.device_count() >= 1, "no GPU visible: these tests must run on the MI355X box"
-    hmrm.set_device(0)
-    return hmrm
 
 
 @pytest.fixture(scope="module")
