@@ -445,6 +445,10 @@ struct PixelId {
 	int tile_y; // tile row of the launch this workgroup renders (wave-uniform)
 	bool live;
 };
+// The row map of a launch that renders the whole frame in frame order: no bands, no launch order, no calibration records.
+__host__ __device__ __forceinline__ RowMap whole_frame_rows(const DevFrame &f) {
+	return RowMap{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+}
 // Frame row of local row `lrow` of the launch's output (contiguous strip or cyclic bands).
 __device__ __forceinline__ int frame_row_of(const RowMap &rows, int lrow) {
 	if (rows.band_rows > 0) {

@@ -2,7 +2,8 @@
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
 // render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
 // counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip, render_lit_sum.hip, render_baked.hip
-// and render_baked_aa.hip, each with a __global__ kernel of its own.
+// and render_baked_aa.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
+// switch and derived constant with its reasons.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
 // the reference loop main/hmap.cpp:978-1058; two bit-preserving restructurings:
@@ -50,6 +51,7 @@
 #include "leap_diag.hpp"
 #include "launch_common.hpp"
 #include "march_dispatch.hpp"
+#include "march_family.hpp"
 #include "render.hpp"
 
 #pragma clang fp contract(off)
@@ -58,25 +60,8 @@ namespace hmrm {
 
 namespace {
 
-#ifndef HMRM_GROUP
-#define HMRM_GROUP 4
-#endif
-constexpr int kGroup = HMRM_GROUP; // U: positions per speculative group of the production kernel
-// ... and of the plain-groups instantiation (LEAP = false: no leaps, every height load of the reference is executed --
-// what the scene's probe picks on content that admits no jumps, and the kernel SURVEY 8(d)'s byte roofline is defined
-// for).  That kernel waits for its gathers 70 % of the time at 17 % VALU busy (profiles/r05_C3_group_rocprof.txt): more
-// loads in flight per lane pay until the registers cost resident waves -- C3 2.61 ms with 4, 2.37 with 6, 2.57 with 8
-// (profiles/r05_raw/group_len_ab.txt).  Deciding the hit test from a float copy of the table, doubles only where that is
-// unsafe, halves the bytes and changes little: the gathers are bound by lanes, not bytes (r05_experiments.txt section 4).
-#ifndef HMRM_GROUP_PLAIN
-#define HMRM_GROUP_PLAIN 6
-#endif
-constexpr int kGroupPlain = HMRM_GROUP_PLAIN;
-// ... and of the record kernel; the most refusals in a row its back-off counts (attempts every 2^n-th trip at most)
-#ifndef HMRM_GROUP_REC
-#define HMRM_GROUP_REC 6
-#endif
-constexpr int kGroupRec = HMRM_GROUP_REC;
+// (the group lengths kGroup, kGroupPlain and kGroupRec, and the geometry frames' A/B switches: march_family.hpp, beside U)
+// the most refusals in a row the record kernel's back-off counts (attempts every 2^n-th trip at most)
 #ifndef HMRM_REC_BACKOFF
 #define HMRM_REC_BACKOFF 6
 #endif
@@ -97,17 +82,6 @@ constexpr double kUpRatio = HMRM_UP_RATIO; // see the level policy in k_render_f
 #define HMRM_EARLY_LOAD 1
 #endif
 constexpr bool kEarlyLoad = HMRM_EARLY_LOAD != 0;
-// Geometry frames (GEOM below), for A/B builds of render_geometry.hip: HMRM_GEOM_CHAIN 1 keeps the hit point the way the ray
-// batches do (a select chain over the group's positions into three doubles held across the loop) instead of KEEP_P's re-add;
-// HMRM_GEOM_CARRY 0 reads the level state off the level at every attempt instead of carrying it.  The defaults are what the
-// registers decided: DESIGN.md 5.16.
-#ifndef HMRM_GEOM_CHAIN
-#define HMRM_GEOM_CHAIN 0
-#endif
-#ifndef HMRM_GEOM_CARRY
-#define HMRM_GEOM_CARRY 0
-#endif
-constexpr bool kGeomChain = HMRM_GEOM_CHAIN != 0, kGeomCarry = HMRM_GEOM_CARRY != 0;
 
 // ---- bilinear quality mode (HMRM_BILINEAR; a build-side addition, not in the reference) ----
 // Same definition, operation for operation, as oracle/hmrm_oracle.c "bilinear quality mode":
@@ -202,115 +176,23 @@ __device__ __forceinline__ DevRay cell_ray_of(const CellRules &c, const DevFrame
 #else
 #define HMRM_OCCUPANCY_ATTR
 #endif
-// SAMP: 0 nearest cell (the reference), 1 bilinear quality mode, 2 nearest cell with float thresholds
-// (`thr` then points at the float copy of the table).
-// One wave's 8 x 8 pixels: wave `wave` of the workgroup-sized tile (tile_x, grid row gy).  Returns the tile row rendered
-// (-1: the grid row does not exist).  k_render_fast calls it with the tile = blockIdx (one tile per workgroup); round 4's
-// persistent-tile experiment (resident waves pulling tiles from queue heads) called it in a loop and was 1.4-1.9 x slower:
-// profiles/r04_experiments.txt section 1, code at commit 80527e9.
-// AA: the antialiased epilogue (device_common.hpp store_box_filtered; instantiated in render_fast_aa.hip and, with LIT and / or
-// SHADE, in the three render_*_aa.hip units of march_lit_aa.hpp).  It comes after the LIT / SHADE epilogues -- a sample is lit and
-// shaded on its own, then filtered -- and outside `if (pid.live)`: every lane of the wave reaches it together, whatever the
-// lanes did in the LIT loop, whose ballot only the live lanes take part in.
-// PROJ 4 (instantiated in render_rays.hip only): a batch of caller-supplied rays (hmrm_trace_rays; frame.hpp RayBatch) -- the
-// lane's ray is loaded from `batch`, not made from a camera, and instead of a pixel the lane writes its hmrm_ray_hit record,
-// which wants distance()'s value for misses too and the ray's exact step count: the two things the instrumented
-// instantiation computes (COUNT below), without its diagnostics or its wave-wide counters.  `out` is not used then.
-// SEG (instantiated in render_segments.hip and render_interior.hip only; hmrm_trace_segments, hmrm_render_interior): the two
-// segment rules of frame.hpp SegRules -- a ray whose origin is strictly inside the box enters it at d = +0.0 instead of
-// missing, and a ray ends after its own number of height loads (HMRM_RAY_END) -- written like PROJ == 4, as `if constexpr`
-// statements beside the others' own.  The loop needs nothing new: it is position based and each lane has its budget.
-// LIT (instantiated in render_lit.hip only; hmrm_render_lit, frame.hpp SunRules; implies SEG): sun shadows.  "Entry, then the
-// march loop" runs a second time for the wave: a lane whose primary ray hit keeps its pixel and marches its shadow ray -- a
-// segment ray under the interior rule from (P.x, P.y, t) towards the sun -- through the SAME loop; the other lanes sit the
-// second pass out.  Nothing per pixel goes through memory between the two.  Again `if constexpr` statements beside the
-// others' own and a per-lane struct that is empty unless LIT (device_common.hpp LitState).
-// SHADE (instantiated in render_shaded.hip and render_lit_shaded.hip only; hmrm_render_shaded; implies SEG): diffuse sun
-// shading.  An epilogue: a lane whose primary ray hit -- and, LIT, whose shadow ray did not -- computes its diffuse level from
-// the threshold table (device_common.hpp diffuse_level) and keeps a weighted pixel; `sun` brings the direction and the
-// ambient level.  Across the loop it keeps the hit's cell index (nearest-cell modes: hcell, which every family keeps for the
-// colour) or the hit point (bilinear: LitState's, or hqx / hqy, which the leap kernels keep for the colour too).  (LIT:
-// computing the level at the phase switch instead and carrying it through the shadow march in the saved pixel's alpha byte
-// holds no cell index, but the compiler then keeps more across the march, not less: DESIGN.md 5.12.)
-// PROJ 5 (instantiated in render_cells.hip only; hmrm_cell_map, frame.hpp CellRules; needs SEG): a cell map.  The "frame" is the
-// rect, a lane owns one map cell, a wave 8 x 8 of them; the lane's ray is made from the cell index and the cell's own entry of
-// `thr` (device_common.hpp cell_ray), enters the loop like a shadow ray (shadow_entry: the interior rule is always on), and the
-// epilogue stores ONE BYTE -- the ray's status, or the weight of SHADE's arithmetic -- through `out`, which points at bytes then
-// (`out_stride_px` counts bytes).  HMRM_MAP_NO_SHADOWS gives every lane d = inf: the wave skips the loop.  Again `if constexpr`
-// statements beside the others' own; the ray is made again in the epilogue rather than held across the march.
-// SUM (instantiated in render_cell_sums.hip only; hmrm_cell_map_sum, frame.hpp CellSums; needs PROJ 5): an accumulated cell map.
-// LIT's "entry, then the march loop, once more" generalised: the wave runs it once per target of a wave-uniform list, the lane
-// folds each pass's value -- k_cell_map's byte for that target, or 1 for a ray that did not hit -- into a register, and the
-// epilogue stores ONE 16-bit WORD through `out` (`out_stride_px` counts bytes).  Capped rays are counted per pass.
-// GEOM (instantiated in render_geometry.hip only; hmrm_render_geometry, frame.hpp GeomPlanes; implies SEG): a geometry frame.  An
-// epilogue: beside the pixel the lane stores its hit cell, the distance from its ray's origin to int_point and the surface
-// gradient SHADE takes its level from, each through a pointer of `geo` that may be null -- and so may `out`: the colour is not
-// fetched then.  A lane that hit leaves the loop with int_point in x, y, z (KEEP_P's re-add, with z stepped like x and y) and
-// with hcell; the ray's origin is made again in the epilogue.  Again `if constexpr` statements beside the others' own.
-// LSUM (instantiated in render_lit_sum.hip only; hmrm_render_lit_sum, frame.hpp LightSum; needs LIT, without SHADE -- whether the
-// weights are diffuse is a run-time flag): an accumulated lit frame, LIT and SUM joined.  The primary march runs once; then the
-// wave runs "entry, then the march loop" once per direction of a wave-uniform list for the lanes whose primary ray hit, each of
-// which folds the pass's weight -- hmrm_render_shaded's for that direction -- into a register; the epilogue stores ONE pixel at
-// the weight sum / (255 n) through `out` and / or the sum as ONE 16-bit word through `lsum.light`, either of which may be null.
-// Across the passes a lane keeps LitState's hit point, hcell, the sum and (wave-uniform) the pass; the gradient and the lane's
-// pixel are made again.  With HMRM_SHADE_NO_SHADOWS no shadow pass runs: the n levels are computed behind the primary march.
-// Termination: every pass is the march loop with a budget of its own, min(step cap, the shadow rays' limit) <= the step cap, and
-// the outer loop runs at most 1 + n times -- the primary pass and one per direction, the pass number only ever grows.
-// BAKED (instantiated in render_baked.hip and render_baked_aa.hip only; hmrm_render_baked, frame.hpp BakedLight; implies SEG): a
-// baked-light frame.  An epilogue: a lane whose primary ray hit fetches its colour behind the loop, as GEOM and LSUM do, loads
-// its light from the scene's plane -- one 16-bit load at hcell, or four at the bilinear mode's neighbours of the kept hit point,
-// mixed like the colour -- and keeps the pixel at that weight (device_common.hpp shade_baked).  With AA the weighted sample goes
-// to the box filter.  Again `if constexpr` statements beside the others' own.
-template <int PROJ, bool STATS, int GWM, int LEAP, int SAMP, bool AA, bool SEG = false, bool LIT = false, bool SHADE = false,
-          bool SUM = false, bool GEOM = false, bool LSUM = false, bool BAKED = false>
+// One wave's 8 x 8 pixels (cells; or 64 batch rays): wave `wave` of the workgroup-sized tile (tile_x, grid row gy), for the family
+// F = Family<TAG, PROJ, GWM, LEAP, SAMP> (march_family.hpp: what each switch and derived constant means) with the tag's arguments
+// `a`.  Returns the tile row rendered (-1: the grid row does not exist).  k_render_fast calls it with the tile = blockIdx (one tile
+// per workgroup); round 4's persistent-tile experiment (resident waves pulling tiles from queue heads) called it in a loop and was
+// 1.4-1.9 x slower: profiles/r04_experiments.txt section 1, code at commit 80527e9.
+// Every feature is written as `if constexpr` statements beside the others' own, so that the families without it keep their
+// instructions.
+template <class F, class... ARGS>
 __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                 const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
                                                 int64_t out_stride_px, int tiles_y, const StatsOut &st, int tile_x, unsigned gy,
-                                                int wave, int lane, const RayBatch &batch, const SegRules &seg = SegRules{},
-                                                const SunRules &sun = SunRules{}, const CellRules &cells = CellRules{},
-                                                const CellSums &sums = CellSums{}, const GeomPlanes &geo = GeomPlanes{},
-                                                const LightSum &lsum = LightSum{}, const BakedLight &baked = BakedLight{}) {
-	constexpr bool CELLS = PROJ == 5;
-	static_assert(!BAKED || (SEG && !CELLS && PROJ != 4 && !STATS && !LIT && !SHADE && !GEOM), "baked-light frames: plain frames under the segment rules");
-	static_assert(!LSUM || (LIT && !SHADE && !AA), "accumulated lit frames: the lit kernels' marches, the weights by a run-time flag");
-	static_assert(!GEOM || (SEG && !CELLS && PROJ != 4 && !STATS && !AA && !LIT && !SHADE), "geometry frames: plain frames under the segment rules");
-	static_assert(!SUM || CELLS, "accumulated cell maps: the cell kernels' march, once per target");
-	static_assert(!CELLS || (SEG && !STATS && !AA && !LIT && !SHADE), "cell maps: segment rays, one byte per cell");
-	static_assert(!LIT || (SEG && PROJ != 4), "sun shadows: frames, under the segment rules");
-	static_assert(!SHADE || (SEG && PROJ != 4), "sun shading: frames, under the segment rules");
-	constexpr bool BILINEAR = SAMP == 1, F32 = SAMP == 2;
-	// KEEP_P: a lane that hit leaves the loop with its hit point in x, y (LIT: and t in z).  SHADE with bilinear sampling wants
-	// the point too; without LIT the plain groups take it that way, the leap kernels keep the hit's exact cell coordinates
-	// instead (KEEP_Q) -- each the cheaper of the two in registers for its family, DESIGN.md 5.12 -- and from them they also
-	// mix the pixel behind the loop (DEFER), shaded or not.
-	// GEOM wants the whole point, in every sampling mode: KEEP_P with z stepped like x and y (no threshold is kept), which holds
-	// nothing across the loop -- RAYS' select chain keeps three doubles more.
-	constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && LEAP != 0 && !GEOM;
-	// BAKED with bilinear sampling wants the point like SHADE: KEEP_Q in the leap kernels, KEEP_P in the plain groups.
-	constexpr bool KEEP_P = LIT || ((SHADE || BAKED) && BILINEAR && !KEEP_Q) || (GEOM && !kGeomChain);
-	constexpr bool CHAIN = PROJ == 4 || (GEOM && kGeomChain); // (the hit point by RAYS' select chain: hx, hy, hz)
-	constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
-	// DEFER: a hit lane's colour is fetched behind the march loop, from the hit cell it leaves the loop with (hcell below; the
-	// bilinear mode: and from the hit point, KEEP_P / KEEP_Q), not inside it.  Two exceptions keep the in-loop form.  The record
-	// kernels of the interior and the shaded frames without shadow rays: two of them sit on the scalar registers' limit and the
-	// epilogue's load costs them a spill slot (profiles/r09_registers.txt).  And the bilinear mode of the plain groups: leaving
-	// the loop with the hit point made that kernel 20 % SLOWER where it was measured (0.263 -> 0.316 ms, profiles/r09_ab.txt).
-	// (GEOM: always behind the loop -- a null colour target skips the fetch there, a scalar branch)
-	// (LSUM: always behind the loop, like GEOM -- and behind every march: the hit point outlives them)
-	// (BAKED: behind the loop too -- the light is loaded beside the colour, from the same cell or point -- except in its record
-	// kernels, which keep the interior family's in-loop fetch: deferred, the orthographic one with power-of-two grid widths took
-	// 36 bytes of scratch)
-	constexpr bool DEFER = GEOM || LSUM || (BAKED && LEAP != 2) || (!CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0));
-	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
-	static_assert(!SEG || !STATS, "segment rules: production kernels only");
-	static_assert(!SEG || !AA || LIT || SHADE || BAKED, "segment rules: antialiased for the sun-lit and baked-light frames only");
-	constexpr bool REC = LEAP == 2;                     // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
-	// CARRY: a ray holds its level state in a register (see the leap state below).  The cell maps, the sun shadows, the ray batches
-	// and the shaded record kernels sit on a register granule: a register more would cost them a resident wave per SIMD -- as it
-	// would six of the geometry kernels (general grid widths: 73 against 71 vector registers, 81 against 80 with window records).
-	constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !RAYS && !((SHADE || BAKED) && REC) && !(GEOM && !kGeomCarry);
-	constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
-	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
+                                                int wave, int lane, const ARGS &...args) {
+	const typename F::Args a{args...}; // (the tag's arguments under their names: references, nothing is copied)
+	constexpr int PROJ = F::PROJ, GWM = F::GWM, LEAP = F::LEAP, SAMP = F::SAMP, U = F::U;
+	constexpr bool STATS = F::STATS, AA = F::AA, SEG = F::SEG, LIT = F::LIT, SHADE = F::SHADE, SUM = F::SUM, GEOM = F::GEOM, LSUM = F::LSUM;
+	constexpr bool BAKED = F::BAKED, CELLS = F::CELLS, RAYS = F::RAYS, COUNT = F::COUNT, BILINEAR = F::BILINEAR, F32 = F::F32, REC = F::REC;
+	constexpr bool KEEP_Q = F::KEEP_Q, KEEP_P = F::KEEP_P, CHAIN = F::CHAIN, DEFER = F::DEFER, CARRY = F::CARRY;
 	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
 	const float *__restrict__ mip = BILINEAR ? f.mipbuf_bil : f.mipbuf; // the pyramid this sampling mode leaps on
 	PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, lane);
@@ -319,7 +201,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	int64_t ray_index = 0;
 	if constexpr (RAYS) {
 		ray_index = (int64_t)pid.py * kBatchW + pid.px;
-		pid.live = pid.live && ray_index < batch.n;
+		pid.live = pid.live && ray_index < a.batch.n;
 	}
 	LoopDiag<STATS> diag; // (empty unless STATS: leap_diag.hpp)
 	diag.start();
@@ -331,11 +213,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 
 	if (pid.live) {
 		DevRay ray = make_ray<PROJ>(f, pid.px, pid.py);
-		if constexpr (RAYS) ray = batch_ray(batch, ray_index); // (make_ray<4>'s value is dead)
-		if constexpr (CELLS) ray = cell_ray_of<SAMP>(cells, f, thr, pid.px, pid.py); // (make_ray<5>'s too)
+		if constexpr (RAYS) ray = batch_ray(a.batch, ray_index); // (make_ray<4>'s value is dead)
+		if constexpr (CELLS) ray = cell_ray_of<SAMP>(a.cells, f, thr, pid.px, pid.py); // (make_ray<5>'s too)
 		if constexpr (SUM) { // (... towards the list's first target, not CellRules' own)
-			sm.rules = cells;
-			sum_target(sums, 0, &sm.rules);
+			sm.rules = a.cells;
+			sum_target(a.sums, 0, &sm.rules);
 			ray = cell_ray_of<SAMP>(sm.rules, f, thr, pid.px, pid.py);
 		}
 		// most rays of a frame never touch the box: prove the miss cheaply where possible (the instrumented
@@ -344,7 +226,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		// parity tests compare its d with the oracle's bit for bit)
 		double d = __builtin_huge_val();
 		if constexpr (CELLS) { // (most origins are strictly inside: no slab test unless one is not; no ray at all without shadows)
-			if ((cells.flags & kMapNoShadows) == 0u) d = shadow_entry(ray, f);
+			if ((a.cells.flags & kMapNoShadows) == 0u) d = shadow_entry(ray, f);
 		} else
 		if (COUNT || !slab_points_away<PROJ>(ray, f)) {
 			const int verdict = slab_classify(ray, f, !COUNT, &d);
@@ -355,8 +237,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		if constexpr (SEG) {
 			sg.d_record = d; // (a record keeps distance()'s own value, not the d that was used)
 			if constexpr (!CELLS) // (shadow_entry has applied the rule)
-			if (seg.interior != 0u && origin_strictly_inside(ray, f)) d = 0.0; // as if distance() had returned +0.0
-			sg.budget = segment_budget(seg, RAYS ? ray_index : 0, f.step_cap, &sg.ends);
+			if (a.seg.interior != 0u && origin_strictly_inside(ray, f)) d = 0.0; // as if distance() had returned +0.0
+			sg.budget = segment_budget(a.seg, RAYS ? ray_index : 0, f.step_cap, &sg.ends);
 		}
 
 		uint32_t rgba = 0;
@@ -384,7 +266,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		// 255 or, HMRM_SHADE_DIFFUSE, that of the level of the primary hit.  (The hit cell, or the hit point, goes through an empty
 		// statement: the gradient made from it does not depend on the direction, and the compiler would otherwise make it once,
 		// before the first pass, and hold it in vector registers across every march -- the lesson of SUM's cell.)
-		[[maybe_unused]] auto sum_weight = [&](bool shadowed, const double (&s)[3]) -> uint32_t {
+		[[maybe_unused]] auto sum_weight = [&](const SunRules &sun, const LightSum &lsum, bool shadowed, const double (&s)[3]) -> uint32_t {
 			uint32_t w = shadowed ? sun.ambient : 255u;
 			if constexpr (LSUM) {
 				if ((lsum.flags & kShadeDiffuse) != 0u && !shadowed) {
@@ -414,7 +296,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				y = y + f.nudge * ray.dy;
 				z = z + f.nudge * ray.dz;
 				double step_dist = f.step_dist;
-				if constexpr (LIT) step_dist = lt.phase ? sun.step_dist : step_dist; // (a shadow ray's own)
+				if constexpr (LIT) step_dist = lt.phase ? a.sun.step_dist : step_dist; // (a shadow ray's own)
 				const double sx = step_dist * ray.dx; // hmap.cpp:1037, loop invariant
 				const double sy = step_dist * ray.dy;
 				const double sz = step_dist * ray.dz;
@@ -934,30 +816,30 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					if (__builtin_amdgcn_ballot_w64(real_hit) != 0ull) {
 						lt.phase = 1;
 						lt.dz = ray.dz;
-						if ((lsum.flags & kShadeNoShadows) != 0u) { // (no march: the n weights of the lanes that hit, here)
+						if ((a.lsum.flags & kShadeNoShadows) != 0u) { // (no march: the n weights of the lanes that hit, here)
 #pragma unroll 1
-							for (int k = 0; k < lsum.n; ++k) {
-								sum_direction(lsum, k, sdir);
-								if (lt.primary_hit) lm.acc += sum_weight(false, sdir);
+							for (int k = 0; k < a.lsum.n; ++k) {
+								sum_direction(a.lsum, k, sdir);
+								if (lt.primary_hit) lm.acc += sum_weight(a.sun, a.lsum, false, sdir);
 							}
 						} else {
 							again = true;
 						}
 					}
 				} else {
-					sum_direction(lsum, lm.k, sdir); // (loaded again behind the march rather than held across it)
-					if (lt.primary_hit) lm.acc += sum_weight(real_hit, sdir);
+					sum_direction(a.lsum, lm.k, sdir); // (loaded again behind the march rather than held across it)
+					if (lt.primary_hit) lm.acc += sum_weight(a.sun, a.lsum, real_hit, sdir);
 					++lm.k;
-					again = lm.k < lsum.n;
+					again = lm.k < a.lsum.n;
 				}
 				if (again) {
-					sum_direction(lsum, lm.k, sdir);
+					sum_direction(a.lsum, lm.k, sdir);
 					ray.px = lt.hx; ray.py = lt.hy; ray.pz = lt.t; // (shadow_ray's, towards direction k)
 					ray.dx = sdir[0]; ray.dy = sdir[1]; ray.dz = sdir[2];
 					d = __builtin_huge_val();
 					if (lt.primary_hit) {
 						d = shadow_entry(ray, f);
-						sg.budget = segment_budget(SegRules{nullptr, sun.max_steps, 1u}, 0, f.step_cap, &sg.ends);
+						sg.budget = segment_budget(SegRules{nullptr, a.sun.max_steps, 1u}, 0, f.step_cap, &sg.ends);
 					}
 					real_hit = false;
 				}
@@ -984,11 +866,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 						// (every lane takes the new ray -- a lane that keeps its old one would hold it in registers through the
 						// second march for nothing -- and only its dz, for the miss shade, is put aside)
 						lt.dz = ray.dz;
-						ray = shadow_ray(lt, sun);
+						ray = shadow_ray(lt, a.sun);
 						d = __builtin_huge_val();
 						if (real_hit) {
 							d = shadow_entry(ray, f);
-							sg.budget = segment_budget(SegRules{nullptr, sun.max_steps, 1u}, 0, f.step_cap, &sg.ends);
+							sg.budget = segment_budget(SegRules{nullptr, a.sun.max_steps, 1u}, 0, f.step_cap, &sg.ends);
 						}
 						real_hit = false;
 					}
@@ -1012,9 +894,9 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				sm.acc += capped ? 0x10000u : 0u; // (the sum is below 2^16: the passes the step cap stopped are counted above it)
 				my_cap = 0u;
 				uint32_t v = real_hit ? 0u : 1u;
-				if ((cells.flags & kMapWeight) != 0u) {
+				if ((a.cells.flags & kMapWeight) != 0u) {
 					uint32_t q = 0u;
-					if ((cells.flags & kMapDiffuse) != 0u && !real_hit) { // the level of the cell under its direction towards this target
+					if ((a.cells.flags & kMapDiffuse) != 0u && !real_hit) { // the level of the cell under its direction towards this target
 						const DevRay own = cell_ray_of<SAMP>(sm.rules, f, thr, spx, spy);
 						const double s[3] = {own.dx, own.dy, own.dz};
 						if constexpr (BILINEAR) {
@@ -1022,20 +904,20 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							cell_coords_of(own.px, own.py, qxc, qyc);
 							q = diffuse_level_bilinear(f, thr, bil_setup(qxc, qyc, f.map_w, f.map_h), s);
 						} else {
-							q = diffuse_level_nearest<F32>(f, thr, (unsigned)index_2d(cells.y0 + spy, f.map_w, cells.x0 + spx), s);
+							q = diffuse_level_nearest<F32>(f, thr, (unsigned)index_2d(a.cells.y0 + spy, f.map_w, a.cells.x0 + spx), s);
 						}
 					}
-					v = cell_weight(cells, real_hit, q);
+					v = cell_weight(a.cells, real_hit, q);
 				}
 				sm.acc += v;
 				++sm.k;
-				again = sm.k < sums.n;
+				again = sm.k < a.sums.n;
 				if (again) {
-					sum_target(sums, sm.k, &sm.rules);
+					sum_target(a.sums, sm.k, &sm.rules);
 					ray = cell_ray_of<SAMP>(sm.rules, f, thr, spx, spy);
 					d = __builtin_huge_val();
-					if ((cells.flags & kMapNoShadows) == 0u) d = shadow_entry(ray, f);
-					sg.budget = segment_budget(seg, 0, f.step_cap, &sg.ends);
+					if ((a.cells.flags & kMapNoShadows) == 0u) d = shadow_entry(ray, f);
+					sg.budget = segment_budget(a.seg, 0, f.step_cap, &sg.ends);
 					real_hit = false;
 				}
 			}
@@ -1057,7 +939,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					cell_coords_of(lt.hx, lt.hy, qxh, qyh);
 					lit_rgba = bilinear_pixel(qxh, qyh);
 				} else lit_rgba = shade_hit(f, cmap[hcell]);
-				rgba = shade_summed(lit_rgba, lm.acc & 0xffffu, (uint32_t)lsum.n);
+				rgba = shade_summed(lit_rgba, lm.acc & 0xffffu, (uint32_t)a.lsum.n);
 			}
 			ray.dz = lt.phase ? lt.dz : ray.dz; // (the primary ray's, for the miss shade)
 		} else
@@ -1066,18 +948,18 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				uint32_t lit_rgba = lt.rgba;
 				if constexpr (DEFER && !BILINEAR) lit_rgba = shade_hit(f, cmap[hcell]);
 				if constexpr (SHADE) { // ... at the weight of its diffuse level; a shadowed pixel keeps the ambient weight
-					uint32_t w = sun.ambient;
+					uint32_t w = a.sun.ambient;
 					if (!real_hit) {
 						if constexpr (BILINEAR) {
 							cell_coords_of(lt.hx, lt.hy, qxh, qyh);
-							w = shade_weight(sun.ambient, diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), sun.dir));
+							w = shade_weight(a.sun.ambient, diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), a.sun.dir));
 						} else {
-							w = shade_weight(sun.ambient, diffuse_level_nearest<F32>(f, thr, hcell, sun.dir));
+							w = shade_weight(a.sun.ambient, diffuse_level_nearest<F32>(f, thr, hcell, a.sun.dir));
 						}
 					}
 					rgba = shade_weighted(lit_rgba, w);
 				} else
-				rgba = real_hit ? shade_shadowed(lit_rgba, sun.ambient) : lit_rgba;
+				rgba = real_hit ? shade_shadowed(lit_rgba, a.sun.ambient) : lit_rgba;
 				real_hit = true;
 			}
 			ray.dz = lt.phase ? lt.dz : ray.dz; // (the primary ray's, for the miss shade)
@@ -1085,17 +967,17 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			if (real_hit) {
 				uint32_t q;
 				if constexpr (BILINEAR) {
-					q = diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), sun.dir);
-				} else q = diffuse_level_nearest<F32>(f, thr, hcell, sun.dir);
-				rgba = shade_weighted(rgba, shade_weight(sun.ambient, q));
+					q = diffuse_level_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h), a.sun.dir);
+				} else q = diffuse_level_nearest<F32>(f, thr, hcell, a.sun.dir);
+				rgba = shade_weighted(rgba, shade_weight(a.sun.ambient, q));
 			}
 		}
 		if constexpr (BAKED) { // (every hit pixel at the weight of its baked light; an alpha-0 hit cell's background too)
 			if (real_hit) {
 				uint32_t light;
-				if constexpr (BILINEAR) light = baked_light_bilinear(baked.plane, bil_setup(qxh, qyh, f.map_w, f.map_h));
-				else light = baked.plane[hcell];
-				rgba = shade_baked(rgba, light, baked.full_scale);
+				if constexpr (BILINEAR) light = baked_light_bilinear(a.baked.plane, bil_setup(qxh, qyh, f.map_w, f.map_h));
+				else light = a.baked.plane[hcell];
+				rgba = shade_baked(rgba, light, a.baked.full_scale);
 			}
 		}
 
@@ -1109,58 +991,56 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		}
 		// (row and pitch are below 2^31, api.cpp: one 32 x 32 -> 64-bit multiply-add)
 		if constexpr (LSUM) { // (the lane's pixel is made again from its number in the wave; each pointer test is a scalar branch)
-			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave,
-			                                      (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
 			if (out != nullptr) out[(uint64_t)(uint32_t)me.lrow * (uint32_t)out_stride_px + (uint32_t)me.px] = rgba;
-			if (lsum.light != nullptr) {
-				uint8_t *row = reinterpret_cast<uint8_t *>(lsum.light) + (uint64_t)(uint32_t)me.lrow * (uint64_t)lsum.light_stride;
+			if (a.lsum.light != nullptr) {
+				uint8_t *row = reinterpret_cast<uint8_t *>(a.lsum.light) + (uint64_t)(uint32_t)me.lrow * (uint64_t)a.lsum.light_stride;
 				reinterpret_cast<uint16_t *>(row)[(uint32_t)me.px] = real_hit ? (uint16_t)lm.acc : (uint16_t)0xffffu;
 			}
 		} else
 		if constexpr (SUM) { // (one 16-bit store per lane: hmrm.h fixes the alignment at 2 bytes, so a wave's row is not widened further)
-			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave,
-			                                      (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
 			uint8_t *row = reinterpret_cast<uint8_t *>(out) + (uint64_t)(uint32_t)me.lrow * (uint64_t)out_stride_px;
 			reinterpret_cast<uint16_t *>(row)[(uint32_t)me.px] = (uint16_t)sm.acc;
 		} else
 		if constexpr (CELLS) {
 			uint32_t v = real_hit ? 1u : (my_cap != 0u ? 2u : (sg.ended ? 3u : 0u)); // HMRM_RAY_*
-			if ((cells.flags & kMapWeight) != 0u) {
+			if ((a.cells.flags & kMapWeight) != 0u) {
 				uint32_t q = 0u;
-				if ((cells.flags & kMapDiffuse) != 0u && !real_hit) { // the level of the cell under its own direction
-					const DevRay own = cell_ray_of<SAMP>(cells, f, thr, pid.px, pid.py);
+				if ((a.cells.flags & kMapDiffuse) != 0u && !real_hit) { // the level of the cell under its own direction
+					const DevRay own = cell_ray_of<SAMP>(a.cells, f, thr, pid.px, pid.py);
 					const double s[3] = {own.dx, own.dy, own.dz};
 					if constexpr (BILINEAR) {
-						const double qxc = GWM == 0 ? own.px : (GWM == 2 ? own.px / f.grid_width : own.px * f.inv_grid_width);
-						const double qyc = GWM == 0 ? -own.py : (GWM == 2 ? -own.py / f.grid_width : -own.py * f.inv_grid_width);
+						double qxc, qyc;
+						cell_coords_of(own.px, own.py, qxc, qyc);
 						q = diffuse_level_bilinear(f, thr, bil_setup(qxc, qyc, f.map_w, f.map_h), s);
 					} else {
-						q = diffuse_level_nearest<F32>(f, thr, (unsigned)index_2d(cells.y0 + pid.py, f.map_w, cells.x0 + pid.px), s);
+						q = diffuse_level_nearest<F32>(f, thr, (unsigned)index_2d(a.cells.y0 + pid.py, f.map_w, a.cells.x0 + pid.px), s);
 					}
 				}
-				v = cell_weight(cells, real_hit, q);
+				v = cell_weight(a.cells, real_hit, q);
 			}
 			reinterpret_cast<uint8_t *>(out)[(uint64_t)(uint32_t)pid.lrow * (uint64_t)out_stride_px + (uint32_t)pid.px] = (uint8_t)v;
 		} else
 		if constexpr (GEOM) { // (a capped ray is no hit in any plane; its pixel is the miss shade, as in every frame)
 			if (out != nullptr) out[(uint64_t)(uint32_t)pid.lrow * (uint32_t)out_stride_px + (uint32_t)pid.px] = rgba;
-			store_geometry<PROJ>(f, geo, pid, real_hit, hcell, hqx, hqy, hz);
-			if (geo.slope != nullptr) {
+			store_geometry<PROJ>(f, a.geo, pid, real_hit, hcell, hqx, hqy, hz);
+			if (a.geo.slope != nullptr) {
 				Gradient g{0.0, 0.0};
 				if (real_hit) {
 					if constexpr (BILINEAR) g = gradient_bilinear(f, thr, bil_setup(qxh, qyh, f.map_w, f.map_h));
 					else g = gradient_nearest<F32>(f, thr, hcell);
 				}
-				store_slope(geo, pid, real_hit, g.gx, g.gy);
+				store_slope(a.geo, pid, real_hit, g.gx, g.gy);
 			}
 		} else
 		if constexpr (RAYS) {
 			const unsigned cy = hcell / (unsigned)f.map_w; // (gridx, gridy of hmap.cpp:1001-1004 from gridx + gridy * W)
 			if constexpr (SEG) {
-				store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy,
+				store_batch_hit(a.batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy,
 				                sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
 			} else
-			store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy, d,
+			store_batch_hit(a.batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy, d,
 			                (uint32_t)my_steps, rgba);
 		} else if constexpr (AA) aa_rgba = rgba;
 		else out[(uint64_t)(uint32_t)pid.lrow * (uint32_t)out_stride_px + (uint32_t)pid.px] = rgba;
@@ -1169,8 +1049,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	}
 	// (the sun-lit families make the lane's number again instead of holding it across their marches)
 	if constexpr (AA && SEG)
-		store_box_filtered(out, out_stride_px, f.aa_shift, (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), pid.px,
-		                   pid.lrow, pid.live, aa_rgba);
+		store_box_filtered(out, out_stride_px, f.aa_shift, (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), pid.px, pid.lrow, pid.live, aa_rgba);
 	else if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, lane, pid.px, pid.lrow, pid.live, aa_rgba);
 	// (SUM: capped rays are counted per ray, up to n per lane -- publish_counters' production path adds one per lane)
 	if constexpr (LSUM) { // (likewise: the primary ray once and every shadow ray, up to 1 + n per lane)

@@ -26,9 +26,9 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
 	// calibration launches only (RowMap::measure): when did this wave start
 	unsigned long long wave_t0 = 0;
 	if (!STATS && rows.measure) wave_t0 = __builtin_amdgcn_s_memrealtime();
-	const int tile_y = render_wave_tile<PROJ, STATS, GWM, LEAP, SAMP, AA>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
-	                                                                  blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	                                                                  (int)(threadIdx.x & 63), RayBatch{});
+	const int tile_y = render_wave_tile<Family<FramesOf<STATS, AA>, PROJ, GWM, LEAP, SAMP>>(
+	    f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x, blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
+	    (int)(threadIdx.x & 63));
 	if (!STATS && rows.measure && tile_y >= 0 && (threadIdx.x & 63) == 0) {
 		// record of a tile row: [0] start of its first workgroup (rows are handed out left to right), [1 + k] longest
 		// wave among the tile columns = k mod 32 (32 addresses per row: the atomics of a row's 2 x 480 waves spread out)

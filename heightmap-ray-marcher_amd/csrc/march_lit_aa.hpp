@@ -13,9 +13,9 @@ template <bool LIT, bool SHADE, int PROJ, int GWM, int LEAP, int SAMP>
 __device__ __forceinline__ void lit_aa_wave_tile(const DevFrame &f, const RowMap &rows, const double *__restrict__ thr,
                                                  const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out, int64_t out_stride_px,
                                                  int tiles_y, const StatsOut &st, const SegRules &seg, const SunRules &sun) {
-	(void)render_wave_tile<PROJ, false, GWM, LEAP, SAMP, true, true, LIT, SHADE>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
-	                                                                           blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	                                                                           (int)(threadIdx.x & 63), RayBatch{}, seg, sun);
+	(void)render_wave_tile<Family<Antialiased<Sun<LIT, SHADE>>, PROJ, GWM, LEAP, SAMP>>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st,
+	                                                                                     (int)blockIdx.x, blockIdx.z * 32768u + blockIdx.y,
+	                                                                                     (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63), seg, sun);
 }
 
 } // namespace hmrm

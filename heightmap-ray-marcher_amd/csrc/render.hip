@@ -250,7 +250,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_render(const DevFrame f, cons
 __global__ __launch_bounds__(kBlockThreads) void k_trace_rays_literal(const DevFrame f, const double *__restrict__ thr,
                                                                       const uint32_t *__restrict__ cmap, const RayBatch batch,
                                                                       int tiles_y, StatsOut st) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const RowMap rows = whole_frame_rows(f);
 	const PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, 0, blockIdx.z * 32768u + blockIdx.x, (int)(threadIdx.x >> 6),
 	                                       (int)(threadIdx.x & 63));
 	render_lane_literal<4, false, false>(f, pid, thr, cmap, nullptr, 0, st, batch);
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_render_shaded_literal_aa(cons
 __global__ __launch_bounds__(kBlockThreads) void k_trace_segments_literal(const DevFrame f, const double *__restrict__ thr,
                                                                           const uint32_t *__restrict__ cmap, const RayBatch batch,
                                                                           const SegRules seg, int tiles_y, StatsOut st) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const RowMap rows = whole_frame_rows(f);
 	const PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, 0, blockIdx.z * 32768u + blockIdx.x, (int)(threadIdx.x >> 6),
 	                                       (int)(threadIdx.x & 63));
 	render_lane_literal<4, false, false, true>(f, pid, thr, cmap, nullptr, 0, st, batch, seg);
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_trace_segments_literal(const 
 __global__ __launch_bounds__(kBlockThreads) void k_cell_map_literal(const DevFrame f, const double *__restrict__ thr,
                                                                     uint8_t *__restrict__ out, int64_t stride_bytes,
                                                                     const CellRules cells, int tiles_y, StatsOut st) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const RowMap rows = whole_frame_rows(f);
 	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
 	LitState<true> lt;
 	DevRay ray{};
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_cell_map_sum_literal(const De
                                                                         uint16_t *__restrict__ out, int64_t stride_bytes,
                                                                         const CellRules cells, const CellSums sums, int tiles_y,
                                                                         StatsOut st) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const RowMap rows = whole_frame_rows(f);
 	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
 	const int cx = cells.x0 + pid.px, cy = cells.y0 + pid.py;
 	const size_t cell = pid.live ? (size_t)cy * (size_t)f.map_w + (size_t)cx : 0; // (gridx + gridy * W of the lane's cell)
@@ -656,7 +656,7 @@ hipError_t launch_trace_segments_literal(const DevFrame &f, const double *d_thr,
 
 hipError_t launch_cell_map_literal(const DevFrame &f, const double *d_thr, uint8_t *d_out, int64_t stride_bytes, const CellRules &cells,
                                    unsigned long long *d_counters, hipStream_t stream) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const RowMap rows = whole_frame_rows(f);
 	const LaunchGrid g = tile_grid(f, rows);
 	if (g.tiles_y == 0) return g.err;
 	hipLaunchKernelGGL(k_cell_map_literal, g.grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_out, stride_bytes, cells, g.tiles_y,
@@ -666,7 +666,7 @@ hipError_t launch_cell_map_literal(const DevFrame &f, const double *d_thr, uint8
 
 hipError_t launch_cell_map_sum_literal(const DevFrame &f, const double *d_thr, uint16_t *d_out, int64_t stride_bytes,
                                        const CellRules &cells, const CellSums &sums, unsigned long long *d_counters, hipStream_t stream) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const RowMap rows = whole_frame_rows(f);
 	const LaunchGrid g = tile_grid(f, rows);
 	if (g.tiles_y == 0) return g.err;
 	hipLaunchKernelGGL(k_cell_map_sum_literal, g.grid, dim3(kBlockThreads), 0, stream, f, d_thr, d_out, stride_bytes, cells, sums,

@@ -17,9 +17,9 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
                                                                                                  int64_t out_stride_px, int tiles_y,
                                                                                                  StatsOut st, const SegRules seg,
                                                                                                  const BakedLight baked) {
-	(void)render_wave_tile<PROJ, false, GWM, LEAP, SAMP, false, true, false, false, false, false, false, true>(
+	(void)render_wave_tile<Family<Baked, PROJ, GWM, LEAP, SAMP>>(
 	    f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x, blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	    (int)(threadIdx.x & 63), RayBatch{}, seg, SunRules{}, CellRules{}, CellSums{}, GeomPlanes{}, LightSum{}, baked);
+	    (int)(threadIdx.x & 63), seg, baked);
 }
 
 hipError_t launch_render_baked(const FrameLaunch &l, FastKernel kernel) {

@@ -11,9 +11,9 @@ template <int PROJ, int GWM, int LEAP, int SAMP>
 __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR void k_render_baked_aa(const DevFrame f, const RowMap rows,
 		const double *__restrict__ thr, const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out, int64_t out_stride_px, int tiles_y,
 		StatsOut st, const SegRules seg, const BakedLight baked) {
-	(void)render_wave_tile<PROJ, false, GWM, LEAP, SAMP, true, true, false, false, false, false, false, true>(
+	(void)render_wave_tile<Family<Antialiased<Baked>, PROJ, GWM, LEAP, SAMP>>(
 	    f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x, blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	    (int)(threadIdx.x & 63), RayBatch{}, seg, SunRules{}, CellRules{}, CellSums{}, GeomPlanes{}, LightSum{}, baked);
+	    (int)(threadIdx.x & 63), seg, baked);
 }
 
 hipError_t launch_render_baked_aa(const FrameLaunch &l, FastKernel kernel) {

@@ -15,11 +15,10 @@ template <int GWM, int LEAP, int SAMP>
 __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR void k_cell_map(const DevFrame f, const double *__restrict__ thr,
                                                                                             uint8_t *__restrict__ out, int64_t stride_bytes,
                                                                                             const CellRules cells, int tiles_y, StatsOut st) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
-	(void)render_wave_tile<5, false, GWM, LEAP, SAMP, false, true>(f, rows, thr, nullptr, reinterpret_cast<uint32_t *>(out), stride_bytes,
-	                                                                tiles_y, st, (int)blockIdx.x, blockIdx.z * 32768u + blockIdx.y,
-	                                                                (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63), RayBatch{},
-	                                                                SegRules{nullptr, cells.max_steps, 1u}, SunRules{}, cells);
+	const RowMap rows = whole_frame_rows(f);
+	(void)render_wave_tile<Family<Cells, 5, GWM, LEAP, SAMP>>(f, rows, thr, nullptr, reinterpret_cast<uint32_t *>(out), stride_bytes, tiles_y, st,
+	                                                           (int)blockIdx.x, blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
+	                                                           (int)(threadIdx.x & 63), SegRules{nullptr, cells.max_steps, 1u}, cells);
 }
 
 hipError_t launch_cell_map(const DevFrame &f, const double *d_thr_f64, const float *d_thr32, uint8_t *d_out, int64_t stride_bytes,
@@ -28,7 +27,7 @@ hipError_t launch_cell_map(const DevFrame &f, const double *d_thr_f64, const flo
 	DevFrame fr = f;
 	const double *d_thr = nullptr;
 	if (const hipError_t e = select_tables(&fr, kernel, d_thr_f64, d_thr32, d_records, &d_thr); e != hipSuccess) return e;
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	const RowMap rows = whole_frame_rows(f);
 	const LaunchGrid g = tile_grid(f, rows);
 	if (g.tiles_y == 0) return g.err;
 	const StatsOut st{d_counters, nullptr, nullptr};

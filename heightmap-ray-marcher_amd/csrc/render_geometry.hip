@@ -17,9 +17,9 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
                                                                                                    int64_t out_stride_px, int tiles_y,
                                                                                                    StatsOut st, const SegRules seg,
                                                                                                    const GeomPlanes geo) {
-	(void)render_wave_tile<PROJ, false, GWM, LEAP, SAMP, false, true, false, false, false, true>(
+	(void)render_wave_tile<Family<Geometry, PROJ, GWM, LEAP, SAMP>>(
 	    f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x, blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	    (int)(threadIdx.x & 63), RayBatch{}, seg, SunRules{}, CellRules{}, CellSums{}, geo);
+	    (int)(threadIdx.x & 63), seg, geo);
 }
 
 hipError_t launch_render_geometry(const FrameLaunch &l, FastKernel kernel) {

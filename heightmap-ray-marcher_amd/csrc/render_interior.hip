@@ -16,9 +16,9 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
                                                                                                    uint32_t *__restrict__ out,
                                                                                                    int64_t out_stride_px, int tiles_y,
                                                                                                    StatsOut st, const SegRules seg) {
-	(void)render_wave_tile<PROJ, false, GWM, LEAP, SAMP, false, true>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
-	                                                                   blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	                                                                   (int)(threadIdx.x & 63), RayBatch{}, seg);
+	(void)render_wave_tile<Family<Interior, PROJ, GWM, LEAP, SAMP>>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
+	                                                                 blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
+	                                                                 (int)(threadIdx.x & 63), seg);
 }
 
 hipError_t launch_render_interior(const FrameLaunch &l, FastKernel kernel) {

@@ -16,9 +16,9 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
                                                                                                        int64_t out_stride_px, int tiles_y,
                                                                                                        StatsOut st, const SegRules seg, const SunRules sun,
                                                                                                        const LightSum lsum) {
-	(void)render_wave_tile<PROJ, false, GWM, LEAP, SAMP, false, true, true, false, false, false, true>(
+	(void)render_wave_tile<Family<LitSum, PROJ, GWM, LEAP, SAMP>>(
 	    f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x, blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	    (int)(threadIdx.x & 63), RayBatch{}, seg, sun, CellRules{}, CellSums{}, GeomPlanes{}, lsum);
+	    (int)(threadIdx.x & 63), seg, sun, lsum);
 }
 
 hipError_t launch_render_lit_sum(const FrameLaunch &l, FastKernel kernel) {

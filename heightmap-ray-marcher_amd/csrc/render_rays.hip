@@ -14,8 +14,8 @@ template <int GWM, int LEAP, int SAMP>
 __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR void k_trace_rays(const DevFrame f, const double *__restrict__ thr,
                                                                                               const uint32_t *__restrict__ cmap,
                                                                                               const RayBatch batch, int tiles_y, StatsOut st) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
-	(void)render_wave_tile<4, false, GWM, LEAP, SAMP, false>(f, rows, thr, cmap, nullptr, 0, tiles_y, st, 0, blockIdx.z * 32768u + blockIdx.x,
+	const RowMap rows = whole_frame_rows(f);
+	(void)render_wave_tile<Family<Rays, 4, GWM, LEAP, SAMP>>(f, rows, thr, cmap, nullptr, 0, tiles_y, st, 0, blockIdx.z * 32768u + blockIdx.x,
 	                                                          (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63), batch);
 }
 

@@ -12,10 +12,10 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
                                                                                                   const uint32_t *__restrict__ cmap,
                                                                                                   const RayBatch batch, const SegRules seg,
                                                                                                   int tiles_y, StatsOut st) {
-	const RowMap rows{0, f.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
-	(void)render_wave_tile<4, false, GWM, LEAP, SAMP, false, true>(f, rows, thr, cmap, nullptr, 0, tiles_y, st, 0,
-	                                                                blockIdx.z * 32768u + blockIdx.x, (int)(threadIdx.x >> 6),
-	                                                                (int)(threadIdx.x & 63), batch, seg);
+	const RowMap rows = whole_frame_rows(f);
+	(void)render_wave_tile<Family<Segments, 4, GWM, LEAP, SAMP>>(f, rows, thr, cmap, nullptr, 0, tiles_y, st, 0,
+	                                                              blockIdx.z * 32768u + blockIdx.x, (int)(threadIdx.x >> 6),
+	                                                              (int)(threadIdx.x & 63), batch, seg);
 }
 
 hipError_t launch_trace_segments(const DevFrame &f, const double *d_thr_f64, const float *d_thr32, const uint32_t *d_cmap,

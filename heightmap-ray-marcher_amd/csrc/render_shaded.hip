@@ -18,9 +18,9 @@ __global__ __launch_bounds__(kBlockThreads, HMRM_MIN_WAVES) HMRM_OCCUPANCY_ATTR 
                                                                                                       uint32_t *__restrict__ out,
                                                                                                       int64_t out_stride_px, int tiles_y,
                                                                                                       StatsOut st, const SegRules seg, const SunRules sun) {
-	(void)render_wave_tile<PROJ, false, GWM, LEAP, SAMP, false, true, false, true>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
-	                                                                          blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
-	                                                                          (int)(threadIdx.x & 63), RayBatch{}, seg, sun);
+	(void)render_wave_tile<Family<Shaded, PROJ, GWM, LEAP, SAMP>>(f, rows, thr, cmap, out, out_stride_px, tiles_y, st, (int)blockIdx.x,
+	                                                               blockIdx.z * 32768u + blockIdx.y, (int)(threadIdx.x >> 6),
+	                                                               (int)(threadIdx.x & 63), seg, sun);
 }
 
 hipError_t launch_render_shaded(const FrameLaunch &l, FastKernel kernel) {

@@ -369,7 +369,7 @@ lib, EXPORTED_SYMBOLS = _load()
 # collected on, so it carries this hash and bench.py refuses one that does not match the tree.
 KERNEL_SOURCES = ("render_fast.hip", "render_rays.hip", "leap_common.hpp", "leap_diag.hpp", "render.hip", "device_common.hpp", "frame.hpp",
                   "render.hpp", "api_internal.hpp", "api_launch.cpp", "api_frames.cpp", "launch_order.cpp", "launch_order.hpp", "camera.cpp", "Makefile",
-                  "march.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip")
+                  "march.hpp", "march_family.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip")
 
 
 def kernel_src_sha() -> str:
