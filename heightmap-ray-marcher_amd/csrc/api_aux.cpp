@@ -126,6 +126,18 @@ void hmrm_config_get_sun(const hmrm_config *c, hmrm_sun *out) {
 	out->ambient = (uint8_t)g.shadow_ambient;
 }
 
+int32_t hmrm_config_water(const hmrm_config *c) { return c->cfg.water; }
+void hmrm_config_get_water(const hmrm_config *c, hmrm_water *out) {
+	const hmrm::Config &g = c->cfg;
+	memset(out, 0, sizeof *out);
+	out->level = g.water_level;
+	out->step_dist = g.have_water_step_dist ? g.water_step_dist : g.step_dist;
+	out->max_steps = (uint32_t)g.water_max_steps;
+	out->flags = (g.interior ? HMRM_TRACE_INTERIOR : 0u) | (g.have_water_color ? HMRM_WATER_OWN_COLOR : 0u);
+	out->reflectivity = (uint8_t)g.water_reflectivity;
+	for (int k = 0; k < 3; ++k) out->color[k] = (uint8_t)g.water_color[k];
+}
+
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *c, int32_t *w, int32_t *h) {
 	if (!c->cfg.have_heightmap) return nullptr;
 	if (w) *w = c->cfg.heightmap.w;

@@ -459,6 +459,69 @@ int hmrm_render_baked(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t 
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes, how);
 }
 
+// ---- water frames: hmrm_render's frame (hmrm_render_interior's with HMRM_TRACE_INTERIOR) whose hit pixels at or below the water
+// level take their mirror ray's pixel blended in, marched by the same launch ----
+// The three refusals of the header, in its order; needs no scene and no device.
+static int check_water(const hmrm_water *w) {
+	if (!w) return fail(HMRM_E_ARG, "NULL water");
+	if (w->flags & ~(HMRM_TRACE_INTERIOR | HMRM_WATER_OWN_COLOR)) return fail(HMRM_E_ARG, "hmrm_water.flags: undefined bit");
+	for (uint8_t r : w->reserved)
+		if (r) return fail(HMRM_E_ARG, "hmrm_water.reserved must be 0");
+	return HMRM_OK;
+}
+
+// Launched the way a lit frame is (FrameRequest::own_kernels): never measured, never the probe, with the scene's current kernel.
+// With the flag every origin is tested by the kernels, whatever the projection.  `device`: `target` is device memory and the launch
+// goes to `stream` without a host sync; else the frame is staged through the scene's frame buffer, rows packed, and copied to the
+// caller's behind the launch.
+static int render_water_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm_water *w, void *target, size_t stride_bytes,
+                               bool device, hipStream_t stream) {
+	int rc = check_water(w);
+	if (rc || (rc = check_camera(cam))) return rc;
+	if (!s || !target) return fail(HMRM_E_ARG, "NULL argument");
+	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+	if (device) {
+		if ((rc = check_device_stride(cam, stride_bytes))) return rc;
+	} else if (stride_bytes < W * 4) return fail(HMRM_E_ARG, "stride_bytes < width*4");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	uint32_t *d_rgba = (uint32_t *)target;
+	int64_t stride_px = (int64_t)(stride_bytes / 4);
+	if (!device) {
+		if ((rc = s->d_frame.reserve(W * H * sizeof(uint32_t)))) return rc;
+		d_rgba = s->d_frame.as<uint32_t>();
+		stride_px = (int64_t)W;
+		stream = s->stream;
+	}
+	FrameSetup fs;
+	if ((rc = setup_frame(s, stream, cam, 0, &fs))) return rc;
+	StreamCtx *const c = fs.c;
+	const hmrm::WaterRules rules{w->level, w->step_dist, w->max_steps, (uint32_t)w->reflectivity,
+	                             (uint32_t)w->color[0] | ((uint32_t)w->color[1] << 8) | ((uint32_t)w->color[2] << 16),
+	                             w->flags & HMRM_WATER_OWN_COLOR};
+	FrameRequest req = plain_request(d_rgba, stride_px);
+	req.interior = (w->flags & HMRM_TRACE_INTERIOR) ? Interior::kByKernels : Interior::kNot;
+	req.water = &rules;
+	if (!device) HIP_TRY(hipEventRecord(s->ev0, s->stream)); // (the host form is timed like hmrm_render: hmrm_last_kernel_ms)
+	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req)) || device) return rc;
+	HIP_TRY(hipEventRecord(s->ev1, s->stream));
+	HIP_TRY(hipMemcpy2DAsync(target, stride_bytes, d_rgba, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
+	rc = finish_host_call(s, c);
+	float ms = 0.f;
+	HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+	g_last_kernel_ms = ms;
+	return rc;
+}
+
+int hmrm_render_water(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint8_t *rgba, size_t stride_bytes) {
+	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, rgba, stride_bytes, false, nullptr);
+}
+
+int hmrm_render_water_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, void *d_rgba,
+                             size_t stride_bytes, void *hip_stream) {
+	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, d_rgba, stride_bytes, true, (hipStream_t)hip_stream);
+}
+
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
                       size_t stride_bytes, hmrm_stats *stats, uint32_t *steps_per_pixel, double *entry_d) {
 	return render_common(const_cast<hmrm_scene *>(scene), cam, rgba, stride_bytes,

@@ -290,9 +290,14 @@ struct FrameRequest {
 	// hmrm_render_baked's frame: the scene's light plane, whose weight the launch applies to the hit pixels; null: none.  Its
 	// primary rays are under the interior rule when `interior` is not kNot, as a geometry frame's are.
 	const hmrm::BakedLight *baked = nullptr;
-	// Frames under the interior rule, with a sun, with geometry planes or with baked light run kernels of their own, with the
-	// scene's current kernel kind (HMRM_KERNEL or the probe's verdict, read only).
-	bool own_kernels() const { return interior != Interior::kNot || lit != nullptr || geom != nullptr || baked != nullptr; }
+	// hmrm_render_water's frame: the water level, the mirror march and the blend; null: none.  Its primary rays are under the
+	// interior rule when `interior` is not kNot, as a geometry frame's are.
+	const hmrm::WaterRules *water = nullptr;
+	// Frames under the interior rule, with a sun, with geometry planes, with baked light or with water run kernels of their own,
+	// with the scene's current kernel kind (HMRM_KERNEL or the probe's verdict, read only).
+	bool own_kernels() const {
+		return interior != Interior::kNot || lit != nullptr || geom != nullptr || baked != nullptr || water != nullptr;
+	}
 	// Special frames -- those and instrumented ones -- are launched in the plain rotation order: never measured, never a probe,
 	// not counted towards the probe.
 	bool special() const { return stats || own_kernels(); }

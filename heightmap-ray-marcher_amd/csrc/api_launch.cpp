@@ -153,6 +153,11 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		l.baked = *req.baked;
 		l.primary_interior = req.interior != Interior::kNot;
 	}
+	if (req.water) { // (likewise)
+		l.family = hmrm::kFrameWater;
+		l.water = *req.water;
+		l.primary_interior = req.interior != Interior::kNot;
+	}
 	if (route.literal) {
 		HIP_TRY(hmrm::launch_frame_literal(l));
 		return HMRM_OK;

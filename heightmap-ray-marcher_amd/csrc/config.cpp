@@ -15,6 +15,7 @@
 //   record orbit|off, devices n, sampling nearest|bilinear, heights f64|f32, antialias 1|2|4|8, interior on|off,
 //   shadows on|off, sun_dir x y z, shadow_ambient n, shadow_step_dist v, shadow_max_steps n
 //   shading on|off, sun_scope single|all, sky_light on|off, baked_light off|sun|sky
+//   water on|off, water_level v, water_reflectivity n, water_color r g b, water_step_dist v, water_max_steps n
 //   sun_map <path.png>, sun_map_lift v                (the whole map's light map, hmrm_cell_map, written by the CLI)
 //   sky_map <path.png>, sky_map_rings r n             (the whole map's sky-view map, hmrm_cell_map_sum, written by the CLI)
 //   range_map <path.pfm>                              (the camera's range plane, hmrm_render_geometry, written by the CLI)
@@ -232,6 +233,47 @@ void baked_light_key(Config &c, std::istream &in, const char *key, std::string *
 	c.log << key << " " << (c.baked_light == 1 ? "sun" : c.baked_light == 2 ? "sky" : "off") << "\n";
 }
 
+// mirror reflections on flat water in the single frame (hmrm_render_water)
+void water_key(Config &c, std::istream &in, const char *key, std::string *) {
+	static const Word words[] = {{"on", 1}, {"1", 1}, {"off", 0}, {"0", 0}};
+	std::string seen;
+	if (!pick(in, words, &c.water, &seen)) c.warn << "WARNING: Unknown water: " << seen << "\n";
+	c.log << key << " " << (c.water ? "on" : "off") << "\n";
+}
+
+void water_reflectivity_key(Config &c, std::istream &in, const char *key, std::string *) { // the mirror pixel's share, of 255
+	long long v = -1;
+	in >> v;
+	if (!in || v < 0 || v > 255) c.warn << "WARNING: water_reflectivity must be 0..255\n";
+	else c.water_reflectivity = (int)v;
+	c.log << key << " " << c.water_reflectivity << "\n";
+}
+
+void water_color_key(Config &c, std::istream &in, const char *key, std::string *) { // the water's own colour instead of the primary pixel
+	long long v[3] = {-1, -1, -1};
+	in >> v[0] >> v[1] >> v[2];
+	if (!in || v[0] < 0 || v[0] > 255 || v[1] < 0 || v[1] > 255 || v[2] < 0 || v[2] > 255) c.warn << "WARNING: water_color must be three values 0..255\n";
+	else {
+		for (int k = 0; k < 3; ++k) c.water_color[k] = (int)v[k];
+		c.have_water_color = true;
+	}
+	c.log << key << " " << c.water_color[0] << " " << c.water_color[1] << " " << c.water_color[2] << "\n";
+}
+
+void water_step_dist_key(Config &c, std::istream &in, const char *key, std::string *) {
+	in >> c.water_step_dist;
+	c.have_water_step_dist = true;
+	c.log << key << " " << c.water_step_dist << "\n";
+}
+
+void water_max_steps_key(Config &c, std::istream &in, const char *key, std::string *) { // 0 = no limit
+	long long v = -1;
+	in >> v;
+	if (!in || v < 0 || v > 0xffffffffll) c.warn << "WARNING: water_max_steps must be 0..4294967295\n";
+	else c.water_max_steps = v;
+	c.log << key << " " << c.water_max_steps << "\n";
+}
+
 // which frames shadows / shading apply to: the plain single frame, or antialiased and recorded ones too
 void sun_scope_key(Config &c, std::istream &in, const char *key, std::string *) {
 	static const Word words[] = {{"single", 0}, {"all", 1}};
@@ -331,6 +373,12 @@ const Row kGrammar[] = {
 	{"sky_map", scalar<&Config::sky_map_path>},
 	{"sky_map_rings", sky_map_rings_key},
 	{"range_map", scalar<&Config::range_map_path>},
+	{"water", water_key},
+	{"water_level", scalar<&Config::water_level>},
+	{"water_reflectivity", water_reflectivity_key},
+	{"water_color", water_color_key},
+	{"water_step_dist", water_step_dist_key},
+	{"water_max_steps", water_max_steps_key},
 };
 
 } // namespace

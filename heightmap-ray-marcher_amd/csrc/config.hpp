@@ -54,6 +54,17 @@ struct Config {
 	// additive: `baked_light off|sun|sky` -- 0, 1, 2: the CLI bakes the scene's light plane once before its frames (hmrm_scene_bake_light:
 	// the sun_map's light under `sun_dir`, or the sky_map's count over `sky_map_rings`) and renders them as baked frames (hmrm_render_baked)
 	int baked_light = 0;
+	// additive: water of the CLI's single frame (hmrm_render_water): `water on|off|1|0`, `water_level v` (a hit at or below it
+	// mirrors), `water_reflectivity 0..255`, `water_color r g b` (the water's own colour: sets HMRM_WATER_OWN_COLOR),
+	// `water_step_dist v` (absent: the camera's step_dist), `water_max_steps n`
+	int water = 0;
+	double water_level = 0.0;
+	int water_reflectivity = 128;
+	int water_color[3] = {0, 0, 0};
+	bool have_water_color = false;
+	double water_step_dist = 0.0;
+	bool have_water_step_dist = false;
+	long long water_max_steps = 0;
 	// additive: `sun_scope single|all` -- 0: shadows / shading apply to the plain single frame only; 1: also with `antialias n` > 1
 	// (hmrm_render_shaded_aa) and to `record orbit` (hmrm_record_orbit_shaded)
 	int sun_scope = 0;

@@ -326,6 +326,25 @@ struct BakedLight {
 	uint32_t full_scale;
 };
 
+// ---- water frames (hmrm_render_water; MIRROR in the kernels) ----
+// Every pixel whose primary ray HIT with t <= level -- t the threshold the hitting load compared z with, as in SunRules -- casts a
+// mirror ray from (P.x, P.y, t) along the primary ray's direction with dir.z negated: a segment ray under the interior rule with
+// step_dist and the limit max_steps (0 = none).  Its pixel m -- the hit cell's colour, or the miss shade of its own dir.z -- is
+// blended into the base b, the primary pixel or `own` with kWaterOwnColor: (b * (255 - r) + m * r + 127) / 255 per channel.  The
+// primary rays' own rules travel in a SegRules beside it.  An extra argument of the water kernels' own __global__ entry points,
+// like SegRules.
+struct WaterRules {
+	double level;
+	double step_dist;
+	uint32_t max_steps;
+	uint32_t reflectivity; // r, 0..255
+	uint32_t own;          // R | G << 8 | B << 16, with kWaterOwnColor in `flags`
+	uint32_t flags;        // kWaterOwnColor or 0
+};
+// (r and the colour packed into one word, a scalar register less, made the compiler take a scratch slot in 30 of the 63
+// instantiations instead of 9: DESIGN.md 5.20)
+constexpr uint32_t kWaterOwnColor = 2u; // (= hmrm.h HMRM_WATER_OWN_COLOR)
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

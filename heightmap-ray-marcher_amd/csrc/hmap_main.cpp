@@ -21,6 +21,9 @@
 // `shading on`, shadow rays unless `shading on` stands without `shadows on`) is written there as a one-component PNG.
 // `sky_map <path.png>`: after that, the whole map's sky-view map (hmrm_cell_map_sum over `sky_map_rings r n` sky directions).
 // `range_map <path.pfm>`: after the frames and before the sun map, the range plane of the configured camera (hmrm_render_geometry).
+// `water on`: the single frame with mirror reflections at or below `water_level` (hmrm_render_water; under the interior rule too
+// when `interior on`); ignored, with a warning, beside `antialias` > 1, `devices` > 1, `record orbit`, `shadows`, `shading` and
+// `baked_light`.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -240,6 +243,7 @@ int main(int argc, char *argv[]) {
 			if (shading) std::cerr << "WARNING: shading is ignored with record orbit\n";
 		}
 		if (sky_light) std::cerr << "WARNING: sky_light is ignored with record orbit\n";
+		if (hmrm_config_water(cfg) != 0) std::cerr << "WARNING: water is ignored with record orbit\n";
 		// `record orbit`: recording_frame_count frames on a circle around the map centre through
 		// the configured camera position, always looking at the centre;
 		// files screenshots/hmap_<epoch>_<n>.png as hmap.cpp:1131-1144.
@@ -316,7 +320,32 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: shading is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
 	if (sky_light && (want_dev > 1 || aa > 1)) // (whatever sun_scope says: there is no antialiased accumulated frame)
 		std::cerr << "WARNING: sky_light is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
-	if (baked) {
+	// `water on`: the single frame with mirror reflections at or below `water_level` (hmrm_render_water) -- the plain frame's only
+	bool water = hmrm_config_water(cfg) != 0;
+	if (water) {
+		const char *beside = aa > 1 ? "antialias > 1" : want_dev > 1 ? "devices > 1" : shadows ? "shadows" : shading ? "shading"
+		                     : baked_mode != 0 ? "baked_light" : nullptr;
+		if (beside) {
+			std::cerr << "WARNING: water is ignored with " << beside << "\n";
+			water = false;
+		}
+	}
+	if (water && sky_light) {
+		std::cerr << "WARNING: sky_light is ignored with water\n";
+		sky_light = false;
+	}
+	if (water) {
+		hmrm_water w;
+		hmrm_config_get_water(cfg, &w);
+		rc = hmrm_render_water(scene, &cam, &w, framebuf.data(), (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height << " rays with water at level " << w.level
+		          << (interior ? " under the interior rule" : "") << "\n";
+	} else if (baked) {
 		// the single frame, antialiased or not, under the light plane baked here: `shadows` and `shading` only chose what was baked
 		if (!bake_light(cfg, scene, cam, baked_mode, shading, shadows)) return 1;
 		rc = hmrm_render_baked(scene, &cam, interior ? HMRM_TRACE_INTERIOR : 0u, aa, framebuf.data(), (size_t)cam.width * 4);

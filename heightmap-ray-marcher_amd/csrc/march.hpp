@@ -1,8 +1,8 @@
 // march.hpp -- the production march for gfx950: render_wave_tile, one wave's 8 x 8 pixels (or 64 batch rays), and its
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
 // render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
-// counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip, render_lit_sum.hip, render_baked.hip
-// and render_baked_aa.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
+// counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip, render_lit_sum.hip, render_baked.hip,
+// render_baked_aa.hip and render_water.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
 // switch and derived constant with its reasons.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
@@ -193,6 +193,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	constexpr bool STATS = F::STATS, AA = F::AA, SEG = F::SEG, LIT = F::LIT, SHADE = F::SHADE, SUM = F::SUM, GEOM = F::GEOM, LSUM = F::LSUM;
 	constexpr bool BAKED = F::BAKED, CELLS = F::CELLS, RAYS = F::RAYS, COUNT = F::COUNT, BILINEAR = F::BILINEAR, F32 = F::F32, REC = F::REC;
 	constexpr bool KEEP_Q = F::KEEP_Q, KEEP_P = F::KEEP_P, CHAIN = F::CHAIN, DEFER = F::DEFER, CARRY = F::CARRY;
+	constexpr bool MIRROR = F::MIRROR;
 	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
 	const float *__restrict__ mip = BILINEAR ? f.mipbuf_bil : f.mipbuf; // the pyramid this sampling mode leaps on
 	PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, lane);
@@ -248,7 +249,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		// of the march loop: its colour (below the loop: one load for all hit lanes of the wave, where the loop had one, and a wait
 		// for it, in every trip in which any lane hit), SHADE's diffuse level and the ray batches' record are all made from it.
 		unsigned hcell = 0u;
-		LitState<LIT> lt; // (empty unless LIT: device_common.hpp)
+		LitState<LIT || MIRROR> lt; // (empty unless LIT or MIRROR: device_common.hpp)
+		// (MIRROR: what LitState::rgba holds between the passes -- the primary hit's cell, below 2^29, or its pixel without the alpha
+		// byte -- and the two flags beside it)
+		[[maybe_unused]] constexpr bool kMirrorKeepsCell = MIRROR && DEFER && !BILINEAR;
+		[[maybe_unused]] constexpr uint32_t kMirrorHit = 0x40000000u, kMirrorWet = 0x80000000u, kMirrorValue = kMirrorKeepsCell ? 0x3fffffffu : 0x00ffffffu;
 		double hqx = 0.0, hqy = 0.0; // (bilinear, no LIT: the hit's exact cell coordinates, KEEP_Q, or SHADE's copy of its x and y, KEEP_P)
 		bool again = false; // (LIT: the wave has shadow rays to march; SUM: targets)
 		// Bilinear mode, behind the march: the exact cell coordinates of a hit point -- the very expressions the group made its
@@ -297,6 +302,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				z = z + f.nudge * ray.dz;
 				double step_dist = f.step_dist;
 				if constexpr (LIT) step_dist = lt.phase ? a.sun.step_dist : step_dist; // (a shadow ray's own)
+				if constexpr (MIRROR) step_dist = lt.phase ? a.water.step_dist : step_dist; // (a mirror ray's own)
 				const double sx = step_dist * ray.dx; // hmap.cpp:1037, loop invariant
 				const double sy = step_dist * ray.dy;
 				const double sz = step_dist * ray.dz;
@@ -796,7 +802,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				if constexpr ((LIT && SHADE && BILINEAR) || LSUM) { // (the primary hit's point outlives the shadow march: the gradient is taken there; LSUM: every pass's ray starts there)
 					if (lt.phase == 0) { lt.hx = x; lt.hy = y; lt.t = z; }
 				} else
-				if constexpr (LIT) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
+				if constexpr (LIT || MIRROR) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
 				else if constexpr (GEOM && kGeomChain) { hqx = hx; hqy = hy; }
 				else if constexpr (GEOM) { hqx = x; hqy = y; hz = z; } // (int_point of a lane that hit)
 				else if constexpr (KEEP_P) { hqx = x; hqy = y; } // (SHADE, bilinear: the same two, for the gradient at P)
@@ -876,6 +882,47 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					}
 				}
 			}
+			if constexpr (MIRROR) {
+				// After the primary rays: the lanes that hit at or below the water level become their mirror rays -- origin, dz, the step
+				// (above) and the budget min(step cap, L) are replaced, dx and dy stay -- and the others get d = inf and sit the pass out.
+				// A wave without a water lane is finished.  What a lane keeps of its primary ray is ONE word, LitState::rgba: the hit
+				// cell (nearest-cell modes with the colour behind the loop: the colour is fetched there, behind both marches, as LIT
+				// does) or the pixel itself (the bilinear mode: made here, where the point is at hand; the in-loop fetch: it is there
+				// already), with "hit" and "water" in the bits the value leaves free -- two lane masks in scalar registers less across
+				// the mirror march, in kernels that sit on the scalar registers' limit.  So hcell and the point are
+				// free for the mirror pass.  Every lane negates its dz, the dry ones too: negated once more behind the loop it is the
+				// primary ray's again, bit for bit, and nothing is put aside for the miss shade.  After the mirror rays: real_hit says
+				// that the mirror ray hit.
+				again = false;
+				if (lt.phase == 0) {
+					uint32_t keep;
+					if constexpr (kMirrorKeepsCell) keep = hcell;
+					else {
+						if constexpr (DEFER) { // (BILINEAR)
+							if (real_hit) {
+								double qxp, qyp;
+								cell_coords_of(lt.hx, lt.hy, qxp, qyp);
+								rgba = bilinear_pixel(qxp, qyp);
+							}
+						}
+						keep = rgba;
+					}
+					const bool wet = real_hit && lt.t <= a.water.level; // (a NaN level: no water)
+					lt.rgba = (keep & kMirrorValue) | (real_hit ? kMirrorHit : 0u) | (wet ? kMirrorWet : 0u);
+					if (__builtin_amdgcn_ballot_w64(wet) != 0ull) {
+						lt.phase = 1;
+						again = true;
+						ray.px = lt.hx; ray.py = lt.hy; ray.pz = lt.t;
+						ray.dz = -ray.dz;
+						d = __builtin_huge_val();
+						if (wet) {
+							d = shadow_entry(ray, f);
+							sg.budget = segment_budget(SegRules{nullptr, a.water.max_steps, 1u}, 0, f.step_cap, &sg.ends);
+						}
+						real_hit = false;
+					}
+				}
+			}
 			if constexpr (SUM) {
 				// After a pass: the lane folds the value of this target's ray into its sum -- the very byte k_cell_map's epilogue below
 				// would store for it, or 1 for a ray that did not hit -- and counts the pass if the step cap stopped it (an END ray is
@@ -921,15 +968,41 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					real_hit = false;
 				}
 			}
-		} while ((LIT || SUM) && again); // (LSUM implies LIT)
+		} while ((LIT || SUM || MIRROR) && again); // (LSUM implies LIT)
 		// The hit lanes' colour: fetched here, once, behind the march (LIT, nearest-cell modes: behind both marches).
 		double qxh = hqx, qyh = hqy; // (bilinear: the hit's cell coordinates, for the colour and SHADE's gradient)
-		if constexpr (BILINEAR && (KEEP_P || GEOM) && !LIT) cell_coords_of(hqx, hqy, qxh, qyh);
+		if constexpr (BILINEAR && (KEEP_P || GEOM) && !LIT && !MIRROR) cell_coords_of(hqx, hqy, qxh, qyh);
 		if constexpr (GEOM) {
 			if (out != nullptr && real_hit) rgba = BILINEAR ? bilinear_pixel(qxh, qyh) : shade_hit(f, cmap[hcell]);
 		} else
-		if constexpr (DEFER && !LIT) {
+		if constexpr (DEFER && !LIT && !MIRROR) {
 			if (real_hit) rgba = BILINEAR ? bilinear_pixel(qxh, qyh) : shade_hit(f, cmap[hcell]);
+		}
+		if constexpr (MIRROR) {
+			// A water lane: its mirror ray's pixel -- the colour of the cell that ray hit, fetched here from the mirror pass's own hcell
+			// (the bilinear mode: and hit point), or for MISS, END and CAPPED the miss shade of the mirror ray's own dz -- blended into
+			// the primary pixel or the water's own colour.  A dry lane that hit keeps its primary pixel.
+			if ((lt.rgba & kMirrorHit) != 0u) {
+				uint32_t kept;
+				if constexpr (kMirrorKeepsCell) kept = shade_hit(f, cmap[lt.rgba & kMirrorValue]);
+				else kept = lt.rgba | 0xff000000u;
+				if ((lt.rgba & kMirrorWet) != 0u) {
+					uint32_t m = rgba; // (the in-loop fetch's, where the family keeps that)
+					if constexpr (DEFER) {
+						if (real_hit) {
+							if constexpr (BILINEAR) {
+								cell_coords_of(lt.hx, lt.hy, qxh, qyh);
+								m = bilinear_pixel(qxh, qyh);
+							} else m = shade_hit(f, cmap[hcell]);
+						}
+					}
+					if (!real_hit) m = shade_miss(f, ray.dz);
+					kept = blend_water(kept, m, a.water);
+				}
+				rgba = kept;
+				real_hit = true;
+			}
+			ray.dz = lt.phase ? -ray.dz : ray.dz; // (the primary ray's, for the miss shade)
 		}
 		if constexpr (LSUM) { // (the colour once, behind every march, and only for a colour target; then the pixel under its sum)
 			real_hit = lt.primary_hit;

@@ -53,7 +53,7 @@ constexpr bool kGeomChain = HMRM_GEOM_CHAIN != 0, kGeomCarry = HMRM_GEOM_CARRY !
 // whose ballot only the live lanes take part in.
 struct Frames {
 	static constexpr bool STATS = false, AA = false, SEG = false, LIT = false, SHADE = false, SUM = false, GEOM = false, LSUM = false,
-	                      BAKED = false;
+	                      BAKED = false, MIRROR = false;
 	struct Args {};
 };
 template <bool STATS_, bool AA_> struct FramesOf : Frames {
@@ -147,6 +147,20 @@ struct Baked : Frames {
 	static constexpr bool SEG = true, BAKED = true;
 	struct Args { const SegRules &seg; const BakedLight &baked; };
 };
+// MIRROR (render_water.hip; hmrm_render_water, frame.hpp WaterRules; implies SEG): a water frame.  LIT's second pass with a ray of
+// the lane's own and a colour for a result: a lane whose primary ray hit at or below the water level keeps its pixel and marches its
+// mirror ray -- a segment ray under the interior rule from (P.x, P.y, t) along the primary direction with dz negated -- through the
+// SAME loop; the other lanes sit the second pass out.  Between the passes the lane keeps LitState's hit point, as a lit lane
+// does, and ONE word of its primary ray -- the hit cell or the pixel, with "hit" and "water" in its free bits (march.hpp); the
+// mirror pass leaves its own hit cell in hcell and its own hit point in x, y (KEEP_P), from which the mirror colour is fetched
+// behind the loop; the primary ray's dz is the mirror ray's
+// negated once more, so nothing is put aside for the miss shade.
+// Termination: the outer loop runs at most twice -- the phase only goes from 0 to 1 -- and each pass is the march loop with a budget
+// of its own, the step cap or min(step cap, the mirror rays' limit).
+struct Water : Frames {
+	static constexpr bool SEG = true, MIRROR = true;
+	struct Args { const SegRules &seg; const WaterRules &water; };
+};
 
 // ---- a family: its tag's switches, the four dispatched values, and what follows from them ----
 // SAMP: 0 nearest cell (the reference), 1 bilinear quality mode, 2 nearest cell with float thresholds (`thr` then points at the
@@ -155,8 +169,17 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	using Args = typename TAG::Args;
 	static constexpr int PROJ = PROJ_, GWM = GWM_, LEAP = LEAP_, SAMP = SAMP_;
 	static constexpr bool STATS = TAG::STATS, AA = TAG::AA, SEG = TAG::SEG, LIT = TAG::LIT, SHADE = TAG::SHADE, SUM = TAG::SUM,
-	                      GEOM = TAG::GEOM, LSUM = TAG::LSUM, BAKED = TAG::BAKED;
+	                      GEOM = TAG::GEOM, LSUM = TAG::LSUM, BAKED = TAG::BAKED, MIRROR = TAG::MIRROR;
 	static constexpr bool CELLS = PROJ == 5;
+	static_assert(!MIRROR || SEG, "water frames: under the segment rules");
+	static_assert(!MIRROR || !CELLS, "water frames: a camera's frame, not a cell map");
+	static_assert(!MIRROR || PROJ != 4, "water frames: a camera's frame, not a ray batch");
+	static_assert(!MIRROR || !STATS, "water frames: production kernels only");
+	static_assert(!MIRROR || !AA, "water frames: not antialiased");
+	static_assert(!MIRROR || !LIT, "water frames: no sun shadows");
+	static_assert(!MIRROR || !SHADE, "water frames: no sun shading");
+	static_assert(!MIRROR || !GEOM, "water frames: no geometry planes");
+	static_assert(!MIRROR || !BAKED, "water frames: no baked light");
 	static_assert(!BAKED || (SEG && !CELLS && PROJ != 4 && !STATS && !LIT && !SHADE && !GEOM), "baked-light frames: plain frames under the segment rules");
 	static_assert(!LSUM || (LIT && !SHADE && !AA), "accumulated lit frames: the lit kernels' marches, the weights by a run-time flag");
 	static_assert(!GEOM || (SEG && !CELLS && PROJ != 4 && !STATS && !AA && !LIT && !SHADE), "geometry frames: plain frames under the segment rules");
@@ -171,9 +194,10 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	// mix the pixel behind the loop (DEFER), shaded or not.
 	// GEOM wants the whole point, in every sampling mode: KEEP_P with z stepped like x and y (no threshold is kept), which holds
 	// nothing across the loop -- RAYS' select chain keeps three doubles more.
-	static constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && LEAP != 0 && !GEOM;
+	static constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && !MIRROR && LEAP != 0 && !GEOM;
 	// BAKED with bilinear sampling wants the point like SHADE: KEEP_Q in the leap kernels, KEEP_P in the plain groups.
-	static constexpr bool KEEP_P = LIT || ((SHADE || BAKED) && BILINEAR && !KEEP_Q) || (GEOM && !kGeomChain);
+	// MIRROR wants the point and the threshold like LIT, for the mirror ray's origin -- and the mirror ray's own hit point for its colour.
+	static constexpr bool KEEP_P = LIT || MIRROR || ((SHADE || BAKED) && BILINEAR && !KEEP_Q) || (GEOM && !kGeomChain);
 	static constexpr bool CHAIN = PROJ == 4 || (GEOM && kGeomChain); // (the hit point by RAYS' select chain: hx, hy, hz)
 	static constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	// DEFER: a hit lane's colour is fetched behind the march loop, from the hit cell it leaves the loop with (hcell; the
@@ -186,7 +210,9 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	// (BAKED: behind the loop too -- the light is loaded beside the colour, from the same cell or point -- except in its record
 	// kernels, which keep the interior family's in-loop fetch: deferred, the orthographic one with power-of-two grid widths took
 	// 36 bytes of scratch)
-	static constexpr bool DEFER = GEOM || LSUM || (BAKED && LEAP != 2) || (!CELLS && !(LEAP == 2 && SEG && !LIT && !RAYS) && !(BILINEAR && LEAP == 0));
+	// (MIRROR: as LIT -- behind the loop in its record kernels too, in the loop for the bilinear mode of the plain groups, where a
+	// pass's colour simply lands in `rgba`: DESIGN.md 5.20)
+	static constexpr bool DEFER = GEOM || LSUM || (BAKED && LEAP != 2) || (!CELLS && !(LEAP == 2 && SEG && !LIT && !MIRROR && !RAYS) && !(BILINEAR && LEAP == 0));
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || !STATS, "segment rules: production kernels only");
 	static_assert(!SEG || !AA || LIT || SHADE || BAKED, "segment rules: antialiased for the sun-lit and baked-light frames only");
@@ -194,8 +220,8 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	// CARRY: a ray holds its level state in a register (see the leap state in the march loop).  The cell maps, the sun shadows, the
 	// ray batches and the shaded record kernels sit on a register granule: a register more would cost them a resident wave per SIMD
 	// -- as it would six of the geometry kernels (general grid widths: 73 against 71 vector registers, 81 against 80 with window
-	// records).
-	static constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !RAYS && !((SHADE || BAKED) && REC) && !(GEOM && !kGeomCarry);
+	// records).  (MIRROR: LIT's choice, taken over with its two-pass structure; DESIGN.md 5.20 has the counts.)
+	static constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !MIRROR && !RAYS && !((SHADE || BAKED) && REC) && !(GEOM && !kGeomCarry);
 	static constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
 	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
 };

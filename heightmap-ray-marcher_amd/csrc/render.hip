@@ -87,6 +87,8 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 // 3 (hmrm_render_shaded): pass 2, but a hit leaves lit->rgba alone and says SHADOWED in lit->phase -- the caller weights the pixel;
 // `hit_cell` (pass 1, may be null): where the primary hit's cell index gridx + gridy * W goes, for that caller.
 // 4 (hmrm_cell_map): pass 3 for a ray the caller put into *lit itself; the ray's status (HMRM_RAY_*) comes back in lit->phase.
+// 5 (hmrm_render_water): pass 2 for a mirror ray -- the caller hands the lane's own direction, step and limit in `sun` -- whose pixel,
+// the hit cell's colour or the miss shade of its own dz, comes back in lit->rgba.
 template <int PROJ, bool STATS, bool AA, bool SEG = false, int LIT = 0>
 __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId pid, const double *__restrict__ thr,
                                                     const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
@@ -219,6 +221,8 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 			if (real_hit) lit->phase = 1;
 		} else if constexpr (LIT == 4) {
 			lit->phase = real_hit ? 1 : (my_cap != 0u ? 2 : (sg.ended ? 3 : 0));
+		} else if constexpr (LIT == 5) {
+			lit->rgba = rgba;
 		} else
 		if constexpr (RAYS && SEG) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
 		else if constexpr (RAYS) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, d_box, (uint32_t)my_steps, rgba);
@@ -509,6 +513,33 @@ __global__ __launch_bounds__(kBlockThreads) void k_render_baked_literal(const De
 	else if (pid.live) out[(int64_t)pid.lrow * out_stride_px + pid.px] = rgba;
 }
 
+// A pixel of a water frame (hmrm_render_water with HMRM_KERNEL=simple, or on a map with a side of 2^24 cells; frame.hpp WaterRules):
+// the primary ray of a lit pixel -- its colour, whether it hit, where and under which threshold -- then, for a lane that hit at or
+// below the water level, the literal loop once more for its mirror ray -- the camera's ray made again, with dz negated -- and the
+// blend.  Nearest sampling only, like every literal kernel.
+template <int PROJ>
+__global__ __launch_bounds__(kBlockThreads) void k_render_water_literal(const DevFrame f, const RowMap rows,
+                                                                        const double *__restrict__ thr,
+                                                                        const uint32_t *__restrict__ cmap,
+                                                                        uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                        int tiles_y, StatsOut st, const SegRules seg,
+                                                                        const WaterRules water) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, SunRules{}, &lt);
+	const bool wet = pid.live && lt.primary_hit && lt.t <= water.level; // (a NaN level: no water)
+	LitState<true> mr = lt;
+	mr.primary_hit = wet; // (the other lanes sit the pass out)
+	SunRules mirror{{0.0, 0.0, 0.0}, water.step_dist, water.max_steps, 0u};
+	if (wet) {
+		const DevRay primary = make_ray<PROJ>(f, pid.px, pid.py);
+		mirror.dir[0] = primary.dx; mirror.dir[1] = primary.dy; mirror.dir[2] = -primary.dz;
+	}
+	render_lane_literal<PROJ, false, false, true, 5>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
+	                                                 SegRules{nullptr, water.max_steps, 1u}, mirror, &mr);
+	if (pid.live) out[(int64_t)pid.lrow * out_stride_px + pid.px] = wet ? blend_water(lt.rgba, mr.rgba, water) : lt.rgba;
+}
+
 // Per-ray parity hook: GetRay + distance() of one pixel -> out[0..2] pos, [3..5] dir, [6] d.
 template <int PROJ>
 __global__ void k_probe(const DevFrame f, int px, int py, double *__restrict__ out) {
@@ -690,6 +721,7 @@ static hipError_t launch_plain_literal(const FrameLaunch &l); // (hmrm_render's 
 static hipError_t launch_geometry_literal(const FrameLaunch &l); // (hmrm_render_geometry's, and behind them hmrm_render_lit_sum's:
 static hipError_t launch_lit_sum_literal(const FrameLaunch &l);  //  the last kernels of the code object)
 static hipError_t launch_baked_literal(const FrameLaunch &l);    // (hmrm_render_baked's, behind those)
+static hipError_t launch_water_literal(const FrameLaunch &l);    // (hmrm_render_water's, behind those)
 
 // The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
 // shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
@@ -706,6 +738,7 @@ hipError_t launch_frame_literal(const FrameLaunch &l) {
 	if (l.family == kFrameGeometry) return launch_geometry_literal(l);
 	if (l.family == kFrameLitSum) return launch_lit_sum_literal(l);
 	if (l.family == kFrameBaked) return launch_baked_literal(l);
+	if (l.family == kFrameWater) return launch_water_literal(l);
 	if (l.f.aa_shift == 0) switch (l.family) {
 		case kFrameLit:
 			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
@@ -792,6 +825,15 @@ static hipError_t launch_baked_literal(const FrameLaunch &l) {
 	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
 		if (aa) hipLaunchKernelGGL((k_render_baked_literal<proj(), true>), grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.baked);
 		else hipLaunchKernelGGL((k_render_baked_literal<proj(), false>), grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.baked);
+	});
+}
+
+// A water frame: the interior family's arguments and the water's rules.  No antialiased variant, never a measured launch.
+static hipError_t launch_water_literal(const FrameLaunch &l) {
+	if (l.rows.measure != nullptr || l.f.aa_shift != 0 || !l.d_out) return hipErrorInvalidValue;
+	const SegRules seg = frame_seg_rules(l);
+	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
+		hipLaunchKernelGGL(k_render_water_literal<proj()>, grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.water);
 	});
 }
 

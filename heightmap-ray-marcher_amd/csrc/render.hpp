@@ -54,6 +54,9 @@ struct FrameLaunch {
 	// kFrameBaked (hmrm_render_baked): the frame of the plain or, with primary_interior, the interior family, whose hit pixels
 	// take the weight of the scene's light plane (frame.hpp BakedLight); antialiased with f.aa_shift
 	BakedLight baked = BakedLight{nullptr, 0u};
+	// kFrameWater (hmrm_render_water): the frame of the plain or, with primary_interior, the interior family, whose hit pixels at
+	// or below water.level march a mirror ray in the same launch and take its pixel blended in (frame.hpp WaterRules); no AA
+	WaterRules water = WaterRules{0.0, 0.0, 0u, 0u, 0u, 0u};
 };
 // The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups
 // (kPlainGroups), plus exact leaps over empty pyramid windows (kLeaps), or over windows of the record level that are empty but

@@ -288,6 +288,7 @@ hipError_t launch_frame_march(const FrameLaunch &l, FastKernel kernel) {
 	case kFrameGeometry: return launch_render_geometry(l, kernel); // (refuses a factor)
 	case kFrameLitSum: return launch_render_lit_sum(l, kernel); // (refuses a factor)
 	case kFrameBaked: return aa ? launch_render_baked_aa(l, kernel) : launch_render_baked(l, kernel);
+	case kFrameWater: return launch_render_water(l, kernel); // (refuses a factor)
 	default: return aa ? launch_render_fast_aa(l, kernel) : launch_render_fast(l, kernel);
 	}
 }

@@ -135,6 +135,31 @@ class Sun(C.Structure):
 
 assert C.sizeof(Sun) == 48
 
+WATER_OWN_COLOR = 2  # hmrm_water.flags (HMRM_WATER_OWN_COLOR)
+
+
+class Water(C.Structure):
+    """hmrm_water (32 bytes): the water of Scene.render_water"""
+    _fields_ = [("level", C.c_double), ("step_dist", C.c_double), ("max_steps", C.c_uint32), ("flags", C.c_uint32),
+                ("reflectivity", C.c_uint8), ("color", C.c_uint8 * 3), ("reserved", C.c_uint8 * 4)]
+
+    @classmethod
+    def make(cls, level, step_dist, max_steps=0, reflectivity=128, color=None, interior=False):
+        """level: a hit whose threshold t <= level is water; step_dist of the mirror march, in units of |dir|; max_steps: limit of
+        every mirror ray (0 = none); reflectivity 0..255: the mirror pixel's share; color (r, g, b): the water's own colour
+        instead of the primary pixel (HMRM_WATER_OWN_COLOR); interior: the primary rays under the interior rule."""
+        if not 0 <= int(reflectivity) <= 255:
+            raise ValueError("reflectivity must be 0..255")
+        if color is not None and not all(0 <= int(v) <= 255 for v in color):
+            raise ValueError("color components must be 0..255")
+        rgb = (C.c_uint8 * 3)(*(int(v) for v in color)) if color is not None else (C.c_uint8 * 3)()
+        return cls(float(level), float(step_dist), int(max_steps),
+                   (TRACE_INTERIOR if interior else 0) | (WATER_OWN_COLOR if color is not None else 0), int(reflectivity), rgb,
+                   (C.c_uint8 * 4)())
+
+
+assert C.sizeof(Water) == 32
+
 MAP_TOWARDS_POINT, MAP_WEIGHT, MAP_DIFFUSE, MAP_NO_SHADOWS = 1, 2, 4, 8  # hmrm_cell_map_params.flags (HMRM_MAP_*)
 
 
@@ -273,6 +298,10 @@ def _load():
         "hmrm_render_lit_sum_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, i32, C.c_uint32, C.POINTER(LightPlanes), vp]),
         "hmrm_render_interior": (C.c_int, [vp, C.POINTER(Camera), vp, C.c_size_t]),
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
+        "hmrm_render_water": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), vp, C.c_size_t]),
+        "hmrm_render_water_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), vp, C.c_size_t, vp]),
+        "hmrm_config_water": (i32, [vp]),
+        "hmrm_config_get_water": (None, [vp, C.POINTER(Water)]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
         "hmrm_render_shaded_aa": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, i32, vp, C.c_size_t]),
         "hmrm_render_shaded_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, C.c_uint32, C.POINTER(i32)]),
@@ -369,7 +398,8 @@ lib, EXPORTED_SYMBOLS = _load()
 # collected on, so it carries this hash and bench.py refuses one that does not match the tree.
 KERNEL_SOURCES = ("render_fast.hip", "render_rays.hip", "leap_common.hpp", "leap_diag.hpp", "render.hip", "device_common.hpp", "frame.hpp",
                   "render.hpp", "api_internal.hpp", "api_launch.cpp", "api_frames.cpp", "launch_order.cpp", "launch_order.hpp", "camera.cpp", "Makefile",
-                  "march.hpp", "march_family.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip")
+                  "march.hpp", "march_family.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip",
+                  "render_water.hip")
 
 
 def kernel_src_sha() -> str:
@@ -521,6 +551,23 @@ class Scene:
         _check(lib.hmrm_render_lit(self._h, C.byref(cam), C.byref(sun), _ptr(fb), cam.width * 4),
                allow=(HMRM_E_NOTERM,) if allow_capped else ())
         return fb
+
+    def render_water(self, cam: Camera, water: Water, allow_capped=False) -> np.ndarray:
+        """One full frame with mirror reflections on flat water (hmrm_render_water): render()'s frame -- render_interior()'s with
+        Water.make(..., interior=True) -- in which every hit pixel at or below water.level takes its mirror ray's pixel blended
+        in at water.reflectivity / 255 -> HxWx4 uint8.  Capped primary or mirror rays: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
+        _check(lib.hmrm_render_water(self._h, C.byref(cam), C.byref(water), _ptr(fb), cam.width * 4),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
+    def render_water_device(self, cam: Camera, water: Water, d_rgba: int, stride_bytes: int, stream: int = 0):
+        """hmrm_render_water_device: the same frame into device memory at address d_rgba, rows stride_bytes apart, enqueued on
+        `stream` without a host sync; take_capped(stream) reports the capped rays."""
+        self._sync_env()
+        _check(lib.hmrm_render_water_device(self._h, C.byref(cam), C.byref(water), C.c_void_p(d_rgba), int(stride_bytes),
+                                            C.c_void_p(stream)))
 
     def render_shaded(self, cam: Camera, sun: Sun, diffuse=True, shadows=True, allow_capped=False, aa=1) -> np.ndarray:
         """One full frame with diffuse sun shading (hmrm_render_shaded): render_lit()'s frame in which every hit pixel that is
@@ -1191,6 +1238,17 @@ class Config:
         """The sun of the additive keys sun_dir, shadow_step_dist (absent: step_dist), shadow_max_steps, shadow_ambient, interior."""
         out = Sun()
         lib.hmrm_config_get_sun(self._h, C.byref(out))
+        return out
+
+    def water_on(self) -> bool:
+        """Additive `water on|off`: the CLI renders its single frame with hmrm_render_water."""
+        return bool(lib.hmrm_config_water(self._h))
+
+    def water(self) -> Water:
+        """The water of the additive keys water_level, water_step_dist (absent: step_dist), water_max_steps, water_reflectivity,
+        water_color (sets HMRM_WATER_OWN_COLOR), interior."""
+        out = Water()
+        lib.hmrm_config_get_water(self._h, C.byref(out))
         return out
 
     @property

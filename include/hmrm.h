@@ -726,6 +726,62 @@ int hmrm_render_baked_begin(const hmrm_scene *scene, const hmrm_camera *cam, uin
 int hmrm_render_baked_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t baked_flags, void *d_rgba,
                                    size_t stride_bytes, uint32_t flags, int32_t *ticket);
 
+/* ------------------------------------------------------------ water frames */
+/* hmrm_render with mirror reflections on flat water (build-side addition), exact: lakes and sea are cells at one height, and a
+ * pixel that shows one mirrors the far shore and the sky.  One launch; nothing per pixel goes through memory.
+ * PRIMARY PIXEL.  Every pixel first gets hmrm_render's value -- with HMRM_TRACE_INTERIOR in `flags` hmrm_render_interior's; the
+ * primary march is unchanged.
+ * WATER PIXEL.  A pixel whose primary ray HIT (hmap.cpp:1016 fired; an alpha-0 hit cell counts, as in hmrm_render_lit) has t,
+ * exactly hmrm_render_lit's t: the threshold the hitting load compared z with -- heightmap_buf[c] + min_height (HMRM_NEAREST), the
+ * float entry of that table widened to double (HMRM_NEAREST_F32), the interpolated threshold at P (HMRM_BILINEAR).  The pixel is
+ * WATER when t <= level, compared as doubles, as given: a NaN level gives no water, a level of +inf makes every hit water.
+ * Misses, sky, primary rays stopped by the step cap and hits above the level are untouched and cast nothing.
+ * THE MIRROR RAY.  A water pixel casts one mirror ray, an hmrm_trace_segments ray: pos = (P.x, P.y, t), P the reference's int_point
+ * at the hit; dir = (d.x, d.y, -d.z), d the primary ray's direction as the loop used it -- the reflection off a horizontal plane,
+ * exact in IEEE arithmetic, no normal and no normalisation; water->step_dist, water->max_steps, the camera's sampling mode,
+ * HMRM_TRACE_INTERIOR always on.  Nothing is special-cased: an origin with t >= max_height is not strictly inside and goes through
+ * distance() as written; zero, infinite and NaN components and step_dist = 0 go through the same arithmetic.
+ * THE MIRROR PIXEL m is the mirror ray's pixel as hmrm_ray_hit.rgba defines it: a HIT gives the hit cell's colour (the background
+ * for an alpha-0 cell; HMRM_BILINEAR: interpolated at the mirror ray's hit point); MISS, END and CAPPED give the miss shade of the
+ * mirror ray's own dir.z -- the sky gradient for a ray that rises.
+ * THE STORED PIXEL.  b is the primary pixel, or `color` with HMRM_WATER_OWN_COLOR.  Each of R, G and B becomes
+ * (b * (255 - r) + m * r + 127) / 255 in integers, r = reflectivity; A stays 255.  So r = 0 without HMRM_WATER_OWN_COLOR is
+ * hmrm_render byte for byte (the mirror rays are marched all the same), r = 255 is the pure mirror image, and a level below
+ * every threshold is hmrm_render.
+ * CAPPED RAYS.  Capped primary rays and capped mirror rays are counted together; either kind makes the call return HMRM_E_NOTERM
+ * with a valid frame.  END rays are never counted.  A camera looking straight down casts mirror rays straight up: without
+ * max_steps they never leave the grid and run to the cap.
+ * FLOODING IS THE CALLER'S JOB.  The map is not changed and no cell is made flat: clamp the height image from below at the lake's
+ * luminance L, max(pixel, L), before it goes into the scene, and pass the threshold of L -- heightmap_buf's value of L plus
+ * min_height -- as `level`; add a margin below the next luminance step for HMRM_NEAREST_F32, whose t is a rounded float, and for
+ * HMRM_BILINEAR, whose t is interpolated (INTEGRATION.md 2a has the recipe).  Like the shading arithmetic, the blend is tested at
+ * unit world scale only: world scales beyond it are untested.
+ * Refusals (HMRM_E_ARG, with a message) before the scene is looked at, in this order: NULL water; an undefined flag bit;
+ * reserved != 0.  Then the camera checks of hmrm_render, then a NULL scene or target, then the stride (hmrm_render_water:
+ * stride_bytes < width * 4; hmrm_render_water_device: hmrm_render_rows_device's rule -- >= width * 4, a multiple of 4, below 2^33),
+ * then the 2^24-side rule of frames.
+ * hmrm_render_water is synchronous on the scene's stream.  hmrm_render_water_device takes a DEVICE pointer, launches on
+ * hip_stream, does no host sync and reports capped rays through hmrm_scene_take_capped for its stream -- hmrm_trace_rays_device's
+ * contract.  Both are launched like a lit frame: one launch, never measured, never the scene's probe and not counted towards it,
+ * with the scene's current kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST); every kernel
+ * writes the same bytes, the literal loop too (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest sampling only).  All three
+ * projections, grid modes and sampling modes.
+ * OUT OF SCOPE: antialiased, ticketed, recorded, strip and multi-GPU water frames; water combined with shadows, shading or baked
+ * light; refraction, Fresnel terms, waves; a second bounce. */
+#define HMRM_WATER_OWN_COLOR 2u      /* the water's own colour is `color`, not the primary pixel */
+typedef struct hmrm_water {          /* 32 bytes */
+	double   level;        /* a hit is WATER when t <= level; compared as doubles, as given */
+	double   step_dist;    /* of the mirror march, in units of |dir| */
+	uint32_t max_steps;    /* step limit L of every mirror ray, 0 = none (hmrm_trace_segments' rule) */
+	uint32_t flags;        /* HMRM_TRACE_INTERIOR (primary rays under the interior rule), HMRM_WATER_OWN_COLOR; any other bit: HMRM_E_ARG */
+	uint8_t  reflectivity; /* r, 0..255 */
+	uint8_t  color[3];     /* R, G, B with HMRM_WATER_OWN_COLOR */
+	uint8_t  reserved[4];  /* must be 0 */
+} hmrm_water;
+int hmrm_render_water(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint8_t *rgba, size_t stride_bytes);
+int hmrm_render_water_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, void *d_rgba,
+                             size_t stride_bytes, void *hip_stream);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -919,6 +975,13 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * `shading` then only choose what is baked; `sky_light on` is ignored with "WARNING: sky_light is ignored with baked_light";
  * `devices n` > 1 ignores the key with "WARNING: baked_light is ignored with devices > 1"; another value warns "WARNING:
  * Unknown baked_light: v" and keeps the old one),
+ * `water on|off|1|0` (default off; the CLI renders its single frame with hmrm_render_water under hmrm_config_get_water's water;
+ * ignored, with "WARNING: water is ignored with <what>", beside `antialias n` > 1, `devices n` > 1, `record orbit`, `shadows`,
+ * `shading` and `baked_light`; `sky_light on` beside it is ignored with "WARNING: sky_light is ignored with water"; another value
+ * warns "WARNING: Unknown water: v" and keeps the old one), `water_level v`, `water_reflectivity n` (default 128; outside 0..255:
+ * "WARNING: water_reflectivity must be 0..255", the old value stays), `water_color r g b` (sets HMRM_WATER_OWN_COLOR; a component
+ * outside 0..255: "WARNING: water_color must be three values 0..255"), `water_step_dist v` (absent: step_dist),
+ * `water_max_steps n` (default 0 = none; outside 0..4294967295: "WARNING: water_max_steps must be 0..4294967295"),
  * `range_map <path.pfm>` (echoed like `output`; after its frames and before an optional sun_map the CLI writes the range plane
  * of the configured camera -- hmrm_render_geometry with that plane alone, under the interior rule with `interior on` -- as a
  * one-component portable float map, hmrm_write_pfm).
@@ -955,6 +1018,13 @@ const char  *hmrm_config_range_map_path(const hmrm_config *cfg); /* additive `ra
 /* The sun of the additive keys: sun_dir, shadow_step_dist (the config's step_dist when the key was absent),
  * shadow_max_steps, shadow_ambient; flags = HMRM_TRACE_INTERIOR when `interior on`. */
 void         hmrm_config_get_sun(const hmrm_config *cfg, hmrm_sun *out);
+int32_t      hmrm_config_water(const hmrm_config *cfg);         /* additive `water on|off`: 1|0 */
+/* The water of the additive keys: water_level (default 0), water_step_dist (the config's step_dist when the key was absent),
+ * water_max_steps (default 0 = none; a value outside 0..4294967295 is warned about and ignored), water_reflectivity (default 128;
+ * outside 0..255 likewise), water_color r g b (sets HMRM_WATER_OWN_COLOR; a component outside 0..255 likewise);
+ * flags |= HMRM_TRACE_INTERIOR when `interior on`.  `hmap` renders its single frame with hmrm_render_water when `water on`; the key
+ * is ignored, with a warning, beside `antialias` > 1, `devices` > 1, `record orbit`, `shadows`, `shading` and `baked_light`. */
+void         hmrm_config_get_water(const hmrm_config *cfg, hmrm_water *out);
 /* Loaded maps (owned by cfg): RGB8 / RGBA8; NULL until the key was consumed. */
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *cfg, int32_t *w, int32_t *h);
 const uint8_t *hmrm_config_color_rgba(const hmrm_config *cfg, int32_t *w, int32_t *h);

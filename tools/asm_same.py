@@ -11,10 +11,12 @@ lines are dropped and the `.LBB*` labels are renumbered in order of appearance. 
   identical  the same lines in the same order
   reordered  the same descriptor (registers, scratch, LDS, accumulator offset, ...) and the same lines as a multiset:
              only their order differs
-  changed    anything else, a kernel that only one side has included
+  changed    anything else, a kernel that only the parent has included
+  added      a kernel that only the tree has: a new unit's, or a new kernel of an existing unit
 
 Instruction text is compared as opaque lines.  Prints the counts per unit with the names of the kernels that are not
-identical; the exit status is 1 if any kernel changed."""
+identical; the exit status is 1 if any kernel changed.  Added kernels are named and counted and leave the status alone: a feature
+that brings kernels of its own keeps the existing ones, which is what the status says."""
 import collections
 import os
 import re
@@ -53,6 +55,8 @@ def kernels(text):
 
 def classify(a, b):
     """a, b: (lines, descriptor) of one kernel on either side, or None where the side does not have it."""
+    if a is None and b is not None:
+        return "added"
     if a is None or b is None:
         return "changed"
     if a == b:
@@ -78,7 +82,7 @@ def main(argv):
         result = compare_texts(*texts)
         count = collections.Counter(result.values())
         changed += count["changed"]
-        print(f"{unit}: " + ", ".join(f"{count[c]} {c}" for c in CLASSES))
+        print(f"{unit}: " + ", ".join(f"{count[c]} {c}" for c in CLASSES) + (f", {count['added']} added" if count["added"] else ""))
         for name, c in result.items():
             if c != "identical":
                 print(f"    {c}: {name}")
