@@ -474,10 +474,24 @@ static int check_water(const hmrm_water *w) {
 // With the flag every origin is tested by the kernels, whatever the projection.  `device`: `target` is device memory and the launch
 // goes to `stream` without a host sync; else the frame is staged through the scene's frame buffer, rows packed, and copied to the
 // caller's behind the launch.
+// `factor`, `water_mode` (hmrm_render_water_aa): the super frame box-filtered inside the launch, as hmrm_render_aa's, and
+// HMRM_WATER_BAKED, the frame under the scene's light plane; hmrm_render_water and hmrm_render_water_device come with 1 and 0.
+static int check_water_mode(uint32_t water_mode) {
+	if (water_mode & ~HMRM_WATER_BAKED) return fail(HMRM_E_ARG, "water_mode: undefined bit");
+	return HMRM_OK;
+}
+static hmrm::WaterRules water_rules_of(const hmrm_water *w) {
+	return hmrm::WaterRules{w->level, w->step_dist, w->max_steps, (uint32_t)w->reflectivity,
+	                        (uint32_t)w->color[0] | ((uint32_t)w->color[1] << 8) | ((uint32_t)w->color[2] << 16),
+	                        w->flags & HMRM_WATER_OWN_COLOR};
+}
 static int render_water_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm_water *w, void *target, size_t stride_bytes,
-                               bool device, hipStream_t stream) {
+                               bool device, hipStream_t stream, int32_t factor, uint32_t water_mode) {
 	int rc = check_water(w);
-	if (rc || (rc = check_camera(cam))) return rc;
+	if (rc || (rc = check_water_mode(water_mode)) || (rc = check_camera(cam))) return rc;
+	hmrm_camera super;
+	int aa_shift = 0;
+	if ((rc = check_antialias(cam, factor, &super, &aa_shift))) return rc;
 	if (!s || !target) return fail(HMRM_E_ARG, "NULL argument");
 	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
 	if (device) {
@@ -487,6 +501,8 @@ static int render_water_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm
 	std::lock_guard<std::mutex> lk(s->mu);
 	uint32_t *d_rgba = (uint32_t *)target;
 	int64_t stride_px = (int64_t)(stride_bytes / 4);
+	hmrm::BakedLight baked{nullptr, 0u};
+	if ((water_mode & HMRM_WATER_BAKED) && (rc = baked_light_of(s, &baked))) return rc;
 	if (!device) {
 		if ((rc = s->d_frame.reserve(W * H * sizeof(uint32_t)))) return rc;
 		d_rgba = s->d_frame.as<uint32_t>();
@@ -494,14 +510,13 @@ static int render_water_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm
 		stream = s->stream;
 	}
 	FrameSetup fs;
-	if ((rc = setup_frame(s, stream, cam, 0, &fs))) return rc;
+	if ((rc = setup_frame(s, stream, &super, aa_shift, &fs))) return rc;
 	StreamCtx *const c = fs.c;
-	const hmrm::WaterRules rules{w->level, w->step_dist, w->max_steps, (uint32_t)w->reflectivity,
-	                             (uint32_t)w->color[0] | ((uint32_t)w->color[1] << 8) | ((uint32_t)w->color[2] << 16),
-	                             w->flags & HMRM_WATER_OWN_COLOR};
+	const hmrm::WaterRules rules = water_rules_of(w);
 	FrameRequest req = plain_request(d_rgba, stride_px);
 	req.interior = (w->flags & HMRM_TRACE_INTERIOR) ? Interior::kByKernels : Interior::kNot;
 	req.water = &rules;
+	if (water_mode & HMRM_WATER_BAKED) req.baked = &baked;
 	if (!device) HIP_TRY(hipEventRecord(s->ev0, s->stream)); // (the host form is timed like hmrm_render: hmrm_last_kernel_ms)
 	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req)) || device) return rc;
 	HIP_TRY(hipEventRecord(s->ev1, s->stream));
@@ -514,12 +529,17 @@ static int render_water_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm
 }
 
 int hmrm_render_water(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint8_t *rgba, size_t stride_bytes) {
-	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, rgba, stride_bytes, false, nullptr);
+	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, rgba, stride_bytes, false, nullptr, 1, 0u);
+}
+
+int hmrm_render_water_aa(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint32_t water_mode, int32_t factor,
+                         uint8_t *rgba, size_t stride_bytes) {
+	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, rgba, stride_bytes, false, nullptr, factor, water_mode);
 }
 
 int hmrm_render_water_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, void *d_rgba,
                              size_t stride_bytes, void *hip_stream) {
-	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, d_rgba, stride_bytes, true, (hipStream_t)hip_stream);
+	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, d_rgba, stride_bytes, true, (hipStream_t)hip_stream, 1, 0u);
 }
 
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,
@@ -727,9 +747,27 @@ static int apply_baked(const hmrm_scene *s, const BakedTicket &bt, hmrm::BakedLi
 	return HMRM_OK;
 }
 
+// A water ticket (hmrm_render_water_begin, hmrm_render_water_device_begin): the rules, made from the caller's hmrm_water before the
+// begin and copied into the launch; `baked`: under the light plane, looked up under the lock as a baked ticket's is.
+struct WaterTicket {
+	const hmrm::WaterRules *rules = nullptr;
+	bool baked = false;
+	bool interior = false;
+};
+static int apply_water(const hmrm_scene *s, const WaterTicket &wt, hmrm::BakedLight *light, FrameRequest *req) {
+	if (!wt.rules) return HMRM_OK;
+	if (wt.baked) {
+		if (const int rc = baked_light_of(s, light)) return rc;
+		req->baked = light;
+	}
+	req->water = wt.rules;
+	req->interior = wt.interior ? Interior::kByKernels : Interior::kNot;
+	return HMRM_OK;
+}
+
 // `lit` (hmrm_render_shaded_begin): the ticket's frame is a lit one -- launched the way a lit frame is (launch_frame), on the lane.
 static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_t flags, int32_t *ticket, const LitFrame *lit,
-                        const BakedTicket &bt = BakedTicket{}) {
+                        const BakedTicket &bt = BakedTicket{}, const WaterTicket &wt = WaterTicket{}) {
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	hmrm_camera super;
 	int aa_shift = 0;
@@ -740,7 +778,7 @@ static int begin_common(const hmrm_scene *scene, const hmrm_camera *cam, uint32_
 	std::lock_guard<std::mutex> lk(s->mu);
 	hmrm::BakedLight light{nullptr, 0u};
 	FrameRequest req = ticket_request(nullptr, (int64_t)W, flags, lit);
-	if ((rc = apply_baked(s, bt, &light, &req))) return rc;
+	if ((rc = apply_baked(s, bt, &light, &req)) || (rc = apply_water(s, wt, &light, &req))) return rc;
 	int idx = -1;
 	if ((rc = acquire_ticket(s->ring, "hmrm_render_begin", "every frame of the ring is in use (release one)", &idx))) return rc;
 	RingFrame *r = s->ring[(size_t)idx];
@@ -814,7 +852,8 @@ int hmrm_render_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, vo
 }
 
 static int device_begin_common(const hmrm_scene *scene, const hmrm_camera *cam, void *d_rgba, size_t stride_bytes, uint32_t flags,
-                               int32_t *ticket, const LitFrame *lit, const BakedTicket &bt = BakedTicket{}) {
+                               int32_t *ticket, const LitFrame *lit, const BakedTicket &bt = BakedTicket{},
+                               const WaterTicket &wt = WaterTicket{}) {
 	hmrm_scene *s = const_cast<hmrm_scene *>(scene);
 	hmrm_camera super;
 	int aa_shift = 0;
@@ -824,7 +863,7 @@ static int device_begin_common(const hmrm_scene *scene, const hmrm_camera *cam, 
 	std::lock_guard<std::mutex> lk(s->mu);
 	hmrm::BakedLight light{nullptr, 0u};
 	FrameRequest req = ticket_request((uint32_t *)d_rgba, (int64_t)(stride_bytes / 4), flags, lit);
-	if ((rc = apply_baked(s, bt, &light, &req))) return rc;
+	if ((rc = apply_baked(s, bt, &light, &req)) || (rc = apply_water(s, wt, &light, &req))) return rc;
 	int idx = -1;
 	if ((rc = acquire_ticket(s->dev_tickets, "hmrm_render_device_begin", "64 frames in flight (wait for one)", &idx))) return rc;
 	DevTicket *t = s->dev_tickets[(size_t)idx];
@@ -863,6 +902,26 @@ int hmrm_render_baked_device_begin(const hmrm_scene *scene, const hmrm_camera *c
                                    size_t stride_bytes, uint32_t flags, int32_t *ticket) {
 	if (const int rc = check_baked_flags(baked_flags)) return rc;
 	return device_begin_common(scene, cam, d_rgba, stride_bytes, flags, ticket, nullptr, BakedTicket{true, (baked_flags & HMRM_TRACE_INTERIOR) != 0u});
+}
+
+// Water tickets: from the same ring, lanes and pool once more.  HMRM_NO_PROBE is accepted and has no effect: a water frame is
+// never the probe.
+int hmrm_render_water_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint32_t water_mode, uint32_t flags,
+                            int32_t *ticket) {
+	int rc = check_water(water);
+	if (rc || (rc = check_water_mode(water_mode))) return rc;
+	const hmrm::WaterRules rules = water_rules_of(water);
+	return begin_common(scene, cam, flags, ticket, nullptr, BakedTicket{},
+	                    WaterTicket{&rules, (water_mode & HMRM_WATER_BAKED) != 0u, (water->flags & HMRM_TRACE_INTERIOR) != 0u});
+}
+
+int hmrm_render_water_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint32_t water_mode,
+                                   void *d_rgba, size_t stride_bytes, uint32_t flags, int32_t *ticket) {
+	int rc = check_water(water);
+	if (rc || (rc = check_water_mode(water_mode))) return rc;
+	const hmrm::WaterRules rules = water_rules_of(water);
+	return device_begin_common(scene, cam, d_rgba, stride_bytes, flags, ticket, nullptr, BakedTicket{},
+	                           WaterTicket{&rules, (water_mode & HMRM_WATER_BAKED) != 0u, (water->flags & HMRM_TRACE_INTERIOR) != 0u});
 }
 
 int hmrm_render_device_wait(const hmrm_scene *scene, int32_t ticket) {
@@ -925,4 +984,8 @@ int32_t hmrm_band_local_rows(int32_t height, int32_t band_rows, int32_t band_ind
 namespace hmrm {
 int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags) { return check_shaded(sun, shade_flags); } // (record.cpp)
 int check_baked_args(uint32_t baked_flags) { return check_baked_flags(baked_flags); }                         // (likewise)
+int check_water_args(const hmrm_water *water, uint32_t water_mode) {                                          // (likewise)
+	const int rc = check_water(water);
+	return rc ? rc : check_water_mode(water_mode);
+}
 } // namespace hmrm

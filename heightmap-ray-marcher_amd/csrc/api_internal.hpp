@@ -291,7 +291,8 @@ struct FrameRequest {
 	// primary rays are under the interior rule when `interior` is not kNot, as a geometry frame's are.
 	const hmrm::BakedLight *baked = nullptr;
 	// hmrm_render_water's frame: the water level, the mirror march and the blend; null: none.  Its primary rays are under the
-	// interior rule when `interior` is not kNot, as a geometry frame's are.
+	// interior rule when `interior` is not kNot, as a geometry frame's are.  With `baked` too (hmrm_render_water_aa with
+	// HMRM_WATER_BAKED): the water frame under the light plane.
 	const hmrm::WaterRules *water = nullptr;
 	// Frames under the interior rule, with a sun, with geometry planes, with baked light or with water run kernels of their own,
 	// with the scene's current kernel kind (HMRM_KERNEL or the probe's verdict, read only).

@@ -153,8 +153,10 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		l.baked = *req.baked;
 		l.primary_interior = req.interior != Interior::kNot;
 	}
-	if (req.water) { // (likewise)
-		l.family = hmrm::kFrameWater;
+	if (req.water) { // (likewise; with the light plane and / or a factor: one of the water family's three other kinds)
+		const bool aa = f.aa_shift != 0;
+		if (req.baked) l.family = aa ? hmrm::kFrameWaterBakedAA : hmrm::kFrameWaterBaked;
+		else l.family = aa ? hmrm::kFrameWaterAA : hmrm::kFrameWater;
 		l.water = *req.water;
 		l.primary_interior = req.interior != Interior::kNot;
 	}

@@ -65,6 +65,9 @@ struct Config {
 	double water_step_dist = 0.0;
 	bool have_water_step_dist = false;
 	long long water_max_steps = 0;
+	// additive: `water_scope frame|all` -- 0: water applies to the plain single frame only; 1: also with `antialias n` > 1
+	// (hmrm_render_water_aa), to `record orbit` (hmrm_record_orbit_water) and under `baked_light` (HMRM_WATER_BAKED)
+	int water_scope = 0;
 	// additive: `sun_scope single|all` -- 0: shadows / shading apply to the plain single frame only; 1: also with `antialias n` > 1
 	// (hmrm_render_shaded_aa) and to `record orbit` (hmrm_record_orbit_shaded)
 	int sun_scope = 0;

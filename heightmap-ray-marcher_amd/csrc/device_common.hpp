@@ -127,6 +127,17 @@ __device__ __forceinline__ uint32_t shade_shadowed(uint32_t rgba, uint32_t ambie
 // Water frames (frame.hpp WaterRules; hmrm_render_water, MIRROR in the kernels): the stored pixel of a water lane -- the base b,
 // the primary pixel or the water's own colour, and the mirror ray's pixel m mixed per channel, (b * (255 - r) + m * r + 127) / 255
 // in integers; A stays 255.  r = 0 gives b back, r = 255 gives m.
+// (blend_water_base: the mix alone, over a base the caller has chosen -- and, under baked light, weighted -- already.)
+__device__ __forceinline__ uint32_t water_base(uint32_t primary, const WaterRules &w) {
+	return (w.flags & kWaterOwnColor) != 0u ? w.own : primary;
+}
+__device__ __forceinline__ uint32_t blend_water_base(uint32_t b, uint32_t mirror, const WaterRules &w) {
+	const uint32_t r = w.reflectivity, k = 255u - r;
+	const uint32_t c0 = ((b & 255u) * k + (mirror & 255u) * r + 127u) / 255u;
+	const uint32_t c1 = (((b >> 8) & 255u) * k + ((mirror >> 8) & 255u) * r + 127u) / 255u;
+	const uint32_t c2 = (((b >> 16) & 255u) * k + ((mirror >> 16) & 255u) * r + 127u) / 255u;
+	return c0 | (c1 << 8) | (c2 << 16) | 0xff000000u;
+}
 __device__ __forceinline__ uint32_t blend_water(uint32_t primary, uint32_t mirror, const WaterRules &w) {
 	const uint32_t b = (w.flags & kWaterOwnColor) != 0u ? w.own : primary;
 	const uint32_t r = w.reflectivity, k = 255u - r;

@@ -23,7 +23,9 @@
 // `range_map <path.pfm>`: after the frames and before the sun map, the range plane of the configured camera (hmrm_render_geometry).
 // `water on`: the single frame with mirror reflections at or below `water_level` (hmrm_render_water; under the interior rule too
 // when `interior on`); ignored, with a warning, beside `antialias` > 1, `devices` > 1, `record orbit`, `shadows`, `shading` and
-// `baked_light`.
+// `baked_light`.  `water_scope all` lifts three of them: with `antialias n` > 1 the single frame is the antialiased water frame
+// (hmrm_render_water_aa), `record orbit` records water frames (hmrm_record_orbit_water, antialiased with `antialias n`), and
+// `baked_light sun|sky` bakes as usual and then renders those under the plane (HMRM_WATER_BAKED).
 #include <sys/stat.h>
 
 #include <cmath>
@@ -220,6 +222,8 @@ int main(int argc, char *argv[]) {
 	// `sun_scope all`: shadows / shading also apply to antialiased and recorded frames
 	const bool sun_all = hmrm_config_sun_scope(cfg) != 0 && (shadows || shading);
 	const uint32_t shade_flags = shading ? (HMRM_SHADE_DIFFUSE | (shadows ? 0u : HMRM_SHADE_NO_SHADOWS)) : 0u;
+	// `water_scope all`: water also applies to antialiased, recorded and baked-light frames
+	const bool water_all = hmrm_config_water_scope(cfg) != 0 && hmrm_config_water(cfg) != 0;
 	hmrm_scene *scene = NULL;
 	if (hmrm_config_create_scene(cfg, &scene) != HMRM_OK) {
 		std::cerr << hmrm_last_error() << "\n";
@@ -237,13 +241,23 @@ int main(int argc, char *argv[]) {
 			std::cerr << "WARNING: sky_light is ignored with baked_light\n";
 			sky_light = false;
 		}
-		if (!sun_all && !baked) {
+		// (`water_scope all`: the orbit's frames are water frames -- on one device, and beside shadows or shading only under baked light)
+		bool water_orbit = water_all;
+		if (water_orbit) {
+			const char *beside = wanted_devices(cfg, &visible_rec) > 1 ? "devices > 1"
+			                     : baked ? nullptr : shadows ? "shadows" : shading ? "shading" : nullptr;
+			if (beside) {
+				std::cerr << "WARNING: water is ignored with " << beside << "\n";
+				water_orbit = false;
+			}
+		}
+		if (!sun_all && !baked && !water_orbit) {
 			if (interior) std::cerr << "WARNING: interior is ignored with record orbit\n";
 			if (shadows) std::cerr << "WARNING: shadows is ignored with record orbit\n";
 			if (shading) std::cerr << "WARNING: shading is ignored with record orbit\n";
 		}
 		if (sky_light) std::cerr << "WARNING: sky_light is ignored with record orbit\n";
-		if (hmrm_config_water(cfg) != 0) std::cerr << "WARNING: water is ignored with record orbit\n";
+		if (hmrm_config_water(cfg) != 0 && !water_all) std::cerr << "WARNING: water is ignored with record orbit\n";
 		// `record orbit`: recording_frame_count frames on a circle around the map centre through
 		// the configured camera position, always looking at the centre;
 		// files screenshots/hmap_<epoch>_<n>.png as hmap.cpp:1131-1144.
@@ -274,7 +288,15 @@ int main(int argc, char *argv[]) {
 			if (rc == HMRM_OK) rc = hmrm_config_create_scene(cfg, &extra);
 			if (rc == HMRM_OK) scenes.push_back(extra);
 		}
-		if (rc == HMRM_OK && baked) {
+		if (rc == HMRM_OK && water_orbit) {
+			hmrm_water w;
+			hmrm_config_get_water(cfg, &w);
+			if (baked && !bake_light(cfg, scene, cam, baked_mode, shading, shadows)) rc = HMRM_E_DEVICE;
+			else
+				rc = hmrm_record_orbit_water(scenes.data(), (int32_t)scenes.size(), &cam, cx, cy, radius, hang0,
+				                             hmrm_config_recording_frame_count(cfg), dir.c_str(), (long long)id, 0, 1,
+				                             aa > 1 ? HMRM_AA(aa) : 0u, &w, baked ? HMRM_WATER_BAKED : 0u);
+		} else if (rc == HMRM_OK && baked) {
 			if (!bake_light(cfg, scene, cam, baked_mode, shading, shadows)) rc = HMRM_E_DEVICE;
 			else
 				rc = hmrm_record_orbit_baked(scenes.data(), (int32_t)scenes.size(), &cam, cx, cy, radius, hang0,
@@ -311,8 +333,11 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: sky_light is ignored with baked_light\n";
 		sky_light = false;
 	}
+	// (`water_scope all`: the single frame is a water frame whatever the factor, under the baked plane too -- on one device, and
+	// beside shadows or shading only under baked light)
+	const bool water_wide = water_all && want_dev <= 1 && (baked || (!shadows && !shading));
 	const bool lit_aa = sun_all && want_dev <= 1 && aa > 1 && !baked; // (the antialiased lit single frame)
-	if (interior && !lit_aa && !baked && (want_dev > 1 || aa > 1))
+	if (interior && !lit_aa && !baked && !water_wide && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: interior is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
 	if (shadows && !lit_aa && !baked && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: shadows is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
@@ -322,6 +347,13 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: sky_light is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
 	// `water on`: the single frame with mirror reflections at or below `water_level` (hmrm_render_water) -- the plain frame's only
 	bool water = hmrm_config_water(cfg) != 0;
+	if (water && water_all) {
+		const char *beside = want_dev > 1 ? "devices > 1" : baked ? nullptr : shadows ? "shadows" : shading ? "shading" : nullptr;
+		if (beside) {
+			std::cerr << "WARNING: water is ignored with " << beside << "\n";
+			water = false;
+		}
+	} else
 	if (water) {
 		const char *beside = aa > 1 ? "antialias > 1" : want_dev > 1 ? "devices > 1" : shadows ? "shadows" : shading ? "shading"
 		                     : baked_mode != 0 ? "baked_light" : nullptr;
@@ -334,7 +366,21 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: sky_light is ignored with water\n";
 		sky_light = false;
 	}
-	if (water) {
+	if (water && water_all) {
+		// the single frame, antialiased or not, under the light plane baked here or under none
+		hmrm_water w;
+		hmrm_config_get_water(cfg, &w);
+		if (baked && !bake_light(cfg, scene, cam, baked_mode, shading, shadows)) return 1;
+		rc = hmrm_render_water_aa(scene, &cam, &w, baked ? HMRM_WATER_BAKED : 0u, aa, framebuf.data(), (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height * aa * aa << " rays with water at level " << w.level
+		          << (aa > 1 ? " at antialias " + std::to_string(aa) : std::string()) << (baked ? " under baked light" : "")
+		          << (interior ? " under the interior rule" : "") << "\n";
+	} else if (water) {
 		hmrm_water w;
 		hmrm_config_get_water(cfg, &w);
 		rc = hmrm_render_water(scene, &cam, &w, framebuf.data(), (size_t)cam.width * 4);

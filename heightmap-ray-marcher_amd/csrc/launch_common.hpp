@@ -61,7 +61,10 @@ hipError_t launch_render_geometry(const FrameLaunch &l, FastKernel kernel);     
 hipError_t launch_render_lit_sum(const FrameLaunch &l, FastKernel kernel);       // render_lit_sum.hip (no AA variant)
 hipError_t launch_render_baked(const FrameLaunch &l, FastKernel kernel);         // render_baked.hip
 hipError_t launch_render_baked_aa(const FrameLaunch &l, FastKernel kernel);      // render_baked_aa.hip
-hipError_t launch_render_water(const FrameLaunch &l, FastKernel kernel);         // render_water.hip (no AA variant)
+hipError_t launch_render_water(const FrameLaunch &l, FastKernel kernel);         // render_water.hip
+hipError_t launch_render_water_aa(const FrameLaunch &l, FastKernel kernel);      // render_water_aa.hip
+hipError_t launch_render_water_baked(const FrameLaunch &l, FastKernel kernel);   // render_water_baked.hip
+hipError_t launch_render_water_baked_aa(const FrameLaunch &l, FastKernel kernel); // render_water_baked_aa.hip
 
 // The segment rules of a frame launch: no limits, the interior rule for the interior family and where the sun's flags ask.
 inline SegRules frame_seg_rules(const FrameLaunch &l) {

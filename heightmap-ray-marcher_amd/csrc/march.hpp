@@ -2,7 +2,7 @@
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
 // render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
 // counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip, render_lit_sum.hip, render_baked.hip,
-// render_baked_aa.hip and render_water.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
+// render_baked_aa.hip, render_water.hip, render_water_aa.hip, render_water_baked.hip and render_water_baked_aa.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
 // switch and derived constant with its reasons.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
@@ -908,6 +908,20 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 						keep = rgba;
 					}
 					const bool wet = real_hit && lt.t <= a.water.level; // (a NaN level: no water)
+					if constexpr (BAKED && !kMirrorKeepsCell) {
+						// (under baked light, keeps-pixel form: the base -- the primary pixel, or for a wet lane with its own colour that
+						// colour -- takes the weight of the primary hit's light here, where the point and the cell are at hand; A stays
+						// 255, so the packing below holds.  The keeps-cell form weights behind both marches, from the kept cell.)
+						if (real_hit) {
+							uint32_t light;
+							if constexpr (BILINEAR) {
+								double qxl, qyl;
+								cell_coords_of(lt.hx, lt.hy, qxl, qyl);
+								light = baked_light_bilinear(a.baked.plane, bil_setup(qxl, qyl, f.map_w, f.map_h));
+							} else light = a.baked.plane[hcell];
+							keep = shade_baked(wet ? water_base(keep, a.water) : keep, light, a.baked.full_scale);
+						}
+					}
 					lt.rgba = (keep & kMirrorValue) | (real_hit ? kMirrorHit : 0u) | (wet ? kMirrorWet : 0u);
 					if (__builtin_amdgcn_ballot_w64(wet) != 0ull) {
 						lt.phase = 1;
@@ -986,6 +1000,10 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				uint32_t kept;
 				if constexpr (kMirrorKeepsCell) kept = shade_hit(f, cmap[lt.rgba & kMirrorValue]);
 				else kept = lt.rgba | 0xff000000u;
+				if constexpr (BAKED && kMirrorKeepsCell) { // (the base under the primary hit's light: the plane's word beside the colour, from the kept cell)
+					const uint32_t light = a.baked.plane[lt.rgba & kMirrorValue];
+					kept = shade_baked((lt.rgba & kMirrorWet) != 0u ? water_base(kept, a.water) : kept, light, a.baked.full_scale) | 0xff000000u;
+				}
 				if ((lt.rgba & kMirrorWet) != 0u) {
 					uint32_t m = rgba; // (the in-loop fetch's, where the family keeps that)
 					if constexpr (DEFER) {
@@ -996,7 +1014,19 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							} else m = shade_hit(f, cmap[hcell]);
 						}
 					}
+					if constexpr (BAKED) { // (the mirror pixel under the light of the mirror ray's own hit: its cell, or its point)
+						if (real_hit) {
+							uint32_t light;
+							if constexpr (BILINEAR) {
+								cell_coords_of(lt.hx, lt.hy, qxh, qyh);
+								light = baked_light_bilinear(a.baked.plane, bil_setup(qxh, qyh, f.map_w, f.map_h));
+							} else light = a.baked.plane[hcell];
+							m = shade_baked(m, light, a.baked.full_scale);
+						}
+					}
 					if (!real_hit) m = shade_miss(f, ray.dz);
+					if constexpr (BAKED) kept = blend_water_base(kept, m, a.water); // (the base is chosen and weighted already)
+					else
 					kept = blend_water(kept, m, a.water);
 				}
 				rgba = kept;
@@ -1045,7 +1075,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				rgba = shade_weighted(rgba, shade_weight(a.sun.ambient, q));
 			}
 		}
-		if constexpr (BAKED) { // (every hit pixel at the weight of its baked light; an alpha-0 hit cell's background too)
+		if constexpr (BAKED && !MIRROR) { // (every hit pixel at the weight of its baked light; an alpha-0 hit cell's background too; MIRROR has weighted its own)
 			if (real_hit) {
 				uint32_t light;
 				if constexpr (BILINEAR) light = baked_light_bilinear(a.baked.plane, bil_setup(qxh, qyh, f.map_w, f.map_h));

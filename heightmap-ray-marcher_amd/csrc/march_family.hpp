@@ -161,6 +161,18 @@ struct Water : Frames {
 	static constexpr bool SEG = true, MIRROR = true;
 	struct Args { const SegRules &seg; const WaterRules &water; };
 };
+// MIRROR and BAKED (render_water_baked.hip, render_water_baked_aa.hip; hmrm_render_water_aa with HMRM_WATER_BAKED): the water frame
+// under the scene's light plane.  The two definitions composed: the primary pixel (or the water's own colour) takes the weight of the
+// primary hit's light, the mirror pixel that of the mirror ray's hit, then the blend.  In the keeps-cell form (march.hpp
+// kMirrorKeepsCell) both lights are loaded behind the marches, beside the colours, from the kept cell and from hcell -- nothing new
+// is held across the mirror march; in the keeps-pixel form the primary pixel is weighted at the phase switch, where its point or
+// cell is at hand, before it goes into the kept word.  BAKED's own epilogue does not run (the pixel would be weighted twice).
+// DEFER and CARRY are MIRROR's.  Antialiased<Water> and Antialiased<BakedWater> (render_water_aa.hip, render_water_baked_aa.hip): every
+// sample decides "water" on its own, casts its own mirror ray and is weighted and blended before the box filter.
+struct BakedWater : Frames {
+	static constexpr bool SEG = true, MIRROR = true, BAKED = true;
+	struct Args { const SegRules &seg; const WaterRules &water; const BakedLight &baked; };
+};
 
 // ---- a family: its tag's switches, the four dispatched values, and what follows from them ----
 // SAMP: 0 nearest cell (the reference), 1 bilinear quality mode, 2 nearest cell with float thresholds (`thr` then points at the
@@ -175,12 +187,10 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	static_assert(!MIRROR || !CELLS, "water frames: a camera's frame, not a cell map");
 	static_assert(!MIRROR || PROJ != 4, "water frames: a camera's frame, not a ray batch");
 	static_assert(!MIRROR || !STATS, "water frames: production kernels only");
-	static_assert(!MIRROR || !AA, "water frames: not antialiased");
 	static_assert(!MIRROR || !LIT, "water frames: no sun shadows");
 	static_assert(!MIRROR || !SHADE, "water frames: no sun shading");
 	static_assert(!MIRROR || !GEOM, "water frames: no geometry planes");
-	static_assert(!MIRROR || !BAKED, "water frames: no baked light");
-	static_assert(!BAKED || (SEG && !CELLS && PROJ != 4 && !STATS && !LIT && !SHADE && !GEOM), "baked-light frames: plain frames under the segment rules");
+	static_assert(!BAKED || (SEG && !CELLS && PROJ != 4 && !STATS && !LIT && !SHADE && !GEOM), "baked-light frames: plain or water frames under the segment rules");
 	static_assert(!LSUM || (LIT && !SHADE && !AA), "accumulated lit frames: the lit kernels' marches, the weights by a run-time flag");
 	static_assert(!GEOM || (SEG && !CELLS && PROJ != 4 && !STATS && !AA && !LIT && !SHADE), "geometry frames: plain frames under the segment rules");
 	static_assert(!SUM || CELLS, "accumulated cell maps: the cell kernels' march, once per target");
@@ -211,11 +221,11 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	// kernels, which keep the interior family's in-loop fetch: deferred, the orthographic one with power-of-two grid widths took
 	// 36 bytes of scratch)
 	// (MIRROR: as LIT -- behind the loop in its record kernels too, in the loop for the bilinear mode of the plain groups, where a
-	// pass's colour simply lands in `rgba`: DESIGN.md 5.20)
-	static constexpr bool DEFER = GEOM || LSUM || (BAKED && LEAP != 2) || (!CELLS && !(LEAP == 2 && SEG && !LIT && !MIRROR && !RAYS) && !(BILINEAR && LEAP == 0));
+	// pass's colour simply lands in `rgba`: DESIGN.md 5.20; with BAKED too: MIRROR's choice stands)
+	static constexpr bool DEFER = GEOM || LSUM || (BAKED && !MIRROR && LEAP != 2) || (!CELLS && !(LEAP == 2 && SEG && !LIT && !MIRROR && !RAYS) && !(BILINEAR && LEAP == 0));
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || !STATS, "segment rules: production kernels only");
-	static_assert(!SEG || !AA || LIT || SHADE || BAKED, "segment rules: antialiased for the sun-lit and baked-light frames only");
+	static_assert(!SEG || !AA || LIT || SHADE || BAKED || MIRROR, "segment rules: antialiased for the sun-lit, baked-light and water frames only");
 	static constexpr bool REC = LEAP == 2; // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
 	// CARRY: a ray holds its level state in a register (see the leap state in the march loop).  The cell maps, the sun shadows, the
 	// ray batches and the shaded record kernels sit on a register granule: a register more would cost them a resident wave per SIMD

@@ -33,10 +33,14 @@ namespace hmrm {
 int set_error(int code, const char *msg); // (api_scene.cpp: hmrm_last_error's text)
 int check_shaded_args(const hmrm_sun *sun, uint32_t shade_flags); // (api_frames.cpp: the refusals of hmrm_render_shaded_begin's sun)
 int check_baked_args(uint32_t baked_flags);                       // (likewise: hmrm_render_baked_begin's baked_flags)
+int check_water_args(const hmrm_water *water, uint32_t water_mode); // (likewise: hmrm_render_water_begin's water and water_mode)
 }
 
-// What the frames of a sweep are: plain tickets, lit ones (sun, shade_flags) or baked ones (baked_flags).
+// What the frames of a sweep are: plain tickets, lit ones (sun, shade_flags), baked ones (baked_flags) or water ones (water,
+// water_mode).
 struct OrbitFrames {
+	const hmrm_water *water = nullptr;
+	uint32_t water_mode = 0u;
 	const hmrm_sun *sun = nullptr;
 	uint32_t shade_flags = 0u;
 	bool baked = false;
@@ -93,6 +97,19 @@ int hmrm_record_orbit_baked(hmrm_scene *const *scenes, int32_t n_scenes, const h
 	                           what);
 }
 
+// hmrm_record_orbit_flags whose frames are water tickets (hmrm_render_water_begin with `water`, `water_mode` and `flags`).  The
+// water is copied; with HMRM_WATER_BAKED every scene must have a light plane.  Refused before any frame.
+int hmrm_record_orbit_water(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
+                            double centre_y, double radius, double hang0, int32_t frames, const char *dir, long long id,
+                            int32_t encoder_threads, int32_t verbose, uint32_t flags, const hmrm_water *water, uint32_t water_mode) {
+	if (const int rc_w = hmrm::check_water_args(water, water_mode)) return rc_w;
+	OrbitFrames what;
+	what.water = water;
+	what.water_mode = water_mode;
+	return record_orbit_common(scenes, n_scenes, base, centre_x, centre_y, radius, hang0, frames, dir, id, encoder_threads, verbose, flags,
+	                           what);
+}
+
 } // extern "C"
 
 static int record_orbit_common(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x, double centre_y,
@@ -107,16 +124,21 @@ static int record_orbit_common(hmrm_scene *const *scenes, int32_t n_scenes, cons
 		if (const int rc_sun = hmrm::check_shaded_args(sun, shade_flags)) return rc_sun;
 	const bool lit = sun != nullptr;
 	const hmrm_sun the_sun = lit ? *sun : hmrm_sun{};
+	const bool wet = what.water != nullptr; // (checked by the entry point)
+	const hmrm_water the_water = wet ? *what.water : hmrm_water{};
+	const bool need_plane = what.baked || (wet && (what.water_mode & HMRM_WATER_BAKED) != 0u);
 	if (!scenes || n_scenes <= 0 || !base || !dir || frames <= 0)
 		return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit: bad argument");
 	for (int i = 0; i < n_scenes; ++i)
 		if (!scenes[i]) return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit: NULL scene");
 	if (base->width <= 0 || base->height <= 0) return hmrm::set_error(HMRM_E_ARG, "resolution must be positive");
-	if (what.baked)
+	if (need_plane)
 		for (int i = 0; i < n_scenes; ++i) {
 			uint32_t full_scale = 0u;
 			if (const int rc_l = hmrm_scene_light(scenes[i], nullptr, 0, &full_scale)) return rc_l;
-			if (full_scale == 0u) return hmrm::set_error(HMRM_E_ARG, "hmrm_record_orbit_baked: the scene has no light plane");
+			if (full_scale == 0u)
+				return hmrm::set_error(HMRM_E_ARG, wet ? "hmrm_record_orbit_water: the scene has no light plane"
+				                                       : "hmrm_record_orbit_baked: the scene has no light plane");
 		}
 	const size_t W = (size_t)base->width, H = (size_t)base->height;
 	const size_t frame_bytes = W * H * 4;
@@ -230,7 +252,8 @@ static int record_orbit_common(hmrm_scene *const *scenes, int32_t n_scenes, cons
 					hmrm_camera cam;
 					hmrm_orbit_camera(base, centre_x, centre_y, radius, hang0, next, frames, &cam);
 					int32_t ticket = -1;
-					const int rc = what.baked ? hmrm_render_baked_begin(scenes[i], &cam, what.baked_flags, flags, &ticket)
+					const int rc = wet        ? hmrm_render_water_begin(scenes[i], &cam, &the_water, what.water_mode, flags, &ticket)
+					               : what.baked ? hmrm_render_baked_begin(scenes[i], &cam, what.baked_flags, flags, &ticket)
 					               : lit      ? hmrm_render_shaded_begin(scenes[i], &cam, &the_sun, shade_flags, flags, &ticket)
 					                          : hmrm_render_begin_flags(scenes[i], &cam, flags, &ticket);
 					if (rc != HMRM_OK) {

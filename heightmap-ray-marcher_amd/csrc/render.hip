@@ -88,7 +88,8 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 // `hit_cell` (pass 1, may be null): where the primary hit's cell index gridx + gridy * W goes, for that caller.
 // 4 (hmrm_cell_map): pass 3 for a ray the caller put into *lit itself; the ray's status (HMRM_RAY_*) comes back in lit->phase.
 // 5 (hmrm_render_water): pass 2 for a mirror ray -- the caller hands the lane's own direction, step and limit in `sun` -- whose pixel,
-// the hit cell's colour or the miss shade of its own dz, comes back in lit->rgba.
+// the hit cell's colour or the miss shade of its own dz, comes back in lit->rgba; `hit_cell` (may be null): where the mirror ray's
+// hit cell goes, for the light of a water frame under the light plane -- left alone when the ray did not hit.
 template <int PROJ, bool STATS, bool AA, bool SEG = false, int LIT = 0>
 __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId pid, const double *__restrict__ thr,
                                                     const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
@@ -185,6 +186,9 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 						lit->hx = x; lit->hy = y; lit->t = t;
 						if (hit_cell) *hit_cell = (unsigned)cell; // (maps hold at most 2^29 cells)
 						if (hit_z) *hit_z = z;
+					}
+					if constexpr (LIT == 5) {
+						if (hit_cell) *hit_cell = (unsigned)cell;
 					}
 					break;
 				}
@@ -722,6 +726,7 @@ static hipError_t launch_geometry_literal(const FrameLaunch &l); // (hmrm_render
 static hipError_t launch_lit_sum_literal(const FrameLaunch &l);  //  the last kernels of the code object)
 static hipError_t launch_baked_literal(const FrameLaunch &l);    // (hmrm_render_baked's, behind those)
 static hipError_t launch_water_literal(const FrameLaunch &l);    // (hmrm_render_water's, behind those)
+static hipError_t launch_water_literal_more(const FrameLaunch &l); // (hmrm_render_water_aa's, the last kernels of the code object)
 
 // The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
 // shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
@@ -739,6 +744,7 @@ hipError_t launch_frame_literal(const FrameLaunch &l) {
 	if (l.family == kFrameLitSum) return launch_lit_sum_literal(l);
 	if (l.family == kFrameBaked) return launch_baked_literal(l);
 	if (l.family == kFrameWater) return launch_water_literal(l);
+	if (l.family == kFrameWaterAA || l.family == kFrameWaterBaked || l.family == kFrameWaterBakedAA) return launch_water_literal_more(l);
 	if (l.f.aa_shift == 0) switch (l.family) {
 		case kFrameLit:
 			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
@@ -834,6 +840,65 @@ static hipError_t launch_water_literal(const FrameLaunch &l) {
 	const SegRules seg = frame_seg_rules(l);
 	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
 		hipLaunchKernelGGL(k_render_water_literal<proj()>, grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.water);
+	});
+}
+
+// A pixel of an antialiased water frame and / or one under the light plane (hmrm_render_water_aa with HMRM_KERNEL=simple, or on a
+// map with a side of 2^24 cells): k_render_water_literal's two passes, which also hand back the two hit cells; BAKED: the base --
+// the primary pixel, or a wet lane's own colour -- under the plane's word of the primary hit's cell, and the mirror pixel under
+// that of the mirror ray's hit cell (MISS, END and CAPPED: the miss shade, untouched), then the blend.  AA: the lane's sample goes
+// to the wave's box filter (every lane of the wave calls it, so no lane returns before) and not to memory.  Kernels of their own:
+// k_render_water_literal keeps its instructions.
+template <int PROJ, bool AA, bool BAKED>
+__global__ __launch_bounds__(kBlockThreads) void k_render_water_literal_more(const DevFrame f, const RowMap rows,
+                                                                             const double *__restrict__ thr,
+                                                                             const uint32_t *__restrict__ cmap,
+                                                                             uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                             int tiles_y, StatsOut st, const SegRules seg,
+                                                                             const WaterRules water, const BakedLight baked) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	unsigned cell = 0u, mcell = ~0u; // (mcell: the mirror ray's hit cell, if it hit)
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, SunRules{}, &lt, &cell);
+	const bool wet = pid.live && lt.primary_hit && lt.t <= water.level; // (a NaN level: no water)
+	LitState<true> mr = lt;
+	mr.primary_hit = wet; // (the other lanes sit the pass out)
+	SunRules mirror{{0.0, 0.0, 0.0}, water.step_dist, water.max_steps, 0u};
+	if (wet) {
+		const DevRay primary = make_ray<PROJ>(f, pid.px, pid.py);
+		mirror.dir[0] = primary.dx; mirror.dir[1] = primary.dy; mirror.dir[2] = -primary.dz;
+	}
+	render_lane_literal<PROJ, false, false, true, 5>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
+	                                                 SegRules{nullptr, water.max_steps, 1u}, mirror, &mr, &mcell);
+	uint32_t rgba = 0u;
+	if (pid.live) {
+		rgba = lt.rgba;
+		if constexpr (BAKED) {
+			if (lt.primary_hit) {
+				rgba = shade_baked(wet ? water_base(rgba, water) : rgba, baked.plane[cell], baked.full_scale) | 0xff000000u;
+				if (wet) {
+					uint32_t m = mr.rgba;
+					if (mcell != ~0u) m = shade_baked(m, baked.plane[mcell], baked.full_scale);
+					rgba = blend_water_base(rgba, m, water);
+				}
+			}
+		} else if (wet) rgba = blend_water(rgba, mr.rgba, water);
+	}
+	if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, (int)(threadIdx.x & 63), pid.px, pid.lrow, pid.live, rgba);
+	else if (pid.live) out[(int64_t)pid.lrow * out_stride_px + pid.px] = rgba;
+}
+
+// Such a frame: the water family's arguments and, where the family has it, the plane.  Never a measured launch.
+static hipError_t launch_water_literal_more(const FrameLaunch &l) {
+	const bool aa = l.family != kFrameWaterBaked, baked = l.family != kFrameWaterAA;
+	if (l.rows.measure != nullptr || (l.f.aa_shift != 0) != aa || !l.d_out) return hipErrorInvalidValue;
+	if (baked && (!l.baked.plane || l.baked.full_scale < 1u || l.baked.full_scale > 65535u)) return hipErrorInvalidValue;
+	const SegRules seg = frame_seg_rules(l);
+	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
+		const dim3 block(kBlockThreads);
+		if (l.family == kFrameWaterAA) hipLaunchKernelGGL((k_render_water_literal_more<proj(), true, false>), grid, block, 0, l.stream, args..., seg, l.water, l.baked);
+		else if (l.family == kFrameWaterBaked) hipLaunchKernelGGL((k_render_water_literal_more<proj(), false, true>), grid, block, 0, l.stream, args..., seg, l.water, l.baked);
+		else hipLaunchKernelGGL((k_render_water_literal_more<proj(), true, true>), grid, block, 0, l.stream, args..., seg, l.water, l.baked);
 	});
 }
 

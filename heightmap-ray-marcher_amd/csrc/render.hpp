@@ -55,7 +55,9 @@ struct FrameLaunch {
 	// take the weight of the scene's light plane (frame.hpp BakedLight); antialiased with f.aa_shift
 	BakedLight baked = BakedLight{nullptr, 0u};
 	// kFrameWater (hmrm_render_water): the frame of the plain or, with primary_interior, the interior family, whose hit pixels at
-	// or below water.level march a mirror ray in the same launch and take its pixel blended in (frame.hpp WaterRules); no AA
+	// or below water.level march a mirror ray in the same launch and take its pixel blended in (frame.hpp WaterRules).
+	// kFrameWaterAA, kFrameWaterBaked, kFrameWaterBakedAA (hmrm_render_water_aa): that frame antialiased with f.aa_shift, under
+	// `baked` (both the primary and the mirror pixel take the weight of their own hit's light before the blend), and both
 	WaterRules water = WaterRules{0.0, 0.0, 0u, 0u, 0u, 0u};
 };
 // The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups

@@ -289,6 +289,9 @@ hipError_t launch_frame_march(const FrameLaunch &l, FastKernel kernel) {
 	case kFrameLitSum: return launch_render_lit_sum(l, kernel); // (refuses a factor)
 	case kFrameBaked: return aa ? launch_render_baked_aa(l, kernel) : launch_render_baked(l, kernel);
 	case kFrameWater: return launch_render_water(l, kernel); // (refuses a factor)
+	case kFrameWaterAA: return launch_render_water_aa(l, kernel); // (refuses a frame without one)
+	case kFrameWaterBaked: return launch_render_water_baked(l, kernel); // (refuses a factor)
+	case kFrameWaterBakedAA: return launch_render_water_baked_aa(l, kernel); // (refuses a frame without one)
 	default: return aa ? launch_render_fast_aa(l, kernel) : launch_render_fast(l, kernel);
 	}
 }

@@ -136,6 +136,7 @@ class Sun(C.Structure):
 assert C.sizeof(Sun) == 48
 
 WATER_OWN_COLOR = 2  # hmrm_water.flags (HMRM_WATER_OWN_COLOR)
+WATER_BAKED = 1  # water_mode (HMRM_WATER_BAKED): the water frame under the scene's light plane
 
 
 class Water(C.Structure):
@@ -300,6 +301,14 @@ def _load():
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
         "hmrm_render_water": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), vp, C.c_size_t]),
         "hmrm_render_water_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), vp, C.c_size_t, vp]),
+        "hmrm_render_water_aa": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), C.c_uint32, i32, vp, C.c_size_t]),
+        "hmrm_render_water_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), C.c_uint32, C.c_uint32, C.POINTER(i32)]),
+        "hmrm_render_water_device_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), C.c_uint32, vp, C.c_size_t, C.c_uint32,
+                                                     C.POINTER(i32)]),
+        "hmrm_record_orbit_water": (C.c_int, [C.POINTER(vp), i32, C.POINTER(Camera), C.c_double, C.c_double, C.c_double,
+                                              C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32, C.c_uint32, C.POINTER(Water),
+                                              C.c_uint32]),
+        "hmrm_config_water_scope": (i32, [vp]),
         "hmrm_config_water": (i32, [vp]),
         "hmrm_config_get_water": (None, [vp, C.POINTER(Water)]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
@@ -399,7 +408,7 @@ lib, EXPORTED_SYMBOLS = _load()
 KERNEL_SOURCES = ("render_fast.hip", "render_rays.hip", "leap_common.hpp", "leap_diag.hpp", "render.hip", "device_common.hpp", "frame.hpp",
                   "render.hpp", "api_internal.hpp", "api_launch.cpp", "api_frames.cpp", "launch_order.cpp", "launch_order.hpp", "camera.cpp", "Makefile",
                   "march.hpp", "march_family.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip",
-                  "render_water.hip")
+                  "render_water.hip", "render_water_aa.hip", "render_water_baked.hip", "render_water_baked_aa.hip")
 
 
 def kernel_src_sha() -> str:
@@ -568,6 +577,35 @@ class Scene:
         self._sync_env()
         _check(lib.hmrm_render_water_device(self._h, C.byref(cam), C.byref(water), C.c_void_p(d_rgba), int(stride_bytes),
                                             C.c_void_p(stream)))
+
+    def render_water_aa(self, cam: Camera, water: Water, factor=1, baked=False, allow_capped=False) -> np.ndarray:
+        """render_water's frame antialiased (factor 1, 2, 4 or 8: factor x factor box-filtered samples per pixel inside the
+        launch, every sample deciding "water", casting its mirror ray and blended on its own) and / or, baked=True, under the
+        scene's light plane (hmrm_render_water_aa with HMRM_WATER_BAKED: the primary pixel or the water's own colour at the weight
+        of the primary hit's light, the mirror pixel at that of its own hit, then the blend) -> HxWx4 uint8."""
+        self._sync_env()
+        fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
+        _check(lib.hmrm_render_water_aa(self._h, C.byref(cam), C.byref(water), WATER_BAKED if baked else 0, int(factor), _ptr(fb),
+                                        cam.width * 4),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
+    def render_water_begin(self, cam: Camera, water: Water, baked=False, aa=1, no_probe=False) -> int:
+        """render_begin for a water frame (hmrm_render_water_begin) -> ticket of the same ring: render_wait / render_release.
+        The water is copied; no_probe is accepted and has no effect."""
+        self._sync_env()
+        t = C.c_int32()
+        _check(lib.hmrm_render_water_begin(self._h, C.byref(cam), C.byref(water), WATER_BAKED if baked else 0,
+                                           (NO_PROBE if no_probe else 0) | aa_flags(aa), C.byref(t)))
+        return int(t.value)
+
+    def render_water_device_begin(self, cam: Camera, water: Water, d_rgba: int, stride_bytes: int, baked=False, aa=1) -> int:
+        """render_device_begin for a water frame (hmrm_render_water_device_begin) -> ticket for render_device_wait."""
+        self._sync_env()
+        t = C.c_int32()
+        _check(lib.hmrm_render_water_device_begin(self._h, C.byref(cam), C.byref(water), WATER_BAKED if baked else 0,
+                                                  C.c_void_p(d_rgba), int(stride_bytes), aa_flags(aa), C.byref(t)))
+        return int(t.value)
 
     def render_shaded(self, cam: Camera, sun: Sun, diffuse=True, shadows=True, allow_capped=False, aa=1) -> np.ndarray:
         """One full frame with diffuse sun shading (hmrm_render_shaded): render_lit()'s frame in which every hit pixel that is
@@ -1089,6 +1127,19 @@ def record_orbit_shaded(scenes, base: Camera, centre_x, centre_y, radius, hang0,
            allow=(HMRM_E_NOTERM,))
 
 
+def record_orbit_water(scenes, base: Camera, centre_x, centre_y, radius, hang0, frames, directory, rec_id, water: Water, baked=False,
+                       aa=1, encoder_threads=0, verbose=False):
+    """record_orbit_multi whose frames are water ones (hmrm_record_orbit_water); baked=True: under the light plane, which every
+    scene then needs."""
+    for s in scenes:
+        s._sync_env()
+    arr = (C.c_void_p * len(scenes))(*[s._h for s in scenes])
+    _check(lib.hmrm_record_orbit_water(arr, len(scenes), C.byref(base), centre_x, centre_y, radius, hang0, frames,
+                                       os.fsencode(directory), rec_id, encoder_threads, int(verbose), aa_flags(aa),
+                                       C.byref(water), WATER_BAKED if baked else 0),
+           allow=(HMRM_E_NOTERM,))
+
+
 def record_orbit_baked(scenes, base: Camera, centre_x, centre_y, radius, hang0, frames, directory, rec_id, interior=False, aa=1,
                        encoder_threads=0, verbose=False):
     """record_orbit_multi whose frames are baked-light ones (hmrm_record_orbit_baked): every scene needs a light plane."""
@@ -1239,6 +1290,10 @@ class Config:
         out = Sun()
         lib.hmrm_config_get_sun(self._h, C.byref(out))
         return out
+
+    def water_scope(self) -> int:
+        """Additive `water_scope frame|all`: 0 | 1 -- whether water also applies to antialiased, recorded and baked-light frames."""
+        return int(lib.hmrm_config_water_scope(self._h))
 
     def water_on(self) -> bool:
         """Additive `water on|off`: the CLI renders its single frame with hmrm_render_water."""

@@ -766,8 +766,9 @@ int hmrm_render_baked_device_begin(const hmrm_scene *scene, const hmrm_camera *c
  * with the scene's current kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST); every kernel
  * writes the same bytes, the literal loop too (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest sampling only).  All three
  * projections, grid modes and sampling modes.
- * OUT OF SCOPE: antialiased, ticketed, recorded, strip and multi-GPU water frames; water combined with shadows, shading or baked
- * light; refraction, Fresnel terms, waves; a second bounce. */
+ * OUT OF SCOPE: strip and multi-GPU water frames (hmrm_render_multi), statistics and geometry planes of a water frame; water
+ * combined with shadow rays or diffuse shading; refraction, Fresnel terms, waves; a second bounce.  Antialiased, ticketed and
+ * recorded water frames, and water under the scene's baked light: below. */
 #define HMRM_WATER_OWN_COLOR 2u      /* the water's own colour is `color`, not the primary pixel */
 typedef struct hmrm_water {          /* 32 bytes */
 	double   level;        /* a hit is WATER when t <= level; compared as doubles, as given */
@@ -781,6 +782,45 @@ typedef struct hmrm_water {          /* 32 bytes */
 int hmrm_render_water(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint8_t *rgba, size_t stride_bytes);
 int hmrm_render_water_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, void *d_rgba,
                              size_t stride_bytes, void *hip_stream);
+/* The water frame's second step: antialiased, ticketed, recorded, and under the scene's light plane.  `water_mode` is an argument
+ * of its own, not a bit of hmrm_water.flags, whose undefined bits stay refused; hmrm_render_water and hmrm_render_water_device do
+ * not change.
+ * THE BAKED WATER FRAME (water_mode & HMRM_WATER_BAKED) composes hmrm_render_water and hmrm_render_baked and adds nothing.  L of a
+ * hit is hmrm_render_baked's L of that hit: for the nearest modes the plane's word of the hit cell, for HMRM_BILINEAR the
+ * interpolated word at the hit point, in that definition's operation order; weight(c, L) is its min(255, (c * L + D / 2) / D) per
+ * channel.  Every pixel whose primary ray HIT, wet or dry, has b' = weight(b, L of the primary hit), b the primary pixel or, for a
+ * WATER pixel with HMRM_WATER_OWN_COLOR, the water's `color`; an alpha-0 hit cell's background is weighted too.  A water pixel's
+ * mirror pixel is m' = weight(m, L of the mirror ray's hit) when the mirror ray's status is HIT; for MISS, END and CAPPED m' is that
+ * ray's miss shade, untouched.  The stored pixel is hmrm_render_water's blend of b' and m'; a dry pixel stores b'; misses and capped
+ * primary rays are untouched.  So L = D everywhere is hmrm_render_water byte for byte, a level below every threshold is
+ * hmrm_render_baked, r = 0 without HMRM_WATER_OWN_COLOR is hmrm_render_baked, and water_mode 0 with factor 1 is hmrm_render_water.
+ * ANTIALIASING.  factor is 1, 2, 4 or 8: the result is the water frame (baked or not) of hmrm_render_aa's super camera, box-filtered
+ * with its formula inside the launch.  Every sample decides "water" on its own, casts its own mirror ray and is weighted and blended
+ * on its own before the filter.
+ * TICKETS (hmrm_render_water_begin, hmrm_render_water_device_begin) come from the same rings, lanes and device-ticket pool as the
+ * plain, lit and baked tickets and are waited for and released with the same calls.  `flags` takes HMRM_AA(n), and HMRM_NO_PROBE,
+ * which is accepted and has no effect.  *water is copied at begin.  The light plane is looked up under the scene's lock at begin: a
+ * ticket begun before hmrm_scene_set_light finishes with the old plane.
+ * THE RECORDER (hmrm_record_orbit_water) is hmrm_record_orbit_flags whose frames are water tickets; it checks the water, the mode
+ * and every scene's plane before any frame and writes no file on refusal.
+ * CAPPED RAYS.  Primary and mirror rays are counted together, per sample, as in hmrm_render_water, and reported the way the
+ * corresponding baked entry reports them.
+ * Refusals (HMRM_E_ARG, with a message), in this order: hmrm_render_water's three of the water; an undefined bit in water_mode;
+ * those of hmrm_render_aa (tickets: those of hmrm_render_begin_flags) in their order; a NULL scene; with HMRM_WATER_BAKED "the scene
+ * has no light plane"; the 2^24-side rule.
+ * Launched like every water frame: one launch, never measured, never the probe and not counted towards it, with the scene's
+ * current kernel; every kernel writes the same bytes, the literal loop too (nearest sampling only). */
+#define HMRM_WATER_BAKED 1u          /* water_mode: the frame under the scene's light plane */
+int hmrm_render_water_aa(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint32_t water_mode,
+                         int32_t factor, uint8_t *rgba, size_t stride_bytes);
+int hmrm_render_water_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint32_t water_mode,
+                            uint32_t flags, int32_t *ticket);
+int hmrm_render_water_device_begin(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, uint32_t water_mode,
+                                   void *d_rgba, size_t stride_bytes, uint32_t flags, int32_t *ticket);
+int hmrm_record_orbit_water(hmrm_scene *const *scenes, int32_t n_scenes, const hmrm_camera *base, double centre_x,
+                            double centre_y, double radius, double hang0, int32_t frames, const char *dir, long long id,
+                            int32_t encoder_threads, int32_t verbose, uint32_t flags, const hmrm_water *water,
+                            uint32_t water_mode);
 
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
@@ -982,6 +1022,10 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * "WARNING: water_reflectivity must be 0..255", the old value stays), `water_color r g b` (sets HMRM_WATER_OWN_COLOR; a component
  * outside 0..255: "WARNING: water_color must be three values 0..255"), `water_step_dist v` (absent: step_dist),
  * `water_max_steps n` (default 0 = none; outside 0..4294967295: "WARNING: water_max_steps must be 0..4294967295"),
+ * `water_scope frame|all` (default frame: everything above; with `all`, `water on` goes through `antialias n`
+ * (hmrm_render_water_aa) and `record orbit` (hmrm_record_orbit_water), and `baked_light sun|sky` bakes as described and then
+ * renders those with HMRM_WATER_BAKED; beside `devices n` > 1, `shadows` and `shading` without `baked_light`, and `sky_light` the
+ * key is still ignored with its warnings; another value warns "WARNING: Unknown water_scope: v" and keeps the old one),
  * `range_map <path.pfm>` (echoed like `output`; after its frames and before an optional sun_map the CLI writes the range plane
  * of the configured camera -- hmrm_render_geometry with that plane alone, under the interior rule with `interior on` -- as a
  * one-component portable float map, hmrm_write_pfm).
@@ -1025,6 +1069,7 @@ int32_t      hmrm_config_water(const hmrm_config *cfg);         /* additive `wat
  * flags |= HMRM_TRACE_INTERIOR when `interior on`.  `hmap` renders its single frame with hmrm_render_water when `water on`; the key
  * is ignored, with a warning, beside `antialias` > 1, `devices` > 1, `record orbit`, `shadows`, `shading` and `baked_light`. */
 void         hmrm_config_get_water(const hmrm_config *cfg, hmrm_water *out);
+int32_t      hmrm_config_water_scope(const hmrm_config *cfg);   /* additive `water_scope frame|all`: 0|1 */
 /* Loaded maps (owned by cfg): RGB8 / RGBA8; NULL until the key was consumed. */
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *cfg, int32_t *w, int32_t *h);
 const uint8_t *hmrm_config_color_rgba(const hmrm_config *cfg, int32_t *w, int32_t *h);
