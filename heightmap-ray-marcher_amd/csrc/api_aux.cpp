@@ -109,6 +109,7 @@ int32_t hmrm_config_sky_light(const hmrm_config *c) { return c->cfg.sky_light; }
 int32_t hmrm_config_baked_light(const hmrm_config *c) { return c->cfg.baked_light; }
 int32_t hmrm_config_sun_scope(const hmrm_config *c) { return c->cfg.sun_scope; }
 int32_t hmrm_config_water_scope(const hmrm_config *c) { return c->cfg.water_scope; }
+int32_t hmrm_config_water_light(const hmrm_config *c) { return c->cfg.water_light; }
 const char *hmrm_config_sun_map_path(const hmrm_config *c) { return c->cfg.sun_map_path.c_str(); }
 double hmrm_config_sun_map_lift(const hmrm_config *c) { return c->cfg.sun_map_lift; }
 const char *hmrm_config_sky_map_path(const hmrm_config *c) { return c->cfg.sky_map_path.c_str(); }

@@ -476,6 +476,8 @@ static int check_water(const hmrm_water *w) {
 // caller's behind the launch.
 // `factor`, `water_mode` (hmrm_render_water_aa): the super frame box-filtered inside the launch, as hmrm_render_aa's, and
 // HMRM_WATER_BAKED, the frame under the scene's light plane; hmrm_render_water and hmrm_render_water_device come with 1 and 0.
+// `sun`, `shade_flags` (hmrm_render_water_lit, `lit`): the sun-lit water frame -- hmrm_render_shaded's four refusals come behind the
+// water's three, the primary rays are under the interior rule when either flags word asks, and the launch is the family's own.
 static int check_water_mode(uint32_t water_mode) {
 	if (water_mode & ~HMRM_WATER_BAKED) return fail(HMRM_E_ARG, "water_mode: undefined bit");
 	return HMRM_OK;
@@ -486,8 +488,10 @@ static hmrm::WaterRules water_rules_of(const hmrm_water *w) {
 	                        w->flags & HMRM_WATER_OWN_COLOR};
 }
 static int render_water_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm_water *w, void *target, size_t stride_bytes,
-                               bool device, hipStream_t stream, int32_t factor, uint32_t water_mode) {
+                               bool device, hipStream_t stream, int32_t factor, uint32_t water_mode, bool lit = false,
+                               const hmrm_sun *sun = nullptr, uint32_t shade_flags = 0u) {
 	int rc = check_water(w);
+	if (!rc && lit) rc = check_shaded(sun, shade_flags);
 	if (rc || (rc = check_water_mode(water_mode)) || (rc = check_camera(cam))) return rc;
 	hmrm_camera super;
 	int aa_shift = 0;
@@ -512,10 +516,18 @@ static int render_water_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm
 	FrameSetup fs;
 	if ((rc = setup_frame(s, stream, &super, aa_shift, &fs))) return rc;
 	StreamCtx *const c = fs.c;
-	const hmrm::WaterRules rules = water_rules_of(w);
+	hmrm::WaterRules rules = water_rules_of(w);
 	FrameRequest req = plain_request(d_rgba, stride_px);
 	req.interior = (w->flags & HMRM_TRACE_INTERIOR) ? Interior::kByKernels : Interior::kNot;
 	req.water = &rules;
+	hmrm::SunRules sun_rules{};
+	if (lit) {
+		sun_rules = hmrm::SunRules{{sun->dir[0], sun->dir[1], sun->dir[2]}, sun->step_dist, sun->max_steps, sun->ambient};
+		rules.flags |= ((shade_flags & HMRM_SHADE_DIFFUSE) ? hmrm::kWaterSunDiffuse : 0u) |
+		               ((shade_flags & HMRM_SHADE_NO_SHADOWS) ? hmrm::kWaterSunNoShadows : 0u);
+		if (sun->flags & HMRM_TRACE_INTERIOR) req.interior = Interior::kByKernels;
+		req.water_sun = &sun_rules;
+	}
 	if (water_mode & HMRM_WATER_BAKED) req.baked = &baked;
 	if (!device) HIP_TRY(hipEventRecord(s->ev0, s->stream)); // (the host form is timed like hmrm_render: hmrm_last_kernel_ms)
 	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req)) || device) return rc;
@@ -540,6 +552,18 @@ int hmrm_render_water_aa(const hmrm_scene *scene, const hmrm_camera *cam, const 
 int hmrm_render_water_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, void *d_rgba,
                              size_t stride_bytes, void *hip_stream) {
 	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, d_rgba, stride_bytes, true, (hipStream_t)hip_stream, 1, 0u);
+}
+
+// The sun-lit water frame: hmrm_render_water and hmrm_render_shaded composed, in one launch of a family of its own.
+int hmrm_render_water_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, const hmrm_sun *sun,
+                          uint32_t shade_flags, uint8_t *rgba, size_t stride_bytes) {
+	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, rgba, stride_bytes, false, nullptr, 1, 0u, true, sun, shade_flags);
+}
+
+int hmrm_render_water_lit_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, const hmrm_sun *sun,
+                                 uint32_t shade_flags, void *d_rgba, size_t stride_bytes, void *hip_stream) {
+	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, d_rgba, stride_bytes, true, (hipStream_t)hip_stream, 1, 0u,
+	                           true, sun, shade_flags);
 }
 
 int hmrm_render_stats(const hmrm_scene *scene, const hmrm_camera *cam, uint8_t *rgba,

@@ -294,6 +294,8 @@ struct FrameRequest {
 	// interior rule when `interior` is not kNot, as a geometry frame's are.  With `baked` too (hmrm_render_water_aa with
 	// HMRM_WATER_BAKED): the water frame under the light plane.
 	const hmrm::WaterRules *water = nullptr;
+	// hmrm_render_water_lit's frame: `water` (with the shade flags in its flags word, frame.hpp kWaterSun*) and this sun; null: none.
+	const hmrm::SunRules *water_sun = nullptr;
 	// Frames under the interior rule, with a sun, with geometry planes, with baked light or with water run kernels of their own,
 	// with the scene's current kernel kind (HMRM_KERNEL or the probe's verdict, read only).
 	bool own_kernels() const {

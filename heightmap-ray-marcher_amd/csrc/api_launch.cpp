@@ -159,6 +159,10 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 		else l.family = aa ? hmrm::kFrameWaterAA : hmrm::kFrameWater;
 		l.water = *req.water;
 		l.primary_interior = req.interior != Interior::kNot;
+		if (req.water_sun) { // (the sun-lit water frame: neither a factor nor the plane reaches here with it)
+			l.family = hmrm::kFrameWaterLit;
+			l.sun = *req.water_sun;
+		}
 	}
 	if (route.literal) {
 		HIP_TRY(hmrm::launch_frame_literal(l));

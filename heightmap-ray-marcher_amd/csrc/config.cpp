@@ -16,7 +16,7 @@
 //   shadows on|off, sun_dir x y z, shadow_ambient n, shadow_step_dist v, shadow_max_steps n
 //   shading on|off, sun_scope single|all, sky_light on|off, baked_light off|sun|sky
 //   water on|off, water_level v, water_reflectivity n, water_color r g b, water_step_dist v, water_max_steps n,
-//   water_scope frame|all
+//   water_scope frame|all, water_light off|sun
 //   sun_map <path.png>, sun_map_lift v                (the whole map's light map, hmrm_cell_map, written by the CLI)
 //   sky_map <path.png>, sky_map_rings r n             (the whole map's sky-view map, hmrm_cell_map_sum, written by the CLI)
 //   range_map <path.pfm>                              (the camera's range plane, hmrm_render_geometry, written by the CLI)
@@ -283,6 +283,14 @@ void water_scope_key(Config &c, std::istream &in, const char *key, std::string *
 	c.log << key << " " << (c.water_scope ? "all" : "frame") << "\n";
 }
 
+// what lights a water frame beside `shadows` / `shading`: nothing (water is ignored there), or the sun (hmrm_render_water_lit)
+void water_light_key(Config &c, std::istream &in, const char *key, std::string *) {
+	static const Word words[] = {{"off", 0}, {"sun", 1}};
+	std::string seen;
+	if (!pick(in, words, &c.water_light, &seen)) c.warn << "WARNING: Unknown water_light: " << seen << "\n";
+	c.log << key << " " << (c.water_light ? "sun" : "off") << "\n";
+}
+
 // which frames shadows / shading apply to: the plain single frame, or antialiased and recorded ones too
 void sun_scope_key(Config &c, std::istream &in, const char *key, std::string *) {
 	static const Word words[] = {{"single", 0}, {"all", 1}};
@@ -384,6 +392,7 @@ const Row kGrammar[] = {
 	{"range_map", scalar<&Config::range_map_path>},
 	{"water", water_key},
 	{"water_scope", water_scope_key},
+	{"water_light", water_light_key},
 	{"water_level", scalar<&Config::water_level>},
 	{"water_reflectivity", water_reflectivity_key},
 	{"water_color", water_color_key},

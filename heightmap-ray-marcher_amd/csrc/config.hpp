@@ -68,6 +68,9 @@ struct Config {
 	// additive: `water_scope frame|all` -- 0: water applies to the plain single frame only; 1: also with `antialias n` > 1
 	// (hmrm_render_water_aa), to `record orbit` (hmrm_record_orbit_water) and under `baked_light` (HMRM_WATER_BAKED)
 	int water_scope = 0;
+	// additive: `water_light off|sun` -- 0: `water on` beside `shadows` / `shading` is ignored; 1: that single frame is the sun-lit
+	// water frame (hmrm_render_water_lit) -- one device, `antialias 1`, no `baked_light`
+	int water_light = 0;
 	// additive: `sun_scope single|all` -- 0: shadows / shading apply to the plain single frame only; 1: also with `antialias n` > 1
 	// (hmrm_render_shaded_aa) and to `record orbit` (hmrm_record_orbit_shaded)
 	int sun_scope = 0;

@@ -344,6 +344,9 @@ struct WaterRules {
 // (r and the colour packed into one word, a scalar register less, made the compiler take a scratch slot in 30 of the 63
 // instantiations instead of 9: DESIGN.md 5.20)
 constexpr uint32_t kWaterOwnColor = 2u; // (= hmrm.h HMRM_WATER_OWN_COLOR)
+// The sun-lit water frame (hmrm_render_water_lit; SUNLIT in the kernels) takes its sun in a SunRules beside the WaterRules and
+// hmrm_render_shaded's two flags in `flags`, above the water's own: read at run time, the same for the whole launch.
+constexpr uint32_t kWaterSunDiffuse = 0x100u, kWaterSunNoShadows = 0x200u;
 
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when

@@ -25,7 +25,9 @@
 // when `interior on`); ignored, with a warning, beside `antialias` > 1, `devices` > 1, `record orbit`, `shadows`, `shading` and
 // `baked_light`.  `water_scope all` lifts three of them: with `antialias n` > 1 the single frame is the antialiased water frame
 // (hmrm_render_water_aa), `record orbit` records water frames (hmrm_record_orbit_water, antialiased with `antialias n`), and
-// `baked_light sun|sky` bakes as usual and then renders those under the plane (HMRM_WATER_BAKED).
+// `baked_light sun|sky` bakes as usual and then renders those under the plane (HMRM_WATER_BAKED).  `water_light sun`: `water on`
+// beside `shadows on` and / or `shading on` is the sun-lit water frame (hmrm_render_water_lit, with the shaded single frame's
+// flags) -- one device, `antialias 1`, no `baked_light`, either `water_scope`; elsewhere the warnings above stand.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -347,15 +349,17 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: sky_light is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
 	// `water on`: the single frame with mirror reflections at or below `water_level` (hmrm_render_water) -- the plain frame's only
 	bool water = hmrm_config_water(cfg) != 0;
+	// `water_light sun`: beside shadows and / or shading that frame is the sun-lit water frame (hmrm_render_water_lit)
+	const bool water_lit = water && hmrm_config_water_light(cfg) != 0 && (shadows || shading) && baked_mode == 0 && want_dev <= 1 && aa == 1;
 	if (water && water_all) {
-		const char *beside = want_dev > 1 ? "devices > 1" : baked ? nullptr : shadows ? "shadows" : shading ? "shading" : nullptr;
+		const char *beside = want_dev > 1 ? "devices > 1" : (baked || water_lit) ? nullptr : shadows ? "shadows" : shading ? "shading" : nullptr;
 		if (beside) {
 			std::cerr << "WARNING: water is ignored with " << beside << "\n";
 			water = false;
 		}
 	} else
 	if (water) {
-		const char *beside = aa > 1 ? "antialias > 1" : want_dev > 1 ? "devices > 1" : shadows ? "shadows" : shading ? "shading"
+		const char *beside = water_lit ? nullptr : aa > 1 ? "antialias > 1" : want_dev > 1 ? "devices > 1" : shadows ? "shadows" : shading ? "shading"
 		                     : baked_mode != 0 ? "baked_light" : nullptr;
 		if (beside) {
 			std::cerr << "WARNING: water is ignored with " << beside << "\n";
@@ -366,7 +370,21 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: sky_light is ignored with water\n";
 		sky_light = false;
 	}
-	if (water && water_all) {
+	if (water && water_lit) {
+		hmrm_water w;
+		hmrm_config_get_water(cfg, &w);
+		hmrm_sun sun;
+		hmrm_config_get_sun(cfg, &sun);
+		rc = hmrm_render_water_lit(scene, &cam, &w, &sun, shade_flags, framebuf.data(), (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height << " rays with water at level " << w.level
+		          << (shading ? (shadows ? " with sun shading and sun shadows" : " with sun shading") : " with sun shadows")
+		          << (interior ? " under the interior rule" : "") << "\n";
+	} else if (water && water_all) {
 		// the single frame, antialiased or not, under the light plane baked here or under none
 		hmrm_water w;
 		hmrm_config_get_water(cfg, &w);

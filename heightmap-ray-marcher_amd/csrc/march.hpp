@@ -2,7 +2,7 @@
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
 // render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
 // counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip, render_lit_sum.hip, render_baked.hip,
-// render_baked_aa.hip, render_water.hip, render_water_aa.hip, render_water_baked.hip and render_water_baked_aa.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
+// render_baked_aa.hip, render_water.hip, render_water_aa.hip, render_water_baked.hip, render_water_baked_aa.hip and render_water_lit.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
 // switch and derived constant with its reasons.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
@@ -193,7 +193,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	constexpr bool STATS = F::STATS, AA = F::AA, SEG = F::SEG, LIT = F::LIT, SHADE = F::SHADE, SUM = F::SUM, GEOM = F::GEOM, LSUM = F::LSUM;
 	constexpr bool BAKED = F::BAKED, CELLS = F::CELLS, RAYS = F::RAYS, COUNT = F::COUNT, BILINEAR = F::BILINEAR, F32 = F::F32, REC = F::REC;
 	constexpr bool KEEP_Q = F::KEEP_Q, KEEP_P = F::KEEP_P, CHAIN = F::CHAIN, DEFER = F::DEFER, CARRY = F::CARRY;
-	constexpr bool MIRROR = F::MIRROR;
+	constexpr bool MIRROR = F::MIRROR, SUNLIT = F::SUNLIT;
 	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
 	const float *__restrict__ mip = BILINEAR ? f.mipbuf_bil : f.mipbuf; // the pyramid this sampling mode leaps on
 	PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, lane);
@@ -254,6 +254,9 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		// byte -- and the two flags beside it)
 		[[maybe_unused]] constexpr bool kMirrorKeepsCell = MIRROR && DEFER && !BILINEAR;
 		[[maybe_unused]] constexpr uint32_t kMirrorHit = 0x40000000u, kMirrorWet = 0x80000000u, kMirrorValue = kMirrorKeepsCell ? 0x3fffffffu : 0x00ffffffu;
+		// (SUNLIT: the keeps-cell form gives up one bit of the value -- a cell is below 2^29 -- for "the primary hit is shadowed"; the
+		// keeps-pixel form has "the mirror ray hit" in a free bit above the pixel, the keeps-cell form says that with hcell: all ones = no)
+		[[maybe_unused]] constexpr uint32_t kSunShadowed = 0x20000000u, kSunMirrorHit = 0x10000000u, kSunValue = kMirrorKeepsCell ? 0x1fffffffu : 0x00ffffffu;
 		double hqx = 0.0, hqy = 0.0; // (bilinear, no LIT: the hit's exact cell coordinates, KEEP_Q, or SHADE's copy of its x and y, KEEP_P)
 		bool again = false; // (LIT: the wave has shadow rays to march; SUM: targets)
 		// Bilinear mode, behind the march: the exact cell coordinates of a hit point -- the very expressions the group made its
@@ -292,6 +295,32 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			return w;
 		};
 
+		// SUNLIT: the weight of a hit under the sun -- hmrm_render_shaded's: the ambient level for a shadowed hit, else 255 or,
+		// kWaterSunDiffuse, that of the level at the hit's cell (nearest-cell modes) or point (bilinear).
+		[[maybe_unused]] auto sun_weight = [&](const SunRules &sun, const WaterRules &water, bool shadowed, unsigned cell_at, double px, double py) -> uint32_t {
+			uint32_t w = shadowed ? sun.ambient : 255u;
+			if constexpr (SUNLIT) {
+				if ((water.flags & kWaterSunDiffuse) != 0u && !shadowed) {
+					uint32_t q;
+					if constexpr (BILINEAR) {
+						double qxs, qys;
+						cell_coords_of(px, py, qxs, qys);
+						q = diffuse_level_bilinear(f, thr, bil_setup(qxs, qys, f.map_w, f.map_h), sun.dir);
+					} else q = diffuse_level_nearest<F32>(f, thr, cell_at, sun.dir);
+					w = shade_weight(sun.ambient, q);
+				}
+			}
+			return w;
+		};
+		// SUNLIT: the lane's camera ray, made again from its number in the wave (which goes through an empty statement, so that
+		// nothing of it is made before the marches and held across them).
+		[[maybe_unused]] auto camera_ray_again = [&]() -> DevRay {
+			int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+			asm volatile("" : "+v"(ln));
+			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, ln);
+			return make_ray<PROJ>(f, me.px, me.py);
+		};
+
 		do { // (once; LIT: once more with the shadow rays; SUM: once per target; LSUM: once more per direction)
 			if (!(d == __builtin_huge_val()) && !(d < 0.0)) { // intersection(), AABB.cpp:33-44
 				double x = ray.px + d * ray.dx;
@@ -302,6 +331,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				z = z + f.nudge * ray.dz;
 				double step_dist = f.step_dist;
 				if constexpr (LIT) step_dist = lt.phase ? a.sun.step_dist : step_dist; // (a shadow ray's own)
+				if constexpr (SUNLIT) step_dist = lt.phase == 0 ? step_dist : ((lt.phase & 1) ? a.sun.step_dist : a.water.step_dist); // (passes 1, 3: a shadow ray's; 2: a mirror ray's)
+				else
 				if constexpr (MIRROR) step_dist = lt.phase ? a.water.step_dist : step_dist; // (a mirror ray's own)
 				const double sx = step_dist * ray.dx; // hmap.cpp:1037, loop invariant
 				const double sy = step_dist * ray.dy;
@@ -709,6 +740,9 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 									qyh = hit_j == j ? QY[j] : qyh;
 								}
 								// (DEFER: the colour's five loads, its weights and mixes come behind the loop, bilinear_pixel below)
+								if constexpr (!DEFER && SUNLIT) { // (a shadow ray has no colour, and the mirror pixel in `rgba` outlives pass 3: a scalar branch)
+									if ((lt.phase & 1) == 0) rgba = shade_hit_bilinear(f, cmap, (int)hit_cell, bil_setup(qxh, qyh, f.map_w, f.map_h));
+								} else
 								if constexpr (!DEFER && !CELLS) // (a cell map has no colours: `cmap` is null)
 								rgba = shade_hit_bilinear(f, cmap, (int)hit_cell, bil_setup(qxh, qyh, f.map_w, f.map_h));
 								if constexpr (KEEP_Q) { hqx = qxh; hqy = qyh; }
@@ -716,6 +750,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 							// (DEFER: no colour here, nothing reads it before the pixel is stored -- see hcell)
 							if constexpr (!DEFER && !BILINEAR && !CELLS) rgba = shade_hit(f, cmap[hit_cell]);
 							if constexpr (LIT) hcell = lt.phase ? hcell : hit_cell; // (the primary ray's)
+							else if constexpr (SUNLIT) hcell = (lt.phase & 1) ? hcell : hit_cell; // (the primary ray's, then the mirror ray's)
 							else hcell = hit_cell;
 							real_hit = true;
 							if constexpr (CHAIN) {
@@ -766,10 +801,14 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								t = F32 ? (double)thr32[c] : thr[c];
 							}
 							if (zs < t) { // hmap.cpp:1016
+								if constexpr (!DEFER && SUNLIT) { // (as in the group)
+									if ((lt.phase & 1) == 0) rgba = BILINEAR ? shade_hit_bilinear(f, cmap, c, b) : shade_hit(f, cmap[c]);
+								} else
 								if constexpr (!DEFER && !CELLS) rgba = BILINEAR ? shade_hit_bilinear(f, cmap, c, b) : shade_hit(f, cmap[c]);
 								real_hit = true;
 								if constexpr (KEEP_Q) { hqx = qx; hqy = qy; }
 								if constexpr (LIT) hcell = lt.phase ? hcell : (unsigned)c; // (as in the group: the colour comes behind the loop)
+								else if constexpr (SUNLIT) hcell = (lt.phase & 1) ? hcell : (unsigned)c;
 								else hcell = (unsigned)c;
 								if constexpr (CHAIN) { hx = xs; hy = ys; hz = zs; }
 								if constexpr (KEEP_P) { x = xs; y = ys; z = GEOM ? zs : t; } // (as above)
@@ -801,6 +840,9 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				if constexpr (SEG && COUNT) my_steps = (unsigned long long)(unsigned)(sg.budget - budget);
 				if constexpr ((LIT && SHADE && BILINEAR) || LSUM) { // (the primary hit's point outlives the shadow march: the gradient is taken there; LSUM: every pass's ray starts there)
 					if (lt.phase == 0) { lt.hx = x; lt.hy = y; lt.t = z; }
+				} else
+				if constexpr (SUNLIT) { // (the primary hit's point outlives pass 1, the mirror hit's pass 3: a shadow ray's own is not kept)
+					if ((lt.phase & 1) == 0) { lt.hx = x; lt.hy = y; lt.t = z; }
 				} else
 				if constexpr (LIT || MIRROR) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
 				else if constexpr (GEOM && kGeomChain) { hqx = hx; hqy = hy; }
@@ -882,6 +924,73 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					}
 				}
 			}
+			if constexpr (SUNLIT) {
+				// Behind every pass (march_family.hpp SunWater): the lane counts its ray if the step cap stopped it (an END ray is not a
+				// capped one), puts what the pass found into its word, and the wave takes the next pass that any of its lanes needs.
+				// Behind pass 0 the word is made as MIRROR makes it, "wet" decided by the same comparison; the keeps-pixel form chooses the
+				// base there -- a wet lane's own colour in place of its pixel -- and weights it as soon as the weight is known: here
+				// without shadow rays, behind pass 1 with them.  Behind pass 1 real_hit says SHADOWED for the lanes that hit, behind
+				// pass 2 that the mirror ray hit, behind pass 3 SHADOWED for the mirror hits.
+				again = false;
+				if (my_cap != 0u && !sg.ends) atomicAdd(&st.counters[2], 1ull);
+				my_cap = 0u;
+				const bool shadows = (a.water.flags & kWaterSunNoShadows) == 0u;
+				int next = 4;
+				if (lt.phase == 0) {
+					uint32_t keep;
+					if constexpr (kMirrorKeepsCell) keep = hcell;
+					else {
+						if constexpr (DEFER) { // (BILINEAR)
+							if (real_hit) {
+								double qxp, qyp;
+								cell_coords_of(lt.hx, lt.hy, qxp, qyp);
+								rgba = bilinear_pixel(qxp, qyp);
+							}
+						}
+						keep = rgba;
+					}
+					const bool wet = real_hit && lt.t <= a.water.level; // (a NaN level: no water)
+					if constexpr (!kMirrorKeepsCell) {
+						keep = wet ? water_base(keep, a.water) : keep;
+						if (!shadows && real_hit) keep = shade_weighted(keep, sun_weight(a.sun, a.water, false, hcell, lt.hx, lt.hy));
+					}
+					lt.rgba = (keep & kSunValue) | (real_hit ? kMirrorHit : 0u) | (wet ? kMirrorWet : 0u);
+					if (shadows && __builtin_amdgcn_ballot_w64(real_hit) != 0ull) next = 1;
+					else if (__builtin_amdgcn_ballot_w64(wet) != 0ull) next = 2;
+				} else if (lt.phase == 1) {
+					if constexpr (kMirrorKeepsCell) lt.rgba |= real_hit ? kSunShadowed : 0u;
+					else if ((lt.rgba & kMirrorHit) != 0u)
+						lt.rgba = (shade_weighted(lt.rgba, sun_weight(a.sun, a.water, real_hit, hcell, lt.hx, lt.hy)) & kSunValue) | (lt.rgba & ~kSunValue);
+					if (__builtin_amdgcn_ballot_w64((lt.rgba & kMirrorWet) != 0u) != 0ull) next = 2;
+				} else if (lt.phase == 2) {
+					if constexpr (kMirrorKeepsCell) hcell = real_hit ? hcell : ~0u;
+					else lt.rgba |= real_hit ? kSunMirrorHit : 0u;
+					if (shadows && __builtin_amdgcn_ballot_w64(real_hit) != 0ull) next = 3;
+				}
+				if (next < 4) {
+					// The next pass's rays: a shadow ray from the kept point towards the sun (1: of a lane that hit; 3: of a lane whose
+					// mirror ray just hit -- real_hit still says so), or (2) the mirror ray of a wet lane, MIRROR's: the primary direction
+					// with dz negated, from the same point.  Every lane takes the new ray, the lanes without one at d = inf.
+					const bool marches = next == 2 ? (lt.rgba & kMirrorWet) != 0u : real_hit;
+					lt.phase = next;
+					again = true;
+					ray.px = lt.hx; ray.py = lt.hy; ray.pz = lt.t;
+					uint32_t limit = a.sun.max_steps;
+					if (next == 2) {
+						const DevRay primary = camera_ray_again();
+						ray.dx = primary.dx; ray.dy = primary.dy; ray.dz = -primary.dz;
+						limit = a.water.max_steps;
+					} else {
+						ray.dx = a.sun.dir[0]; ray.dy = a.sun.dir[1]; ray.dz = a.sun.dir[2];
+					}
+					d = __builtin_huge_val();
+					if (marches) {
+						d = shadow_entry(ray, f);
+						sg.budget = segment_budget(SegRules{nullptr, limit, 1u}, 0, f.step_cap, &sg.ends);
+					}
+					real_hit = false;
+				}
+			} else
 			if constexpr (MIRROR) {
 				// After the primary rays: the lanes that hit at or below the water level become their mirror rays -- origin, dz, the step
 				// (above) and the budget min(step cap, L) are replaced, dx and dy stay -- and the others get d = inf and sit the pass out.
@@ -992,6 +1101,43 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		if constexpr (DEFER && !LIT && !MIRROR) {
 			if (real_hit) rgba = BILINEAR ? bilinear_pixel(qxh, qyh) : shade_hit(f, cmap[hcell]);
 		}
+		if constexpr (SUNLIT) {
+			// Behind the last pass.  A lane that hit: its base -- its pixel, or a wet lane's own colour -- at the weight of the primary hit
+			// (keeps-cell form: colour and level fetched here from the kept cell; keeps-pixel form: done behind pass 1).  A wet lane: its
+			// mirror ray's pixel -- the colour at the mirror hit's cell (the bilinear mode: and point) at the weight of THAT hit, whose
+			// shadow ray pass 3 marched (real_hit: shadowed), or for MISS, END and CAPPED the miss shade of the mirror ray's own dz,
+			// untouched -- blended in.  The primary direction's dz is made again for the miss shades.
+			const double primary_dz = lt.phase == 0 ? ray.dz : camera_ray_again().dz;
+			if ((lt.rgba & kMirrorHit) != 0u) {
+				const bool wet = (lt.rgba & kMirrorWet) != 0u;
+				uint32_t kept;
+				if constexpr (kMirrorKeepsCell) {
+					const unsigned pcell = lt.rgba & kSunValue;
+					kept = shade_hit(f, cmap[pcell]);
+					kept = shade_weighted(wet ? water_base(kept, a.water) : kept, sun_weight(a.sun, a.water, (lt.rgba & kSunShadowed) != 0u, pcell, 0.0, 0.0)) | 0xff000000u;
+				} else kept = lt.rgba | 0xff000000u;
+				if (wet) {
+					uint32_t m = rgba; // (the in-loop fetch's, where the family keeps that)
+					bool mirror_hit;
+					if constexpr (kMirrorKeepsCell) mirror_hit = hcell != ~0u;
+					else mirror_hit = (lt.rgba & kSunMirrorHit) != 0u;
+					if (mirror_hit) {
+						if constexpr (DEFER) {
+							if constexpr (BILINEAR) {
+								double qxm, qym;
+								cell_coords_of(lt.hx, lt.hy, qxm, qym);
+								m = bilinear_pixel(qxm, qym);
+							} else m = shade_hit(f, cmap[hcell]);
+						}
+						m = shade_weighted(m, sun_weight(a.sun, a.water, lt.phase == 3 && real_hit, hcell, lt.hx, lt.hy));
+					} else m = shade_miss(f, -primary_dz);
+					kept = blend_water_base(kept, m, a.water);
+				}
+				rgba = kept;
+				real_hit = true;
+			} else real_hit = false;
+			ray.dz = primary_dz; // (for the miss shade)
+		} else
 		if constexpr (MIRROR) {
 			// A water lane: its mirror ray's pixel -- the colour of the cell that ray hit, fetched here from the mirror pass's own hcell
 			// (the bilinear mode: and hit point), or for MISS, END and CAPPED the miss shade of the mirror ray's own dz -- blended into
@@ -1145,6 +1291,11 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 			} else
 			store_batch_hit(a.batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, (int)(hcell - cy * (unsigned)f.map_w), (int)cy, d,
 			                (uint32_t)my_steps, rgba);
+		} else if constexpr (SUNLIT) { // (the lane's pixel is made again from its number in the wave, as LSUM's: not held across four marches)
+			int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+			asm volatile("" : "+v"(ln));
+			const PixelId me = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, ln);
+			out[(uint64_t)(uint32_t)me.lrow * (uint32_t)out_stride_px + (uint32_t)me.px] = rgba;
 		} else if constexpr (AA) aa_rgba = rgba;
 		else out[(uint64_t)(uint32_t)pid.lrow * (uint32_t)out_stride_px + (uint32_t)pid.px] = rgba;
 		if (STATS && st.steps_per_pixel)

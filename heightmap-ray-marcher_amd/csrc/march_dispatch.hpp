@@ -19,9 +19,10 @@ enum FastKernel { kPlainGroups = 0, kLeaps = 1, kRecords = 2 };
 // `shade_flags`, which its kernels read at run time.  kFrameBaked: the baked-light frame's (hmrm_render_baked), set by the launch
 // path like kFrameGeometry.  kFrameWater: the water frame's (hmrm_render_water), set by the launch path likewise,
 // as are its antialiased form, its form under the light plane and both (hmrm_render_water_aa): kFrameWaterAA, kFrameWaterBaked and
-// kFrameWaterBakedAA.
+// kFrameWaterBakedAA.  kFrameWaterLit: the sun-lit water frame's (hmrm_render_water_lit), set by the launch path too; one family for
+// its four `shade_flags`, which its kernels read at run time.
 enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded, kFrameGeometry, kFrameLitSum, kFrameBaked, kFrameWater, kFrameWaterAA,
-                   kFrameWaterBaked, kFrameWaterBakedAA };
+                   kFrameWaterBaked, kFrameWaterBakedAA, kFrameWaterLit };
 
 // Which launch a frame gets.  `forced`: HMRM_KERNEL (2: simple); `huge_side`: a map side of 2^24 cells or more -- the production
 // kernel indexes cells and windows with 24-bit multiplies, leap_common.hpp index_2d; `interior`: hmrm_render_interior's frame

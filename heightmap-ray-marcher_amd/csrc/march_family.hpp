@@ -53,7 +53,7 @@ constexpr bool kGeomChain = HMRM_GEOM_CHAIN != 0, kGeomCarry = HMRM_GEOM_CARRY !
 // whose ballot only the live lanes take part in.
 struct Frames {
 	static constexpr bool STATS = false, AA = false, SEG = false, LIT = false, SHADE = false, SUM = false, GEOM = false, LSUM = false,
-	                      BAKED = false, MIRROR = false;
+	                      BAKED = false, MIRROR = false, SUNLIT = false;
 	struct Args {};
 };
 template <bool STATS_, bool AA_> struct FramesOf : Frames {
@@ -173,6 +173,28 @@ struct BakedWater : Frames {
 	static constexpr bool SEG = true, MIRROR = true, BAKED = true;
 	struct Args { const SegRules &seg; const WaterRules &water; const BakedLight &baked; };
 };
+// MIRROR and SUNLIT (render_water_lit.hip; hmrm_render_water_lit): the sun-lit water frame, hmrm_render_water and hmrm_render_shaded
+// composed.  "Entry, then the march loop" runs up to four times for the wave: (0) the primary rays, (1) the shadow rays of the lanes
+// that hit, (2) the mirror rays of the wet lanes, (3) the shadow rays of the wet lanes whose mirror ray hit; a lane without a ray sits
+// a pass out at d = inf, a pass no lane needs is skipped by a ballot.  SUNLIT is a switch of its own, not LIT: LIT's blocks (its phase
+// switch, its epilogue, its hcell and lt rules) are written for two passes and collide with MIRROR's.  Whether the weights are
+// diffuse and whether the shadow passes run are run-time flags, as in LSUM -- they travel in WaterRules::flags (frame.hpp
+// kWaterSunDiffuse, kWaterSunNoShadows), wave-uniform scalar branches -- so this is one family, not four.
+// Between the marches a lane keeps LitState's hit point -- the primary hit's outlives pass 1, as LSUM's does: the mirror ray starts
+// there; the mirror hit's replaces it in pass 2 and outlives pass 3 -- and ONE word per hit.  Keeps-cell form: the primary hit's cell
+// with "hit", "wet" and "shadowed" in its three free bits, and the mirror hit's cell in hcell (all ones: the mirror ray did not hit);
+// colours and diffuse levels are fetched behind the marches.  Keeps-pixel form (bilinear): the primary pixel, weighted behind pass 1
+// where its point is still at hand, with "hit", "wet" and "mirror ray hit" beside it.  The primary direction is not kept at all: the
+// lane makes its camera ray again from its number in the wave, for the mirror ray and for the miss shades -- the same operations,
+// the same bits.  A capped ray is counted behind the pass it belongs to; nothing is held for that.
+// DEFER and CARRY are MIRROR's choices, taken over with its structure and not decided again.
+// Termination: the pass number is wave-uniform and only grows -- 0, then 1 or 2 or the end, ... -- so the outer loop runs at most four
+// times, and each pass is the march loop with a budget of its own: the step cap, min(step cap, the sun's limit) for passes 1 and 3,
+// min(step cap, the water's limit) for pass 2.
+struct SunWater : Frames {
+	static constexpr bool SEG = true, MIRROR = true, SUNLIT = true;
+	struct Args { const SegRules &seg; const WaterRules &water; const SunRules &sun; };
+};
 
 // ---- a family: its tag's switches, the four dispatched values, and what follows from them ----
 // SAMP: 0 nearest cell (the reference), 1 bilinear quality mode, 2 nearest cell with float thresholds (`thr` then points at the
@@ -182,13 +204,15 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	static constexpr int PROJ = PROJ_, GWM = GWM_, LEAP = LEAP_, SAMP = SAMP_;
 	static constexpr bool STATS = TAG::STATS, AA = TAG::AA, SEG = TAG::SEG, LIT = TAG::LIT, SHADE = TAG::SHADE, SUM = TAG::SUM,
 	                      GEOM = TAG::GEOM, LSUM = TAG::LSUM, BAKED = TAG::BAKED, MIRROR = TAG::MIRROR;
+	static constexpr bool SUNLIT = TAG::SUNLIT; // (shadowed and shaded on both sides of the mirror: the one tag with MIRROR and a sun)
 	static constexpr bool CELLS = PROJ == 5;
 	static_assert(!MIRROR || SEG, "water frames: under the segment rules");
 	static_assert(!MIRROR || !CELLS, "water frames: a camera's frame, not a cell map");
 	static_assert(!MIRROR || PROJ != 4, "water frames: a camera's frame, not a ray batch");
 	static_assert(!MIRROR || !STATS, "water frames: production kernels only");
-	static_assert(!MIRROR || !LIT, "water frames: no sun shadows");
-	static_assert(!MIRROR || !SHADE, "water frames: no sun shading");
+	static_assert(!MIRROR || !LIT, "water frames: no sun shadows by LIT's two passes (SUNLIT has its own four)");
+	static_assert(!MIRROR || !SHADE, "water frames: no sun shading by SHADE's epilogue (SUNLIT weights both sides itself)");
+	static_assert(!SUNLIT || (MIRROR && !BAKED && !AA), "sun-lit water frames: water frames, neither under the light plane nor antialiased");
 	static_assert(!MIRROR || !GEOM, "water frames: no geometry planes");
 	static_assert(!BAKED || (SEG && !CELLS && PROJ != 4 && !STATS && !LIT && !SHADE && !GEOM), "baked-light frames: plain or water frames under the segment rules");
 	static_assert(!LSUM || (LIT && !SHADE && !AA), "accumulated lit frames: the lit kernels' marches, the weights by a run-time flag");

@@ -90,6 +90,8 @@ __global__ __launch_bounds__(256) void k_prepare_heights(const uint8_t *__restri
 // 5 (hmrm_render_water): pass 2 for a mirror ray -- the caller hands the lane's own direction, step and limit in `sun` -- whose pixel,
 // the hit cell's colour or the miss shade of its own dz, comes back in lit->rgba; `hit_cell` (may be null): where the mirror ray's
 // hit cell goes, for the light of a water frame under the light plane -- left alone when the ray did not hit.
+// 6 (hmrm_render_water_lit): pass 5 that also leaves where the mirror ray hit, and under which threshold, in *lit as pass 1 does --
+// the origin of that hit's own shadow ray.  A mode of its own: pass 5's callers keep their instructions.
 template <int PROJ, bool STATS, bool AA, bool SEG = false, int LIT = 0>
 __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId pid, const double *__restrict__ thr,
                                                     const uint32_t *__restrict__ cmap, uint32_t *__restrict__ out,
@@ -190,6 +192,10 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 					if constexpr (LIT == 5) {
 						if (hit_cell) *hit_cell = (unsigned)cell;
 					}
+					if constexpr (LIT == 6) {
+						lit->hx = x; lit->hy = y; lit->t = t;
+						if (hit_cell) *hit_cell = (unsigned)cell;
+					}
 					break;
 				}
 				x = x + sx;
@@ -225,7 +231,7 @@ __device__ __forceinline__ void render_lane_literal(const DevFrame &f, PixelId p
 			if (real_hit) lit->phase = 1;
 		} else if constexpr (LIT == 4) {
 			lit->phase = real_hit ? 1 : (my_cap != 0u ? 2 : (sg.ended ? 3 : 0));
-		} else if constexpr (LIT == 5) {
+		} else if constexpr (LIT == 5 || LIT == 6) {
 			lit->rgba = rgba;
 		} else
 		if constexpr (RAYS && SEG) store_batch_hit(batch, ray_index, real_hit, my_cap != 0u, hx, hy, hz, hgx, hgy, sg.d_record, (uint32_t)my_steps, rgba, sg.ended);
@@ -726,7 +732,8 @@ static hipError_t launch_geometry_literal(const FrameLaunch &l); // (hmrm_render
 static hipError_t launch_lit_sum_literal(const FrameLaunch &l);  //  the last kernels of the code object)
 static hipError_t launch_baked_literal(const FrameLaunch &l);    // (hmrm_render_baked's, behind those)
 static hipError_t launch_water_literal(const FrameLaunch &l);    // (hmrm_render_water's, behind those)
-static hipError_t launch_water_literal_more(const FrameLaunch &l); // (hmrm_render_water_aa's, the last kernels of the code object)
+static hipError_t launch_water_literal_more(const FrameLaunch &l); // (hmrm_render_water_aa's, behind those)
+static hipError_t launch_water_lit_literal(const FrameLaunch &l);  // (hmrm_render_water_lit's, the last kernels of the code object)
 
 // The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
 // shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
@@ -745,6 +752,7 @@ hipError_t launch_frame_literal(const FrameLaunch &l) {
 	if (l.family == kFrameBaked) return launch_baked_literal(l);
 	if (l.family == kFrameWater) return launch_water_literal(l);
 	if (l.family == kFrameWaterAA || l.family == kFrameWaterBaked || l.family == kFrameWaterBakedAA) return launch_water_literal_more(l);
+	if (l.family == kFrameWaterLit) return launch_water_lit_literal(l);
 	if (l.f.aa_shift == 0) switch (l.family) {
 		case kFrameLit:
 			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
@@ -899,6 +907,65 @@ static hipError_t launch_water_literal_more(const FrameLaunch &l) {
 		if (l.family == kFrameWaterAA) hipLaunchKernelGGL((k_render_water_literal_more<proj(), true, false>), grid, block, 0, l.stream, args..., seg, l.water, l.baked);
 		else if (l.family == kFrameWaterBaked) hipLaunchKernelGGL((k_render_water_literal_more<proj(), false, true>), grid, block, 0, l.stream, args..., seg, l.water, l.baked);
 		else hipLaunchKernelGGL((k_render_water_literal_more<proj(), true, true>), grid, block, 0, l.stream, args..., seg, l.water, l.baked);
+	});
+}
+
+// A pixel of a sun-lit water frame (hmrm_render_water_lit with HMRM_KERNEL=simple, or on a map with a side of 2^24 cells): the literal
+// loop up to four times -- the primary ray, its hit's shadow ray, a wet lane's mirror ray, that ray's hit's shadow ray -- then
+// hmrm_render_shaded's weight on either side of the mirror and hmrm_render_water's blend.  Each pass counts its own capped rays.
+// Whether shadow rays are cast and whether the weights are diffuse are the launch's flags (frame.hpp kWaterSun*): scalar branches.
+template <int PROJ>
+__global__ __launch_bounds__(kBlockThreads) void k_render_water_lit_literal(const DevFrame f, const RowMap rows,
+                                                                            const double *__restrict__ thr,
+                                                                            const uint32_t *__restrict__ cmap,
+                                                                            uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                            int tiles_y, StatsOut st, const SegRules seg,
+                                                                            const WaterRules water, const SunRules sun) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	const bool shadows = (water.flags & kWaterSunNoShadows) == 0u, diffuse = (water.flags & kWaterSunDiffuse) != 0u;
+	const SegRules sun_seg{nullptr, sun.max_steps, 1u};
+	LitState<true> lt;
+	unsigned cell = 0u, mcell = ~0u; // (mcell: the mirror ray's hit cell, if it hit)
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, sun, &lt, &cell);
+	const bool wet = pid.live && lt.primary_hit && lt.t <= water.level; // (a NaN level: no water)
+	LitState<true> ps = lt; // (the primary hit's shadow ray: SHADOWED comes back in ps.phase)
+	if (shadows) render_lane_literal<PROJ, false, false, true, 3>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, sun_seg, sun, &ps);
+	LitState<true> mr = lt;
+	mr.primary_hit = wet; // (the other lanes sit the pass out)
+	SunRules mirror{{0.0, 0.0, 0.0}, water.step_dist, water.max_steps, 0u};
+	if (wet) {
+		const DevRay primary = make_ray<PROJ>(f, pid.px, pid.py);
+		mirror.dir[0] = primary.dx; mirror.dir[1] = primary.dy; mirror.dir[2] = -primary.dz;
+	}
+	render_lane_literal<PROJ, false, false, true, 6>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{},
+	                                                 SegRules{nullptr, water.max_steps, 1u}, mirror, &mr, &mcell);
+	LitState<true> ms = mr; // (the mirror hit's shadow ray, from the point and threshold pass 6 left)
+	ms.primary_hit = wet && mcell != ~0u;
+	ms.phase = 0;
+	if (shadows) render_lane_literal<PROJ, false, false, true, 3>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, sun_seg, sun, &ms);
+	if (!pid.live) return;
+	auto weight_of = [&](bool shadowed, unsigned c) -> uint32_t {
+		if (shadowed) return sun.ambient;
+		return diffuse ? shade_weight(sun.ambient, diffuse_level_nearest<false>(f, thr, c, sun.dir)) : 255u;
+	};
+	uint32_t rgba = lt.rgba;
+	if (lt.primary_hit) {
+		rgba = shade_weighted(wet ? water_base(rgba, water) : rgba, weight_of(ps.phase != 0, cell)) | 0xff000000u;
+		if (wet) {
+			uint32_t m = mr.rgba; // (MISS, END and CAPPED: the miss shade, untouched)
+			if (mcell != ~0u) m = shade_weighted(m, weight_of(ms.phase != 0, mcell));
+			rgba = blend_water_base(rgba, m, water);
+		}
+	}
+	out[(int64_t)pid.lrow * out_stride_px + pid.px] = rgba;
+}
+
+// Such a frame: the water family's arguments and the sun.  No antialiased variant, never a measured launch.
+static hipError_t launch_water_lit_literal(const FrameLaunch &l) {
+	if (l.rows.measure != nullptr || l.f.aa_shift != 0 || !l.d_out) return hipErrorInvalidValue;
+	const SegRules seg = frame_seg_rules(l);
+	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
+		hipLaunchKernelGGL(k_render_water_lit_literal<proj()>, grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.water, l.sun);
 	});
 }
 

@@ -58,6 +58,8 @@ struct FrameLaunch {
 	// or below water.level march a mirror ray in the same launch and take its pixel blended in (frame.hpp WaterRules).
 	// kFrameWaterAA, kFrameWaterBaked, kFrameWaterBakedAA (hmrm_render_water_aa): that frame antialiased with f.aa_shift, under
 	// `baked` (both the primary and the mirror pixel take the weight of their own hit's light before the blend), and both
+	// kFrameWaterLit (hmrm_render_water_lit): kFrameWater's frame under `sun`, both sides of the mirror at hmrm_render_shaded's weight;
+	// the two shade flags travel in water.flags (frame.hpp kWaterSunDiffuse, kWaterSunNoShadows); no AA
 	WaterRules water = WaterRules{0.0, 0.0, 0u, 0u, 0u, 0u};
 };
 // The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups

@@ -301,6 +301,8 @@ def _load():
         "hmrm_render_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), vp, C.c_size_t]),
         "hmrm_render_water": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), vp, C.c_size_t]),
         "hmrm_render_water_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), vp, C.c_size_t, vp]),
+        "hmrm_render_water_lit": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
+        "hmrm_render_water_lit_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t, vp]),
         "hmrm_render_water_aa": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), C.c_uint32, i32, vp, C.c_size_t]),
         "hmrm_render_water_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), C.c_uint32, C.c_uint32, C.POINTER(i32)]),
         "hmrm_render_water_device_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Water), C.c_uint32, vp, C.c_size_t, C.c_uint32,
@@ -309,6 +311,7 @@ def _load():
                                               C.c_double, i32, C.c_char_p, C.c_longlong, i32, i32, C.c_uint32, C.POINTER(Water),
                                               C.c_uint32]),
         "hmrm_config_water_scope": (i32, [vp]),
+        "hmrm_config_water_light": (i32, [vp]),
         "hmrm_config_water": (i32, [vp]),
         "hmrm_config_get_water": (None, [vp, C.POINTER(Water)]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
@@ -408,7 +411,8 @@ lib, EXPORTED_SYMBOLS = _load()
 KERNEL_SOURCES = ("render_fast.hip", "render_rays.hip", "leap_common.hpp", "leap_diag.hpp", "render.hip", "device_common.hpp", "frame.hpp",
                   "render.hpp", "api_internal.hpp", "api_launch.cpp", "api_frames.cpp", "launch_order.cpp", "launch_order.hpp", "camera.cpp", "Makefile",
                   "march.hpp", "march_family.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip",
-                  "render_water.hip", "render_water_aa.hip", "render_water_baked.hip", "render_water_baked_aa.hip")
+                  "render_water.hip", "render_water_aa.hip", "render_water_baked.hip", "render_water_baked_aa.hip",
+                  "render_water_lit.hip")
 
 
 def kernel_src_sha() -> str:
@@ -577,6 +581,26 @@ class Scene:
         self._sync_env()
         _check(lib.hmrm_render_water_device(self._h, C.byref(cam), C.byref(water), C.c_void_p(d_rgba), int(stride_bytes),
                                             C.c_void_p(stream)))
+
+    def render_water_lit(self, cam: Camera, water: Water, sun: Sun, diffuse=True, shadows=True, allow_capped=False) -> np.ndarray:
+        """One full sun-lit water frame (hmrm_render_water_lit): render_water's and render_shaded's frames composed in one launch
+        -- every hit pixel, wet or dry, at render_shaded's weight of its hit under `sun` (`diffuse`, `shadows` as there), a wet
+        pixel's mirror pixel at the weight of the mirror ray's own hit, then render_water's blend -> HxWx4 uint8.  Capped primary,
+        mirror or shadow rays: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        fb = np.empty((cam.height, cam.width, 4), dtype=np.uint8)
+        _check(lib.hmrm_render_water_lit(self._h, C.byref(cam), C.byref(water), C.byref(sun), shade_flags(diffuse, shadows), _ptr(fb),
+                                         cam.width * 4),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
+    def render_water_lit_device(self, cam: Camera, water: Water, sun: Sun, d_rgba: int, stride_bytes: int, diffuse=True, shadows=True,
+                                stream: int = 0):
+        """hmrm_render_water_lit_device: the same frame into device memory at address d_rgba, rows stride_bytes apart, enqueued on
+        `stream` without a host sync; take_capped(stream) reports the capped rays."""
+        self._sync_env()
+        _check(lib.hmrm_render_water_lit_device(self._h, C.byref(cam), C.byref(water), C.byref(sun), shade_flags(diffuse, shadows),
+                                                C.c_void_p(d_rgba), int(stride_bytes), C.c_void_p(stream)))
 
     def render_water_aa(self, cam: Camera, water: Water, factor=1, baked=False, allow_capped=False) -> np.ndarray:
         """render_water's frame antialiased (factor 1, 2, 4 or 8: factor x factor box-filtered samples per pixel inside the
@@ -1294,6 +1318,10 @@ class Config:
     def water_scope(self) -> int:
         """Additive `water_scope frame|all`: 0 | 1 -- whether water also applies to antialiased, recorded and baked-light frames."""
         return int(lib.hmrm_config_water_scope(self._h))
+
+    def water_light(self) -> int:
+        """Additive `water_light off|sun`: 0 | 1 -- whether `water on` beside shadows / shading is the sun-lit water frame."""
+        return int(lib.hmrm_config_water_light(self._h))
 
     def water_on(self) -> bool:
         """Additive `water on|off`: the CLI renders its single frame with hmrm_render_water."""

@@ -766,9 +766,9 @@ int hmrm_render_baked_device_begin(const hmrm_scene *scene, const hmrm_camera *c
  * with the scene's current kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST); every kernel
  * writes the same bytes, the literal loop too (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest sampling only).  All three
  * projections, grid modes and sampling modes.
- * OUT OF SCOPE: strip and multi-GPU water frames (hmrm_render_multi), statistics and geometry planes of a water frame; water
- * combined with shadow rays or diffuse shading; refraction, Fresnel terms, waves; a second bounce.  Antialiased, ticketed and
- * recorded water frames, and water under the scene's baked light: below. */
+ * OUT OF SCOPE: strip and multi-GPU water frames (hmrm_render_multi), statistics and geometry planes of a water frame;
+ * refraction, Fresnel terms, waves; a second bounce.  Antialiased, ticketed and recorded water frames, and water under the scene's
+ * baked light: below.  Water combined with shadow rays and diffuse shading: hmrm_render_water_lit, below those. */
 #define HMRM_WATER_OWN_COLOR 2u      /* the water's own colour is `color`, not the primary pixel */
 typedef struct hmrm_water {          /* 32 bytes */
 	double   level;        /* a hit is WATER when t <= level; compared as doubles, as given */
@@ -821,6 +821,46 @@ int hmrm_record_orbit_water(hmrm_scene *const *scenes, int32_t n_scenes, const h
                             double centre_y, double radius, double hang0, int32_t frames, const char *dir, long long id,
                             int32_t encoder_threads, int32_t verbose, uint32_t flags, const hmrm_water *water,
                             uint32_t water_mode);
+
+/* THE SUN-LIT WATER FRAME composes hmrm_render_water and hmrm_render_shaded and adds nothing.  It follows the pattern of the baked
+ * water frame, with hmrm_render_shaded's weight in place of the plane's.
+ * Inputs: a camera, an hmrm_water, an hmrm_sun, and shade_flags, with HMRM_SHADE_DIFFUSE and HMRM_SHADE_NO_SHADOWS as today.  The
+ * primary rays run under the interior rule when water->flags or sun->flags carries HMRM_TRACE_INTERIOR.
+ * 1. PRIMARY PIXEL, t, WATER.  These are exactly hmrm_render_water's: the same primary march, the same threshold t, the same
+ *    t <= level comparison.
+ * 2. WEIGHT OF A HIT.  w(hit) is hmrm_render_shaded's w for that hit under sun and shade_flags:
+ *    - Without HMRM_SHADE_NO_SHADOWS, the hit casts hmrm_render_lit's shadow ray.  Its origin is (H.x, H.y, t_H), with H the hit's
+ *      int_point and t_H the threshold its hitting load compared z with.  It uses sun->dir, sun->step_dist and sun->max_steps, with
+ *      the interior rule on.  A shadow ray whose status is HIT gives w = ambient.
+ *    - Otherwise w = 255 without HMRM_SHADE_DIFFUSE.  With it, w = ambient + ((255 - ambient) * q + 127) / 255.  q is the level of
+ *      that hit from the existing arithmetic: the hit's cell for the nearest modes, the hit's point for bilinear.
+ *    - weight(c, w) = (c * w + 127) / 255 per channel.
+ * 3. BASE.  Every pixel whose primary ray HIT, wet or dry, has b' = weight(b, w(primary hit)).  b is the primary pixel, or for a
+ *    WATER pixel with HMRM_WATER_OWN_COLOR the water's color.  An alpha-0 cell's background is weighted too, as in
+ *    hmrm_render_shaded.
+ * 4. MIRROR PIXEL.  A WATER pixel casts hmrm_render_water's mirror ray, unchanged.
+ *    - If that ray's status is HIT, m' = weight(m, w(mirror hit)).  Its own shadow ray starts at the mirror ray's int_point and the
+ *      threshold of the mirror ray's hitting load.  Its own diffuse level is taken at the mirror hit's cell or point.
+ *    - For MISS, END and CAPPED, m' is the mirror ray's miss shade, untouched.
+ * 5. STORED PIXEL.  A WATER pixel stores hmrm_render_water's blend of b' and m'.  A dry hit stores b'.  Misses and capped primary
+ *    rays are untouched.
+ * 6. CAPPED RAYS.  All four kinds are counted together: primary rays, primary shadow rays, mirror rays and mirror shadow rays.  END
+ *    rays are never counted.  Either kind returns HMRM_E_NOTERM with a valid frame.
+ * Consequences, each byte for byte: a level below every threshold, or a NaN level, gives hmrm_render_shaded; r = 0 without own
+ * colour gives hmrm_render_shaded; HMRM_SHADE_NO_SHADOWS alone gives hmrm_render_water; ambient = 255 gives hmrm_render_water under
+ * any flags (the shadow rays are marched all the same).
+ * Refusals are HMRM_E_ARG with a message and come before the scene is looked at, in this order: hmrm_render_water's three of the
+ * water; hmrm_render_shaded's four of the sun and shade_flags; then as hmrm_render_water / hmrm_render_water_device.
+ * hmrm_render_water_lit is synchronous on the scene's stream; hmrm_render_water_lit_device is hmrm_render_water_device's form.
+ * Launched like every water frame: one launch, never measured, never the probe and not counted towards it, with the scene's
+ * current kernel; every kernel writes the same bytes, the literal loop too (nearest sampling only).  A wave marches up to four
+ * times in that launch; nothing per pixel goes through memory.
+ * OUT OF SCOPE: antialiased, ticketed and recorded lit water frames; lit water under the baked plane; several suns; strips and
+ * multi-GPU. */
+int hmrm_render_water_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, const hmrm_sun *sun,
+                          uint32_t shade_flags, uint8_t *rgba, size_t stride_bytes);
+int hmrm_render_water_lit_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, const hmrm_sun *sun,
+                                 uint32_t shade_flags, void *d_rgba, size_t stride_bytes, void *hip_stream);
 
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
@@ -1067,9 +1107,16 @@ int32_t      hmrm_config_water(const hmrm_config *cfg);         /* additive `wat
  * water_max_steps (default 0 = none; a value outside 0..4294967295 is warned about and ignored), water_reflectivity (default 128;
  * outside 0..255 likewise), water_color r g b (sets HMRM_WATER_OWN_COLOR; a component outside 0..255 likewise);
  * flags |= HMRM_TRACE_INTERIOR when `interior on`.  `hmap` renders its single frame with hmrm_render_water when `water on`; the key
- * is ignored, with a warning, beside `antialias` > 1, `devices` > 1, `record orbit`, `shadows`, `shading` and `baked_light`. */
+ * is ignored, with a warning, beside `antialias` > 1, `devices` > 1, `record orbit`, `shadows`, `shading` and `baked_light`
+ * (`water_scope all` and `water_light sun`, below, lift some of these). */
 void         hmrm_config_get_water(const hmrm_config *cfg, hmrm_water *out);
 int32_t      hmrm_config_water_scope(const hmrm_config *cfg);   /* additive `water_scope frame|all`: 0|1 */
+/* Additive `water_light off|sun` (default off; another value warns "WARNING: Unknown water_light: v" and keeps the old one): 0|1.
+ * With `sun`, `hmap` renders `water on` beside `shadows on` and / or `shading on` with hmrm_render_water_lit -- the sun and the
+ * shade flags the shaded single frame would get -- when there is no `baked_light`, one device and `antialias 1`, under either
+ * `water_scope`; beside `antialias` > 1, `devices` > 1, `record orbit` or `baked_light` the existing warnings stand.  With `off`
+ * nothing changes. */
+int32_t      hmrm_config_water_light(const hmrm_config *cfg);
 /* Loaded maps (owned by cfg): RGB8 / RGBA8; NULL until the key was consumed. */
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *cfg, int32_t *w, int32_t *h);
 const uint8_t *hmrm_config_color_rgba(const hmrm_config *cfg, int32_t *w, int32_t *h);

@@ -15,8 +15,13 @@ comparison alternate in the same process, --warmup launches of each come first, 
       resolution each way: the super frame is (a)'s frame, so the two also stand beside (a)'s.
   (d) the water frame under the scene's light plane (HMRM_WATER_BAKED; a formula plane, full scale 1000: the cost does not depend
       on the words) against hmrm_render_baked and, once more, against the plain water frame.
+  (e) the sun-lit water frame (hmrm_render_water_lit, diffuse levels and shadow rays, a sun 15 degrees above the horizon) beside the
+      water frame, beside hmrm_render_shaded with the same flags, and beside the multi-launch route it replaces: hmrm_render_shaded
+      plus an hmrm_trace_segments_device batch of the frame's mirror rays plus one of the mirror hits' shadow rays, both prepared
+      beforehand -- copies and glue not counted.  The tool checks that the batches' records (with the primary hits' shadow batch, for
+      the check alone) reproduce the frame.
 
-    python tools/water_bench.py [--pairs 9] [--warmup 8] [--share 0.27] [--res 3840x2160]
+    python tools/water_bench.py [--pairs 9] [--warmup 8] [--share 0.27] [--res 3840x2160] [--cases abcde]
 """
 import argparse
 import importlib
@@ -46,12 +51,124 @@ def box_filter_2(frame):
     return out
 
 
+def diffuse_weights(records, thr2d, params, sun_dir, ambient, shadowed):
+    """hmrm_render_shaded's weight of every record that hit, nearest sampling, in include/hmrm.h's operation order (255 elsewhere)."""
+    mh, mw = thr2d.shape
+    hit = records["status"] == hm.RAY_HIT
+    cx, cy = np.where(hit, records["cell_x"], 0).astype(np.int64), np.where(hit, records["cell_y"], 0).astype(np.int64)
+    xm, xp, ym, yp = np.maximum(cx - 1, 0), np.minimum(cx + 1, mw - 1), np.maximum(cy - 1, 0), np.minimum(cy + 1, mh - 1)
+    gw = params.grid_width
+    s = np.asarray(sun_dir, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        gx = np.where(xp > xm, (thr2d[cy, xp] - thr2d[cy, xm]) / ((xp - xm).astype(np.float64) * gw), 0.0)
+        gy = np.where(yp > ym, (thr2d[yp, cx] - thr2d[ym, cx]) / ((yp - ym).astype(np.float64) * gw), 0.0)
+        nx, ny = -gx, gy
+        k = ((nx * s[0] + ny * s[1]) + s[2]) / np.sqrt(((nx * nx + ny * ny) + 1.0) * ((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]))
+        q = (np.where(k > 0.0, np.where(k < 1.0, k, 1.0), 0.0) * 255.0 + 0.5).astype(np.int64)
+    w = int(ambient) + ((255 - int(ambient)) * q + 127) // 255
+    return np.where(hit, np.where(shadowed, int(ambient), w), 255)
+
+
+def weighted(rgba, w):
+    out = rgba.copy()
+    out[:, 0:3] = ((rgba[:, 0:3].astype(np.int64) * w[:, None] + 127) // 255).astype(np.uint8)
+    return out
+
+
+def lit_water_case(args, torch, scene, cam, params, wl, rays, order, heights, level, water, bg, frame_ms, results):
+    """(e): the sun-lit water frame beside the water frame, the shaded frame and the multi-launch route."""
+    sun_dir, ambient = (0.837, 0.483, 0.259), 96
+    sun = hm.Sun.make(sun_dir, cam.step_dist, ambient=ambient)
+    thr2d = heights + params.min_height
+    thr = thr2d.reshape(-1)
+    f_lit_water = lambda: frame_ms(lambda: scene.render_water_lit(cam, water, sun))
+    f_water = lambda: frame_ms(lambda: scene.render_water(cam, water))
+    f_shaded = lambda: frame_ms(lambda: scene.render_shaded(cam, sun))
+    lw1_ms, water_ms = alternate(f_lit_water, f_water, args.warmup, args.pairs)
+    lw2_ms, shaded_ms = alternate(f_lit_water, f_shaded, args.warmup, args.pairs)
+    # the batches: the frame's mirror rays and the mirror hits' shadow rays, in the frame kernel's wave order
+    stream = torch.cuda.Stream()
+
+    def segments(batch_rays):
+        """-> (records of the batch, a callable that runs it once more and returns its time by events)"""
+        k = batch_rays.shape[0]
+        d_rays = torch.from_numpy(np.ascontiguousarray(batch_rays)).cuda()
+        d_hits = torch.zeros(max(k, 1) * 56, dtype=torch.uint8, device="cuda")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+
+        def run():
+            with torch.cuda.stream(stream):
+                e0.record(stream)
+                scene.trace_segments_device(d_rays.data_ptr(), k, d_hits.data_ptr(), cam.step_dist, bg=bg, interior=True,
+                                            stream=stream.cuda_stream)
+                e1.record(stream)
+            e1.synchronize()
+            return float(e0.elapsed_time(e1))
+
+        run()
+        scene.take_capped(stream.cuda_stream, allow_capped=True)
+        return d_hits.cpu().numpy().view(hm.RAY_HIT_DTYPE)[:k].copy(), run, (d_rays, d_hits)
+
+    def shadow_rays_of(records):
+        hit = records["status"] == hm.RAY_HIT
+        cell = np.where(hit, records["cell_x"].astype(np.int64) + records["cell_y"].astype(np.int64) * wl.map_size, 0)
+        out = np.empty((int(hit.sum()), 6), dtype=np.float64)
+        out[:, 0:2] = records["point"][hit, 0:2]
+        out[:, 2] = thr[cell[hit]]
+        out[:, 3:6] = np.asarray(sun_dir, dtype=np.float64)
+        return hit, out
+
+    primary = scene.trace_rays(rays, cam.step_dist, bg=bg)
+    hit, srays = shadow_rays_of(primary)
+    cell = np.where(hit, primary["cell_x"].astype(np.int64) + primary["cell_y"].astype(np.int64) * wl.map_size, 0)
+    wet = hit & (thr[cell] <= level)
+    mrays = np.empty((int(wet.sum()), 6), dtype=np.float64)
+    mrays[:, 0:2] = primary["point"][wet, 0:2]
+    mrays[:, 2] = thr[cell[wet]]
+    mrays[:, 3:5] = rays[wet, 3:5]
+    mrays[:, 5] = -rays[wet, 5]
+    mirror, run_mirror, keep1 = segments(mrays)
+    mhit, msrays = shadow_rays_of(mirror)
+    mshadow, run_mshadow, keep2 = segments(msrays)
+    lw3_ms, mirror_ms = alternate(f_lit_water, run_mirror, args.warmup, args.pairs)
+    lw4_ms, mshadow_ms = alternate(f_lit_water, run_mshadow, args.warmup, args.pairs)
+    scene.take_capped(stream.cuda_stream, allow_capped=True)
+    # the check: the records reproduce the frame (the primary hits' shadow batch is run for this alone)
+    shadow, _run, keep3 = segments(srays)
+    shadowed = np.zeros(primary.shape[0], dtype=bool)
+    shadowed[hit] = shadow["status"] == hm.RAY_HIT
+    mshadowed = np.zeros(mirror.shape[0], dtype=bool)
+    mshadowed[mhit] = mshadow["status"] == hm.RAY_HIT
+    want = weighted(primary["rgba"], diffuse_weights(primary, thr2d, params, sun_dir, ambient, shadowed))
+    m = weighted(mirror["rgba"], diffuse_weights(mirror, thr2d, params, sun_dir, ambient, mshadowed))
+    r = int(water.reflectivity)
+    want[wet, 0:3] = ((want[wet, 0:3].astype(np.int64) * (255 - r) + m[:, 0:3].astype(np.int64) * r + 127) // 255).astype(np.uint8)
+    frame = scene.render_water_lit(cam, water, sun).reshape(-1, 4)[order]
+    agree = bool((frame == want).all())
+    route = statistics.median(shaded_ms) + statistics.median(mirror_ms) + statistics.median(mshadow_ms)
+    lit_all = lw1_ms + lw2_ms + lw3_ms + lw4_ms
+    r_water = sorted(x / y for x, y in zip(lw1_ms, water_ms))
+    r_shaded = sorted(x / y for x, y in zip(lw2_ms, shaded_ms))
+    print(f"(e) sun-lit water frame {med(lit_all)}; beside the water frame {med(water_ms)}: ratio {statistics.median(r_water):.3f} "
+          f"[{r_water[0]:.3f} .. {r_water[-1]:.3f}]; beside hmrm_render_shaded {med(shaded_ms)}: ratio {statistics.median(r_shaded):.3f} "
+          f"[{r_shaded[0]:.3f} .. {r_shaded[-1]:.3f}]; mirror batch of {mrays.shape[0]} rays {med(mirror_ms)}; mirror hits' shadow batch of "
+          f"{msrays.shape[0]} rays {med(mshadow_ms)}; hmrm_render_shaded + the two batches {route:.4f} ms; frame / route "
+          f"{statistics.median(lit_all) / route:.3f}; shadowed primary hits {int(shadowed.sum())} of {int(hit.sum())}, shadowed mirror hits "
+          f"{int(mshadowed.sum())} of {int(mhit.sum())}; the batches' records reproduce the frame: {agree}; kernel {scene.kernel_choice()}", flush=True)
+    results.append({"case": "e", "lit_water_ms": lit_all, "water_ms": water_ms, "shaded_ms": shaded_ms, "mirror_batch_ms": mirror_ms,
+                    "mirror_shadow_batch_ms": mshadow_ms, "mirror_rays": int(mrays.shape[0]), "mirror_shadow_rays": int(msrays.shape[0]),
+                    "agree": agree})
+    del keep1, keep2, keep3
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--share", type=float, default=0.27)
     ap.add_argument("--res", default="3840x2160")
+    ap.add_argument("--cases", default="abcde", help="which comparisons to run; (b) needs (a)'s times")
     args = ap.parse_args()
     import torch
     hm.set_device(0)
@@ -83,6 +200,13 @@ def main():
     def frame_ms(fn):
         fn()
         return float(lib.hmrm_last_kernel_ms())
+
+    if "e" in args.cases:
+        lit_water_case(args, torch, scene, cam, params, wl, rays, order, heights, level, water, bg, frame_ms, results)
+    if not set("abcd") & set(args.cases):
+        scene.close()
+        print(json.dumps(results))
+        return
 
     # ---- (a) the water frame against hmrm_render ----
     f_water = lambda: frame_ms(lambda: scene.render_water(cam, water))
