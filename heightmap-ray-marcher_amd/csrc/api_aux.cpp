@@ -140,6 +140,28 @@ void hmrm_config_get_water(const hmrm_config *c, hmrm_water *out) {
 	for (int k = 0; k < 3; ++k) out->color[k] = (uint8_t)g.water_color[k];
 }
 
+int32_t hmrm_config_haze(const hmrm_config *c) { return c->cfg.haze; }
+int32_t hmrm_config_haze_law(const hmrm_config *c) { return c->cfg.haze_law; }
+double hmrm_config_haze_density(const hmrm_config *c) { return c->cfg.haze_density; }
+double hmrm_config_haze_far(const hmrm_config *c) { return c->cfg.haze_far; }
+void hmrm_config_get_haze(const hmrm_config *c, hmrm_haze *out, uint8_t *table) {
+	const hmrm::Config &g = c->cfg;
+	if (out) {
+		memset(out, 0, sizeof *out);
+		out->start = g.haze_start;
+		out->scale = (double)g.haze_entries / (g.haze_far - g.haze_start);
+		out->n = (uint32_t)g.haze_entries;
+		out->flags = (g.interior ? HMRM_TRACE_INTERIOR : 0u) | (g.haze_sky ? HMRM_HAZE_SKY : 0u);
+		for (int k = 0; k < 3; ++k) out->color[k] = (uint8_t)g.haze_color[k];
+	}
+	if (table) (void)hmrm::fill_haze_table(g.haze_law, g.haze_density, g.haze_entries, table);
+}
+int hmrm_haze_table(int32_t law, double density, int32_t n, uint8_t *out) {
+	if (!hmrm::fill_haze_table(law, density, n, out))
+		return fail(HMRM_E_ARG, "hmrm_haze_table: law must be HMRM_HAZE_LINEAR, _EXP or _EXP2, n 1 .. 4096 and out not NULL");
+	return HMRM_OK;
+}
+
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *c, int32_t *w, int32_t *h) {
 	if (!c->cfg.have_heightmap) return nullptr;
 	if (w) *w = c->cfg.heightmap.w;

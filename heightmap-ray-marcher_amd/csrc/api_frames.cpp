@@ -554,6 +554,83 @@ int hmrm_render_water_device(const hmrm_scene *scene, const hmrm_camera *cam, co
 	return render_water_common(const_cast<hmrm_scene *>(scene), cam, water, d_rgba, stride_bytes, true, (hipStream_t)hip_stream, 1, 0u);
 }
 
+// ---- haze frames: hmrm_render's frame (hmrm_render_interior's with HMRM_TRACE_INTERIOR, hmrm_render_aa's with a factor) whose pixels
+// are blended towards one colour by the byte of the caller's table at their range, in the same launch ----
+// The five refusals of the header, in its order; needs no scene and no device.
+static_assert(sizeof(hmrm_haze) == 32 && offsetof(hmrm_haze, color) == 24, "hmrm_haze has padding");
+static int check_haze(const hmrm_haze *h, const void *table) {
+	if (!h) return fail(HMRM_E_ARG, "NULL haze");
+	if (h->flags & ~(HMRM_TRACE_INTERIOR | HMRM_HAZE_SKY)) return fail(HMRM_E_ARG, "hmrm_haze.flags: undefined bit");
+	for (uint8_t r : h->reserved)
+		if (r) return fail(HMRM_E_ARG, "hmrm_haze.reserved must be 0");
+	if (h->n < 1u || h->n > (uint32_t)hmrm::kMaxHazeEntries)
+		return fail(HMRM_E_ARG, "hmrm_haze.n must be 1 .. 4096 (got " + std::to_string(h->n) + ")");
+	if (!table) return fail(HMRM_E_ARG, "haze: NULL table");
+	return HMRM_OK;
+}
+
+// Launched the way an interior frame is (FrameRequest::own_kernels): never measured, never the probe, with the scene's current
+// kernel.  With the flag every origin is tested by the kernels, whatever the projection.  `device`: `table` and `target` are device
+// memory and the launch goes to `stream` without a host sync; else the table is staged through the scene's target list, as
+// hmrm_render_lit_sum's directions are, the frame through the scene's frame buffer, rows packed, and copied to the caller's behind
+// the launch.
+static int render_haze_common(hmrm_scene *s, const hmrm_camera *cam, const hmrm_haze *h, const void *table, int32_t factor, void *target,
+                              size_t stride_bytes, bool device, hipStream_t stream) {
+	int rc = check_haze(h, table);
+	if (rc) return rc;
+	if (factor != 1 && factor != 2 && factor != 4 && factor != 8) // (check_antialias's own refusal, ahead of the camera it needs for the rest)
+		return fail(HMRM_E_ARG, "antialias factor must be 1, 2, 4 or 8 (got " + std::to_string(factor) + ")");
+	if ((rc = check_camera(cam))) return rc;
+	hmrm_camera super;
+	int aa_shift = 0;
+	if ((rc = check_antialias(cam, factor, &super, &aa_shift))) return rc;
+	if (!s || !target) return fail(HMRM_E_ARG, "NULL argument");
+	const size_t W = (size_t)cam->width, H = (size_t)cam->height;
+	if (device) {
+		if ((rc = check_device_stride(cam, stride_bytes))) return rc;
+	} else if (stride_bytes < W * 4) return fail(HMRM_E_ARG, "stride_bytes < width*4");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	uint32_t *d_rgba = (uint32_t *)target;
+	int64_t stride_px = (int64_t)(stride_bytes / 4);
+	hmrm::HazeRules rules{static_cast<const uint8_t *>(table), h->start, h->scale, h->n,
+	                      (uint32_t)h->color[0] | ((uint32_t)h->color[1] << 8) | ((uint32_t)h->color[2] << 16), h->flags & HMRM_HAZE_SKY};
+	if (!device) {
+		if ((rc = s->d_frame.reserve(W * H * sizeof(uint32_t))) || (rc = s->d_targets.reserve((size_t)h->n))) return rc;
+		d_rgba = s->d_frame.as<uint32_t>();
+		stride_px = (int64_t)W;
+		stream = s->stream;
+		rules.table = s->d_targets.as<uint8_t>();
+		HIP_TRY(hipMemcpyAsync(s->d_targets.ptr, table, (size_t)h->n, hipMemcpyHostToDevice, s->stream));
+	}
+	FrameSetup fs;
+	if ((rc = setup_frame(s, stream, &super, aa_shift, &fs))) return rc;
+	StreamCtx *const c = fs.c;
+	FrameRequest req = plain_request(d_rgba, stride_px);
+	req.interior = (h->flags & HMRM_TRACE_INTERIOR) ? Interior::kByKernels : Interior::kNot;
+	req.haze = &rules;
+	if (!device) HIP_TRY(hipEventRecord(s->ev0, s->stream)); // (the host form is timed like hmrm_render: hmrm_last_kernel_ms)
+	if ((rc = launch_frame(s, c, fs.f, fs.slot, fs.rows, req)) || device) return rc;
+	HIP_TRY(hipEventRecord(s->ev1, s->stream));
+	HIP_TRY(hipMemcpy2DAsync(target, stride_bytes, d_rgba, W * 4, W * 4, H, hipMemcpyDeviceToHost, s->stream));
+	rc = finish_host_call(s, c);
+	float ms = 0.f;
+	HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+	g_last_kernel_ms = ms;
+	return rc;
+}
+
+int hmrm_render_haze(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_haze *haze, const uint8_t *table, int32_t factor,
+                     uint8_t *rgba, size_t stride_bytes) {
+	return render_haze_common(const_cast<hmrm_scene *>(scene), cam, haze, table, factor, rgba, stride_bytes, false, nullptr);
+}
+
+int hmrm_render_haze_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_haze *haze, const void *d_table, int32_t factor,
+                            void *d_rgba, size_t stride_bytes, void *hip_stream) {
+	return render_haze_common(const_cast<hmrm_scene *>(scene), cam, haze, d_table, factor, d_rgba, stride_bytes, true,
+	                          (hipStream_t)hip_stream);
+}
+
 // The sun-lit water frame: hmrm_render_water and hmrm_render_shaded composed, in one launch of a family of its own.
 int hmrm_render_water_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, const hmrm_sun *sun,
                           uint32_t shade_flags, uint8_t *rgba, size_t stride_bytes) {

@@ -218,7 +218,7 @@ struct hmrm_scene {
 	DeviceScratch d_hits;    // ... and host records out (hmrm::BatchHit); hmrm_pick's one record
 	DeviceScratch d_limits;  // hmrm_trace_segments' per-ray limits (uint32)
 	DeviceScratch d_cells;   // hmrm_cell_map's rect of bytes, hmrm_cell_map_sum's rect of 16-bit words: rows packed
-	DeviceScratch d_targets; // hmrm_cell_map_sum's targets and hmrm_render_lit_sum's directions: three doubles each
+	DeviceScratch d_targets; // hmrm_cell_map_sum's targets and hmrm_render_lit_sum's directions: three doubles each; hmrm_render_haze's table
 	DeviceScratch d_geom;    // hmrm_render_geometry's planes: the wanted ones back to back, slope first, rows packed
 	DeviceScratch d_light;   // hmrm_render_lit_sum's light plane (uint16), rows packed
 	// The scene's baked light plane (hmrm_scene_set_light, hmrm_scene_bake_light): map_w x map_h uint16, rows packed, read by the
@@ -296,10 +296,13 @@ struct FrameRequest {
 	const hmrm::WaterRules *water = nullptr;
 	// hmrm_render_water_lit's frame: `water` (with the shade flags in its flags word, frame.hpp kWaterSun*) and this sun; null: none.
 	const hmrm::SunRules *water_sun = nullptr;
-	// Frames under the interior rule, with a sun, with geometry planes, with baked light or with water run kernels of their own,
+	// hmrm_render_haze's frame: the table (device memory), the index arithmetic and the colour; null: none.  Its primary rays are
+	// under the interior rule when `interior` is not kNot, as a geometry frame's are.
+	const hmrm::HazeRules *haze = nullptr;
+	// Frames under the interior rule, with a sun, with geometry planes, with baked light, with water or with haze run kernels of their own,
 	// with the scene's current kernel kind (HMRM_KERNEL or the probe's verdict, read only).
 	bool own_kernels() const {
-		return interior != Interior::kNot || lit != nullptr || geom != nullptr || baked != nullptr || water != nullptr;
+		return interior != Interior::kNot || lit != nullptr || geom != nullptr || baked != nullptr || water != nullptr || haze != nullptr;
 	}
 	// Special frames -- those and instrumented ones -- are launched in the plain rotation order: never measured, never a probe,
 	// not counted towards the probe.

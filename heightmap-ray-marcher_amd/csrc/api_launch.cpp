@@ -164,6 +164,11 @@ int launch_kernel(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, const hm
 			l.sun = *req.water_sun;
 		}
 	}
+	if (req.haze) { // (likewise; a factor picks the family's antialiased kernels in its launchers)
+		l.family = hmrm::kFrameHaze;
+		l.haze = *req.haze;
+		l.primary_interior = req.interior != Interior::kNot;
+	}
 	if (route.literal) {
 		HIP_TRY(hmrm::launch_frame_literal(l));
 		return HMRM_OK;

@@ -17,6 +17,8 @@
 //   shading on|off, sun_scope single|all, sky_light on|off, baked_light off|sun|sky
 //   water on|off, water_level v, water_reflectivity n, water_color r g b, water_step_dist v, water_max_steps n,
 //   water_scope frame|all, water_light off|sun
+//   haze on|off, haze_start v, haze_far v, haze_law linear|exp|exp2, haze_density v, haze_color r g b, haze_sky on|off,
+//   haze_entries n
 //   sun_map <path.png>, sun_map_lift v                (the whole map's light map, hmrm_cell_map, written by the CLI)
 //   sky_map <path.png>, sky_map_rings r n             (the whole map's sky-view map, hmrm_cell_map_sum, written by the CLI)
 //   range_map <path.pfm>                              (the camera's range plane, hmrm_render_geometry, written by the CLI)
@@ -291,6 +293,45 @@ void water_light_key(Config &c, std::istream &in, const char *key, std::string *
 	c.log << key << " " << (c.water_light ? "sun" : "off") << "\n";
 }
 
+// distance fog in the single frame (hmrm_render_haze)
+void haze_key(Config &c, std::istream &in, const char *key, std::string *) {
+	static const Word words[] = {{"on", 1}, {"1", 1}, {"off", 0}, {"0", 0}};
+	std::string seen;
+	if (!pick(in, words, &c.haze, &seen)) c.warn << "WARNING: Unknown haze: " << seen << "\n";
+	c.log << key << " " << (c.haze ? "on" : "off") << "\n";
+}
+
+void haze_sky_key(Config &c, std::istream &in, const char *key, std::string *) { // the pixels that did not hit at the table's last entry
+	static const Word words[] = {{"on", 1}, {"1", 1}, {"off", 0}, {"0", 0}};
+	std::string seen;
+	if (!pick(in, words, &c.haze_sky, &seen)) c.warn << "WARNING: Unknown haze_sky: " << seen << "\n";
+	c.log << key << " " << (c.haze_sky ? "on" : "off") << "\n";
+}
+
+void haze_law_key(Config &c, std::istream &in, const char *key, std::string *) { // the table's law, hmrm_haze_table's
+	static const Word words[] = {{"linear", 0}, {"exp", 1}, {"exp2", 2}};
+	std::string seen;
+	if (!pick(in, words, &c.haze_law, &seen)) c.warn << "WARNING: Unknown haze_law: " << seen << "\n";
+	c.log << key << " " << words[c.haze_law].text << "\n";
+}
+
+void haze_color_key(Config &c, std::istream &in, const char *key, std::string *) {
+	long long v[3] = {-1, -1, -1};
+	in >> v[0] >> v[1] >> v[2];
+	if (!in || v[0] < 0 || v[0] > 255 || v[1] < 0 || v[1] > 255 || v[2] < 0 || v[2] > 255) c.warn << "WARNING: haze_color must be three values 0..255\n";
+	else
+		for (int k = 0; k < 3; ++k) c.haze_color[k] = (int)v[k];
+	c.log << key << " " << c.haze_color[0] << " " << c.haze_color[1] << " " << c.haze_color[2] << "\n";
+}
+
+void haze_entries_key(Config &c, std::istream &in, const char *key, std::string *) { // the table's length
+	long long v = -1;
+	in >> v;
+	if (!in || v < 1 || v > 4096) c.warn << "WARNING: haze_entries must be 1..4096\n";
+	else c.haze_entries = (int)v;
+	c.log << key << " " << c.haze_entries << "\n";
+}
+
 // which frames shadows / shading apply to: the plain single frame, or antialiased and recorded ones too
 void sun_scope_key(Config &c, std::istream &in, const char *key, std::string *) {
 	static const Word words[] = {{"single", 0}, {"all", 1}};
@@ -398,6 +439,14 @@ const Row kGrammar[] = {
 	{"water_color", water_color_key},
 	{"water_step_dist", water_step_dist_key},
 	{"water_max_steps", water_max_steps_key},
+	{"haze", haze_key},
+	{"haze_start", scalar<&Config::haze_start>},
+	{"haze_far", scalar<&Config::haze_far>},
+	{"haze_law", haze_law_key},
+	{"haze_density", scalar<&Config::haze_density>},
+	{"haze_color", haze_color_key},
+	{"haze_sky", haze_sky_key},
+	{"haze_entries", haze_entries_key},
 };
 
 } // namespace
@@ -435,6 +484,18 @@ bool Config::consume(std::istream &input, std::string *fatal) {
 		m << "heightmap dimensions (" << heightmap.w << "x" << heightmap.h
 		  << ") must match colormap dimensions (" << colormap.w << "x" << colormap.h << ")";
 		return die(m.str());
+	}
+	return true;
+}
+
+bool fill_haze_table(int law, double density, int n, unsigned char *out) {
+	if (law < 0 || law > 2 || n < 1 || n > 4096 || !out) return false;
+	for (int i = 0; i < n; ++i) {
+		const double x = ((double)i + 0.5) / (double)n;
+		const double dx = density * x;
+		const double t = law == 0 ? 1.0 - x : (law == 1 ? std::exp(-density * x) : std::exp(-(dx * dx)));
+		const int v = (int)(255.0 * (1.0 - t) + 0.5);
+		out[i] = (unsigned char)(v > 255 ? 255 : v);
 	}
 	return true;
 }

@@ -90,6 +90,16 @@ struct Config {
 	// additive: `range_map <path.pfm>` -- the CLI also writes the range plane of the configured camera's geometry frame
 	// (hmrm_render_geometry; under the interior rule with `interior on`) there as a one-component portable float map
 	std::string range_map_path;
+	// additive: haze of the CLI's single frame (hmrm_render_haze): `haze on|off|1|0`, `haze_start v` and `haze_far v` (the ranges
+	// of the table's first and last entry: scale = entries / (far - start)), `haze_law linear|exp|exp2` and `haze_density v`
+	// (hmrm_haze_table's), `haze_color r g b`, `haze_sky on|off|1|0` (HMRM_HAZE_SKY), `haze_entries n` (1 .. 4096)
+	int haze = 0;
+	double haze_start = 0.0, haze_far = 1000.0;
+	int haze_law = 1;
+	double haze_density = 3.0;
+	int haze_color[3] = {200, 210, 220};
+	int haze_sky = 0;
+	int haze_entries = 256;
 
 	bool heightmap_dirty = false; // should_update_heightmap, sticky until taken
 	std::ostringstream log;       // what the reference prints to stdout
@@ -103,5 +113,9 @@ struct Config {
 	bool consume(std::istream &input, std::string *fatal);
 
 };
+
+// hmrm_haze_table (hmrm.h): out[i] = min(255, (int)(255 * (1 - T) + 0.5)), x = (i + 0.5) / n, T by `law` with libm's exp.
+// False for an unknown law, n outside 1 .. 4096 or a null `out`.
+bool fill_haze_table(int law, double density, int n, unsigned char *out);
 
 } // namespace hmrm

@@ -146,6 +146,18 @@ __device__ __forceinline__ uint32_t blend_water(uint32_t primary, uint32_t mirro
 	const uint32_t c2 = (((b >> 16) & 255u) * k + ((mirror >> 16) & 255u) * r + 127u) / 255u;
 	return c0 | (c1 << 8) | (c2 << 16) | 0xff000000u;
 }
+// Haze frames (hmrm_render_haze; frame.hpp HazeRules).  The table's entry of a range r: u = (r - start) * scale -- one subtract,
+// one multiply -- then n - 1 for u >= n - 1, else the truncation of a positive u, else 0 (a NaN u fails both tests).  And the pixel
+// under the entry's byte f: the water's blend with the haze colour for a mirror pixel and f for the reflectivity.
+__device__ __forceinline__ uint32_t haze_index(const HazeRules &h, double r) {
+	const double u = (r - h.start) * h.scale;
+	const uint32_t last = h.n - 1u;
+	return u >= (double)last ? last : (u > 0.0 ? (uint32_t)(int)u : 0u);
+}
+__device__ __forceinline__ uint32_t blend_haze(uint32_t rgba, const HazeRules &h, uint32_t index) {
+	const uint32_t amount = h.table[index];
+	return blend_water_base(rgba, h.color, WaterRules{0.0, 0.0, 0u, amount, 0u, 0u});
+}
 
 // The diffuse level q in 0..255 of a surface with the gradient (gx, gy) -- gy along the rows, which grow towards decreasing
 // world y -- under the sun direction s as given: n = (-gx, gy, 1), q = round(255 * clamp(n.s / (|n| |s|), 0, 1)), every
@@ -566,14 +578,18 @@ __device__ __forceinline__ void store_box_filtered(uint32_t *__restrict__ out, i
 // hit in cell `cell` at int_point = (x, y, z), or did not hit.  The pointers are kernel arguments: each test is a scalar branch.
 // The ray's origin is made again here rather than held across the march (it is per pixel only for orthographic frames); the
 // range is hmrm.h's: sqrt((ex * ex + ey * ey) + ez * ez) in doubles, correctly rounded, then rounded to float.
+// (The range as a macro that declares ex, ey, ez and r in its user's scope: store_geometry and the haze frames' epilogue
+// (march.hpp) share the very expression, and render_geometry.hip keeps its instructions.)
+#define HMRM_RANGE_FROM(o, x, y, z)                                             \
+	const double ex = (x) - (o).px, ey = (y) - (o).py, ez = (z) - (o).pz;       \
+	const double r = __builtin_sqrt((ex * ex + ey * ey) + ez * ez)
 template <int PROJ>
 __device__ __forceinline__ void store_geometry(const DevFrame &f, const GeomPlanes &geo, const PixelId &pid, bool hit, unsigned cell,
                                                double x, double y, double z) {
 	if (geo.cell != nullptr) geo.cell[(uint64_t)(uint32_t)pid.lrow * (uint64_t)geo.cell_stride + (uint32_t)pid.px] = hit ? (int32_t)cell : -1;
 	if (geo.range != nullptr) {
 		const DevRay o = make_ray<PROJ>(f, pid.px, pid.py);
-		const double ex = x - o.px, ey = y - o.py, ez = z - o.pz;
-		const double r = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+		HMRM_RANGE_FROM(o, x, y, z);
 		geo.range[(uint64_t)(uint32_t)pid.lrow * (uint64_t)geo.range_stride + (uint32_t)pid.px] = hit ? (float)r : __builtin_huge_valf();
 	}
 }

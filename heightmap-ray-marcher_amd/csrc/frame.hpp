@@ -348,6 +348,23 @@ constexpr uint32_t kWaterOwnColor = 2u; // (= hmrm.h HMRM_WATER_OWN_COLOR)
 // hmrm_render_shaded's two flags in `flags`, above the water's own: read at run time, the same for the whole launch.
 constexpr uint32_t kWaterSunDiffuse = 0x100u, kWaterSunNoShadows = 0x200u;
 
+// ---- haze frames (hmrm_render_haze; HAZE in the kernels) ----
+// Every pixel whose primary ray HIT is blended towards `color` by the byte of `table` (device memory, n entries) at its range:
+// r = sqrt((ex * ex + ey * ey) + ez * ez) in doubles, e = int_point - the ray's origin -- the geometry frame's range before its
+// rounding to float -- u = (r - start) * scale, entry n - 1 for u >= n - 1, else (int)u for u > 0, else 0 (NaN: 0); the blend is
+// the water's, (c * (255 - f) + h * f + 127) / 255 per channel.  With kHazeSky the pixels that did not hit take entry n - 1.  The
+// primary rays' own rules travel in a SegRules beside it.  An extra argument of the haze kernels' own __global__ entry points,
+// like SegRules.
+struct HazeRules {
+	const uint8_t *table;
+	double start, scale;
+	uint32_t n;     // 1 .. 4096
+	uint32_t color; // R | G << 8 | B << 16
+	uint32_t flags; // kHazeSky or 0
+};
+constexpr uint32_t kHazeSky = 2u; // (= hmrm.h HMRM_HAZE_SKY)
+constexpr int kMaxHazeEntries = 4096;
+
 // Host: fill everything except the table pointers / thr_max / step_cap.
 // Also fills the spherical tables (host arrays of screen_w / screen_h doubles) when
 // projection == 2 and the pointers are not null.

@@ -260,6 +260,7 @@ int main(int argc, char *argv[]) {
 		}
 		if (sky_light) std::cerr << "WARNING: sky_light is ignored with record orbit\n";
 		if (hmrm_config_water(cfg) != 0 && !water_all) std::cerr << "WARNING: water is ignored with record orbit\n";
+		if (hmrm_config_haze(cfg) != 0) std::cerr << "WARNING: haze is ignored with record orbit\n";
 		// `record orbit`: recording_frame_count frames on a circle around the map centre through
 		// the configured camera position, always looking at the centre;
 		// files screenshots/hmap_<epoch>_<n>.png as hmap.cpp:1131-1144.
@@ -339,7 +340,18 @@ int main(int argc, char *argv[]) {
 	// beside shadows or shading only under baked light)
 	const bool water_wide = water_all && want_dev <= 1 && (baked || (!shadows && !shading));
 	const bool lit_aa = sun_all && want_dev <= 1 && aa > 1 && !baked; // (the antialiased lit single frame)
-	if (interior && !lit_aa && !baked && !water_wide && (want_dev > 1 || aa > 1))
+	// `haze on`: the single frame with distance fog (hmrm_render_haze), antialiased with `antialias n`, under the interior rule with
+	// `interior on` -- on one device, and with neither a sun, nor water, nor a light plane
+	bool haze = hmrm_config_haze(cfg) != 0;
+	if (haze) {
+		const char *beside = shadows ? "shadows" : shading ? "shading" : hmrm_config_water(cfg) != 0 ? "water" : baked_mode != 0 ? "baked_light"
+		                     : sky_light ? "sky_light" : want_dev > 1 ? "devices > 1" : nullptr;
+		if (beside) {
+			std::cerr << "WARNING: haze is ignored with " << beside << "\n";
+			haze = false;
+		}
+	}
+	if (interior && !lit_aa && !baked && !water_wide && !haze && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: interior is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
 	if (shadows && !lit_aa && !baked && (want_dev > 1 || aa > 1))
 		std::cerr << "WARNING: shadows is ignored with " << (aa > 1 ? "antialias > 1" : "devices > 1") << "\n";
@@ -370,7 +382,20 @@ int main(int argc, char *argv[]) {
 		std::cerr << "WARNING: sky_light is ignored with water\n";
 		sky_light = false;
 	}
-	if (water && water_lit) {
+	if (haze) {
+		hmrm_haze hz;
+		std::vector<uint8_t> table(4096);
+		hmrm_config_get_haze(cfg, &hz, table.data());
+		rc = hmrm_render_haze(scene, &cam, &hz, table.data(), aa, framebuf.data(), (size_t)cam.width * 4);
+		if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+			std::cerr << hmrm_last_error() << "\n";
+			return 1;
+		}
+		if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+		std::cout << "rendered " << (long long)cam.width * cam.height * aa * aa << " rays with haze from " << hz.start << " to "
+		          << hmrm_config_haze_far(cfg) << (aa > 1 ? " at antialias " + std::to_string(aa) : std::string())
+		          << (interior ? " under the interior rule" : "") << " in " << hmrm_last_kernel_ms() << " ms (kernel)\n";
+	} else if (water && water_lit) {
 		hmrm_water w;
 		hmrm_config_get_water(cfg, &w);
 		hmrm_sun sun;

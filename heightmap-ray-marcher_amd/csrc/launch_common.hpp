@@ -66,6 +66,8 @@ hipError_t launch_render_water_aa(const FrameLaunch &l, FastKernel kernel);     
 hipError_t launch_render_water_baked(const FrameLaunch &l, FastKernel kernel);   // render_water_baked.hip
 hipError_t launch_render_water_baked_aa(const FrameLaunch &l, FastKernel kernel); // render_water_baked_aa.hip
 hipError_t launch_render_water_lit(const FrameLaunch &l, FastKernel kernel);     // render_water_lit.hip (no AA variant)
+hipError_t launch_render_haze(const FrameLaunch &l, FastKernel kernel);          // render_haze.hip
+hipError_t launch_render_haze_aa(const FrameLaunch &l, FastKernel kernel);       // render_haze_aa.hip
 
 // The segment rules of a frame launch: no limits, the interior rule for the interior family and where the sun's flags ask.
 inline SegRules frame_seg_rules(const FrameLaunch &l) {

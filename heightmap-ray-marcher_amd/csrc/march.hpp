@@ -2,7 +2,7 @@
 // tuning constants.  Instantiated by render_fast.hip and render_fast_aa.hip (frames: march_frame.hpp), render_rays.hip,
 // render_segments.hip, render_interior.hip, render_lit.hip, render_shaded.hip, render_lit_shaded.hip, their antialiased
 // counterparts (march_lit_aa.hpp), render_cells.hip, render_cell_sums.hip, render_geometry.hip, render_lit_sum.hip, render_baked.hip,
-// render_baked_aa.hip, render_water.hip, render_water_aa.hip, render_water_baked.hip, render_water_baked_aa.hip and render_water_lit.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
+// render_baked_aa.hip, render_water.hip, render_water_aa.hip, render_water_baked.hip, render_water_baked_aa.hip, render_water_lit.hip, render_haze.hip and render_haze_aa.hip, each with a __global__ kernel of its own and a family of its own: march_family.hpp, which holds every
 // switch and derived constant with its reasons.
 //
 // Same pixels, same per-ray step counts as k_render (render.hip) and therefore as
@@ -194,6 +194,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 	constexpr bool BAKED = F::BAKED, CELLS = F::CELLS, RAYS = F::RAYS, COUNT = F::COUNT, BILINEAR = F::BILINEAR, F32 = F::F32, REC = F::REC;
 	constexpr bool KEEP_Q = F::KEEP_Q, KEEP_P = F::KEEP_P, CHAIN = F::CHAIN, DEFER = F::DEFER, CARRY = F::CARRY;
 	constexpr bool MIRROR = F::MIRROR, SUNLIT = F::SUNLIT;
+	[[maybe_unused]] constexpr bool HAZE = F::HAZE, POINT = F::POINT;
 	const float *__restrict__ thr32 = reinterpret_cast<const float *>(thr);
 	const float *__restrict__ mip = BILINEAR ? f.mipbuf_bil : f.mipbuf; // the pyramid this sampling mode leaps on
 	PixelId pid = pixel_of_tile_lane(f, rows, tiles_y, tile_x, gy, wave, lane);
@@ -244,7 +245,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 
 		uint32_t rgba = 0;
 		bool real_hit = false;
-		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired; GEOM: hz, beside hqx and hqy)
+		double hx = 0.0, hy = 0.0, hz = 0.0; // (RAYS: where hmap.cpp:1016 fired; GEOM, HAZE: hz, beside hqx and hqy)
 		// The cell hmap.cpp:1016 fired in (LIT: for the primary ray).  The one thing a hit lane of the nearest-cell modes carries out
 		// of the march loop: its colour (below the loop: one load for all hit lanes of the wave, where the loop had one, and a wait
 		// for it, in every trip in which any lane hit), SHADE's diffuse level and the ray batches' record are all made from it.
@@ -767,13 +768,13 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								// below.  The lane leaves the loop with it in x, y, z, which nothing else reads after a hit, so no
 								// register is held across the loop for it; and X[hit_j] is made again from the group's start with
 								// the same sequential adds (the same bits) so that X[1 .. U-2] need not outlive the cell indices.
-								// (GEOM: int_point itself -- z is stepped like x and y, no threshold is kept)
-								double ox = x, oy = y, ot = GEOM ? z : T[0];
+								// (GEOM, HAZE: int_point itself -- z is stepped like x and y, no threshold is kept)
+								double ox = x, oy = y, ot = POINT ? z : T[0];
 #pragma unroll
 								for (int j = 1; j < U; ++j) {
 									ox = hit_j >= j ? ox + sx : ox;
 									oy = hit_j >= j ? oy + sy : oy;
-									if constexpr (GEOM) ot = hit_j >= j ? ot + sz : ot;
+									if constexpr (POINT) ot = hit_j >= j ? ot + sz : ot;
 									else ot = hit_j == j ? T[j] : ot;
 								}
 								x = ox; y = oy; z = ot;
@@ -811,7 +812,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 								else if constexpr (SUNLIT) hcell = (lt.phase & 1) ? hcell : (unsigned)c;
 								else hcell = (unsigned)c;
 								if constexpr (CHAIN) { hx = xs; hy = ys; hz = zs; }
-								if constexpr (KEEP_P) { x = xs; y = ys; z = GEOM ? zs : t; } // (as above)
+								if constexpr (KEEP_P) { x = xs; y = ys; z = POINT ? zs : t; } // (as above)
 								done = true;
 								break;
 							}
@@ -845,8 +846,8 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 					if ((lt.phase & 1) == 0) { lt.hx = x; lt.hy = y; lt.t = z; }
 				} else
 				if constexpr (LIT || MIRROR) { lt.hx = x; lt.hy = y; lt.t = z; } // (of a lane that hit: see the end of the loop)
-				else if constexpr (GEOM && kGeomChain) { hqx = hx; hqy = hy; }
-				else if constexpr (GEOM) { hqx = x; hqy = y; hz = z; } // (int_point of a lane that hit)
+				else if constexpr (POINT && CHAIN) { hqx = hx; hqy = hy; }
+				else if constexpr (POINT) { hqx = x; hqy = y; hz = z; } // (int_point of a lane that hit)
 				else if constexpr (KEEP_P) { hqx = x; hqy = y; } // (SHADE, bilinear: the same two, for the gradient at P)
 			}
 			if constexpr (LSUM) {
@@ -1094,7 +1095,7 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 		} while ((LIT || SUM || MIRROR) && again); // (LSUM implies LIT)
 		// The hit lanes' colour: fetched here, once, behind the march (LIT, nearest-cell modes: behind both marches).
 		double qxh = hqx, qyh = hqy; // (bilinear: the hit's cell coordinates, for the colour and SHADE's gradient)
-		if constexpr (BILINEAR && (KEEP_P || GEOM) && !LIT && !MIRROR) cell_coords_of(hqx, hqy, qxh, qyh);
+		if constexpr (BILINEAR && (KEEP_P || POINT) && !LIT && !MIRROR) cell_coords_of(hqx, hqy, qxh, qyh);
 		if constexpr (GEOM) {
 			if (out != nullptr && real_hit) rgba = BILINEAR ? bilinear_pixel(qxh, qyh) : shade_hit(f, cmap[hcell]);
 		} else
@@ -1229,11 +1230,22 @@ __device__ __forceinline__ int render_wave_tile(const DevFrame &f, const RowMap 
 				rgba = shade_baked(rgba, light, a.baked.full_scale);
 			}
 		}
+		if constexpr (HAZE) { // (every hit pixel towards the haze colour by the table's byte at its range; an alpha-0 hit cell's background too)
+			if (real_hit) {
+				// (the ray's origin is made again here rather than held across the march, as store_geometry makes it)
+				const DevRay o = make_ray<PROJ>(f, pid.px, pid.py);
+				HMRM_RANGE_FROM(o, hqx, hqy, hz);
+				rgba = blend_haze(rgba, a.haze, haze_index(a.haze, r));
+			}
+		}
 
 		// (CELLS: a cell map has no pixel and counts no hits -- `rgba`, the miss shade and my_hit are dead there and compile to
 		// nothing; the family's entry passes SegRules::interior = 1 for the record, the rule itself is shadow_entry's above)
 		if (real_hit) my_hit = 1;
 		else rgba = shade_miss(f, ray.dz);
+		if constexpr (HAZE) { // (the sky as hazy as the farthest terrain: a scalar branch; capped rays are non-hits here too)
+			if ((a.haze.flags & kHazeSky) != 0u && !real_hit) rgba = blend_haze(rgba, a.haze, a.haze.n - 1u);
+		}
 		if constexpr (SEG) { // an END ray is not a capped one: not counted, never HMRM_E_NOTERM
 			sg.ended = my_cap != 0u && sg.ends;
 			my_cap = sg.ended ? 0u : my_cap;

@@ -20,9 +20,10 @@ enum FastKernel { kPlainGroups = 0, kLeaps = 1, kRecords = 2 };
 // path like kFrameGeometry.  kFrameWater: the water frame's (hmrm_render_water), set by the launch path likewise,
 // as are its antialiased form, its form under the light plane and both (hmrm_render_water_aa): kFrameWaterAA, kFrameWaterBaked and
 // kFrameWaterBakedAA.  kFrameWaterLit: the sun-lit water frame's (hmrm_render_water_lit), set by the launch path too; one family for
-// its four `shade_flags`, which its kernels read at run time.
-enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded, kFrameGeometry, kFrameLitSum, kFrameBaked, kFrameWater, kFrameWaterAA,
-                   kFrameWaterBaked, kFrameWaterBakedAA, kFrameWaterLit };
+// its four `shade_flags`, which its kernels read at run time.  kFrameHaze: the haze frame's (hmrm_render_haze), set by the launch
+// path like kFrameGeometry; its antialiased form is its launchers' matter, as the baked-light family's is, beside which it stands.
+enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded, kFrameGeometry, kFrameLitSum, kFrameBaked, kFrameHaze, kFrameWater,
+                   kFrameWaterAA, kFrameWaterBaked, kFrameWaterBakedAA, kFrameWaterLit };
 
 // Which launch a frame gets.  `forced`: HMRM_KERNEL (2: simple); `huge_side`: a map side of 2^24 cells or more -- the production
 // kernel indexes cells and windows with 24-bit multiplies, leap_common.hpp index_2d; `interior`: hmrm_render_interior's frame

@@ -39,6 +39,19 @@ constexpr int kGroupRec = HMRM_GROUP_REC;
 #define HMRM_GEOM_CARRY 0
 #endif
 constexpr bool kGeomChain = HMRM_GEOM_CHAIN != 0, kGeomCarry = HMRM_GEOM_CARRY != 0;
+// Haze frames (HAZE below), for A/B builds of render_haze.hip and render_haze_aa.hip: HMRM_HAZE_CHAIN and HMRM_HAZE_CARRY as the
+// geometry frames' two; HMRM_HAZE_DEFER 1 fetches the colour behind the loop in every instantiation, as GEOM does, 0 leaves the
+// interior family's choice.  The defaults are what the registers decided: DESIGN.md 5.23.
+#ifndef HMRM_HAZE_CHAIN
+#define HMRM_HAZE_CHAIN 0
+#endif
+#ifndef HMRM_HAZE_CARRY
+#define HMRM_HAZE_CARRY 0
+#endif
+#ifndef HMRM_HAZE_DEFER
+#define HMRM_HAZE_DEFER 1
+#endif
+constexpr bool kHazeChain = HMRM_HAZE_CHAIN != 0, kHazeCarry = HMRM_HAZE_CARRY != 0, kHazeDefer = HMRM_HAZE_DEFER != 0;
 
 } // namespace
 
@@ -53,7 +66,7 @@ constexpr bool kGeomChain = HMRM_GEOM_CHAIN != 0, kGeomCarry = HMRM_GEOM_CARRY !
 // whose ballot only the live lanes take part in.
 struct Frames {
 	static constexpr bool STATS = false, AA = false, SEG = false, LIT = false, SHADE = false, SUM = false, GEOM = false, LSUM = false,
-	                      BAKED = false, MIRROR = false, SUNLIT = false;
+	                      BAKED = false, MIRROR = false, SUNLIT = false, HAZE = false;
 	struct Args {};
 };
 template <bool STATS_, bool AA_> struct FramesOf : Frames {
@@ -195,6 +208,16 @@ struct SunWater : Frames {
 	static constexpr bool SEG = true, MIRROR = true, SUNLIT = true;
 	struct Args { const SegRules &seg; const WaterRules &water; const SunRules &sun; };
 };
+// HAZE (render_haze.hip, render_haze_aa.hip; hmrm_render_haze, frame.hpp HazeRules; implies SEG): a haze frame.  An epilogue: a lane
+// whose primary ray hit leaves the loop with int_point in x, y, z as a geometry lane does, makes its ray's origin again, computes
+// the range with the geometry frame's expression -- in doubles, not rounded to float -- loads ONE byte of the table at the index
+// made from it and blends its pixel towards the haze colour with the water's blend; with kHazeSky the lanes that did not hit blend
+// their miss shade at the table's last entry.  With AA the hazed sample goes to the box filter.  The kernel evaluates no
+// transcendental: the table is the caller's.
+struct Haze : Frames {
+	static constexpr bool SEG = true, HAZE = true;
+	struct Args { const SegRules &seg; const HazeRules &haze; };
+};
 
 // ---- a family: its tag's switches, the four dispatched values, and what follows from them ----
 // SAMP: 0 nearest cell (the reference), 1 bilinear quality mode, 2 nearest cell with float thresholds (`thr` then points at the
@@ -205,7 +228,11 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	static constexpr bool STATS = TAG::STATS, AA = TAG::AA, SEG = TAG::SEG, LIT = TAG::LIT, SHADE = TAG::SHADE, SUM = TAG::SUM,
 	                      GEOM = TAG::GEOM, LSUM = TAG::LSUM, BAKED = TAG::BAKED, MIRROR = TAG::MIRROR;
 	static constexpr bool SUNLIT = TAG::SUNLIT; // (shadowed and shaded on both sides of the mirror: the one tag with MIRROR and a sun)
+	static constexpr bool HAZE = TAG::HAZE;
 	static constexpr bool CELLS = PROJ == 5;
+	static constexpr bool POINT = GEOM || HAZE; // (a hit lane leaves the loop with int_point in full: z stepped like x and y)
+	static_assert(!HAZE || (SEG && !CELLS && PROJ != 4 && !STATS && !LIT && !SHADE && !GEOM && !BAKED && !MIRROR),
+	              "haze frames: plain frames under the segment rules, antialiased or not");
 	static_assert(!MIRROR || SEG, "water frames: under the segment rules");
 	static_assert(!MIRROR || !CELLS, "water frames: a camera's frame, not a cell map");
 	static_assert(!MIRROR || PROJ != 4, "water frames: a camera's frame, not a ray batch");
@@ -227,12 +254,13 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	// instead (KEEP_Q) -- each the cheaper of the two in registers for its family, DESIGN.md 5.12 -- and from them they also
 	// mix the pixel behind the loop (DEFER), shaded or not.
 	// GEOM wants the whole point, in every sampling mode: KEEP_P with z stepped like x and y (no threshold is kept), which holds
-	// nothing across the loop -- RAYS' select chain keeps three doubles more.
-	static constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && !MIRROR && LEAP != 0 && !GEOM;
+	// nothing across the loop -- RAYS' select chain keeps three doubles more.  HAZE wants the same (POINT), for
+	// its range; its own answers: DESIGN.md 5.23.
+	static constexpr bool KEEP_Q = BILINEAR && !CELLS && !LIT && !MIRROR && LEAP != 0 && !POINT;
 	// BAKED with bilinear sampling wants the point like SHADE: KEEP_Q in the leap kernels, KEEP_P in the plain groups.
 	// MIRROR wants the point and the threshold like LIT, for the mirror ray's origin -- and the mirror ray's own hit point for its colour.
-	static constexpr bool KEEP_P = LIT || MIRROR || ((SHADE || BAKED) && BILINEAR && !KEEP_Q) || (GEOM && !kGeomChain);
-	static constexpr bool CHAIN = PROJ == 4 || (GEOM && kGeomChain); // (the hit point by RAYS' select chain: hx, hy, hz)
+	static constexpr bool KEEP_P = LIT || MIRROR || ((SHADE || BAKED) && BILINEAR && !KEEP_Q) || (GEOM && !kGeomChain) || (HAZE && !kHazeChain);
+	static constexpr bool CHAIN = PROJ == 4 || (GEOM && kGeomChain) || (HAZE && kHazeChain); // (the hit point by RAYS' select chain: hx, hy, hz)
 	static constexpr bool RAYS = PROJ == 4, COUNT = STATS || RAYS;
 	// DEFER: a hit lane's colour is fetched behind the march loop, from the hit cell it leaves the loop with (hcell; the
 	// bilinear mode: and from the hit point, KEEP_P / KEEP_Q), not inside it.  Two exceptions keep the in-loop form.  The record
@@ -246,16 +274,18 @@ template <class TAG, int PROJ_, int GWM_, int LEAP_, int SAMP_> struct Family {
 	// 36 bytes of scratch)
 	// (MIRROR: as LIT -- behind the loop in its record kernels too, in the loop for the bilinear mode of the plain groups, where a
 	// pass's colour simply lands in `rgba`: DESIGN.md 5.20; with BAKED too: MIRROR's choice stands)
-	static constexpr bool DEFER = GEOM || LSUM || (BAKED && !MIRROR && LEAP != 2) || (!CELLS && !(LEAP == 2 && SEG && !LIT && !MIRROR && !RAYS) && !(BILINEAR && LEAP == 0));
+	// (HAZE: behind the loop in every instantiation, like GEOM -- what that costs the two kinds the interior family keeps in the
+	// loop: DESIGN.md 5.23)
+	static constexpr bool DEFER = GEOM || LSUM || (HAZE && kHazeDefer) || (BAKED && !MIRROR && LEAP != 2) || (!CELLS && !(LEAP == 2 && SEG && !LIT && !MIRROR && !RAYS) && !(BILINEAR && LEAP == 0));
 	static_assert(!RAYS || (!AA && !STATS), "ray batches: neither antialiased nor instrumented");
 	static_assert(!SEG || !STATS, "segment rules: production kernels only");
-	static_assert(!SEG || !AA || LIT || SHADE || BAKED || MIRROR, "segment rules: antialiased for the sun-lit, baked-light and water frames only");
+	static_assert(!SEG || !AA || LIT || SHADE || BAKED || MIRROR || HAZE, "segment rules: antialiased for the sun-lit, baked-light, water and haze frames only");
 	static constexpr bool REC = LEAP == 2; // leaps over window records instead of the pyramid (frame.hpp WindowRecord)
 	// CARRY: a ray holds its level state in a register (see the leap state in the march loop).  The cell maps, the sun shadows, the
 	// ray batches and the shaded record kernels sit on a register granule: a register more would cost them a resident wave per SIMD
 	// -- as it would six of the geometry kernels (general grid widths: 73 against 71 vector registers, 81 against 80 with window
 	// records).  (MIRROR: LIT's choice, taken over with its two-pass structure; DESIGN.md 5.20 has the counts.)
-	static constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !MIRROR && !RAYS && !((SHADE || BAKED) && REC) && !(GEOM && !kGeomCarry);
+	static constexpr bool CARRY = LEAP != 0 && !CELLS && !LIT && !MIRROR && !RAYS && !((SHADE || BAKED) && REC) && !(GEOM && !kGeomCarry) && !(HAZE && !kHazeCarry);
 	static constexpr int U = LEAP == 1 ? kGroup : (REC ? kGroupRec : kGroupPlain); // positions per speculative group
 	static_assert(!REC || SAMP == 0, "records bound the nearest cell's double thresholds only");
 };

@@ -733,7 +733,8 @@ static hipError_t launch_lit_sum_literal(const FrameLaunch &l);  //  the last ke
 static hipError_t launch_baked_literal(const FrameLaunch &l);    // (hmrm_render_baked's, behind those)
 static hipError_t launch_water_literal(const FrameLaunch &l);    // (hmrm_render_water's, behind those)
 static hipError_t launch_water_literal_more(const FrameLaunch &l); // (hmrm_render_water_aa's, behind those)
-static hipError_t launch_water_lit_literal(const FrameLaunch &l);  // (hmrm_render_water_lit's, the last kernels of the code object)
+static hipError_t launch_water_lit_literal(const FrameLaunch &l);  // (hmrm_render_water_lit's, behind those)
+static hipError_t launch_haze_literal(const FrameLaunch &l);       // (hmrm_render_haze's, the last kernels of the code object)
 
 // The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
 // shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
@@ -753,6 +754,7 @@ hipError_t launch_frame_literal(const FrameLaunch &l) {
 	if (l.family == kFrameWater) return launch_water_literal(l);
 	if (l.family == kFrameWaterAA || l.family == kFrameWaterBaked || l.family == kFrameWaterBakedAA) return launch_water_literal_more(l);
 	if (l.family == kFrameWaterLit) return launch_water_lit_literal(l);
+	if (l.family == kFrameHaze) return launch_haze_literal(l);
 	if (l.f.aa_shift == 0) switch (l.family) {
 		case kFrameLit:
 			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
@@ -966,6 +968,48 @@ static hipError_t launch_water_lit_literal(const FrameLaunch &l) {
 	const SegRules seg = frame_seg_rules(l);
 	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
 		hipLaunchKernelGGL(k_render_water_lit_literal<proj()>, grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.water, l.sun);
+	});
+}
+
+// A pixel of a haze frame (hmrm_render_haze with HMRM_KERNEL=simple, or on a map with a side of 2^24 cells; frame.hpp HazeRules): the
+// primary ray of a lit pixel -- its colour, whether it hit and where -- then the range of a geometry frame, in doubles, the table's
+// byte at its index and the blend; with kHazeSky a pixel that did not hit blends at the table's last entry.  AA: the lane's sample
+// goes to the wave's box filter (every lane of the wave calls it, so no lane returns before) and not to memory.  Nearest sampling
+// only, like every literal kernel.
+template <int PROJ, bool AA>
+__global__ __launch_bounds__(kBlockThreads) void k_render_haze_literal(const DevFrame f, const RowMap rows,
+                                                                       const double *__restrict__ thr,
+                                                                       const uint32_t *__restrict__ cmap,
+                                                                       uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                       int tiles_y, StatsOut st, const SegRules seg,
+                                                                       const HazeRules haze) {
+	const PixelId pid = pixel_of_lane(f, rows, tiles_y);
+	LitState<true> lt;
+	unsigned cell = 0u;
+	double hz = 0.0;
+	render_lane_literal<PROJ, false, false, true, 1>(f, pid, thr, cmap, out, out_stride_px, st, RayBatch{}, seg, SunRules{}, &lt, &cell, &hz);
+	uint32_t rgba = 0u;
+	if (pid.live) {
+		rgba = lt.rgba;
+		if (lt.primary_hit) {
+			const DevRay o = make_ray<PROJ>(f, pid.px, pid.py);
+			HMRM_RANGE_FROM(o, lt.hx, lt.hy, hz);
+			rgba = blend_haze(rgba, haze, haze_index(haze, r));
+		} else if ((haze.flags & kHazeSky) != 0u) rgba = blend_haze(rgba, haze, haze.n - 1u);
+	}
+	if constexpr (AA) store_box_filtered(out, out_stride_px, f.aa_shift, (int)(threadIdx.x & 63), pid.px, pid.lrow, pid.live, rgba);
+	else if (pid.live) out[(int64_t)pid.lrow * out_stride_px + pid.px] = rgba;
+}
+
+// Such a frame: the interior family's arguments and the haze's rules, antialiased or not.  Never a measured launch.
+static hipError_t launch_haze_literal(const FrameLaunch &l) {
+	if (l.rows.measure != nullptr || !l.d_out) return hipErrorInvalidValue;
+	if (!l.haze.table || l.haze.n < 1u || l.haze.n > (uint32_t)kMaxHazeEntries) return hipErrorInvalidValue;
+	const SegRules seg = frame_seg_rules(l);
+	const bool aa = l.f.aa_shift != 0;
+	return launch_literal(l, StatsOut{l.d_counters, nullptr, nullptr}, [&](auto proj, dim3 grid, const auto &...args) {
+		if (aa) hipLaunchKernelGGL((k_render_haze_literal<proj(), true>), grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.haze);
+		else hipLaunchKernelGGL((k_render_haze_literal<proj(), false>), grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.haze);
 	});
 }
 

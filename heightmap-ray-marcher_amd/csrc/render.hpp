@@ -61,6 +61,9 @@ struct FrameLaunch {
 	// kFrameWaterLit (hmrm_render_water_lit): kFrameWater's frame under `sun`, both sides of the mirror at hmrm_render_shaded's weight;
 	// the two shade flags travel in water.flags (frame.hpp kWaterSunDiffuse, kWaterSunNoShadows); no AA
 	WaterRules water = WaterRules{0.0, 0.0, 0u, 0u, 0u, 0u};
+	// kFrameHaze (hmrm_render_haze): the frame of the plain or, with primary_interior, the interior family, whose pixels are blended
+	// towards the haze colour by the table's byte at their range (frame.hpp HazeRules); antialiased with f.aa_shift
+	HazeRules haze = HazeRules{nullptr, 0.0, 0.0, 0u, 0u, 0u};
 };
 // The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups
 // (kPlainGroups), plus exact leaps over empty pyramid windows (kLeaps), or over windows of the record level that are empty but

@@ -161,6 +161,46 @@ class Water(C.Structure):
 
 assert C.sizeof(Water) == 32
 
+HAZE_SKY = 2  # hmrm_haze.flags (HMRM_HAZE_SKY): the pixels that did not hit are blended at the table's last entry
+HAZE_LINEAR, HAZE_EXP, HAZE_EXP2 = 0, 1, 2  # hmrm_haze_table's laws (HMRM_HAZE_*)
+MAX_HAZE_ENTRIES = 4096
+
+
+class Haze(C.Structure):
+    """hmrm_haze (32 bytes): the haze of Scene.render_haze"""
+    _fields_ = [("start", C.c_double), ("scale", C.c_double), ("n", C.c_uint32), ("flags", C.c_uint32),
+                ("color", C.c_uint8 * 3), ("reserved", C.c_uint8 * 5)]
+
+    @classmethod
+    def make(cls, start, far, n, color, sky=False, interior=False):
+        """start, far: the ranges at which the table's first entry ends and its last begins -- scale = n / (far - start), in
+        doubles; n: the table's length; color (r, g, b): what a pixel is blended towards; sky: HMRM_HAZE_SKY; interior: the
+        primary rays under the interior rule."""
+        if not all(0 <= int(v) <= 255 for v in color):
+            raise ValueError("color components must be 0..255")
+        h = cls.raw(float(start), float(n) / (float(far) - float(start)), n, color,
+                    (TRACE_INTERIOR if interior else 0) | (HAZE_SKY if sky else 0))
+        return h
+
+    @classmethod
+    def raw(cls, start, scale, n, color, flags=0):
+        """The struct from `start` and `scale` as given (NaN, infinite, zero and negative values are legal)."""
+        return cls(float(start), float(scale), int(n), int(flags), (C.c_uint8 * 3)(*(int(v) for v in color)), (C.c_uint8 * 5)())
+
+
+assert C.sizeof(Haze) == 32
+
+
+def haze_table(law: int, density: float, n: int) -> np.ndarray:
+    """hmrm_haze_table: n bytes of HAZE_LINEAR, HAZE_EXP or HAZE_EXP2 at `density` (host arithmetic, libm's exp)."""
+    if not 1 <= int(n) <= MAX_HAZE_ENTRIES:
+        raise HmrmError(HMRM_E_ARG, "hmrm_haze_table: n must be 1 .. 4096")
+    out = np.zeros(int(n), dtype=np.uint8)
+    rc = lib.hmrm_haze_table(int(law), float(density), int(n), out.ctypes.data)
+    if rc != HMRM_OK:
+        raise HmrmError(rc, lib.hmrm_last_error().decode(errors="replace"))
+    return out
+
 MAP_TOWARDS_POINT, MAP_WEIGHT, MAP_DIFFUSE, MAP_NO_SHADOWS = 1, 2, 4, 8  # hmrm_cell_map_params.flags (HMRM_MAP_*)
 
 
@@ -314,6 +354,14 @@ def _load():
         "hmrm_config_water_light": (i32, [vp]),
         "hmrm_config_water": (i32, [vp]),
         "hmrm_config_get_water": (None, [vp, C.POINTER(Water)]),
+        "hmrm_render_haze": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Haze), vp, i32, vp, C.c_size_t]),
+        "hmrm_render_haze_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Haze), vp, i32, vp, C.c_size_t, vp]),
+        "hmrm_haze_table": (C.c_int, [i32, C.c_double, i32, vp]),
+        "hmrm_config_haze": (i32, [vp]),
+        "hmrm_config_get_haze": (None, [vp, C.POINTER(Haze), vp]),
+        "hmrm_config_haze_law": (i32, [vp]),
+        "hmrm_config_haze_density": (C.c_double, [vp]),
+        "hmrm_config_haze_far": (C.c_double, [vp]),
         "hmrm_render_shaded": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, vp, C.c_size_t]),
         "hmrm_render_shaded_aa": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, i32, vp, C.c_size_t]),
         "hmrm_render_shaded_begin": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Sun), C.c_uint32, C.c_uint32, C.POINTER(i32)]),
@@ -412,7 +460,7 @@ KERNEL_SOURCES = ("render_fast.hip", "render_rays.hip", "leap_common.hpp", "leap
                   "render.hpp", "api_internal.hpp", "api_launch.cpp", "api_frames.cpp", "launch_order.cpp", "launch_order.hpp", "camera.cpp", "Makefile",
                   "march.hpp", "march_family.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip",
                   "render_water.hip", "render_water_aa.hip", "render_water_baked.hip", "render_water_baked_aa.hip",
-                  "render_water_lit.hip")
+                  "render_water_lit.hip", "render_haze.hip", "render_haze_aa.hip")
 
 
 def kernel_src_sha() -> str:
@@ -630,6 +678,29 @@ class Scene:
         _check(lib.hmrm_render_water_device_begin(self._h, C.byref(cam), C.byref(water), WATER_BAKED if baked else 0,
                                                   C.c_void_p(d_rgba), int(stride_bytes), aa_flags(aa), C.byref(t)))
         return int(t.value)
+
+    def render_haze(self, cam: Camera, haze: Haze, table, factor=1, allow_capped=False, pad_px=0) -> np.ndarray:
+        """One full frame with distance fog (hmrm_render_haze): render()'s frame -- render_interior()'s for a haze made with
+        interior=True; factor 2, 4 or 8: antialiased like render_aa, every sample hazed on its own -- whose hit pixels are blended
+        towards haze.color by the byte of `table` (haze.n uint8) at their range, the others at its last entry with sky=True
+        -> HxWx4 uint8.  pad_px: the rows are written pad_px pixels wider (returned whole, untouched bytes are 0xA5).  Capped
+        rays: HMRM_E_NOTERM unless allow_capped."""
+        self._sync_env()
+        t = np.ascontiguousarray(table, dtype=np.uint8).reshape(-1)
+        if t.size < int(haze.n):
+            raise ValueError("render_haze: the table is shorter than haze.n")
+        fb = np.full((cam.height, cam.width + int(pad_px), 4), 0xA5, dtype=np.uint8)
+        _check(lib.hmrm_render_haze(self._h, C.byref(cam), C.byref(haze), _ptr(t), int(factor), _ptr(fb),
+                                    (cam.width + int(pad_px)) * 4),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
+    def render_haze_device(self, cam: Camera, haze: Haze, d_table: int, d_rgba: int, stride_bytes: int, factor=1, stream: int = 0):
+        """The same frame into DEVICE memory on a caller stream (hmrm_render_haze_device): d_table the device address of haze.n
+        bytes, d_rgba that of the frame; no host sync, capped rays through take_capped(stream)."""
+        self._sync_env()
+        _check(lib.hmrm_render_haze_device(self._h, C.byref(cam), C.byref(haze), C.c_void_p(d_table), int(factor), C.c_void_p(d_rgba),
+                                           int(stride_bytes), C.c_void_p(stream)))
 
     def render_shaded(self, cam: Camera, sun: Sun, diffuse=True, shadows=True, allow_capped=False, aa=1) -> np.ndarray:
         """One full frame with diffuse sun shading (hmrm_render_shaded): render_lit()'s frame in which every hit pixel that is
@@ -1333,6 +1404,28 @@ class Config:
         out = Water()
         lib.hmrm_config_get_water(self._h, C.byref(out))
         return out
+
+    def haze_on(self) -> bool:
+        """Additive `haze on|off`: the CLI renders its single frame with hmrm_render_haze."""
+        return bool(lib.hmrm_config_haze(self._h))
+
+    def haze(self):
+        """The haze of the additive keys haze_start, haze_far, haze_entries, haze_color, haze_sky, interior, and its table
+        (haze_law, haze_density) -> (Haze, uint8 array of haze.n entries)."""
+        out = Haze()
+        table = np.zeros(MAX_HAZE_ENTRIES, dtype=np.uint8)
+        lib.hmrm_config_get_haze(self._h, C.byref(out), table.ctypes.data)
+        return out, table[:int(out.n)].copy()
+
+    def haze_law(self) -> int:
+        """Additive `haze_law linear|exp|exp2`: HAZE_LINEAR | HAZE_EXP | HAZE_EXP2."""
+        return int(lib.hmrm_config_haze_law(self._h))
+
+    def haze_density(self) -> float:
+        return float(lib.hmrm_config_haze_density(self._h))
+
+    def haze_far(self) -> float:
+        return float(lib.hmrm_config_haze_far(self._h))
 
     @property
     def output_path(self) -> str:

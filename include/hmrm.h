@@ -552,7 +552,7 @@ int hmrm_sky_directions(int32_t rings, int32_t per_ring, double *out_xyz);
 
 /* ---------------------------------------------------------- geometry frames */
 /* The geometry behind the picture (build-side addition), exact: a depth plane to composite a caller's own objects over the
- * terrain or for distance fog, an ID plane to pick any pixel without a second call, a slope plane to relight a still frame
+ * terrain (distance fog alone needs no plane: haze frames, below), an ID plane to pick any pixel without a second call, a slope plane to relight a still frame
  * under a moving sun without marching again (INTEGRATION.md 2a has the three recipes).  It is the screen-space counterpart of
  * the cell maps: the march already knows all of it for every pixel, and an epilogue of the same launch stores it -- no ray is
  * read from memory and no record is written.
@@ -862,6 +862,65 @@ int hmrm_render_water_lit(const hmrm_scene *scene, const hmrm_camera *cam, const
 int hmrm_render_water_lit_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_water *water, const hmrm_sun *sun,
                                  uint32_t shade_flags, void *d_rgba, size_t stride_bytes, void *hip_stream);
 
+/* -------------------------------------------------------------- haze frames */
+/* hmrm_render with distance fog (build-side addition), exact: a far ridge fades towards one haze colour, blended by the kernel
+ * before the pixel is stored -- and before the box filter of an antialiased frame.  One launch; no range plane and no second
+ * kernel.  (A caller who composites objects of their own still takes the range plane of hmrm_render_geometry: INTEGRATION.md 2a.)
+ * A HAZE FRAME is hmrm_render's frame; with HMRM_TRACE_INTERIOR in haze->flags it is hmrm_render_interior's frame; with `factor` 2,
+ * 4 or 8 it is hmrm_render_aa's frame (of either kind of primary ray).  In each case every pixel, or every sample of the super
+ * camera, is blended towards haze->color by an amount read from the caller's table at the pixel's range.
+ * RANGE.  r is the geometry frame's range BEFORE its rounding to float: e = int_point - the ray's origin,
+ * r = sqrt((ex * ex + ey * ey) + ez * ez) in plain IEEE doubles in this order, no contraction, the sqrt correctly rounded.
+ * INDEX.  u = (r - start) * scale: one double subtract, then one double multiply.  i = n - 1 if u >= (double)(n - 1); else
+ * i = (int)u, the truncation, if u > 0; else i = 0 -- a NaN u takes index 0.  start and scale are used as given: NaN, infinite,
+ * zero and negative values go through the same arithmetic and are not refused.
+ * AMOUNT.  f = table[i], a byte; n is 1 .. 4096.
+ * THE STORED PIXEL OF A HIT (hmap.cpp:1016 fired; an alpha-0 hit cell counts, as in hmrm_render_lit, and its background colour is
+ * hazed too): each of R, G and B becomes (c * (255 - f) + h * f + 127) / 255 in integers, h = haze->color; A stays 255 -- the water
+ * frame's blend.
+ * NON-HITS -- the miss shade, and rays stopped by the step cap -- are untouched; with HMRM_HAZE_SKY they are blended at
+ * f = table[n - 1]: the sky is as hazy as the farthest terrain.
+ * ANTIALIASING.  Every sample is hazed on its own, then hmrm_render_aa's box filter runs.
+ * CAPPED RAYS are counted and reported as in hmrm_render_interior / hmrm_render_aa: hmrm_render_haze returns HMRM_E_NOTERM with a
+ * valid frame, hmrm_render_haze_device reports through hmrm_scene_take_capped for its stream.
+ * Consequences, each byte for byte: a table of zeros gives hmrm_render / hmrm_render_interior / hmrm_render_aa; a table of 255s
+ * with HMRM_HAZE_SKY gives a frame of the haze colour; without HMRM_HAZE_SKY the non-hit pixels are hmrm_render's; the order of the
+ * entries matters only through i.  The kernel evaluates no transcendental -- the law is the table's -- which is why the frame is
+ * bit-exact.  Like the shading arithmetic, the range is tested at unit world scale only.
+ * hmrm_haze_table (host only) fills out[i] = min(255, (int)(255 * (1 - T) + 0.5)), x = (i + 0.5) / n, with T = 1 - x
+ * (HMRM_HAZE_LINEAR), T = exp(-density * x) (HMRM_HAZE_EXP) or T = exp(-(density * x) * (density * x)) (HMRM_HAZE_EXP2), exp the
+ * host's libm; HMRM_E_ARG for another law, n outside 1 .. 4096 or NULL out.
+ * Refusals (HMRM_E_ARG, with a message) before the scene is looked at, in this order: NULL haze; an undefined flag bit;
+ * reserved != 0; n outside 1 .. 4096; NULL table; a factor that is not 1, 2, 4 or 8; the camera checks of hmrm_render, and behind
+ * them hmrm_render_aa's limit on the super frame, which needs the camera; a NULL scene or target; the stride (hmrm_render_haze:
+ * stride_bytes < width * 4; hmrm_render_haze_device: hmrm_render_rows_device's rule -- >= width * 4, a multiple of 4, below 2^33);
+ * the 2^24-side rule of frames.
+ * hmrm_render_haze is synchronous on the scene's stream and stages the n bytes of the table through a scene-owned device buffer.
+ * hmrm_render_haze_device takes a DEVICE table of n bytes and a DEVICE target, launches on hip_stream and does no host sync --
+ * hmrm_trace_rays_device's contract.  Both are launched like an interior frame: one launch, never measured, never the scene's
+ * probe and not counted towards it, with the scene's current kernel (HMRM_KERNEL or the probe's verdict; the window records apply
+ * to HMRM_NEAREST); every kernel writes the same bytes, the literal loop too (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest
+ * sampling only).  All three projections, grid modes and sampling modes.
+ * OUT OF SCOPE: tickets and lanes; the recorder; row strips, bands and hmrm_render_multi; statistics; haze combined with a sun,
+ * the scene's light plane or water; height-dependent fog. */
+#define HMRM_HAZE_SKY 2u             /* the pixels that did not hit are blended at table[n - 1] */
+#define HMRM_HAZE_LINEAR 0
+#define HMRM_HAZE_EXP    1
+#define HMRM_HAZE_EXP2   2
+typedef struct hmrm_haze {           /* 32 bytes */
+	double   start;        /* range at which entry 0 ends being the only entry */
+	double   scale;        /* entries per unit of range */
+	uint32_t n;            /* table length, 1 .. 4096 */
+	uint32_t flags;        /* HMRM_TRACE_INTERIOR, HMRM_HAZE_SKY; any other bit: HMRM_E_ARG */
+	uint8_t  color[3];     /* R, G, B of the haze */
+	uint8_t  reserved[5];  /* must be 0 */
+} hmrm_haze;
+int hmrm_render_haze(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_haze *haze, const uint8_t *table, int32_t factor,
+                     uint8_t *rgba, size_t stride_bytes);
+int hmrm_render_haze_device(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_haze *haze, const void *d_table,
+                            int32_t factor, void *d_rgba, size_t stride_bytes, void *hip_stream);
+int hmrm_haze_table(int32_t law, double density, int32_t n, uint8_t *out);   /* host only */
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -1068,7 +1127,15 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * key is still ignored with its warnings; another value warns "WARNING: Unknown water_scope: v" and keeps the old one),
  * `range_map <path.pfm>` (echoed like `output`; after its frames and before an optional sun_map the CLI writes the range plane
  * of the configured camera -- hmrm_render_geometry with that plane alone, under the interior rule with `interior on` -- as a
- * one-component portable float map, hmrm_write_pfm).
+ * one-component portable float map, hmrm_write_pfm),
+ * `haze on|off|1|0` (default off; the CLI renders its single frame with hmrm_render_haze under hmrm_config_get_haze's haze and
+ * table, with `antialias n` for the factor and HMRM_TRACE_INTERIOR for `interior on`; ignored, with "WARNING: haze is ignored with
+ * <what>", beside `shadows`, `shading`, `water`, `baked_light`, `sky_light`, `record orbit` and `devices n` > 1; another value
+ * warns "WARNING: Unknown haze: v" and keeps the old one), `haze_start v` (default 0), `haze_far v` (default 1000: scale = n / (far - start)),
+ * `haze_law linear|exp|exp2` (default exp; another value warns "WARNING: Unknown haze_law: v"), `haze_density v` (default 3),
+ * `haze_color r g b` (default 200 210 220; a component outside 0..255: "WARNING: haze_color must be three values 0..255"),
+ * `haze_sky on|off|1|0` (default off: HMRM_HAZE_SKY; another value warns "WARNING: Unknown haze_sky: v"), `haze_entries n`
+ * (default 256; outside 1..4096: "WARNING: haze_entries must be 1..4096", the old value stays).
  * Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
@@ -1117,6 +1184,14 @@ int32_t      hmrm_config_water_scope(const hmrm_config *cfg);   /* additive `wat
  * `water_scope`; beside `antialias` > 1, `devices` > 1, `record orbit` or `baked_light` the existing warnings stand.  With `off`
  * nothing changes. */
 int32_t      hmrm_config_water_light(const hmrm_config *cfg);
+int32_t      hmrm_config_haze(const hmrm_config *cfg);          /* additive `haze on|off`: 1|0 */
+/* The haze of the additive keys: start = haze_start, scale = haze_entries / (haze_far - haze_start) in doubles, n = haze_entries,
+ * color = haze_color, flags = HMRM_HAZE_SKY for `haze_sky on` | HMRM_TRACE_INTERIOR for `interior on`; and, when `table` is not
+ * NULL, its n bytes (room for 4096 always suffices): hmrm_haze_table(haze_law, haze_density, n).  `out` may be NULL. */
+void         hmrm_config_get_haze(const hmrm_config *cfg, hmrm_haze *out, uint8_t *table);
+int32_t      hmrm_config_haze_law(const hmrm_config *cfg);      /* additive `haze_law linear|exp|exp2`: HMRM_HAZE_* */
+double       hmrm_config_haze_density(const hmrm_config *cfg);  /* additive `haze_density v` */
+double       hmrm_config_haze_far(const hmrm_config *cfg);      /* additive `haze_far v` */
 /* Loaded maps (owned by cfg): RGB8 / RGBA8; NULL until the key was consumed. */
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *cfg, int32_t *w, int32_t *h);
 const uint8_t *hmrm_config_color_rgba(const hmrm_config *cfg, int32_t *w, int32_t *h);
