@@ -162,6 +162,20 @@ int hmrm_haze_table(int32_t law, double density, int32_t n, uint8_t *out) {
 	return HMRM_OK;
 }
 
+int32_t hmrm_config_view_count(const hmrm_config *c) { return (int32_t)c->cfg.views.size(); }
+const char *hmrm_config_views_output(const hmrm_config *c) { return c->cfg.views_output.c_str(); }
+void hmrm_config_get_views(const hmrm_config *c, hmrm_camera *out) {
+	if (!out) return;
+	size_t k = 0;
+	for (const hmrm::Config::View &v : c->cfg.views) {
+		hmrm_camera &cam = out[k++];
+		hmrm_config_get_camera(c, &cam);
+		for (int a = 0; a < 3; ++a) cam.pos[a] = v.pos[a];
+		cam.hang = v.hang;
+		cam.vang = v.vang;
+	}
+}
+
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *c, int32_t *w, int32_t *h) {
 	if (!c->cfg.have_heightmap) return nullptr;
 	if (w) *w = c->cfg.heightmap.w;

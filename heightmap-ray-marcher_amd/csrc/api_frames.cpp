@@ -3,6 +3,7 @@
 // scenes, and the kernel timing of bench.py.
 #include <algorithm>
 #include <cstring>
+#include <map>
 #include <new>
 
 #include "api_internal.hpp"
@@ -629,6 +630,219 @@ int hmrm_render_haze_device(const hmrm_scene *scene, const hmrm_camera *cam, con
                             void *d_rgba, size_t stride_bytes, void *hip_stream) {
 	return render_haze_common(const_cast<hmrm_scene *>(scene), cam, haze, d_table, factor, d_rgba, stride_bytes, true,
 	                          (hipStream_t)hip_stream);
+}
+
+// ---- view batches: n cameras of one scene in one launch; view k is hmrm_render's frame of cams[k] (hmrm_render_interior's with
+// HMRM_TRACE_INTERIOR) ----
+// Which spherical tables the views of a batch use, deduplicated within the batch: views that agree in (hang, hfov, width) -- bit
+// for bit -- share a pair of column tables, views that agree in (vang, hfov, width, height) a pair of row tables; tables are
+// numbered in the order of their first view, whose index goes to *_first.  Another projection has no tables: every index -1.
+struct ViewTables {
+	std::vector<int32_t> col_of, row_of;       // per view
+	std::vector<int32_t> col_first, row_first; // per table: the first view that uses it
+};
+static uint64_t bits_of(double v) {
+	uint64_t b;
+	memcpy(&b, &v, sizeof b);
+	return b;
+}
+static void plan_view_tables(const hmrm_camera *cams, int32_t n, ViewTables *t) {
+	t->col_of.assign((size_t)n, -1);
+	t->row_of.assign((size_t)n, -1);
+	t->col_first.clear();
+	t->row_first.clear();
+	if (cams[0].projection != HMRM_SPHERICAL) return;
+	// (width and height are the batch's: the keys are the angles and hfov)
+	std::map<std::pair<uint64_t, uint64_t>, int32_t> cols, rows;
+	for (int32_t k = 0; k < n; ++k) {
+		const uint64_t fov = bits_of(cams[k].hfov);
+		auto c = cols.emplace(std::make_pair(bits_of(cams[k].hang), fov), (int32_t)t->col_first.size());
+		if (c.second) t->col_first.push_back(k);
+		t->col_of[(size_t)k] = c.first->second;
+		auto r = rows.emplace(std::make_pair(bits_of(cams[k].vang), fov), (int32_t)t->row_first.size());
+		if (r.second) t->row_first.push_back(k);
+		t->row_of[(size_t)k] = r.first->second;
+	}
+}
+
+// The refusals of the header, in its order; needs no scene and no device.
+static int check_views(const void *scene, const hmrm_camera *cams, int32_t n, uint32_t flags, const void *target, size_t stride_bytes,
+                       size_t view_stride_bytes, bool device) {
+	if (!cams) return fail(HMRM_E_ARG, "views: NULL cams");
+	if (n < 1 || n > HMRM_MAX_VIEWS) return fail(HMRM_E_ARG, "views: n must be 1 .. 65536 (got " + std::to_string(n) + ")");
+	if (flags & ~HMRM_TRACE_INTERIOR) return fail(HMRM_E_ARG, "views: flags: undefined bit");
+	for (int32_t k = 1; k < n; ++k) {
+		const char *field = cams[k].width != cams[0].width ? "width" : cams[k].height != cams[0].height ? "height"
+		                    : cams[k].projection != cams[0].projection ? "projection" : cams[k].sampling != cams[0].sampling ? "sampling" : nullptr;
+		if (field) return fail(HMRM_E_ARG, "views: view " + std::to_string(k) + " differs from view 0 in " + field + ", which a batch shares");
+	}
+	int rc = check_camera(&cams[0]); // (hmrm_render's camera rules look at the four shared fields only)
+	if (rc) return rc;
+	if (!scene || !target) return fail(HMRM_E_ARG, "NULL argument");
+	const size_t W = (size_t)cams[0].width, H = (size_t)cams[0].height;
+	if (device) {
+		if ((rc = check_device_stride(&cams[0], stride_bytes))) return rc;
+	} else if (stride_bytes < W * 4) return fail(HMRM_E_ARG, "stride_bytes < width*4");
+	// (the host form takes any stride: the products are made in 128 bits)
+	const unsigned __int128 view_bytes = (unsigned __int128)H * stride_bytes;
+	if (view_stride_bytes < view_bytes || (device && (view_stride_bytes & 3)))
+		return fail(HMRM_E_ARG, device ? "views: view_stride_bytes must be >= height * stride_bytes and a multiple of 4"
+		                               : "views: view_stride_bytes must be >= height * stride_bytes");
+	if ((unsigned __int128)(n - 1) * view_stride_bytes + (unsigned __int128)(H - 1) * stride_bytes + W * 4 > ((unsigned __int128)1 << 40))
+		return fail(HMRM_E_ARG, "views: the batch's last byte lies at or beyond 2^40");
+	int tile_w = 1, tile_h = 1;
+	hmrm::render_tile_shape(&tile_w, &tile_h);
+	if ((int64_t)n * (int64_t)((H + (size_t)tile_h - 1) / (size_t)tile_h) > (int64_t)65535 * 32768)
+		return fail(HMRM_E_ARG, "views: the batch has more tile rows than a launch's grid holds (65535 * 32768)");
+	return HMRM_OK;
+}
+
+// One batch.  `device`: `target` is device memory and everything goes to `stream` without a host wait; else the batch is rendered
+// into the scene's frame buffer, views and rows packed, on the scene's stream and copied to the caller's behind the launch.
+static int render_views_common(hmrm_scene *s, const hmrm_camera *cams, int32_t n, uint32_t flags, void *target, size_t stride_bytes,
+                               size_t view_stride_bytes, bool device, hipStream_t stream) {
+	int rc = check_views(s, cams, n, flags, target, stride_bytes, view_stride_bytes, device);
+	if (rc) return rc;
+	const size_t W = (size_t)cams[0].width, H = (size_t)cams[0].height;
+	const bool spherical = cams[0].projection == HMRM_SPHERICAL;
+	ViewTables tables;
+	plan_view_tables(cams, n, &tables);
+	constexpr size_t kRecDoubles = sizeof(hmrm::DevFrame) / sizeof(double);
+	static_assert(sizeof(hmrm::DevFrame) % sizeof(double) == 0, "the records are uploaded as doubles");
+	const size_t n_col = tables.col_first.size(), n_row = tables.row_first.size();
+	const size_t col_base = (size_t)n * kRecDoubles, row_base = col_base + n_col * 2 * W, total = row_base + n_row * 2 * H;
+	if (total * sizeof(double) > kMaxViewStagingBytes)
+		return fail(HMRM_E_ARG, "views: the batch's records and distinct spherical tables exceed 256 MiB (" + std::to_string(n_col) +
+		                            " column and " + std::to_string(n_row) + " row tables)");
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::mutex> lk(s->mu);
+	uint32_t *d_rgba = (uint32_t *)target;
+	int64_t stride_px = (int64_t)(stride_bytes / 4), view_stride_px = (int64_t)(view_stride_bytes / 4);
+	if (!device) {
+		if ((rc = s->d_frame.reserve((size_t)n * W * H * sizeof(uint32_t)))) return rc;
+		d_rgba = s->d_frame.as<uint32_t>();
+		stride_px = (int64_t)W;
+		view_stride_px = (int64_t)(W * H);
+		stream = s->stream;
+	}
+	StreamCtx *c = nullptr;
+	if ((rc = ctx_for(s, stream, &c))) return rc;
+	if (cams[0].sampling == HMRM_BILINEAR && (rc = ensure_bilinear_pyramid(s))) return rc;
+	ViewsKernel kern;
+	if ((rc = pick_views_kernel(s, c, cams[0].sampling, &kern))) return rc;
+	// the device arena: only grows; one that launches of this stream may still read is retired, not freed
+	for (size_t i = c->retired_views.size(); i-- > 0;) {
+		const hipError_t e = hipEventQuery(c->retired_views[i].after);
+		if (e == hipErrorNotReady) (void)hipGetLastError();
+		if (e != hipSuccess) continue;
+		(void)hipEventDestroy(c->retired_views[i].after);
+		(void)hipFree(c->retired_views[i].ptr);
+		c->retired_views.erase(c->retired_views.begin() + (long)i);
+	}
+	if (total > c->d_views_cap) {
+		if (c->d_views) {
+			RetiredArena r{c->d_views, nullptr};
+			HIP_TRY(hipEventCreateWithFlags(&r.after, hipEventDisableTiming));
+			HIP_TRY(hipEventRecord(r.after, c->stream));
+			c->retired_views.push_back(r);
+			c->d_views = nullptr;
+		}
+		const size_t cap = std::max(total, 2 * c->d_views_cap);
+		c->d_views_cap = 0;
+		HIP_TRY(hipMalloc((void **)&c->d_views, cap * sizeof(double)));
+		c->d_views_cap = cap;
+	}
+	ViewStage *stage = nullptr;
+	if ((rc = acquire_view_stage(c, total, ++s->clock, &stage))) return rc;
+	double *const h = stage->h, *const d = c->d_views;
+	const bool interior = (flags & HMRM_TRACE_INTERIOR) != 0;
+	const bool records = !kern.literal && kern.kind == hmrm::kRecords;
+	// the records: build_frame per camera (glibc's trig: the bits of n single renders), the scene's part and the knobs as a
+	// single frame gets them, the tables' places in the arena; spread over the host pool for large n
+	hmrm::parallel_ranges(n, 256, [&](int b, int e) {
+		for (int k = b; k < e; ++k) {
+			hmrm::HostCamera hc;
+			to_host_camera(&cams[k], &hc);
+			hmrm::DevFrame fr{};
+			hmrm::build_frame(hc, s->map_w, s->map_h, s->params.min_height, s->params.max_height, s->params.grid_width, &fr, nullptr, nullptr,
+			                  nullptr, nullptr);
+			finish_frame_record(s, cams[k].sampling, &fr);
+			apply_scene_knobs(s, &fr);
+			fr.aa_shift = 0;
+			if (records) fr.mipbuf_bil = reinterpret_cast<const float *>(s->d_records); // (launch_common.hpp select_tables)
+			if (spherical) {
+				const double *cc = d + col_base + (size_t)tables.col_of[(size_t)k] * 2 * W;
+				const double *rs = d + row_base + (size_t)tables.row_of[(size_t)k] * 2 * H;
+				fr.col_cos_ha = cc;
+				fr.col_sin_ha = cc + W;
+				fr.row_sin_va = rs;
+				fr.row_cos_va = rs + H;
+			}
+			memcpy(h + (size_t)k * kRecDoubles, &fr, sizeof fr);
+		}
+	});
+	// the distinct tables: items [0, n_col * W) are columns, the rest rows
+	if (spherical) {
+		const int64_t items = (int64_t)(n_col * W + n_row * H);
+		// (W, H <= 2^29 and the arena's limit keep `items` far below 2^31)
+		hmrm::parallel_ranges((int)items, 1024, [&](int b, int e) {
+			int64_t i = b;
+			while (i < e) {
+				const bool col = i < (int64_t)(n_col * W);
+				const int64_t j = col ? i : i - (int64_t)(n_col * W);
+				const int64_t side = col ? (int64_t)W : (int64_t)H;
+				const int64_t t = j / side, first = j - t * side;
+				const int64_t last = std::min<int64_t>(side, first + (e - i));
+				hmrm::HostCamera hc;
+				to_host_camera(&cams[col ? tables.col_first[(size_t)t] : tables.row_first[(size_t)t]], &hc);
+				if (col) hmrm::fill_col_tables(hc, (int32_t)first, (int32_t)last, h + col_base + (size_t)t * 2 * W, h + col_base + (size_t)t * 2 * W + W);
+				else hmrm::fill_row_tables(hc, (int32_t)first, (int32_t)last, h + row_base + (size_t)t * 2 * H, h + row_base + (size_t)t * 2 * H + H);
+				i += last - first;
+			}
+		});
+	}
+	// stream order puts the upload behind every earlier kernel of this stream that read the arena and in front of the batch's own
+	HIP_TRY(hmrm::launch_upload_tables(stage->h_dev, d, total, c->stream));
+	HIP_TRY(hipEventRecord(stage->uploaded, c->stream));
+	stage->used = true;
+	hmrm::DevFrame f0;
+	memcpy(&f0, h, sizeof f0);
+	if (!device) HIP_TRY(hipEventRecord(s->ev0, s->stream)); // (the host form is timed like hmrm_render: hmrm_last_kernel_ms)
+	if ((rc = launch_views(s, c, kern, f0, reinterpret_cast<const hmrm::DevFrame *>(d), n, interior, d_rgba, stride_px, view_stride_px)) || device)
+		return rc;
+	HIP_TRY(hipEventRecord(s->ev1, s->stream));
+	if (view_stride_bytes == H * stride_bytes) // (the views' rows are equally spaced: one copy)
+		HIP_TRY(hipMemcpy2DAsync(target, stride_bytes, d_rgba, W * 4, W * 4, (size_t)n * H, hipMemcpyDeviceToHost, s->stream));
+	else
+		for (int32_t k = 0; k < n; ++k)
+			HIP_TRY(hipMemcpy2DAsync((uint8_t *)target + (size_t)k * view_stride_bytes, stride_bytes, d_rgba + (size_t)k * W * H, W * 4, W * 4, H,
+			                         hipMemcpyDeviceToHost, s->stream));
+	rc = finish_host_call(s, c);
+	float ms = 0.f;
+	HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+	g_last_kernel_ms = ms;
+	return rc;
+}
+
+int hmrm_render_views(const hmrm_scene *scene, const hmrm_camera *cams, int32_t n, uint32_t flags, uint8_t *rgba, size_t stride_bytes,
+                      size_t view_stride_bytes) {
+	return render_views_common(const_cast<hmrm_scene *>(scene), cams, n, flags, rgba, stride_bytes, view_stride_bytes, false, nullptr);
+}
+
+int hmrm_render_views_device(const hmrm_scene *scene, const hmrm_camera *cams, int32_t n, uint32_t flags, void *d_rgba, size_t stride_bytes,
+                             size_t view_stride_bytes, void *hip_stream) {
+	return render_views_common(const_cast<hmrm_scene *>(scene), cams, n, flags, d_rgba, stride_bytes, view_stride_bytes, true,
+	                           (hipStream_t)hip_stream);
+}
+
+int hmrm_debug_views_tables(const hmrm_camera *cams, int32_t n, int32_t *out_col_index, int32_t *out_row_index) {
+	if (!cams || !out_col_index || !out_row_index) return fail(HMRM_E_ARG, "NULL argument");
+	if (n < 1 || n > HMRM_MAX_VIEWS) return fail(HMRM_E_ARG, "views: n must be 1 .. 65536 (got " + std::to_string(n) + ")");
+	ViewTables t;
+	plan_view_tables(cams, n, &t);
+	memcpy(out_col_index, t.col_of.data(), (size_t)n * sizeof(int32_t));
+	memcpy(out_row_index, t.row_of.data(), (size_t)n * sizeof(int32_t));
+	return HMRM_OK;
 }
 
 // The sun-lit water frame: hmrm_render_water and hmrm_render_shaded composed, in one launch of a family of its own.

@@ -105,6 +105,28 @@ struct FrameSlot {
 	hipEvent_t measured = nullptr; // after the read-back of a measured launch
 };
 
+// View batches (hmrm_render_views): a batch's frame records and its distinct spherical tables are written by the host into one
+// pinned, device-mapped block and copied into the context's device arena by a small kernel of the launch stream (render.hpp
+// launch_upload_tables), as a cached record's tables are -- no host wait.  `uploaded` is recorded behind that kernel: the host
+// rewrites a block only when the event has passed, and takes another block of the ring while it has not (FrameSlot::uploaded's
+// rule, without its wait).  With every block of the ring in flight the host waits for the oldest.
+struct ViewStage {
+	double *h = nullptr, *h_dev = nullptr; // pinned memory and the same as the device sees it
+	size_t cap = 0;                        // doubles
+	hipEvent_t uploaded = nullptr;
+	bool used = false; // `uploaded` has been recorded at least once
+	uint64_t stamp = 0;
+};
+constexpr int kViewStages = 4;
+// The bytes a batch may stage: n records and the distinct tables (hmrm.h HMRM_MAX_VIEWS_STAGING).
+constexpr size_t kMaxViewStagingBytes = (size_t)256 << 20;
+// A device arena that was outgrown while launches of its stream might still read it: freed once `after`, recorded on the stream
+// when it was replaced, has passed -- looked at by the stream's next batch -- or with the context.
+struct RetiredArena {
+	void *ptr;
+	hipEvent_t after;
+};
+
 // Everything a launch mutates, per HIP stream: launches on different streams of one scene never
 // share a table or a counter (hmrm_render_rows_device takes the caller's stream).
 struct StreamCtx {
@@ -126,6 +148,12 @@ struct StreamCtx {
 	unsigned long long *d_counters = nullptr;
 	bool probe_in_flight = false; // the scene's shadow probe uses this context's calibration records
 	unsigned long long capped_seen = 0; // value of [2] the host has already reported
+	// view batches: the ring of staging blocks and the device arena (records, then column tables, then row tables); both only grow.
+	// Stream order puts a batch's upload behind the previous batch's kernel, so one arena serves every batch of the stream
+	ViewStage view_stages[kViewStages];
+	double *d_views = nullptr;
+	size_t d_views_cap = 0; // doubles
+	std::vector<RetiredArena> retired_views;
 };
 
 // One slot of the asynchronous read-back ring (hmrm_render_begin/_wait/_release): a device frame
@@ -318,12 +346,23 @@ int ensure_bilinear_pyramid(hmrm_scene *s);
 int drain_scene_streams(hmrm_scene *s, bool own_too);
 int ensure_light_plane(hmrm_scene *s);
 void drop_light_plane(hmrm_scene *s);
-// api_launch.cpp.  prepare_frame, wait_for_measure_fence, launch_frame, new_capped, take_capped, finish_host_call: s->mu held.
+// api_launch.cpp.  prepare_frame, wait_for_measure_fence, launch_frame, pick_views_kernel, acquire_view_stage, launch_views, new_capped,
+// take_capped, finish_host_call: s->mu held.
 int check_camera(const hmrm_camera *cam);
 void to_host_camera(const hmrm_camera *cam, hmrm::HostCamera *hc);
 int prepare_frame(hmrm_scene *s, StreamCtx *c, const hmrm_camera *cam, hmrm::DevFrame *f, FrameSlot **slot_out);
 int wait_for_measure_fence(hmrm_scene *s, StreamCtx *c);
 int launch_frame(hmrm_scene *s, StreamCtx *c, const hmrm::DevFrame &f, FrameSlot *slot, const hmrm::RowMap &rows, const FrameRequest &req);
+void finish_frame_record(const hmrm_scene *s, int sampling, hmrm::DevFrame *fr);
+void apply_scene_knobs(const hmrm_scene *s, hmrm::DevFrame *f);
+struct ViewsKernel {
+	bool literal;
+	hmrm::FastKernel kind;
+};
+int pick_views_kernel(hmrm_scene *s, StreamCtx *c, int sampling, ViewsKernel *out);
+int acquire_view_stage(StreamCtx *c, size_t doubles, uint64_t stamp, ViewStage **out);
+int launch_views(hmrm_scene *s, StreamCtx *c, const ViewsKernel &k, const hmrm::DevFrame &f0, const hmrm::DevFrame *d_frames, int32_t n,
+                 bool interior, uint32_t *d_out, int64_t out_stride_px, int64_t view_stride_px);
 unsigned long long new_capped(StreamCtx *c, unsigned long long now);
 int take_capped(StreamCtx *c, unsigned long long *out);
 int finish_host_call(hmrm_scene *s, StreamCtx *c, unsigned long long *capped_out = nullptr);

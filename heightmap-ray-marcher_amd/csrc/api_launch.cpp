@@ -334,17 +334,7 @@ int prepare_frame(hmrm_scene *s, StreamCtx *c, const hmrm_camera *cam, hmrm::Dev
 			const int rc2 = ensure_bilinear_pyramid(s);
 			if (rc2 != HMRM_OK) return rc2;
 		}
-		// (informational: the kernel reads the whole-map bound from the pyramid's top plane, rounded up to
-		// float like every window maximum -- which also bounds the float copy of a threshold)
-		fr.thr_max = cam->sampling == HMRM_BILINEAR ? s->thr_max_bil : s->thr_max;
-		// the finest level whose windows have at least min_window cells (camera.cpp's hint)
-		fr.min_level = 0;
-		while (fr.min_level < hmrm::kMipLevels - 1 && hmrm::win_cells(fr.min_level) < fr.min_window)
-			++fr.min_level;
-		fr.mipbuf = s->d_mipbuf;
-		fr.mipbuf_bil = s->d_mipbuf_bil;
-		fr.mip_row = s->mip_row;
-		fr.mip_plane_shift = s->mip_plane_shift;
+		finish_frame_record(s, cam->sampling, &fr);
 		slot->cam = *cam;
 		slot->params = s->params;
 		slot->thr_max_bits = thr_bits;
@@ -358,12 +348,98 @@ int prepare_frame(hmrm_scene *s, StreamCtx *c, const hmrm_camera *cam, hmrm::Dev
 	}
 	slot->stamp = ++s->clock;
 	*f = slot->frame;
-	// per-scene settings (not part of the cached record)
+	apply_scene_knobs(s, f);
+	if (slot_out) *slot_out = slot;
+	return HMRM_OK;
+}
+
+// What a frame record takes from the scene once build_frame (camera.cpp) has made it from the camera: the part of the cached
+// record that is the scene's.  (A bilinear record's pyramid exists: ensure_bilinear_pyramid is its caller's matter.)
+void finish_frame_record(const hmrm_scene *s, int sampling, hmrm::DevFrame *fr) {
+	// (informational: the kernel reads the whole-map bound from the pyramid's top plane, rounded up to
+	// float like every window maximum -- which also bounds the float copy of a threshold)
+	fr->thr_max = sampling == HMRM_BILINEAR ? s->thr_max_bil : s->thr_max;
+	// the finest level whose windows have at least min_window cells (camera.cpp's hint)
+	fr->min_level = 0;
+	while (fr->min_level < hmrm::kMipLevels - 1 && hmrm::win_cells(fr->min_level) < fr->min_window)
+		++fr->min_level;
+	fr->mipbuf = s->d_mipbuf;
+	fr->mipbuf_bil = s->d_mipbuf_bil;
+	fr->mip_row = s->mip_row;
+	fr->mip_plane_shift = s->mip_plane_shift;
+}
+
+// ... and the per-scene settings, which are not part of the cached record.
+void apply_scene_knobs(const hmrm_scene *s, hmrm::DevFrame *f) {
 	f->step_cap = s->knobs.step_cap;
 	f->diag_mode = s->knobs.diag_mode;
 	if (s->knobs.min_level >= 0) f->min_level = s->knobs.min_level;
 	if (s->knobs.finest_pause >= 0) f->finest_pause = s->knobs.finest_pause;
-	if (slot_out) *slot_out = slot;
+}
+
+// ---- view batches (hmrm_render_views): the launch path of api_frames.cpp render_views_common ----
+// Which kernel renders a batch: the literal loop (HMRM_KERNEL=simple, a huge side) or a march kernel of the scene's standing
+// verdict, as a frame with kernels of its own gets it (launch_frame): never a probe, never a measured launch, and behind the
+// scene's measure fence like every launch.  Decided before the records are built: the record kernel finds its table in them.
+int pick_views_kernel(hmrm_scene *s, StreamCtx *c, int sampling, ViewsKernel *out) {
+	const bool huge_side = s->map_w >= (1 << 24) || s->map_h >= (1 << 24);
+	const hmrm::FrameRoute route = hmrm::route_frame(s->knobs.kernel, huge_side, sampling, false, true, false, 0u);
+	if (route.refused) return fail(HMRM_E_ARG, "maps with a side of 2^24 cells or more support nearest sampling only");
+	int rc = wait_for_measure_fence(s, c);
+	if (rc) return rc;
+	poll_shadow_probe(s);
+	const bool use_group = s->knobs.kernel == 0 && s->knobs.try_group && s->choice.use_group;
+	out->literal = route.literal;
+	out->kind = (hmrm::FastKernel)hmrm::pick_fast_kernel(s->knobs.kernel, use_group, sampling == 0 && s->d_records, s->choice);
+	if (!route.literal && out->kind == hmrm::kRecords && (rc = ensure_records(s))) return rc;
+	return HMRM_OK;
+}
+
+// A staging block of at least `doubles` that no upload still reads, without a host wait while the ring has one; blocks only grow
+// (a block that is too small and free is replaced by one twice its size at least).
+int acquire_view_stage(StreamCtx *c, size_t doubles, uint64_t stamp, ViewStage **out) {
+	ViewStage *pick = nullptr, *oldest = &c->view_stages[0];
+	for (ViewStage &v : c->view_stages) {
+		if (v.stamp < oldest->stamp) oldest = &v;
+		bool free_now = !v.used;
+		if (!free_now) {
+			const hipError_t e = hipEventQuery(v.uploaded);
+			if (e == hipErrorNotReady) (void)hipGetLastError(); // (busy is no error: not left behind for the caller's next check)
+			free_now = e == hipSuccess;
+		}
+		if (!free_now) continue;
+		if (!pick || (pick->cap < doubles && v.cap > pick->cap)) pick = &v; // (the first free block, or a larger one where that is too small)
+	}
+	if (!pick) { // (every block's upload is still in flight: the one host wait of this path)
+		HIP_TRY(hipEventSynchronize(oldest->uploaded));
+		pick = oldest;
+	}
+	if (pick->cap < doubles) {
+		if (pick->h) (void)hipHostFree(pick->h);
+		pick->h = pick->h_dev = nullptr;
+		const size_t cap = std::max(doubles, 2 * pick->cap);
+		pick->cap = 0;
+		HIP_TRY(hipHostMalloc((void **)&pick->h, cap * sizeof(double), hipHostMallocMapped));
+		HIP_TRY(hipHostGetDevicePointer((void **)&pick->h_dev, pick->h, 0));
+		pick->cap = cap;
+	}
+	if (!pick->uploaded) HIP_TRY(hipEventCreateWithFlags(&pick->uploaded, hipEventDisableTiming));
+	pick->stamp = stamp;
+	*out = pick;
+	return HMRM_OK;
+}
+
+// The one launch of a batch whose records lie at d_frames (f0: view 0's, on the host).
+int launch_views(hmrm_scene *s, StreamCtx *c, const ViewsKernel &k, const hmrm::DevFrame &f0, const hmrm::DevFrame *d_frames, int32_t n,
+                 bool interior, uint32_t *d_out, int64_t out_stride_px, int64_t view_stride_px) {
+	const hmrm::RowMap rows{0, f0.screen_h, 0, 0, 1, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {0, 0, 0, 0}, nullptr};
+	hmrm::FrameLaunch l{s->d_thr, s->d_thr32, s->d_cmap, s->d_records, d_out, out_stride_px, c->d_counters, nullptr, nullptr, false, f0, rows,
+	                    hmrm::kFrameViews, hmrm::SunRules{}, interior, hmrm::GeomPlanes{}, c->stream};
+	l.d_frames = d_frames;
+	l.n_views = n;
+	l.view_stride_px = view_stride_px;
+	if (k.literal) HIP_TRY(hmrm::launch_frame_literal(l));
+	else HIP_TRY(hmrm::launch_frame_march(l, k.kind));
 	return HMRM_OK;
 }
 

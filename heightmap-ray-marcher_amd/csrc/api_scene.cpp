@@ -75,6 +75,15 @@ void destroy_ctx(StreamCtx *c) {
 	if (c->d_arena) (void)hipFree(c->d_arena);
 	if (c->h_arena) (void)hipHostFree(c->h_arena);
 	if (c->d_counters) (void)hipFree(c->d_counters);
+	for (ViewStage &v : c->view_stages) {
+		if (v.uploaded) (void)hipEventDestroy(v.uploaded);
+		if (v.h) (void)hipHostFree(v.h);
+	}
+	for (RetiredArena &r : c->retired_views) {
+		(void)hipEventDestroy(r.after);
+		(void)hipFree(r.ptr);
+	}
+	if (c->d_views) (void)hipFree(c->d_views);
 	delete c;
 }
 

@@ -19,6 +19,7 @@
 //   water_scope frame|all, water_light off|sun
 //   haze on|off, haze_start v, haze_far v, haze_law linear|exp|exp2, haze_density v, haze_color r g b, haze_sky on|off,
 //   haze_entries n
+//   view x y z hang vang (repeatable, at most 64), views_output <prefix>   (the CLI's view batch, hmrm_render_views)
 //   sun_map <path.png>, sun_map_lift v                (the whole map's light map, hmrm_cell_map, written by the CLI)
 //   sky_map <path.png>, sky_map_rings r n             (the whole map's sky-view map, hmrm_cell_map_sum, written by the CLI)
 //   range_map <path.pfm>                              (the camera's range plane, hmrm_render_geometry, written by the CLI)
@@ -332,6 +333,19 @@ void haze_entries_key(Config &c, std::istream &in, const char *key, std::string 
 	c.log << key << " " << c.haze_entries << "\n";
 }
 
+// one more camera of the CLI's view batch (hmrm_render_views): position and the two angles, in the `hang` / `vang` keys' unit
+void view_key(Config &c, std::istream &in, const char *key, std::string *) {
+	double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+	in >> v[0] >> v[1] >> v[2] >> v[3] >> v[4];
+	if ((int)c.views.size() >= kMaxConfigViews) {
+		c.warn << "WARNING: too many views\n";
+		return;
+	}
+	c.views.push_back(Config::View{{v[0], v[1], v[2]}, degrees_to_rads(v[3]), degrees_to_rads(v[4])});
+	const Config::View &w = c.views.back();
+	c.log << key << " " << w.pos[0] << " " << w.pos[1] << " " << w.pos[2] << " " << rads_to_degrees(w.hang) << " " << rads_to_degrees(w.vang) << "\n";
+}
+
 // which frames shadows / shading apply to: the plain single frame, or antialiased and recorded ones too
 void sun_scope_key(Config &c, std::istream &in, const char *key, std::string *) {
 	static const Word words[] = {{"single", 0}, {"all", 1}};
@@ -447,6 +461,8 @@ const Row kGrammar[] = {
 	{"haze_color", haze_color_key},
 	{"haze_sky", haze_sky_key},
 	{"haze_entries", haze_entries_key},
+	{"view", view_key},
+	{"views_output", scalar<&Config::views_output>},
 };
 
 } // namespace

@@ -5,6 +5,7 @@
 #include <istream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "image_io.hpp"
 
@@ -100,6 +101,13 @@ struct Config {
 	int haze_color[3] = {200, 210, 220};
 	int haze_sky = 0;
 	int haze_entries = 256;
+	// additive: `view x y z hang vang` (repeatable, at most kMaxConfigViews lines; angles in the unit of the `hang` and `vang` keys,
+	// degrees, kept in radians) -- one more camera of the CLI's view batch (hmrm_render_views), everything else from the main
+	// camera; a line beyond the limit warns "WARNING: too many views" and is dropped -- and `views_output <prefix>`, echoed like
+	// `output`: the batch's frames go to <prefix>000.png, <prefix>001.png, ...
+	struct View { double pos[3], hang, vang; };
+	std::vector<View> views;
+	std::string views_output;
 
 	bool heightmap_dirty = false; // should_update_heightmap, sticky until taken
 	std::ostringstream log;       // what the reference prints to stdout
@@ -113,6 +121,8 @@ struct Config {
 	bool consume(std::istream &input, std::string *fatal);
 
 };
+
+constexpr int kMaxConfigViews = 64;
 
 // hmrm_haze_table (hmrm.h): out[i] = min(255, (int)(255 * (1 - T) + 0.5)), x = (i + 0.5) / n, T by `law` with libm's exp.
 // False for an unknown law, n outside 1 .. 4096 or a null `out`.

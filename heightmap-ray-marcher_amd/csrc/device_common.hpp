@@ -442,6 +442,18 @@ struct StatsOut {
 };
 
 
+// A frame record fetched from device memory at a wave-uniform address (view batches: render_views.hip, render.hip), as a copy made
+// of 32-bit words.  Every field then comes out of scalar loads, the background's bytes too: the scalar unit of gfx950 has no byte
+// loads, and read through a reference to the device record f.bg[i] became vector loads.  The compiler keeps no
+// copy in memory: the words live in scalar registers like a kernel argument's.
+typedef uint32_t __attribute__((may_alias)) FrameWord;
+__device__ __forceinline__ void copy_frame_words(DevFrame *dst, const DevFrame *__restrict__ src) {
+	static_assert(sizeof(DevFrame) % sizeof(uint32_t) == 0 && alignof(DevFrame) >= alignof(uint32_t), "whole words");
+#pragma unroll
+	for (unsigned i = 0; i < sizeof(DevFrame) / sizeof(uint32_t); ++i)
+		reinterpret_cast<FrameWord *>(dst)[i] = reinterpret_cast<const FrameWord *>(src)[i];
+}
+
 // Miss shade: hmap.cpp:1041-1057.
 __device__ __forceinline__ uint32_t shade_miss(const DevFrame &f, double dz) {
 	if (dz > 0.0) {

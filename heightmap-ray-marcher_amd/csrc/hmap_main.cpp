@@ -21,6 +21,8 @@
 // `shading on`, shadow rays unless `shading on` stands without `shadows on`) is written there as a one-component PNG.
 // `sky_map <path.png>`: after that, the whole map's sky-view map (hmrm_cell_map_sum over `sky_map_rings r n` sky directions).
 // `range_map <path.pfm>`: after the frames and before the sun map, the range plane of the configured camera (hmrm_render_geometry).
+// `view x y z hang vang` (up to 64 lines) with `views_output <prefix>`: after the frames and before the range map, those cameras --
+// everything else from the configured one -- as ONE view batch (hmrm_render_views), written to <prefix>000.png, <prefix>001.png, ...
 // `water on`: the single frame with mirror reflections at or below `water_level` (hmrm_render_water; under the interior rule too
 // when `interior on`); ignored, with a warning, beside `antialias` > 1, `devices` > 1, `record orbit`, `shadows`, `shading` and
 // `baked_light`.  `water_scope all` lifts three of them: with `antialias n` > 1 the single frame is the antialiased water frame
@@ -81,6 +83,41 @@ static bool write_range_map(hmrm_config *cfg, hmrm_scene *scene, const hmrm_came
 		return false;
 	}
 	std::cout << "Saved range map at " << path << "\n";
+	return true;
+}
+
+// `view x y z hang vang` lines with `views_output <prefix>`: those cameras as one view batch (hmrm_render_views; under the interior
+// rule with `interior on`), written to <prefix>000.png, <prefix>001.png, ...  One key without the other warns and does nothing.
+// Returns false when the batch could not be rendered or a file not written.
+static bool write_views(hmrm_config *cfg, hmrm_scene *scene, bool interior) {
+	const int32_t n = hmrm_config_view_count(cfg);
+	const std::string prefix = hmrm_config_views_output(cfg);
+	if (n == 0 && prefix.empty()) return true;
+	if (n == 0 || prefix.empty()) {
+		std::cerr << (n == 0 ? "WARNING: views_output is ignored without a view\n" : "WARNING: view is ignored without views_output\n");
+		return true;
+	}
+	std::vector<hmrm_camera> cams((size_t)n);
+	hmrm_config_get_views(cfg, cams.data());
+	const size_t stride = (size_t)cams[0].width * 4, view = stride * (size_t)cams[0].height;
+	std::vector<uint8_t> frames(view * (size_t)n);
+	const int rc = hmrm_render_views(scene, cams.data(), n, interior ? HMRM_TRACE_INTERIOR : 0u, frames.data(), stride, view);
+	if (rc != HMRM_OK && rc != HMRM_E_NOTERM) {
+		std::cerr << hmrm_last_error() << "\n";
+		return false;
+	}
+	if (rc == HMRM_E_NOTERM) std::cerr << "WARNING: " << hmrm_last_error() << "\n";
+	std::cout << "rendered " << n << " views in " << hmrm_last_kernel_ms() << " ms (kernel)\n";
+	for (int32_t k = 0; k < n; ++k) {
+		char num[16];
+		snprintf(num, sizeof num, "%03d", (int)k);
+		const std::string path = prefix + num + ".png";
+		if (hmrm_write_png(path.c_str(), cams[0].width, cams[0].height, 4, frames.data() + view * (size_t)k, stride) != HMRM_OK) {
+			std::cerr << "Failed to write view to " << path << "\n";
+			return false;
+		}
+		std::cout << "Saved view at " << path << "\n";
+	}
 	return true;
 }
 
@@ -317,6 +354,7 @@ int main(int argc, char *argv[]) {
 			                             aa > 1 ? HMRM_AA(aa) : 0u);
 		if (rc != HMRM_OK) std::cerr << hmrm_last_error() << "\n";
 		for (size_t i = 1; i < scenes.size(); ++i) hmrm_scene_destroy(scenes[i]);
+		if (rc == HMRM_OK && !write_views(cfg, scene, interior)) rc = HMRM_E_IO;
 		if (rc == HMRM_OK && !write_range_map(cfg, scene, cam, interior)) rc = HMRM_E_IO;
 		if (rc == HMRM_OK && !write_sun_map(cfg, scene, cam, shading, shadows)) rc = HMRM_E_IO;
 		if (rc == HMRM_OK && !write_sky_map(cfg, scene, cam)) rc = HMRM_E_IO;
@@ -564,6 +602,7 @@ int main(int argc, char *argv[]) {
 		std::cerr << "Failed to write screenshot to " << path << "\n";
 	else
 		std::cout << "Saved screenshot at " << path << "\n";
+	if (wrc == HMRM_OK && !write_views(cfg, scene, interior)) wrc = HMRM_E_IO;
 	if (wrc == HMRM_OK && !write_range_map(cfg, scene, cam, interior)) wrc = HMRM_E_IO;
 	if (wrc == HMRM_OK && !write_sun_map(cfg, scene, cam, shading, shadows)) wrc = HMRM_E_IO;
 	if (wrc == HMRM_OK && !write_sky_map(cfg, scene, cam)) wrc = HMRM_E_IO;

@@ -24,6 +24,19 @@ inline LaunchGrid tile_grid(const DevFrame &f, const RowMap &rows) {
 	return {dim3((unsigned)tiles_x, folded_rows(tiles_y), row_folds(tiles_y)), tiles_y, hipSuccess};
 }
 
+// A view batch (hmrm_render_views): one workgroup per tile of every view, tile columns in x, the n_views * tiles_y_view tile rows
+// in y, folded like a frame's.  tiles_y is ONE view's tile rows.  The row count is made in 64 bits: a batch whose rows do not
+// fit the grid (65535 slabs of 32768) is refused.
+constexpr int64_t kMaxViewTileRows = (int64_t)65535 * 32768;
+inline LaunchGrid views_grid(const DevFrame &f, int n_views) {
+	const int tiles_x = (f.screen_w + kTileW - 1) / kTileW;
+	const int tiles_y = (f.screen_h + kTileH - 1) / kTileH;
+	if (tiles_x <= 0 || tiles_y <= 0 || n_views <= 0) return {dim3(), 0, hipSuccess};
+	const int64_t rows = (int64_t)n_views * tiles_y;
+	if (rows > kMaxViewTileRows) return {dim3(), 0, hipErrorInvalidValue};
+	return {dim3((unsigned)tiles_x, (unsigned)(rows < 32768 ? rows : 32768), (unsigned)((rows + 32767) / 32768)), tiles_y, hipSuccess};
+}
+
 // A ray batch: the batch as a frame kBatchW pixels wide (frame.hpp RayBatch), one workgroup per 128 consecutive rays,
 // grid rows in x.  An empty batch is no error; one that is too long, or whose frame does not hold it, is.
 inline LaunchGrid batch_grid(const DevFrame &f, const RayBatch &batch) {
@@ -68,6 +81,7 @@ hipError_t launch_render_water_baked_aa(const FrameLaunch &l, FastKernel kernel)
 hipError_t launch_render_water_lit(const FrameLaunch &l, FastKernel kernel);     // render_water_lit.hip (no AA variant)
 hipError_t launch_render_haze(const FrameLaunch &l, FastKernel kernel);          // render_haze.hip
 hipError_t launch_render_haze_aa(const FrameLaunch &l, FastKernel kernel);       // render_haze_aa.hip
+hipError_t launch_render_views(const FrameLaunch &l, FastKernel kernel);         // render_views.hip (view batches; no AA variant)
 
 // The segment rules of a frame launch: no limits, the interior rule for the interior family and where the sun's flags ask.
 inline SegRules frame_seg_rules(const FrameLaunch &l) {

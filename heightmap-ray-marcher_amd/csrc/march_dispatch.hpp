@@ -21,8 +21,9 @@ enum FastKernel { kPlainGroups = 0, kLeaps = 1, kRecords = 2 };
 // as are its antialiased form, its form under the light plane and both (hmrm_render_water_aa): kFrameWaterAA, kFrameWaterBaked and
 // kFrameWaterBakedAA.  kFrameWaterLit: the sun-lit water frame's (hmrm_render_water_lit), set by the launch path too; one family for
 // its four `shade_flags`, which its kernels read at run time.  kFrameHaze: the haze frame's (hmrm_render_haze), set by the launch
-// path like kFrameGeometry; its antialiased form is its launchers' matter, as the baked-light family's is, beside which it stands.
-enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded, kFrameGeometry, kFrameLitSum, kFrameBaked, kFrameHaze, kFrameWater,
+// path like kFrameGeometry; its antialiased form is its launchers' matter, as the baked-light family's is, beside which it stands.  kFrameViews: a view batch's
+// (hmrm_render_views), set by its own launch path (api_launch.cpp launch_views); it stands beside kFrameHaze.
+enum FrameFamily { kFramePlain = 0, kFrameInterior, kFrameLit, kFrameShaded, kFrameLitShaded, kFrameGeometry, kFrameLitSum, kFrameBaked, kFrameHaze, kFrameViews, kFrameWater,
                    kFrameWaterAA, kFrameWaterBaked, kFrameWaterBakedAA, kFrameWaterLit };
 
 // Which launch a frame gets.  `forced`: HMRM_KERNEL (2: simple); `huge_side`: a map side of 2^24 cells or more -- the production

@@ -734,7 +734,8 @@ static hipError_t launch_baked_literal(const FrameLaunch &l);    // (hmrm_render
 static hipError_t launch_water_literal(const FrameLaunch &l);    // (hmrm_render_water's, behind those)
 static hipError_t launch_water_literal_more(const FrameLaunch &l); // (hmrm_render_water_aa's, behind those)
 static hipError_t launch_water_lit_literal(const FrameLaunch &l);  // (hmrm_render_water_lit's, behind those)
-static hipError_t launch_haze_literal(const FrameLaunch &l);       // (hmrm_render_haze's, the last kernels of the code object)
+static hipError_t launch_haze_literal(const FrameLaunch &l);       // (hmrm_render_haze's, behind those)
+static hipError_t launch_views_literal(const FrameLaunch &l);      // (hmrm_render_views', the last kernels of the code object)
 
 // The interior family's kernel takes the segment rules behind the common arguments, the lit and shaded ones the sun too; the
 // shaded ones are built without shadow rays (kFrameShaded) and with them (kFrameLitShaded).  (The families one by one and in
@@ -755,6 +756,7 @@ hipError_t launch_frame_literal(const FrameLaunch &l) {
 	if (l.family == kFrameWaterAA || l.family == kFrameWaterBaked || l.family == kFrameWaterBakedAA) return launch_water_literal_more(l);
 	if (l.family == kFrameWaterLit) return launch_water_lit_literal(l);
 	if (l.family == kFrameHaze) return launch_haze_literal(l);
+	if (l.family == kFrameViews) return launch_views_literal(l);
 	if (l.f.aa_shift == 0) switch (l.family) {
 		case kFrameLit:
 			return launch_literal(l, st, [&](auto proj, dim3 grid, const auto &...args) {
@@ -1011,6 +1013,38 @@ static hipError_t launch_haze_literal(const FrameLaunch &l) {
 		if (aa) hipLaunchKernelGGL((k_render_haze_literal<proj(), true>), grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.haze);
 		else hipLaunchKernelGGL((k_render_haze_literal<proj(), false>), grid, dim3(kBlockThreads), 0, l.stream, args..., seg, l.haze);
 	});
+}
+
+// A pixel of a view batch (hmrm_render_views with HMRM_KERNEL=simple, or on a map with a side of 2^24 cells): k_render_interior_literal's
+// pixel of the view this workgroup belongs to -- the frame record read from the batch's device array at a wave-uniform index, as
+// render_views.hip does -- stored into that view's part of the target.  Nearest sampling only, like every literal kernel.
+template <int PROJ>
+__global__ __launch_bounds__(kBlockThreads) void k_render_views_literal(const DevFrame *__restrict__ frames, int n_views, int tiles_y_view,
+                                                                        const double *__restrict__ thr,
+                                                                        const uint32_t *__restrict__ cmap,
+                                                                        uint32_t *__restrict__ out, int64_t out_stride_px,
+                                                                        int64_t view_stride_px, StatsOut st, const SegRules seg) {
+	const unsigned gy = blockIdx.z * 32768u + blockIdx.y;
+	const unsigned view = (unsigned)__builtin_amdgcn_readfirstlane((int)(gy / (unsigned)tiles_y_view));
+	if (view >= (unsigned)n_views) return;
+	DevFrame f; // (a copy made of 32-bit words, not a reference: device_common.hpp copy_frame_words)
+	copy_frame_words(&f, frames + view);
+	const PixelId pid = pixel_of_tile_lane(f, whole_frame_rows(f), tiles_y_view, (int)blockIdx.x, gy - view * (unsigned)tiles_y_view,
+	                                       (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));
+	render_lane_literal<PROJ, false, false, true>(f, pid, thr, cmap, out + (int64_t)view * view_stride_px, out_stride_px, st, RayBatch{}, seg);
+}
+
+// Such a batch: render_views.hip's grid and arguments.  Never a measured launch.
+static hipError_t launch_views_literal(const FrameLaunch &l) {
+	if (l.f.aa_shift != 0 || l.rows.measure != nullptr || !l.d_frames || l.n_views < 1 || !l.d_out) return hipErrorInvalidValue;
+	const LaunchGrid g = views_grid(l.f, l.n_views);
+	if (g.tiles_y == 0) return g.err;
+	const SegRules seg = frame_seg_rules(l);
+	dispatch_projection(l.f.projection, [&](auto proj) {
+		hipLaunchKernelGGL(k_render_views_literal<proj()>, g.grid, dim3(kBlockThreads), 0, l.stream, l.d_frames, l.n_views, g.tiles_y, l.d_thr,
+		                   l.d_cmap, l.d_out, l.out_stride_px, l.view_stride_px, StatsOut{l.d_counters, nullptr, nullptr}, seg);
+	});
+	return hipGetLastError();
 }
 
 } // namespace hmrm

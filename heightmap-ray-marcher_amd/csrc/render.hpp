@@ -64,6 +64,13 @@ struct FrameLaunch {
 	// kFrameHaze (hmrm_render_haze): the frame of the plain or, with primary_interior, the interior family, whose pixels are blended
 	// towards the haze colour by the table's byte at their range (frame.hpp HazeRules); antialiased with f.aa_shift
 	HazeRules haze = HazeRules{nullptr, 0.0, 0.0, 0u, 0u, 0u};
+	// kFrameViews (hmrm_render_views): n_views frames of the plain or, with primary_interior, the interior family in one launch.
+	// d_frames: their records in device memory, complete (tables, pyramid -- or, for kRecords, the record table -- and knobs); `f` is
+	// view 0's record on the host, for what the launch dispatches on; view k lands at d_out + k * view_stride_px; `rows` is the
+	// identity of one view
+	const DevFrame *d_frames = nullptr;
+	int32_t n_views = 0;
+	int64_t view_stride_px = 0;
 };
 // The production kernels (march.hpp; one translation unit per family and AA variant, launch_common.hpp): speculative step groups
 // (kPlainGroups), plus exact leaps over empty pyramid windows (kLeaps), or over windows of the record level that are empty but

@@ -294,6 +294,7 @@ hipError_t launch_frame_march(const FrameLaunch &l, FastKernel kernel) {
 	case kFrameWaterBakedAA: return launch_render_water_baked_aa(l, kernel); // (refuses a frame without one)
 	case kFrameWaterLit: return launch_render_water_lit(l, kernel); // (refuses a factor)
 	case kFrameHaze: return aa ? launch_render_haze_aa(l, kernel) : launch_render_haze(l, kernel);
+	case kFrameViews: return launch_render_views(l, kernel); // (refuses a factor)
 	default: return aa ? launch_render_fast_aa(l, kernel) : launch_render_fast(l, kernel);
 	}
 }

@@ -357,6 +357,12 @@ def _load():
         "hmrm_render_haze": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Haze), vp, i32, vp, C.c_size_t]),
         "hmrm_render_haze_device": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Haze), vp, i32, vp, C.c_size_t, vp]),
         "hmrm_haze_table": (C.c_int, [i32, C.c_double, i32, vp]),
+        "hmrm_render_views": (C.c_int, [vp, vp, i32, C.c_uint32, vp, C.c_size_t, C.c_size_t]),
+        "hmrm_render_views_device": (C.c_int, [vp, vp, i32, C.c_uint32, vp, C.c_size_t, C.c_size_t, vp]),
+        "hmrm_debug_views_tables": (C.c_int, [vp, i32, vp, vp]),
+        "hmrm_config_view_count": (i32, [vp]),
+        "hmrm_config_get_views": (None, [vp, vp]),
+        "hmrm_config_views_output": (C.c_char_p, [vp]),
         "hmrm_config_haze": (i32, [vp]),
         "hmrm_config_get_haze": (None, [vp, C.POINTER(Haze), vp]),
         "hmrm_config_haze_law": (i32, [vp]),
@@ -460,7 +466,28 @@ KERNEL_SOURCES = ("render_fast.hip", "render_rays.hip", "leap_common.hpp", "leap
                   "render.hpp", "api_internal.hpp", "api_launch.cpp", "api_frames.cpp", "launch_order.cpp", "launch_order.hpp", "camera.cpp", "Makefile",
                   "march.hpp", "march_family.hpp", "march_frame.hpp", "march_dispatch.hpp", "launch_common.hpp", "render_baked.hip", "render_baked_aa.hip",
                   "render_water.hip", "render_water_aa.hip", "render_water_baked.hip", "render_water_baked_aa.hip",
-                  "render_water_lit.hip", "render_haze.hip", "render_haze_aa.hip")
+                  "render_water_lit.hip", "render_haze.hip", "render_haze_aa.hip", "render_views.hip")
+
+
+MAX_VIEWS = 65536  # hmrm_render_views' largest batch (HMRM_MAX_VIEWS)
+VIEWS_INTERIOR = 1  # its one flag (HMRM_TRACE_INTERIOR)
+
+
+def camera_array(cams):
+    """(ctypes array of Camera, n) of a sequence of Camera, or of such an array as it is."""
+    if isinstance(cams, C.Array) and getattr(cams, "_type_", None) is Camera:
+        return cams, len(cams)
+    cams = list(cams)
+    return (Camera * len(cams))(*cams), len(cams)
+
+
+def views_tables(cams):
+    """hmrm_debug_views_tables: which column tables and which row tables the views of a batch share -> (col_index, row_index),
+    int32 arrays; -1 everywhere for a batch that is not spherical."""
+    arr, n = camera_array(cams)
+    col, row = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    _check(lib.hmrm_debug_views_tables(arr, n, _ptr(col), _ptr(row)))
+    return col, row
 
 
 def kernel_src_sha() -> str:
@@ -701,6 +728,30 @@ class Scene:
         self._sync_env()
         _check(lib.hmrm_render_haze_device(self._h, C.byref(cam), C.byref(haze), C.c_void_p(d_table), int(factor), C.c_void_p(d_rgba),
                                            int(stride_bytes), C.c_void_p(stream)))
+
+    def render_views(self, cams, interior=False, allow_capped=False, pad_px=0, pad_rows=0) -> np.ndarray:
+        """A view batch (hmrm_render_views): the frames of `cams` -- a sequence of Camera or a ctypes array of them, all of one
+        width, height, projection and sampling -- in ONE launch; view k is render()'s frame of cams[k], render_interior()'s with
+        interior=True -> (n, H, W, 4) uint8.  pad_px / pad_rows: the rows are written pad_px pixels wider and the views pad_rows
+        rows apart (returned whole, (n, H + pad_rows, W + pad_px, 4); untouched bytes are 0xA5).  Capped rays: HMRM_E_NOTERM
+        unless allow_capped."""
+        self._sync_env()
+        arr, n = camera_array(cams)
+        w, h = (int(arr[0].width), int(arr[0].height)) if n else (0, 0)
+        fb = np.full((max(n, 1), h + int(pad_rows), w + int(pad_px), 4), 0xA5, dtype=np.uint8)
+        stride = (w + int(pad_px)) * 4
+        _check(lib.hmrm_render_views(self._h, arr, n, VIEWS_INTERIOR if interior else 0, _ptr(fb), stride, stride * (h + int(pad_rows))),
+               allow=(HMRM_E_NOTERM,) if allow_capped else ())
+        return fb
+
+    def render_views_device(self, cams, d_ptr: int, stride_bytes: int, view_stride_bytes: int, interior=False, stream: int = 0):
+        """The same batch into DEVICE memory on a caller stream (hmrm_render_views_device): view k at d_ptr + k *
+        view_stride_bytes, rows stride_bytes apart (e.g. an (n, H, W, 4) uint8 torch tensor: tensor.data_ptr(), W * 4, H * W * 4);
+        no host wait, capped rays through take_capped(stream)."""
+        self._sync_env()
+        arr, n = camera_array(cams)
+        _check(lib.hmrm_render_views_device(self._h, arr, n, VIEWS_INTERIOR if interior else 0, C.c_void_p(d_ptr), int(stride_bytes),
+                                            int(view_stride_bytes), C.c_void_p(stream)))
 
     def render_shaded(self, cam: Camera, sun: Sun, diffuse=True, shadows=True, allow_capped=False, aa=1) -> np.ndarray:
         """One full frame with diffuse sun shading (hmrm_render_shaded): render_lit()'s frame in which every hit pixel that is
@@ -1426,6 +1477,19 @@ class Config:
 
     def haze_far(self) -> float:
         return float(lib.hmrm_config_haze_far(self._h))
+
+    def views(self):
+        """The cameras of the additive `view x y z hang vang` lines (at most 64): the main camera with each line's position and
+        angles -> list of Camera."""
+        n = int(lib.hmrm_config_view_count(self._h))
+        arr = (Camera * max(n, 1))()
+        lib.hmrm_config_get_views(self._h, arr)
+        return [arr[k] for k in range(n)]
+
+    @property
+    def views_output(self) -> str:
+        """Additive `views_output <prefix>`: "" = none."""
+        return lib.hmrm_config_views_output(self._h).decode()
 
     @property
     def output_path(self) -> str:

@@ -921,6 +921,60 @@ int hmrm_render_haze_device(const hmrm_scene *scene, const hmrm_camera *cam, con
                             int32_t factor, void *d_rgba, size_t stride_bytes, void *hip_stream);
 int hmrm_haze_table(int32_t law, double density, int32_t n, uint8_t *out);   /* host only */
 
+/* -------------------------------------------------------------- view batches */
+/* Many cameras of one scene in ONE launch (build-side addition): the six faces of an environment probe, a stereo pair, a strip of
+ * thumbnails, a few hundred small views for agents.  Below about a megapixel a frame's time is launch cost and the tail of a short
+ * grid; a batch pays both once.
+ * VIEW k OF A BATCH is, byte for byte, hmrm_render's frame of cams[k]; with HMRM_TRACE_INTERIOR in `flags` it is
+ * hmrm_render_interior's frame of cams[k].  Nothing is shared between views except the scene.
+ * BATCH SIZE.  n is 1 .. HMRM_MAX_VIEWS.
+ * UNIFORM FIELDS.  All cameras share width, height, projection and sampling: what the launch dispatches on and what fixes its grid.
+ * FREE FIELDS.  Everything else may differ per view: pos, hang, vang, hfov, ortho_width, step_dist, the background.
+ * TARGET LAYOUT.  View k starts at byte k * view_stride_bytes of the target; its rows are stride_bytes apart.  Bytes between rows
+ * and between views are not written.
+ * REFUSALS (HMRM_E_ARG, with a message) before the scene is looked at, in this order:
+ *   1. NULL cams;
+ *   2. n outside 1 .. HMRM_MAX_VIEWS;
+ *   3. an undefined flag bit (defined: HMRM_TRACE_INTERIOR);
+ *   4. a camera that differs from cams[0] in one of the four uniform fields -- the message names the first such view and the field
+ *      -- and then cams[0] itself where hmrm_render's camera checks refuse it (they look at those four fields only);
+ *   5. a NULL scene or target;
+ *   6. the stride.  hmrm_render_views: stride_bytes < width * 4.  hmrm_render_views_device: hmrm_render_rows_device's rule -- >=
+ *      width * 4, a multiple of 4, below 2^33;
+ *   7. view_stride_bytes < height * stride_bytes; hmrm_render_views_device only: it must also be a multiple of 4;
+ *   8. a batch whose last byte, (n - 1) * view_stride_bytes + (height - 1) * stride_bytes + width * 4 - 1, lies at or beyond 2^40;
+ *   9. a batch of more than 65535 * 32768 tile rows, n * ceil(height / 16): the launch's grid does not hold them;
+ *  10. a batch whose frame records (352 bytes per view) and DISTINCT spherical tables exceed HMRM_MAX_VIEWS_STAGING bytes: it is
+ *      refused, not truncated.  Spherical views that agree bit for bit in (hang, hfov, width) share one pair of column tables, 16 *
+ *      width bytes; views that agree in (vang, hfov, width, height) share one pair of row tables, 16 * height bytes: a cube of
+ *      agents looking the same way, or an orbit at one vang, costs one row table.
+ * Behind them the 2^24-side rule of frames.
+ * CAPPED RAYS.  hmrm_render_views returns HMRM_E_NOTERM with valid frames when a ray of any view reached the step cap, as
+ * hmrm_render_interior does; hmrm_render_views_device reports through hmrm_scene_take_capped for its stream.  The count is the
+ * batch's, not per view.
+ * SYNCHRONY.  hmrm_render_views is synchronous on the scene's stream, renders into a scene-owned device buffer and reads the frames
+ * back.  hmrm_render_views_device takes a DEVICE target, launches on hip_stream and does no host wait -- not for the upload of its
+ * frame records and tables either: they travel through pinned memory the stream's launch state owns and are copied in stream
+ * order; an event guards the reuse of each of its four staging blocks, so batches on one stream may follow each other at once (a
+ * fifth batch while four uploads are still in flight waits for the oldest).  The first call on a stream, and a call that needs
+ * larger blocks than any before it, allocate.
+ * KERNELS.  One launch, never measured, never the scene's probe and not counted towards it, with the scene's current kernel
+ * (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST); every kernel writes the same bytes, the literal
+ * loop too (HMRM_KERNEL=simple, maps with a side >= 2^24: nearest sampling only).  All three projections, grid modes and sampling
+ * modes.
+ * OUT OF SCOPE: antialiasing; tickets and lanes; the recorder; row strips, bands and hmrm_render_multi; statistics; launch-order
+ * calibration and the probe; every other family (sun, water, baked light, haze, geometry planes). */
+#define HMRM_MAX_VIEWS 65536
+#define HMRM_MAX_VIEWS_STAGING (256u << 20)
+int hmrm_render_views(const hmrm_scene *scene, const hmrm_camera *cams, int32_t n, uint32_t flags,
+                      uint8_t *rgba, size_t stride_bytes, size_t view_stride_bytes);
+int hmrm_render_views_device(const hmrm_scene *scene, const hmrm_camera *cams, int32_t n, uint32_t flags,
+                             void *d_rgba, size_t stride_bytes, size_t view_stride_bytes, void *hip_stream);
+/* Host only, for tests: which pair of column tables and which pair of row tables each view of such a batch uses -- tables numbered
+ * from 0 in the order of their first view; -1 for every view of a batch that is not spherical.  Looks at nothing but n (1 ..
+ * HMRM_MAX_VIEWS) and the cameras. */
+int hmrm_debug_views_tables(const hmrm_camera *cams, int32_t n, int32_t *out_col_index, int32_t *out_row_index);
+
 /* Picking: the ray of pixel (px, py) of `cam` (ImagePlane::GetRay on the device, as hmrm_debug_ray) traced with the camera's
  * step_dist, background and sampling.  hit->rgba is that pixel of hmrm_render.  A convenience (two small launches and a
  * host sync), not a hot path: trace a batch for many pixels.  HMRM_E_NOTERM when the ray was stopped by the step cap. */
@@ -1135,7 +1189,13 @@ int32_t hmrm_orbit_frame_owner(int32_t frame, int32_t n_devices);
  * `haze_law linear|exp|exp2` (default exp; another value warns "WARNING: Unknown haze_law: v"), `haze_density v` (default 3),
  * `haze_color r g b` (default 200 210 220; a component outside 0..255: "WARNING: haze_color must be three values 0..255"),
  * `haze_sky on|off|1|0` (default off: HMRM_HAZE_SKY; another value warns "WARNING: Unknown haze_sky: v"), `haze_entries n`
- * (default 256; outside 1..4096: "WARNING: haze_entries must be 1..4096", the old value stays).
+ * (default 256; outside 1..4096: "WARNING: haze_entries must be 1..4096", the old value stays),
+ * `view x y z hang vang` (repeatable, at most 64 lines: one more camera of the CLI's view batch, hmrm_render_views -- position and
+ * the two angles, in the unit the `hang` and `vang` keys take; everything else comes from the main camera as it stands when the
+ * views are asked for; echoed like `pos` and the angles; a 65th line warns "WARNING: too many views" and is dropped),
+ * `views_output <prefix>` (echoed like `output`; with at least one `view` the CLI renders the views with ONE hmrm_render_views call
+ * after its frames, HMRM_TRACE_INTERIOR for `interior on`, and writes <prefix>000.png, <prefix>001.png, ...; one key without the
+ * other warns "WARNING: view is ignored without views_output" / "WARNING: views_output is ignored without a view").
  * Unknown key -> "WARNING: Unknown identifier: k". */
 hmrm_config *hmrm_config_create(void);
 void         hmrm_config_destroy(hmrm_config *cfg);
@@ -1192,6 +1252,10 @@ void         hmrm_config_get_haze(const hmrm_config *cfg, hmrm_haze *out, uint8_
 int32_t      hmrm_config_haze_law(const hmrm_config *cfg);      /* additive `haze_law linear|exp|exp2`: HMRM_HAZE_* */
 double       hmrm_config_haze_density(const hmrm_config *cfg);  /* additive `haze_density v` */
 double       hmrm_config_haze_far(const hmrm_config *cfg);      /* additive `haze_far v` */
+int32_t      hmrm_config_view_count(const hmrm_config *cfg);    /* additive `view x y z hang vang`: lines kept, 0 .. 64 */
+/* The cameras of those lines, hmrm_config_view_count of them: hmrm_config_get_camera's camera with the line's pos, hang and vang. */
+void         hmrm_config_get_views(const hmrm_config *cfg, hmrm_camera *out);
+const char  *hmrm_config_views_output(const hmrm_config *cfg);  /* additive `views_output <prefix>`: "" = none */
 /* Loaded maps (owned by cfg): RGB8 / RGBA8; NULL until the key was consumed. */
 const uint8_t *hmrm_config_height_rgb(const hmrm_config *cfg, int32_t *w, int32_t *h);
 const uint8_t *hmrm_config_color_rgba(const hmrm_config *cfg, int32_t *w, int32_t *h);
