@@ -422,8 +422,12 @@ int hmrm_render_lit(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_
  * the way a lit frame is: one launch, never measured, never the scene's probe and not counted towards it, with the scene's
  * current kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST).  All three projections and
  * sampling modes.  Antialiased, ticketed and recorded: the entry points below.  Still no row strips or bands
- * (hmrm_render_rows_device), no hmrm_render_multi, no hmrm_render_cycle, no statistics.  The shading arithmetic is tested at unit world scale
- * only: world scales far beyond a unit-scale scene (the 2^-900 .. 2^900 of the parity tests) are not tested for it. */
+ * (hmrm_render_rows_device), no hmrm_render_multi, no hmrm_render_cycle, no statistics.  The shading arithmetic is tested bit for bit across
+ * world scales (tests/test_world_scale_families_gpu.py): every length times 2^-900 .. 2^900 and decimal scales, grid widths an ulp off a
+ * power of two, relief on top of 1e9, and suns of magnitude 2^-600 .. 2^600.  Two consequences of the arithmetic as written, not
+ * limits of the kernels: a shadow ray starts (0.01 * grid_width) * dir past its origin, so it leaves the grid before its
+ * first load, and shadows nothing, once 0.01 * |dir| exceeds the grid's extent in grid widths (keep |dir| near 1); and q is 0
+ * where s.s or (n.n) * (s.s) overflows, and 0 or 255 where s.s underflows to zero. */
 #define HMRM_SHADE_DIFFUSE    1u
 #define HMRM_SHADE_NO_SHADOWS 2u
 int hmrm_render_shaded(const hmrm_scene *scene, const hmrm_camera *cam, const hmrm_sun *sun,
@@ -493,8 +497,17 @@ int hmrm_render_shaded_device_begin(const hmrm_scene *scene, const hmrm_camera *
  * hmrm_cell_map is synchronous on the scene's stream, one such call at a time per scene.  A cell map is not a frame: no
  * calibration, no probe, not counted towards the probe; hmrm_debug_kernel_choice and every later frame are as they would have
  * been.  It runs the scene's current kernel (HMRM_KERNEL or the probe's verdict; the window records apply to HMRM_NEAREST);
- * every kernel writes the same bytes, the literal loop too (HMRM_KERNEL=simple, maps with a side >= 2^24).  The shading
- * arithmetic is tested at unit world scale only, as for hmrm_render_shaded. */
+ * every kernel writes the same bytes, the literal loop too (HMRM_KERNEL=simple, maps with a side >= 2^24).  Rays, statuses
+ * and weights are tested bit for bit across world scales, as for hmrm_render_shaded (tests/test_world_scale_families_gpu.py).
+ * SUPPORTED RANGE OF POINT MODE: grid_width < 100.  There `dir` = O - pos is a length, so the first position,
+ * pos + (0.01 * grid_width) * dir, lies the FRACTION 0.01 * grid_width of the way from the cell to O, whatever the distance.
+ * While that fraction is small the map is the viewshed described above; it thins out as the fraction grows (the test scene hides
+ * 1818 of 3072 cells at grid_width 1, 1505 at 16, 1039 at 32, 96 at 64); from grid_width = 100 the ray STARTS AT OR BEYOND O and
+ * marches on away from it, so no cell is ever reported hidden, and a few thousand grid widths further every ray has left the
+ * grid before its first load (all MISS).  A world in metres with cells of 100 m or more needs its lengths divided by a constant
+ * before they go in (grid_width, heights, O, lift; step_dist is a fraction of |dir| and stays).  The bytes are the arithmetic
+ * above on both sides of the limit, and are tested there (grid_width 32 and 128); the nudge is the reference's entry nudge,
+ * kept for every ray family alike (DESIGN.md 5.6.4 has the trade-off). */
 #define HMRM_MAP_TOWARDS_POINT 1u  /* target is a point O, not a direction: a viewshed, a point light */
 #define HMRM_MAP_WEIGHT        2u  /* write the light weight w (0..255) instead of the ray's status */
 #define HMRM_MAP_DIFFUSE       4u  /* with WEIGHT: an unshadowed cell gets its diffuse level */
@@ -574,7 +587,9 @@ int hmrm_sky_directions(int32_t rings, int32_t per_ring, double *out_xyz);
  *                            -- the normal is (-gx, gy, 1); else (+0.0f, +0.0f).
  * Nothing is special-cased: alpha-0 hit cells are hits, as in hmrm_render_lit.  Capped rays are non-hits in all planes and are
  * counted as in hmrm_render_interior: hmrm_render_geometry returns HMRM_E_NOTERM with valid planes; END cannot occur (no limit).
- * Like the shading arithmetic, range and slope are tested at unit world scale only.
+ * Like the shading arithmetic, range and slope are tested bit for bit across world scales (tests/test_world_scale_families_gpu.py): ex * ex
+ * is denormal below about 2^-515 (r loses bits, and is 0 from about 2^-540 down) and infinite from about 2^508; the float is +inf
+ * from 2^128, a float denormal below 2^-126 and 0 below 2^-150 -- the casts round to nearest even and keep denormals.
  * Every pointer of the struct may be NULL: that plane is not written, and nothing is fetched for it (no colour without rgba).
  * Rows are `stride` bytes apart; bytes between rows are not touched.
  * Refusals (HMRM_E_ARG, with a message) before the scene is looked at, in this order: NULL planes; an undefined flag bit;
@@ -754,8 +769,8 @@ int hmrm_render_baked_device_begin(const hmrm_scene *scene, const hmrm_camera *c
  * FLOODING IS THE CALLER'S JOB.  The map is not changed and no cell is made flat: clamp the height image from below at the lake's
  * luminance L, max(pixel, L), before it goes into the scene, and pass the threshold of L -- heightmap_buf's value of L plus
  * min_height -- as `level`; add a margin below the next luminance step for HMRM_NEAREST_F32, whose t is a rounded float, and for
- * HMRM_BILINEAR, whose t is interpolated (INTEGRATION.md 2a has the recipe).  Like the shading arithmetic, the blend is tested at
- * unit world scale only: world scales beyond it are untested.
+ * HMRM_BILINEAR, whose t is interpolated (INTEGRATION.md 2a has the recipe).  Like the shading arithmetic, `t <= level`, the mirror
+ * rays and the blend are tested bit for bit across world scales (tests/test_world_scale_families_gpu.py).
  * Refusals (HMRM_E_ARG, with a message) before the scene is looked at, in this order: NULL water; an undefined flag bit;
  * reserved != 0.  Then the camera checks of hmrm_render, then a NULL scene or target, then the stride (hmrm_render_water:
  * stride_bytes < width * 4; hmrm_render_water_device: hmrm_render_rows_device's rule -- >= width * 4, a multiple of 4, below 2^33),
@@ -886,7 +901,8 @@ int hmrm_render_water_lit_device(const hmrm_scene *scene, const hmrm_camera *cam
  * Consequences, each byte for byte: a table of zeros gives hmrm_render / hmrm_render_interior / hmrm_render_aa; a table of 255s
  * with HMRM_HAZE_SKY gives a frame of the haze colour; without HMRM_HAZE_SKY the non-hit pixels are hmrm_render's; the order of the
  * entries matters only through i.  The kernel evaluates no transcendental -- the law is the table's -- which is why the frame is
- * bit-exact.  Like the shading arithmetic, the range is tested at unit world scale only.
+ * bit-exact.  Like the shading arithmetic, the range and the index are tested bit for bit across world scales
+ * (tests/test_world_scale_families_gpu.py), r = 0, denormal and +inf included: from about 2^508 every hit sits on the last entry.
  * hmrm_haze_table (host only) fills out[i] = min(255, (int)(255 * (1 - T) + 0.5)), x = (i + 0.5) / n, with T = 1 - x
  * (HMRM_HAZE_LINEAR), T = exp(-density * x) (HMRM_HAZE_EXP) or T = exp(-(density * x) * (density * x)) (HMRM_HAZE_EXP2), exp the
  * host's libm; HMRM_E_ARG for another law, n outside 1 .. 4096 or NULL out.
